@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — the hot path of Racing-SLAM on MI355X, measured.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config pass|cfg2|cfg3|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config pass|cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR]
 
 --config pass (default; BASELINE.json's metric "match+triangulate+local-BA passes/sec"):
   one STEP = one pass of the hot path over one batch of synthetic input, everything resident in HBM before the
@@ -44,7 +44,7 @@ for _p in (ROOT, os.path.join(ROOT, "oracle")):
 import numpy as np  # noqa: E402
 
 FP64_PEAK_TFLOPS = 78.6   # MI355X fp64 vector == fp64 MFMA peak (public spec)
-HBM_PEAK_GBS = 8000.0     # /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0     # MI355X HBM3E peak (public spec)
 VALU_INT_PEAK_TOPS = 39.3  # 256 CU x 64 lanes x 2.4 GHz 32-bit integer ops (K1's real ceiling)
 METRIC = "match+triangulate+local-BA passes/sec @ 2k kpts/frame, 20-KF\u00d710k-pt window"      # BASELINE.json's string, character for character
 
@@ -788,6 +788,39 @@ def check_pass_parity(meta, cpu_pass, O):
     return not bad, dict(rep, mismatches=bad)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, got):
+    """--dump-outputs: what a caller of the pass receives from its last timed step (gpu_results()), one DIR/<name>.npy per
+    array, in float32 (f32 outputs) or float64 (everything else: f64 outputs, indices, flags, summary fields; exact for them)."""
+    ba = got["ba"]
+    arrays = {
+        "match_descriptors.query": got["mq"], "match_descriptors.train": got["mt"],
+        "match_key_frame.keypoints": got["ra"]["match_kp"], "match_key_frame.points": got["ra"]["match_point"],
+        "match_map.keypoints": got["rb"]["match_kp"], "match_map.points": got["rb"]["match_point"],
+        "triangulate.keep": got["tri"]["keep"], "triangulate.xyz": got["tri"]["xyz"], "triangulate.out_index": got["tri"]["out_index"],
+        "tracks.status": got["trk"]["status"], "tracks.xyz": got["trk"]["xyz"], "tracks.accepted": got["trk"]["accepted"],
+        "tracks.inconsistent": got["trk"]["inconsistent"], "tracks.parallax_cos": got["trk"]["parallax_cos"],
+        "tracks.required_cos": got["trk"]["required_cos"],
+        "build_local_window.frames": got["lw"][0], "build_local_window.optimize": got["lw"][1],
+        "bundle_adjust.cameras": got["cams"], "bundle_adjust.points": got["pts"],
+        "bundle_adjust.summary": [ba[k] for k in ("termination", "iterations", "successful_steps", "usable",
+                                                  "initial_cost", "final_cost", "final_radius")],
+        "unpack_poses.poses": got["after"], "reanchor.points": got["single"],
+    }
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def bench_pass(e, args):
     ctx = e.ctx
     attach_comm(e)
@@ -802,6 +835,8 @@ def bench_pass(e, args):
     elapsed = timed(e, one_pass, args.steps, args.warmup)
     ms_per_step = 1e3 * elapsed / max(args.steps, 1)
     value = e.world * args.steps / elapsed
+    if args.dump_outputs and e.rank == 0:
+        dump_outputs(args.dump_outputs, meta["gpu_results"]())     # now: the timings below reuse the same output buffers
     retries_before = ctx.ba_stats()["handoff_retries"]
     other_ms = 1e3 * timed(e, other, args.steps, args.warmup) / max(args.steps, 1)
     # (front-end chains on forked streams can hold compute units the fused K7 + K8 launch counts on; a lost hand-off
@@ -1237,6 +1272,8 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="time budget of the CPU baseline leg")
     ap.add_argument("--no-shard-rehearsal", action="store_true",
                     help="cfg3 / cfg5 at N = 1: skip the in-process 2 / 4 / 8-shard solves reported beside `value`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="pass: after the timed steps, write what the last timed pass computed (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
     # --gpus N > 1 without a launcher: start one rank per GPU ourselves (python -m torch.distributed.run, rendezvous on
     # 127.0.0.1) BEFORE this process touches a GPU, relay the ranks' output and exit with their status.  On a box with
@@ -1259,6 +1296,8 @@ def main():
                              "in one process; run it with --gpus 1" % (args.gpus, ndev, args.config))
         if args.config == "pass":
             args.config = "cfg3"                 # the pass's only exchange step is the sharded local BA
+    if args.dump_outputs and args.config != "pass":
+        raise SystemExit("--dump-outputs is implemented for --config pass (the flagship workload) only")
     # The end-to-end interface timings run in a child process (tests/host_cpp/bench_boundary.bin).  It is started
     # BEFORE this process initialises the GPU: a process that holds a GPU context must not fork + exec on the box.
     if args.config == "pass" and args.boundary and int(os.environ.get("WORLD_SIZE", "1")) == 1:

@@ -7,6 +7,7 @@ package.  PARITY UNPINNED: the reference ships no fixtures for this path.
 import ctypes as C
 import os
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -78,10 +79,28 @@ def use_baseline(kind):
         _LIB = None
         return lib()
     assert kind in ("fast", "fast_omp")
-    so = os.path.join(_HERE, f"liboracle_{kind}_{cpu_model()[2]}.so")
+    name = f"liboracle_{kind}_{cpu_model()[2]}.so"
     srcs = [os.path.join(_HERE, f) for f in os.listdir(_HERE) if f.endswith((".c", ".h"))]
-    if not os.path.exists(so) or any(os.path.getmtime(x) > os.path.getmtime(so) for x in srcs):
-        subprocess.check_call(["make", "-C", _HERE, "-B", kind, "FAST_OUT=" + os.path.basename(so)], stdout=subprocess.DEVNULL)
+
+    def fresh(path):
+        return os.path.exists(path) and all(os.path.getmtime(x) <= os.path.getmtime(path) for x in srcs)
+
+    so = os.path.join(_HERE, name)
+    if not fresh(so) and not os.access(_HERE, os.W_OK):
+        # a tree the running user cannot write to (installed or checked out by another user): a per-user cache directory
+        cache = os.path.join(tempfile.gettempdir(), "rs-oracle-%d" % os.getuid())
+        os.makedirs(cache, mode=0o700, exist_ok=True)
+        if os.stat(cache).st_uid != os.getuid():
+            raise RuntimeError(f"{cache} belongs to another user: not loading a library from it")
+        so = os.path.join(cache, name)
+    if not fresh(so):
+        tmp = "%s.tmp%d.so" % (so[:-3], os.getpid())        # built under a private name and renamed: a concurrent run never loads half a file
+        try:
+            subprocess.check_call(["make", "-C", _HERE, "-B", kind, "FAST_OUT=" + tmp], stdout=subprocess.DEVNULL)
+            os.replace(tmp, so)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
     _LIB = C.CDLL(so)
     return _LIB
 

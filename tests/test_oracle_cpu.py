@@ -631,3 +631,41 @@ def test_long_track_window_is_ill_conditioned(oracle, synth):
     rc3, rp3, s3 = oracle.bundle_adjust(w3["cams"], w3["cam_free"], w3["points"], w3["obs_ptr"], w3["obs_cam"], w3["obs_uv"], w3["K"])
     cond3 = dense_lm.reduced_system_condition(w3, rc3, rp3, s3["final_radius"])
     assert cond3["final radius"][0] < cond["final radius"][0]
+
+
+# ------------------------------------------------------------------ CPU-baseline builds (bench.py)
+def test_baseline_build_in_a_read_only_tree(tmp_path):
+    """bench.py's CPU baseline compiles -O3 -march=native builds of the oracle when it runs.  In a tree the running user
+    cannot write to, they go to a per-user cache directory, and they compute what the checker build computes."""
+    import os
+    import shutil
+    import subprocess
+    import sys
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle")
+    tree = tmp_path / "oracle"
+    shutil.copytree(src, tree, ignore=lambda d, names: [n for n in names if not n.endswith((".c", ".h", ".py")) and n != "Makefile"])
+    subprocess.check_call(["make", "-s", "-C", str(tree), "liboracle.so"])
+    (tmp_path / "tmp").mkdir()
+    before = sorted(os.listdir(tree))
+    os.chmod(tree, 0o555)
+    code = ("import numpy as np, pyoracle as O\n"
+            "rng = np.random.default_rng(5)\n"
+            "q, t = rng.integers(0, 256, (300, 32), dtype=np.uint8), rng.integers(0, 256, (400, 32), dtype=np.uint8)\n"
+            "t[:150] = q[:150]\n"
+            "ref = O.match_descriptors(q, t)\n"
+            "for kind in ('fast', 'fast_omp'):\n"
+            "    print(O.use_baseline(kind)._name)\n"
+            "    got = O.match_descriptors(q, t)\n"
+            "    assert len(ref[0]) >= 150 and all(np.array_equal(a, b) for a, b in zip(got, ref)), kind\n"
+            "O.use_baseline(None)\n")
+    try:
+        r = subprocess.run([sys.executable, "-B", "-c", code], cwd=str(tree), capture_output=True, text=True, timeout=300,
+                           env=dict(os.environ, TMPDIR=str(tmp_path / "tmp"), PYTHONPATH=str(tree)))
+        after = sorted(os.listdir(tree))
+    finally:
+        os.chmod(tree, 0o755)
+    assert r.returncode == 0, r.stderr[-3000:]
+    libs = r.stdout.split()
+    assert len(libs) == 2 and all(os.path.exists(p) for p in libs)
+    if os.getuid() != 0:                # (root writes through the mode bits: then the builds land next to the sources)
+        assert after == before and all(p.startswith(str(tmp_path / "tmp")) for p in libs)

@@ -1,37 +1,13 @@
-"""Front-end (-fsyntax-only) check of the drop-in translation units in integration/reference_shim/.
+"""Self-contained checks of the drop-in translation units in integration/reference_shim/.
 
-The shims are OUR marshalling code, but they include the reference's own headers and Eigen / OpenCV.  Where the
-reference tree is present (this container; never the GPU box) they are type-checked against the reference's REAL
-headers with the minimal Eigen / OpenCV stand-ins of tests/shim_stubs/ (declarations only; see its README: this is not
-a build of the reference — none of its .cpp files is compiled, nothing is linked or run, no parity claim rests on it).
-It catches what ADVICE r1 found by eye: a missing definition (pose_graph), helpers that do not exist, and signatures
-that drifted from the headers.
+Type-checking them needs the upstream project's own headers, which are not part of this repository: that check is
+integration/check_shim_syntax.py, run by a maintainer against an upstream checkout.  What needs only this repository
+stays here.
 """
 import os
-import shutil
-import subprocess
-import tempfile
-
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/src"
 SHIM = os.path.join(ROOT, "integration", "reference_shim")
-FLAGS = ["-std=c++17", "-fsyntax-only", "-Wall", "-Wno-unused-variable", "-Wno-unused-but-set-variable", "-Wno-reorder",
-         "-I" + os.path.join(ROOT, "tests", "shim_stubs"), "-I" + REF, "-I" + os.path.join(ROOT, "include"), "-I" + SHIM]
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only present in the build container")
-
-
-def _check(path):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    r = subprocess.run([cxx] + FLAGS + [path], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-
-
-@pytest.mark.parametrize("name", ["MapMatcher.cpp", "Triangulation.cpp", "Optimization.cpp", "LocalWindow.cpp"])
-def test_replacement_translation_unit_type_checks(name):
-    _check(os.path.join(SHIM, name))
 
 
 def test_every_declared_function_of_the_four_headers_is_defined():
@@ -42,55 +18,3 @@ def test_every_declared_function_of_the_four_headers_is_defined():
                 "bool bundle_adjust(", "bool pose_graph(", "build_local_window("):
         assert sym in text, sym
     assert text.count("triangulate_points(const") >= 2
-
-
-INC_HARNESS = r'''
-#include <algorithm>
-#include <iostream>
-#include <map>
-#include <unordered_map>
-#include <unordered_set>
-#include "Mapper.h"
-#include "Frame.h"
-#include "Map.h"
-#include "MapPoint.h"
-#include "TrackStore.h"
-#include "Trajectory.h"
-#include "rs_shim_common.h"
-namespace slam {
-namespace {
-// the constants of src/Mapper.cpp:21-39 that the .inc files use (values as in the reference)
-constexpr size_t MIN_NEW_POINTS_PER_KEY_FRAME = 100;
-constexpr float ANY_PARALLAX_COSINE = 1.0F;
-constexpr float TRACK_MAX_REPROJECTION_ERROR = 4.0F;
-constexpr float TRACK_MIN_PARALLAX_COSINE = 0.999848F;
-constexpr float ROTATION_PARALLAX_FACTOR = 0.20F;
-constexpr float MAX_POINT_REPROJECTION_ERROR = 3.0F;
-}
-void Mapper::triangulate_tracks(KeyFrame& key_frame, TrackStore& tracks, const Trajectory& trajectory, FrameDiagnostics& diagnostics)
-{
-    struct Candidate { const Track* track; Eigen::Vector3f position; size_t keypoint_index; float parallax_cosine; float required_cosine; };
-    std::vector<Candidate> candidates;
-    std::vector<TrackId> inconsistent;
-#include "Mapper_triangulate_tracks.inc"
-    for (size_t index : accepted) { const auto& candidate = candidates[index]; (void)candidate.track->sightings.size(); }
-    (void)topped_up;
-}
-void Mapper::cull_points(FrameDiagnostics& diagnostics, KeyFrame& key_frame)
-{
-    std::unordered_set<MapPoint*> local;
-#include "Mapper_cull_points.inc"
-    for (const auto& point : points_to_remove) m_map.remove_point(point);
-}
-}  // namespace slam
-'''
-
-
-def test_mapper_inc_files_type_check_inside_their_functions():
-    """The two optional caller edits, spliced into skeletons of the functions they belong to (kept head / tail of the
-    reference's function reduced to the declarations the block relies on)."""
-    with tempfile.TemporaryDirectory() as d:
-        p = os.path.join(d, "inc_harness.cpp")
-        with open(p, "w") as fh:
-            fh.write(INC_HARNESS)
-        _check(p)
