@@ -704,6 +704,49 @@ int rs_build_local_window(int n_key_frames, int new_frame, int window_size, int 
                           const int32_t* h_pt_ptr, const int32_t* h_pt_obs,
                           int32_t* h_out_frame, uint8_t* h_out_optimize, int32_t* h_out_count);
 
+/* ------------------------------------------------------ KLT: track_features */
+
+/* Tracker::track_features (src/Tracker.cpp:90-131; the same pattern Initialization.cpp:79-90): two pyramidal Lucas-Kanade
+ * passes and the forward-backward filter, on device-resident image pyramids.  The specification is
+ * cv::calcOpticalFlowPyrLK (Bouguet) as restated in tests/klt_ref.py, with one deliberate difference: window sums are
+ * exact int64 sums converted to f32 once (OpenCV accumulates in f32; the difference is below f32 rounding of the sums).
+ *
+ * rs_image holds one frame: the grey level 0, the pyrDown levels (reflect-101) and their int16 Scharr derivatives,
+ * every level padded by `win` (images reflect-101, derivatives zeros).  It is allocated once by rs_image_create and
+ * reused by every upload: a tracker keeps two and swaps them, so each frame is uploaded once and its pyramid is the
+ * "previous" image of the next frame.  Levels above the first whose size is <= win in either direction are not built
+ * (buildOpticalFlowPyramid's clamp).  Envelope: width, height 1 .. 4096; win odd, 5 .. 31; max_level 0 .. 6;
+ * up to 8192 points per call.  Outside it: RS_ERR_UNSUPPORTED. */
+typedef struct rs_image rs_image;
+int rs_image_create(rs_context* ctx, int width, int height, int max_level, int win, rs_image** out_img);
+int rs_image_destroy(rs_image* img);
+/* *h_levels = levels built (1 + the highest level); h_sizes [2 * levels] or NULL: (width, height) of every level. */
+int rs_image_levels(const rs_image* img, int* h_levels, int* h_sizes);
+/* One frame, row pitch in bytes, channels 1 (grey, passed through) or 3 (BGR: cv::cvtColor BGR2GRAY's 8-bit
+ * fixed point, (1868 B + 9617 G + 4899 R + 8192) >> 14; to_gray, src/Tracker.cpp:24-32).  The host buffer may be reused
+ * on return; the pyramid is built asynchronously on the context stream. */
+int rs_image_upload(rs_context* ctx, rs_image* img, const uint8_t* h_pixels, int pitch, int channels);
+/* The same for a frame already on the device (d_pixels must stay valid until the stream reaches this call). */
+int rs_image_upload_device(rs_context* ctx, rs_image* img, const uint8_t* d_pixels, int pitch, int channels);
+/* Diagnostic: the padded level `level`: h_img [(h+2 win)][(w+2 win)] u8 and / or h_deriv [(h+2 win)][(w+2 win)][2] int16
+ * (dx, dy); either may be NULL.  Synchronises the stream. */
+int rs_image_download(rs_context* ctx, const rs_image* img, int level, uint8_t* h_img, int16_t* h_deriv);
+/* cv::calcOpticalFlowPyrLK(from, to, pts, next, status, noArray(), Size(win, win), max_level,
+ * TermCriteria(COUNT + EPS, max_iter, eps), d_guess ? OPTFLOW_USE_INITIAL_FLOW : 0, min_eig) (src/Tracker.cpp:107-110):
+ * d_pts [n][2], d_guess [n][2] or NULL, d_next [n][2], d_status [n] (1 = tracked).  Both images must come from
+ * rs_image_create with the same size and window, win <= that window, max_iter 1 .. 100; the number of levels used is
+ * min(max_level, the clamp for win), which both pyramids must have built. */
+int rs_klt_track(rs_context* ctx, const rs_image* from, const rs_image* to, const float* d_pts, int n, const float* d_guess,
+                 int win, int max_level, int max_iter, double eps, double min_eig, float* d_next, uint8_t* d_status);
+/* Steps 2-4 of track_features in one launch + an ordered compaction (src/Tracker.cpp:107-126): forward LK prev -> next,
+ * backward LK next -> prev from the forward result (window and levels of rs_image_create, 30 iterations, eps 0.01,
+ * minEig 1e-4), then point i is kept iff both passes tracked it, |prev_i - back_i| <= fb_max (f32 difference, f64 norm,
+ * cv::norm), (cvRound(next_i.x), cvRound(next_i.y)) lies inside the image and, with d_mask [height][width] u8 (the static
+ * mask, NULL = none), the mask there is non-zero.  Outputs: d_kept_index [n] ascending, d_kept_pt [n][2] = next_i of each
+ * kept point (capacity n each), d_count [1] (device) — exactly what feeds matches / features.keypoints at :128-131. */
+int rs_track_features(rs_context* ctx, const rs_image* prev, const rs_image* next, const float* d_prev_pts, int n,
+                      const uint8_t* d_mask, float fb_max, int32_t* d_kept_index, float* d_kept_pt, int32_t* d_count);
+
 /* ------------------------------------------------------------- multi-GPU */
 
 #define RS_COMM_ID_BYTES 128

@@ -79,6 +79,56 @@ void Mapper::cull_points(FrameDiagnostics& diagnostics, KeyFrame& key_frame)
 '''
 
 
+# Tracker_track_features.inc spliced into a skeleton of Tracker::track_features (kept head :90-105 reduced to what the
+# block reads).  The block uses a few OpenCV names the Mapper harness does not need (cv::Point, cv::circle, cvRound,
+# Mat::push_back); the check compiles against a copy of tests/shim_stubs/ in a temporary directory whose core.hpp adds
+# their declarations (the stubs themselves stay untouched).
+TRACKER_HARNESS = r"""
+#include "Tracker.h"
+#include "Frame.h"
+#include "rs_shim_common.h"
+namespace slam {
+namespace {
+constexpr int KLT_WINDOW = 21;
+constexpr int KLT_PYRAMID_LEVELS = 4;
+constexpr float KLT_MAX_FORWARD_BACKWARD_ERROR = 1.0F;
+constexpr int KLT_REPLENISH_RADIUS = 5;
+}
+std::pair<ExtractedFeatures, std::vector<FeatureMatch>> Tracker::track_features(const cv::Mat& image)
+{
+    const auto& prev_features = m_last_frame->features();
+    std::vector<cv::Point2f> prev_points;
+    for (const auto& keypoint : prev_features.keypoints) prev_points.push_back(keypoint.pt);
+#include "Tracker_track_features.inc"
+    (void)replenish_mask;
+    return {std::move(features), std::move(matches)};
+}
+}  // namespace slam
+"""
+TRACKER_STUB_EXTRA = """
+    void push_back(const Mat& row);
+"""
+TRACKER_STUB_FREE = """
+namespace cv {
+struct Point { int x, y; Point(int x, int y); };
+void circle(Mat& img, Point center, int radius, double color, int thickness);
+}  // namespace cv
+int cvRound(float value);
+"""
+
+
+def tracker_stubs(dst):
+    """tests/shim_stubs/ copied to dst with the declarations the Tracker block needs added to opencv2/core.hpp"""
+    src = os.path.join(ROOT, "tests", "shim_stubs")
+    shutil.copytree(src, dst)
+    core = os.path.join(dst, "opencv2", "core.hpp")
+    text = open(core).read()
+    head, tail = text.split("    Mat clone() const;\n", 1)
+    text = head + "    Mat clone() const;\n" + TRACKER_STUB_EXTRA + tail + TRACKER_STUB_FREE
+    open(core, "w").write(text)
+    return dst
+
+
 def main(argv):
     if len(argv) != 2 or not os.path.isfile(os.path.join(argv[1], "MapMatcher.h")):
         sys.exit("usage: check_shim_syntax.py <Racing-SLAM checkout>/src  (the directory holding MapMatcher.h)")
@@ -94,6 +144,17 @@ def main(argv):
             if not ok:
                 print(err[-4000:])
                 failed.append(name)
+        tracker = os.path.join(d, "tracker_harness.cpp")
+        with open(tracker, "w") as fh:
+            fh.write(TRACKER_HARNESS)
+        stubs = tracker_stubs(os.path.join(d, "stubs"))
+        cxx = shutil.which("g++") or shutil.which("c++")
+        fl = [f.replace(os.path.join(ROOT, "tests", "shim_stubs"), stubs) for f in flags(upstream_src)]
+        r = subprocess.run([cxx] + fl + [tracker], capture_output=True, text=True)
+        print("%-22s %s" % ("Tracker .inc harness", "ok" if r.returncode == 0 else "FAILED"))
+        if r.returncode:
+            print(r.stderr[-4000:])
+            failed.append("Tracker .inc harness")
     sys.exit(1 if failed else 0)
 
 

@@ -23,6 +23,7 @@ SOURCES = [
     ("triangulate.hip", ["-ffp-contract=off"]),
     ("reproj_match.hip", ["-ffp-contract=off"]),
     ("tracks.hip", ["-ffp-contract=off"]),
+    ("klt.hip", ["-ffp-contract=off"]),
     ("ba.hip", ["-munsafe-fp-atomics"]),
     ("ba_solve.hip", ["-munsafe-fp-atomics"]),
     ("ba_solve_big.hip", ["-munsafe-fp-atomics"]),

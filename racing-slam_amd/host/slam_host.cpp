@@ -153,7 +153,11 @@ Session::Session()
     const int rc = rs_context_create(0, &m_ctx);
     if (rc != RS_OK) throw std::runtime_error("rs_context_create failed (no gfx950 GPU? there is no CPU fallback)");
 }
-Session::~Session() { rs_context_destroy(m_ctx); }
+Session::~Session()
+{
+    for (rs_image* p : m_pyr) rs_image_destroy(p);
+    rs_context_destroy(m_ctx);
+}
 Session& Session::get()
 {
     static Session s;
@@ -664,4 +668,73 @@ std::vector<FrameConfig> build_local_window(const std::vector<std::shared_ptr<Ke
 }
 
 }  // namespace optimization
+// ------------------------------------------------------------------------ Tracker::track_features (src/Tracker.cpp:90-131)
+std::pair<ExtractedFeatures, std::vector<FeatureMatch>> Session::track_features(const Image& prev, const Image& next,
+                                                                                const ExtractedFeatures& prev_features,
+                                                                                const Image& mask)
+{
+    constexpr int KLT_WINDOW = 21, KLT_PYRAMID_LEVELS = 4;     // src/Tracker.cpp:17-19
+    constexpr float KLT_MAX_FORWARD_BACKWARD_ERROR = 1.0F;
+    ExtractedFeatures features;
+    std::vector<FeatureMatch> matches;
+    const int W = next.width, H = next.height;
+    if (prev.width != W || prev.height != H || prev.pixels.size() < (size_t)W * H * prev.channels ||
+        next.pixels.size() < (size_t)W * H * next.channels || (!mask.pixels.empty() && (mask.width != W || mask.height != H))) {
+        std::printf("track_features: frames / mask differ in size\n");
+        return {};
+    }
+    if (m_pyr_w != W || m_pyr_h != H) {
+        for (rs_image*& p : m_pyr) { rs_image_destroy(p); p = nullptr; }
+        for (rs_image*& p : m_pyr)
+            if (!rs_ok(rs_image_create(m_ctx, W, H, KLT_PYRAMID_LEVELS, KLT_WINDOW, &p), "rs_image_create")) { m_pyr_w = 0; return {}; }
+        m_pyr_w = W;
+        m_pyr_h = H;
+        m_next_image = nullptr;
+    }
+    if (m_next_image == &prev && m_next_data == prev.pixels.data()) {
+        m_next ^= 1;                                            // the last call's next frame is this call's previous frame
+    } else if (!rs_ok(rs_image_upload(m_ctx, m_pyr[m_next ^ 1], prev.pixels.data(), W * prev.channels, prev.channels), "rs_image_upload")) {
+        m_next_image = nullptr;
+        return {};
+    }
+    m_next_image = nullptr;
+    if (!rs_ok(rs_image_upload(m_ctx, m_pyr[m_next], next.pixels.data(), W * next.channels, next.channels), "rs_image_upload")) return {};
+    m_next_image = &next;
+    m_next_data = next.pixels.data();
+    const size_t n = prev_features.keypoints.size();
+    std::vector<float> pts(2 * n);
+    for (size_t i = 0; i < n; i++) {
+        pts[2 * i] = prev_features.keypoints[i].pt.x;
+        pts[2 * i + 1] = prev_features.keypoints[i].pt.y;
+    }
+    StageScope scope;
+    DevBuf<float> d_pts(pts), d_kept_pt(2 * n);
+    DevBuf<int32_t> d_kept(n), d_count(1);
+    std::unique_ptr<DevBuf<uint8_t>> d_mask;
+    if (!mask.pixels.empty()) d_mask = std::make_unique<DevBuf<uint8_t>>(mask.pixels);
+    if (!rs_ok(rs_track_features(m_ctx, m_pyr[m_next ^ 1], m_pyr[m_next], d_pts.get(), (int)n, d_mask ? d_mask->get() : nullptr,
+                                 KLT_MAX_FORWARD_BACKWARD_ERROR, d_kept.get(), d_kept_pt.get(), d_count.get()), "rs_track_features"))
+        return {};
+    const auto count = d_count.fetch(1);
+    const auto kept = d_kept.fetch(n);
+    const auto kept_pt = d_kept_pt.fetch(2 * n);
+    stage_sync();
+    const size_t m = (size_t)count[0];
+    features.keypoints.reserve(m);
+    features.descriptors.reserve(m * RS_DESC_BYTES);
+    matches.reserve(m);
+    const bool with_desc = prev_features.descriptors.size() >= n * RS_DESC_BYTES;
+    for (size_t k = 0; k < m; k++) {                            // :128-130
+        const size_t i = (size_t)kept[k];
+        KeyPoint kp = prev_features.keypoints[i];
+        kp.pt = Vec2f{kept_pt[2 * k], kept_pt[2 * k + 1]};
+        matches.emplace_back((int)i, (int)features.keypoints.size());
+        features.keypoints.push_back(kp);
+        if (with_desc)
+            features.descriptors.insert(features.descriptors.end(), prev_features.descriptors.begin() + i * RS_DESC_BYTES,
+                                        prev_features.descriptors.begin() + (i + 1) * RS_DESC_BYTES);
+    }
+    return {std::move(features), std::move(matches)};
+}
+
 }  // namespace slam

@@ -213,16 +213,35 @@ std::vector<FrameConfig> build_local_window(const std::vector<std::shared_ptr<Ke
 const rs_ba_summary& last_summary();
 }  // namespace optimization
 
+// An 8-bit frame (cv::Mat CV_8UC1 / CV_8UC3 BGR), rows packed: pitch = width * channels.
+struct Image {
+    int width = 0, height = 0, channels = 1;
+    std::vector<uint8_t> pixels;
+};
+
 // Process-wide device session (one context per process, SURVEY.md §8b "Threading").
 class Session {
   public:
     static Session& get();
     rs_context* ctx() const { return m_ctx; }
     ~Session();
+    // Tracker::track_features (src/Tracker.cpp:90-131) up to, not including, the replenishment (:133-150): forward and
+    // backward pyramidal LK (window 21, 4 levels) and the forward-backward / border / static-mask filter, as ONE
+    // rs_track_features call.  Returns {features, matches} of :128-131: the tracked keypoints at their new positions
+    // with their descriptor rows, and (previous index, new index) per tracked keypoint.  `mask` with no pixels = none.
+    // The session keeps two device pyramids: when `prev` is the Image passed as `next` to the previous call (same
+    // object, same buffer, unchanged), its pyramid is reused and only `next` is uploaded.
+    std::pair<ExtractedFeatures, std::vector<FeatureMatch>> track_features(const Image& prev, const Image& next,
+                                                                           const ExtractedFeatures& prev_features,
+                                                                           const Image& mask);
 
   private:
     Session();
     rs_context* m_ctx = nullptr;
+    rs_image* m_pyr[2] = {nullptr, nullptr};    // m_pyr[m_next] holds the last `next` frame
+    int m_next = 1, m_pyr_w = 0, m_pyr_h = 0;
+    const Image* m_next_image = nullptr;
+    const uint8_t* m_next_data = nullptr;
 };
 
 }  // namespace slam

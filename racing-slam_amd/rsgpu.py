@@ -21,6 +21,8 @@ EXPORTS = [
     "rs_map_add_keyframe", "rs_map_set_keyframe_pose", "rs_map_add_point", "rs_map_set_position", "rs_map_remove_point",
     "rs_map_add_observation", "rs_map_remove_observation", "rs_map_counts", "rs_map_get_positions", "rs_map_match", "rs_map_pose_graph", "rs_pose_graph", "rs_pose_relative", "rs_transform_points", "rs_map_bundle_adjust", "rs_triangulate", "rs_triangulate_host", "rs_triangulate_matches", "rs_triangulate_matches_batch", "rs_triangulate_tracks", "rs_parallax_requirements", "rs_point_errors", "rs_ba_default_options",
     "rs_bundle_adjust", "rs_bundle_adjust_batch", "rs_ba_get_trace", "rs_ba_get_stats", "rs_ba_get_cameras", "rs_reanchor_points", "rs_reanchor_points_host_poses", "rs_refine_pose", "rs_bundle_adjust_inertial", "rs_refine_pose_inertial", "rs_pack_pose", "rs_unpack_pose", "rs_pack_poses", "rs_unpack_poses", "rs_build_local_window",
+    "rs_image_create", "rs_image_destroy", "rs_image_levels", "rs_image_upload", "rs_image_upload_device", "rs_image_download",
+    "rs_klt_track", "rs_track_features",
     "rs_comm_get_unique_id", "rs_comm_init_rank", "rs_comm_destroy", "rs_comm_init_local", "rs_comm_count", "rs_prof_begin", "rs_prof_end", "rs_prof_counters", "rs_prof_empty_launch",
 ]
 
@@ -672,8 +674,79 @@ class Context:
         self._check(self.lib.rs_prof_empty_launch(self.h, int(n), C.byref(us)), "rs_prof_empty_launch")
         return us.value
 
+    # -- KLT (Tracker::track_features)
+    def image(self, width, height, max_level=4, win=21, frame=None):
+        """rs_image: a device-resident pyramid (grow-free, reused across frames); `frame` (grey [h][w] or BGR [h][w][3]
+        u8, numpy or a device tensor) is uploaded if given."""
+        im = Image(self, width, height, max_level, win)
+        if frame is not None:
+            im.upload(frame)
+        return im
+
+    def klt_track(self, src, dst, d_pts, n, d_guess=None, win=21, max_level=4, max_iter=30, eps=0.01, min_eig=1e-4, out=None):
+        """rs_klt_track (calcOpticalFlowPyrLK): dict(next [n][2] f32, status [n] u8), device tensors."""
+        t = self.torch
+        if out is None:
+            out = dict(next=self.empty((max(n, 1), 2), t.float32), status=self.empty((max(n, 1),), t.uint8))
+        self._check(self.lib.rs_klt_track(self.h, src.h, dst.h, _dp(d_pts), int(n), _dp(d_guess), int(win), int(max_level),
+                                          int(max_iter), C.c_double(eps), C.c_double(min_eig), _dp(out["next"]),
+                                          _dp(out["status"])), "rs_klt_track")
+        return out
+
+    def track_features(self, prev, nxt, d_pts, n, d_mask=None, fb_max=1.0, out=None):
+        """rs_track_features (src/Tracker.cpp:107-126): dict(index [n] i32, pts [n][2] f32, count [1] i32), device
+        tensors; the first count entries are the kept points."""
+        t = self.torch
+        if out is None:
+            out = dict(index=self.empty((max(n, 1),), t.int32), pts=self.empty((max(n, 1), 2), t.float32),
+                       count=self.empty((1,), t.int32))
+        self._check(self.lib.rs_track_features(self.h, prev.h, nxt.h, _dp(d_pts), int(n), _dp(d_mask), C.c_float(fb_max),
+                                               _dp(out["index"]), _dp(out["pts"]), _dp(out["count"])), "rs_track_features")
+        return out
+
     def synchronize(self):
         self._check(self.lib.rs_context_synchronize(self.h), "rs_context_synchronize")
+
+
+class Image:
+    """rs_image: one frame's padded pyramid and Scharr derivatives on the device."""
+
+    def __init__(self, ctx, width, height, max_level=4, win=21):
+        self.ctx, self.width, self.height, self.win = ctx, int(width), int(height), int(win)
+        self.h = C.c_void_p()
+        ctx._check(ctx.lib.rs_image_create(ctx.h, self.width, self.height, int(max_level), self.win, C.byref(self.h)),
+                   "rs_image_create")
+
+    def upload(self, frame):
+        ch = 1 if frame.ndim == 2 else int(frame.shape[2])
+        if isinstance(frame, np.ndarray):
+            a = np.ascontiguousarray(frame, np.uint8)
+            self.ctx._check(self.ctx.lib.rs_image_upload(self.ctx.h, self.h, a.ctypes.data_as(C.c_void_p), a.shape[1] * ch, ch),
+                            "rs_image_upload")
+        else:
+            self.ctx._check(self.ctx.lib.rs_image_upload_device(self.ctx.h, self.h, _dp(frame), int(frame.shape[1]) * ch, ch),
+                            "rs_image_upload_device")
+        return self
+
+    def levels(self):
+        n = C.c_int(0)
+        sizes = (C.c_int * 16)()
+        self.ctx._check(self.ctx.lib.rs_image_levels(self.h, C.byref(n), sizes), "rs_image_levels")
+        return [(sizes[2 * i], sizes[2 * i + 1]) for i in range(n.value)]
+
+    def download(self, level):
+        """padded level: (img [h+2win][w+2win] u8, dx, dy [h+2win][w+2win] int16)"""
+        w, h = self.levels()[level]
+        img = np.zeros((h + 2 * self.win, w + 2 * self.win), np.uint8)
+        der = np.zeros((h + 2 * self.win, w + 2 * self.win, 2), np.int16)
+        self.ctx._check(self.ctx.lib.rs_image_download(self.ctx.h, self.h, int(level), img.ctypes.data_as(C.c_void_p),
+                                                       der.ctypes.data_as(C.c_void_p)), "rs_image_download")
+        return img, der[..., 0].copy(), der[..., 1].copy()
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.rs_image_destroy(self.h)
+            self.h = C.c_void_p()
 
 
 # ---- §8(f) rank 4: the resident map (rs_map / rs_frame) -----------------------------------------------------

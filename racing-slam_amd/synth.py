@@ -409,3 +409,108 @@ def make_pose_graph(n_kf=60, n_loops=3, laps=1.25, drift_rot=2e-3, drift_trans=2
             N[:3, 3] = np.array([3.0, 0.0, -2.0])
         loops.append((i, j, N @ rel))
     return dict(poses=poses, poses_true=T_true, loops=loops, gravity=np.array([0.0, -9.80665, 0.0]))
+
+
+def _value_noise(grid, x, y, scale):
+    """C1 value noise: the lattice `grid` (spacing `scale` pixels) interpolated with smoothstep weights at (x, y)."""
+    gx, gy = x / scale, y / scale
+    x0, y0 = np.floor(gx).astype(np.int64), np.floor(gy).astype(np.int64)
+    tx, ty = gx - x0, gy - y0
+    tx, ty = tx * tx * (3 - 2 * tx), ty * ty * (3 - 2 * ty)
+    h, w = grid.shape
+    x0, y0 = np.clip(x0, 0, w - 2), np.clip(y0, 0, h - 2)
+    g00, g01, g10, g11 = grid[y0, x0], grid[y0, x0 + 1], grid[y0 + 1, x0], grid[y0 + 1, x0 + 1]
+    return (g00 * (1 - tx) + g01 * tx) * (1 - ty) + (g10 * (1 - tx) + g11 * tx) * ty
+
+
+def make_klt_pair(config_id=2, seed=0, n_points=2000):
+    """Two grey frames for the KLT stage (Tracker::track_features, src/Tracker.cpp:90-134) with a known motion.
+    cfg 2: 1920x1080, cfg 1: 640x480.  Frame 1 is multi-scale value noise (periods 3 .. 48 px) over a flat rectangle;
+    frame 2 is frame 1 warped by q = c + s R(theta) (p - c) + t (sub-pixel translation, a slight rotation and scale)
+    with an occluding patch of independent texture pasted in.  Points, [n][2] f32, with `label`:
+      0 textured (high gradient, away from the borders), 1 flat (minEig failures), 2 leaving the image (their motion
+      target lies >= 3 px outside frame 2), 3 inside the occluded patch (forward-backward failures).
+    `mask` is the static mask with a zeroed bottom band (the car's hood); `truth` = the motion target of every point;
+    `bgr1` / `bgr2` are BGR frames whose grey conversion (BT.601, 8-bit) is `img1` / `img2`'s content source."""
+    cfg = pair_config(config_id)
+    W, H = cfg["width"], cfg["height"]
+    rng = rng_for(config_id, 40 + int(seed))
+    scales, amps = (3, 6, 12, 24, 48), (10.0, 18.0, 26.0, 30.0, 34.0)
+    grids = [rng.normal(0, 1, (H // s + 8, W // s + 8)) for s in scales]
+    occ_grid = rng.normal(0, 1, (H // 4 + 8, W // 4 + 8))
+    flat = (int(0.10 * W), int(0.15 * H), int(0.10 * W) + max(W // 10, 90), int(0.15 * H) + max(H // 8, 70))   # x0 y0 x1 y1
+    occ = (int(0.62 * W), int(0.30 * H), int(0.62 * W) + max(W // 8, 110), int(0.30 * H) + max(W // 8, 110))
+    c = np.array([W / 2.0, H / 2.0])
+    theta, s, t = np.deg2rad(0.25 + 0.1 * rng.uniform()), 1.0 + 0.003 * (1 + rng.uniform()), rng.uniform(1.2, 2.4, 2)
+    R = np.array([[np.cos(theta), -np.sin(theta)], [np.sin(theta), np.cos(theta)]])
+
+    def tex(x, y, chan=0):
+        v = 128.0 + sum(a * _value_noise(g, x + 4 * sc + 7 * chan, y + 4 * sc + 3 * chan, sc)
+                        for g, a, sc in zip(grids, amps, scales))
+        inflat = (x >= flat[0] - 0.5) & (x < flat[2] - 0.5) & (y >= flat[1] - 0.5) & (y < flat[3] - 0.5)
+        return np.where(inflat, 96.0, v)
+
+    def warp_inv(x, y):      # frame-2 pixel -> frame-1 position
+        q = np.stack([x - c[0] - t[0], y - c[1] - t[1]], -1) @ R / s     # R^T (q - c - t) / s, row vectors
+        return q[..., 0] + c[0], q[..., 1] + c[1]
+
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+    f1 = tex(xx, yy)
+    u, v = warp_inv(xx, yy)
+    f2 = tex(u, v)
+    inocc = (xx >= occ[0]) & (xx < occ[2]) & (yy >= occ[1]) & (yy < occ[3])
+    f2 = np.where(inocc, 128.0 + 45.0 * _value_noise(occ_grid, xx, yy, 4), f2)
+    q8 = lambda f: np.clip(np.rint(f), 0, 255).astype(np.uint8)      # noqa: E731
+    img1, img2 = q8(f1), q8(f2)
+
+    # points: textured ones at the strongest gradient cells of a coarse grid, then the special sets
+    gy_, gx_ = np.gradient(f1)
+    mag = np.hypot(gx_, gy_)
+    cell = 12
+    n_flat, n_leave, n_occ = 60, 40, 80
+    n_tex = n_points - n_flat - n_leave - n_occ
+    bx, by = 30, 30
+    cand = []
+    for y0 in range(by, H - by - cell, cell):
+        for x0 in range(bx, W - bx - cell, cell):
+            blk = mag[y0:y0 + cell, x0:x0 + cell]
+            k = int(np.argmax(blk))
+            cand.append((blk.flat[k], x0 + k % cell, y0 + k // cell))
+    cand = np.array(cand)
+    px, py = cand[:, 1], cand[:, 2]
+    far = lambda r, m: (px < r[0] - m) | (px >= r[2] + m) | (py < r[1] - m) | (py >= r[3] + m)     # noqa: E731
+    cand = cand[far(flat, 24) & far(occ, 24)]
+    cand = cand[np.argsort(-cand[:, 0], kind="stable")][:n_tex]
+    tex_pts = cand[:, 1:3] + rng.uniform(-0.5, 0.5, (len(cand), 2))
+    flat_pts = np.stack([rng.uniform(flat[0] + 16, flat[2] - 16, n_flat), rng.uniform(flat[1] + 16, flat[3] - 16, n_flat)], 1)
+    occ_pts = np.stack([rng.uniform(occ[0] + 32, occ[2] - 32, n_occ), rng.uniform(occ[1] + 32, occ[3] - 32, n_occ)], 1)
+    # leaving: the motion target lies 3 .. 12 px beyond the right / bottom border of frame 2
+    leave = []
+    while len(leave) < n_leave:
+        side = len(leave) % 2
+        p = np.array([W - 1.0 - rng.uniform(0, 3), rng.uniform(40, H - 40)]) if side == 0 else \
+            np.array([rng.uniform(40, W - 40), H - 1.0 - rng.uniform(0, 3)])
+        q = c + s * R @ (p - c) + t
+        if (q[0] >= W + 2.5) or (q[1] >= H + 2.5):
+            leave.append(p)
+        else:
+            p[side] += 1.0
+            p[side] = min(p[side], (W, H)[side] - 0.01)
+            q = c + s * R @ (p - c) + t
+            if (q[0] >= W + 2.5) or (q[1] >= H + 2.5):
+                leave.append(p)
+    leave_pts = np.array(leave)
+    pts = np.concatenate([tex_pts, flat_pts, leave_pts, occ_pts])
+    label = np.concatenate([np.zeros(len(tex_pts)), np.ones(n_flat), np.full(n_leave, 2), np.full(n_occ, 3)]).astype(np.int8)
+    order = rng.permutation(len(pts))
+    pts, label = pts[order].astype(np.float32), label[order]
+    truth = (pts.astype(np.float64) - c) @ (s * R).T + c + t
+    mask = np.full((H, W), 255, np.uint8)
+    mask[int(0.85 * H):] = 0
+    # BGR frames: per-channel offsets around the grey content (their BT.601 grey is what the tracker sees)
+    def bgr(img):
+        g = img.astype(np.int64)
+        b = np.clip(g + 20, 0, 255); r = np.clip(g - 15, 0, 255)
+        return np.ascontiguousarray(np.stack([b, np.clip(g, 0, 255), r], -1).astype(np.uint8))
+    return dict(img1=img1, img2=img2, bgr1=bgr(img1), bgr2=bgr(img2), pts=pts, label=label, truth=truth, mask=mask,
+                width=W, height=H, motion=dict(theta=theta, scale=s, t=t, centre=c), flat=flat, occluder=occ)

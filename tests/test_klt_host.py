@@ -1,0 +1,63 @@
+"""slam::Session::track_features (racing-slam_amd/host/slam_host.cpp) — the C++ host mirror of Tracker::track_features
+(reference src/Tracker.cpp:90-131) — built against librsgpu and checked against the restatement tests/klt_ref.py."""
+import importlib
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import klt_ref as K
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "tests", "host_cpp", "test_klt_host.bin")
+
+
+def build_klt_host(rs):
+    rs.load()
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    srcs = [os.path.join(ROOT, "tests", "host_cpp", "test_klt_host.cpp"), os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.cpp")]
+    deps = srcs + [os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.h"), os.path.join(ROOT, "include", "rsgpu.h"),
+                   os.path.join(ROOT, "racing-slam_amd", "librsgpu.so")]
+    if os.path.exists(BIN) and all(os.path.getmtime(d) <= os.path.getmtime(BIN) for d in deps):
+        return BIN
+    subprocess.check_call([hipcc, "-O2", "-std=c++17", "-Wall", "-o", BIN] + srcs + [
+        "-L" + os.path.join(ROOT, "racing-slam_amd"), "-lrsgpu", "-Wl,-rpath," + os.path.join(ROOT, "racing-slam_amd"), "-lm"])
+    return BIN
+
+
+def test_klt_host_mirror_compiles(rs):
+    assert os.path.exists(build_klt_host(rs))
+
+
+def _read(path):
+    lines = open(path).read().split("\n")
+    m = int(lines[0])
+    rows = [ln.split() for ln in lines[1:1 + m]]
+    idx = np.array([int(r[0]) for r in rows], np.int32)
+    pts = np.array([[int(r[1], 16), int(r[2], 16)] for r in rows], np.uint32).reshape(-1, 2).view(np.float32)
+    return idx, pts
+
+
+@pytest.mark.gpu
+def test_session_track_features_matches_the_restatement(rs, tmp_path):
+    exe = build_klt_host(rs)
+    synth = importlib.import_module("racing-slam_amd").synth
+    d = synth.make_klt_pair(1)
+    W, H, n = d["width"], d["height"], len(d["pts"])
+    (tmp_path / "meta.txt").write_text(f"{W} {H} {n}\n")
+    for name, arr in [("img1.u8", d["img1"]), ("img2.u8", d["img2"]), ("img3.u8", d["img1"]), ("bgr2.u8", d["bgr2"]),
+                      ("mask.u8", d["mask"]), ("pts.f32", d["pts"])]:
+        np.ascontiguousarray(arr).tofile(str(tmp_path / name))
+    r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    P1, P2 = K.build_pyramid(d["img1"]), K.build_pyramid(d["img2"])
+    Pb = K.build_pyramid(d["bgr2"])
+    want = [K.track_features(P1, P2, d["pts"], d["mask"]), K.track_features(P2, P1, d["pts"], d["mask"]),
+            K.track_features(P1, Pb, d["pts"])]
+    for call, ref in enumerate(want):
+        idx, pts = _read(str(tmp_path / f"out_{call}.txt"))
+        assert np.array_equal(idx, ref["index"]), call
+        assert np.array_equal(pts.view(np.uint32), ref["pts"].view(np.uint32)), call
+    assert min(len(w["index"]) for w in want) > 0.6 * n
