@@ -747,6 +747,45 @@ int rs_klt_track(rs_context* ctx, const rs_image* from, const rs_image* to, cons
 int rs_track_features(rs_context* ctx, const rs_image* prev, const rs_image* next, const float* d_prev_pts, int n,
                       const uint8_t* d_mask, float fb_max, int32_t* d_kept_index, float* d_kept_pt, int32_t* d_count);
 
+/* ------------------------------------------------- GFTT: feature replenishment */
+
+/* The replenishment half of Tracker::track_features (src/Tracker.cpp:127-146) with the ORB extractor
+ * (features/OrbFeatureExtractor.cpp:5-27: cv::GFTTDetector::create(3000, 0.005, 5), then cv::ORB::compute's border
+ * filter; Initialization.cpp:47 and :105 call the same detector with the static mask alone), on level 0 of an rs_image.
+ * The specification is cv::goodFeaturesToTrack(blockSize 3, gradientSize 3, useHarris false) as restated in
+ * tests/gftt_ref.py, with one deliberate difference: the structure-tensor sums are exact integers (OpenCV: f32 sums of
+ * dx, dy scaled by 1 / 3060).  ORB description is NOT done here: descriptors stay with the caller's extractor.
+ *
+ * rs_detector holds the scratch of one image size (allocated once; no allocation per call).  Envelope: width, height
+ * 1 .. 4096 (an rs_image of the same size), max_corners 1 .. 8192, block_size = gradient_size = 3.  Outside it:
+ * RS_ERR_UNSUPPORTED. */
+typedef struct rs_detector rs_detector;
+int rs_detector_create(rs_context* ctx, int width, int height, int max_corners, int block_size, int gradient_size,
+                       rs_detector** out_det);
+int rs_detector_destroy(rs_detector* det);
+/* :127-146 in one call on the context stream, with no host synchronisation:
+ *   replenish mask  d_mask [height][width] u8 (the static mask; NULL = all set) with cv::circle(.., cvRound(pt),
+ *                   exclude_radius, 0, FILLED) (:131) at each of the d_exclude_count[0] points d_exclude_pt [][2]; both
+ *                   are DEVICE pointers, exactly rs_track_features' d_kept_pt / d_count, and the count is read on the
+ *                   device; both NULL = nothing excluded.
+ *   detect          goodFeaturesToTrack(level 0, max_corners, quality, min_distance, replenish mask) (:138), then
+ *                   runByImageBorder(border) (cv::ORB::compute: 31), order kept.
+ *   budget          :140-146: max_total < 0 = no budget (Initialization), else max(0, max_total - d_exclude_count[0]).
+ * Outputs (device): d_pt [max_corners][2] and d_response [max_corners] (the min-eigenvalue, KeyPoint::response) of the
+ * detected corners strongest first; d_counts[0] = corners detected after the border filter (what the reference logs as
+ * "replenished"), d_counts[1] = how many of them the budget appends (a prefix of the list).
+ * Envelope: max_corners 1 .. the detector's, quality in (0, 1], min_distance 0 .. 16 (< 1: no distance filter),
+ * exclude_radius 0 .. 16, border >= 0; up to 8192 excluded points are read. */
+int rs_detect_features(rs_context* ctx, rs_detector* det, const rs_image* img, const uint8_t* d_mask, const float* d_exclude_pt,
+                       const int32_t* d_exclude_count, int exclude_radius, int max_corners, double quality, double min_distance,
+                       int border, int max_total, float* d_pt, float* d_response, int32_t* d_counts);
+/* Diagnostic: cornerMinEigenVal(level 0, 3, 3) as restated (before the threshold), d_eig [height][width] f32 (device). */
+int rs_corner_response(rs_context* ctx, rs_detector* det, const rs_image* img, float* d_eig);
+/* Diagnostic of the last rs_detect_features on `det` (synchronises the stream): h_stats[5] = candidates, accepted by
+ * the distance filter (uncapped), selection rounds used (0 without a filter), rounds run by the single-workgroup
+ * finisher (0 when the fixed round launches sufficed), corners kept by the cap. */
+int rs_detector_stats(rs_context* ctx, const rs_detector* det, int32_t* h_stats);
+
 /* ------------------------------------------------------------- multi-GPU */
 
 #define RS_COMM_ID_BYTES 128

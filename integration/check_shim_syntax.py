@@ -82,7 +82,7 @@ void Mapper::cull_points(FrameDiagnostics& diagnostics, KeyFrame& key_frame)
 # Tracker_track_features.inc spliced into a skeleton of Tracker::track_features (kept head :90-105 reduced to what the
 # block reads).  The block uses a few OpenCV names the Mapper harness does not need (cv::Point, cv::circle, cvRound,
 # Mat::push_back); the check compiles against a copy of tests/shim_stubs/ in a temporary directory whose core.hpp adds
-# their declarations (the stubs themselves stay untouched).
+# their declarations (the stubs themselves stay untouched).  The Tracker harnesses share that copy.
 TRACKER_HARNESS = r"""
 #include "Tracker.h"
 #include "Frame.h"
@@ -116,6 +116,62 @@ void circle(Mat& img, Point center, int radius, double color, int thickness);
 int cvRound(float value);
 """
 
+# Tracker_track_and_replenish.inc spliced into a skeleton of Tracker::track_features (kept head :90-105, kept tail
+# :148-153 reduced to what it reads).  Besides the Tracker block's names it needs the ones of the original lines it
+# repeats (cv::calcOpticalFlowPyrLK, cv::norm, ...), Mat::zeros, and what features/OrbFeatureExtractor.h declares.
+REPLENISH_HARNESS = r"""
+#include "Tracker.h"
+#include "Frame.h"
+#include "features/OrbFeatureExtractor.h"
+#include "rs_shim_common.h"
+namespace slam {
+namespace {
+constexpr int KLT_WINDOW = 21;
+constexpr int KLT_PYRAMID_LEVELS = 4;
+constexpr float KLT_MAX_FORWARD_BACKWARD_ERROR = 1.0F;
+constexpr int KLT_REPLENISH_RADIUS = 5;
+constexpr size_t MAX_TRACKED_FEATURES = 2000;
+}
+std::pair<ExtractedFeatures, std::vector<FeatureMatch>> Tracker::track_features(const cv::Mat& image)
+{
+    cv::Mat prev_gray = m_last_frame->image();
+    cv::Mat next_gray = image;
+    const auto& prev_features = m_last_frame->features();
+    std::vector<cv::Point2f> prev_points;
+    for (const auto& keypoint : prev_features.keypoints) prev_points.push_back(keypoint.pt);
+    std::vector<cv::Point2f> next_points;
+    std::vector<cv::Point2f> back_points;
+    std::vector<uchar> forward_ok;
+    std::vector<uchar> backward_ok;
+    auto window = cv::Size(KLT_WINDOW, KLT_WINDOW);
+#include "Tracker_track_and_replenish.inc"
+    features.descriptors = m_feature_extractor.refresh_descriptors(image, features);
+    (void)new_features.keypoints.size();
+    return {std::move(features), std::move(matches)};
+}
+}  // namespace slam
+"""
+REPLENISH_STUB_EXTRA = """
+    static Mat zeros(int rows, int cols, int type);
+    template <typename T, typename P> const T& at(const P& point) const;
+"""
+REPLENISH_STUB_FREE = """
+#include <memory>
+typedef unsigned char uchar;
+namespace cv {
+struct Size { int width, height; Size(int width, int height); };
+struct NoArray {};
+NoArray noArray();
+template <typename... Args> void calcOpticalFlowPyrLK(const Args&... args);
+Point2f operator-(const Point2f& a, const Point2f& b);
+double norm(const Point2f& v);
+template <typename T> using Ptr = std::shared_ptr<T>;
+class Feature2D { public: virtual ~Feature2D(); };
+class GFTTDetector : public Feature2D { public: static Ptr<GFTTDetector> create(int maxCorners, double qualityLevel, double minDistance); };
+class ORB : public Feature2D { public: static Ptr<ORB> create(); };
+}  // namespace cv
+"""
+
 
 def tracker_stubs(dst):
     """tests/shim_stubs/ copied to dst with the declarations the Tracker block needs added to opencv2/core.hpp"""
@@ -124,7 +180,7 @@ def tracker_stubs(dst):
     core = os.path.join(dst, "opencv2", "core.hpp")
     text = open(core).read()
     head, tail = text.split("    Mat clone() const;\n", 1)
-    text = head + "    Mat clone() const;\n" + TRACKER_STUB_EXTRA + tail + TRACKER_STUB_FREE
+    text = head + "    Mat clone() const;\n" + TRACKER_STUB_EXTRA + REPLENISH_STUB_EXTRA + tail + TRACKER_STUB_FREE + REPLENISH_STUB_FREE
     open(core, "w").write(text)
     return dst
 
@@ -155,6 +211,14 @@ def main(argv):
         if r.returncode:
             print(r.stderr[-4000:])
             failed.append("Tracker .inc harness")
+        replenish = os.path.join(d, "replenish_harness.cpp")
+        with open(replenish, "w") as fh:
+            fh.write(REPLENISH_HARNESS)
+        r = subprocess.run([cxx] + fl + [replenish], capture_output=True, text=True)
+        print("%-22s %s" % ("Replenish .inc harness", "ok" if r.returncode == 0 else "FAILED"))
+        if r.returncode:
+            print(r.stderr[-4000:])
+            failed.append("Replenish .inc harness")
     sys.exit(1 if failed else 0)
 
 

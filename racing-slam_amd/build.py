@@ -24,6 +24,7 @@ SOURCES = [
     ("reproj_match.hip", ["-ffp-contract=off"]),
     ("tracks.hip", ["-ffp-contract=off"]),
     ("klt.hip", ["-ffp-contract=off"]),
+    ("gftt.hip", ["-ffp-contract=off"]),
     ("ba.hip", ["-munsafe-fp-atomics"]),
     ("ba_solve.hip", ["-munsafe-fp-atomics"]),
     ("ba_solve_big.hip", ["-munsafe-fp-atomics"]),

@@ -18,10 +18,8 @@
 // launch of rs_track_features runs the backward pass in the same wave right after the forward pass, then the
 // forward-backward check, the rounding and the mask test; an ordered compaction (the k4_compact pattern) follows.
 #include "common.h"
+#include "klt.h"
 
-#define KLT_MAX_LEVELS 7
-#define KLT_MAX_DIM 4096
-#define KLT_MAX_POINTS 8192
 #define KLT_WAVES 4                 // points (waves) per workgroup
 
 #ifdef RS_KLT_DEBUG
@@ -29,26 +27,6 @@
 #else
 #define KLT_ASSERT(c) ((void)0)
 #endif
-
-struct KltLevel {
-    int w, h, pitch, rows;          // interior size, padded pitch (elements), padded rows
-    uint8_t* img;                   // padded base (pixel (-pad, -pad))
-    short2* der;                    // padded base
-};
-
-struct KltPyr {
-    int levels, pad;
-    KltLevel lv[KLT_MAX_LEVELS];
-};
-
-struct rs_image {
-    rs_context* ctx = nullptr;
-    int width = 0, height = 0, max_level = 0, win = 0;
-    KltPyr pyr{};
-    void* d_buf = nullptr;          // every level, one allocation
-    uint8_t* d_stage = nullptr;     // raw upload of a host frame (width * height * 3 bytes)
-    bool valid = false;             // a frame has been uploaded
-};
 
 // Highest level buildOpticalFlowPyramid builds: level l + 1 exists only if its size exceeds `win` both ways.
 static int klt_num_levels(int w, int h, int win, int max_level)

@@ -156,6 +156,8 @@ Session::Session()
 Session::~Session()
 {
     for (rs_image* p : m_pyr) rs_image_destroy(p);
+    rs_image_destroy(m_det_img);
+    rs_detector_destroy(m_det);
     rs_context_destroy(m_ctx);
 }
 Session& Session::get()
@@ -735,6 +737,67 @@ std::pair<ExtractedFeatures, std::vector<FeatureMatch>> Session::track_features(
                                         prev_features.descriptors.begin() + (i + 1) * RS_DESC_BYTES);
     }
     return {std::move(features), std::move(matches)};
+}
+
+// ------------------------------------------------------------------------ Tracker::track_features (src/Tracker.cpp:127-146)
+int Session::replenish_features(const Image& next, const Image& static_mask, ExtractedFeatures& features, int max_total,
+                                std::vector<float>* responses)
+{
+    constexpr int KLT_REPLENISH_RADIUS = 5;                     // src/Tracker.cpp:20
+    constexpr int GFTT_MAX_CORNERS = 3000, ORB_EDGE = 31;       // cv::GFTTDetector::create(3000, 0.005, 5), ORB's border
+    constexpr double GFTT_QUALITY = 0.005, GFTT_MIN_DISTANCE = 5.0;
+    const int W = next.width, H = next.height;
+    if (next.pixels.size() < (size_t)W * H * next.channels ||
+        (!static_mask.pixels.empty() && (static_mask.width != W || static_mask.height != H))) {
+        std::printf("replenish_features: frame / mask differ in size\n");
+        return -1;
+    }
+    if (m_det_w != W || m_det_h != H) {
+        rs_detector_destroy(m_det);
+        rs_image_destroy(m_det_img);
+        m_det = nullptr;
+        m_det_img = nullptr;
+        m_det_w = m_det_h = 0;
+        if (!rs_ok(rs_detector_create(m_ctx, W, H, GFTT_MAX_CORNERS, 3, 3, &m_det), "rs_detector_create") ||
+            !rs_ok(rs_image_create(m_ctx, W, H, 0, 5, &m_det_img), "rs_image_create"))
+            return -1;
+        m_det_w = W;
+        m_det_h = H;
+    }
+    const rs_image* img = m_det_img;
+    if (m_next_image == &next && m_next_data == next.pixels.data() && m_pyr_w == W && m_pyr_h == H) {
+        img = m_pyr[m_next];                                    // the frame track_features just uploaded
+    } else if (!rs_ok(rs_image_upload(m_ctx, m_det_img, next.pixels.data(), W * next.channels, next.channels), "rs_image_upload")) {
+        return -1;
+    }
+    const size_t n_ex = features.keypoints.size();
+    std::vector<float> ex(2 * std::max<size_t>(n_ex, 1));
+    for (size_t i = 0; i < n_ex; i++) {
+        ex[2 * i] = features.keypoints[i].pt.x;
+        ex[2 * i + 1] = features.keypoints[i].pt.y;
+    }
+    StageScope scope;
+    DevBuf<float> d_ex(ex), d_pt(2 * GFTT_MAX_CORNERS), d_resp(GFTT_MAX_CORNERS);
+    DevBuf<int32_t> d_ex_count(std::vector<int32_t>{(int32_t)n_ex}), d_counts(2);
+    std::unique_ptr<DevBuf<uint8_t>> d_mask;
+    if (!static_mask.pixels.empty()) d_mask = std::make_unique<DevBuf<uint8_t>>(static_mask.pixels);
+    if (!rs_ok(rs_detect_features(m_ctx, m_det, img, d_mask ? d_mask->get() : nullptr, d_ex.get(), d_ex_count.get(),
+                                  KLT_REPLENISH_RADIUS, GFTT_MAX_CORNERS, GFTT_QUALITY, GFTT_MIN_DISTANCE, ORB_EDGE, max_total,
+                                  d_pt.get(), d_resp.get(), d_counts.get()), "rs_detect_features"))
+        return -1;
+    const auto counts = d_counts.fetch(2);
+    const auto pt = d_pt.fetch(2 * GFTT_MAX_CORNERS);
+    const auto resp = d_resp.fetch(GFTT_MAX_CORNERS);
+    stage_sync();
+    const bool with_desc = features.descriptors.size() == n_ex * RS_DESC_BYTES;
+    for (int k = 0; k < counts[1]; k++) {                       // :140-146
+        KeyPoint kp;
+        kp.pt = Vec2f{pt[2 * (size_t)k], pt[2 * (size_t)k + 1]};
+        features.keypoints.push_back(kp);
+        if (with_desc) features.descriptors.insert(features.descriptors.end(), RS_DESC_BYTES, (uint8_t)0);
+        if (responses) responses->push_back(resp[(size_t)k]);
+    }
+    return counts[0];
 }
 
 }  // namespace slam

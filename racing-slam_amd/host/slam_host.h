@@ -234,6 +234,18 @@ class Session {
     std::pair<ExtractedFeatures, std::vector<FeatureMatch>> track_features(const Image& prev, const Image& next,
                                                                            const ExtractedFeatures& prev_features,
                                                                            const Image& mask);
+    // Tracker::track_features' replenishment (src/Tracker.cpp:127-146) with the ORB extractor's detector
+    // (GFTTDetector(3000, 0.005, 5) + ORB's 31-px border filter, features/OrbFeatureExtractor.cpp:5-27), as ONE
+    // rs_detect_features call: the static mask with a filled circle of radius 5 at every keypoint already in `features`,
+    // the corners strongest first, and the first max(0, max_total - features.keypoints.size()) of them appended to
+    // `features` (max_total < 0: all, the Initialization.cpp:47 / :105 case).  Appended keypoints get zero descriptor
+    // rows (when `features` carries rows): the caller's refresh_descriptors (:150) describes every keypoint.  When
+    // `next` is the Image passed as `next` to the last track_features call (same object, same buffer, unchanged), its
+    // device pyramid is reused and nothing is uploaded.  `static_mask` with no pixels = none; `responses`, if given,
+    // receives the appended corners' min-eigenvalues.  Returns the number detected (the reference's "replenished"
+    // count), or -1 on failure.
+    int replenish_features(const Image& next, const Image& static_mask, ExtractedFeatures& features, int max_total,
+                           std::vector<float>* responses = nullptr);
 
   private:
     Session();
@@ -242,6 +254,9 @@ class Session {
     int m_next = 1, m_pyr_w = 0, m_pyr_h = 0;
     const Image* m_next_image = nullptr;
     const uint8_t* m_next_data = nullptr;
+    rs_detector* m_det = nullptr;               // replenish_features: detector scratch and a pyramid of its own
+    rs_image* m_det_img = nullptr;              // (used when the frame is not the last tracked one)
+    int m_det_w = 0, m_det_h = 0;
 };
 
 }  // namespace slam

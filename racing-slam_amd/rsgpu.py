@@ -23,6 +23,7 @@ EXPORTS = [
     "rs_bundle_adjust", "rs_bundle_adjust_batch", "rs_ba_get_trace", "rs_ba_get_stats", "rs_ba_get_cameras", "rs_reanchor_points", "rs_reanchor_points_host_poses", "rs_refine_pose", "rs_bundle_adjust_inertial", "rs_refine_pose_inertial", "rs_pack_pose", "rs_unpack_pose", "rs_pack_poses", "rs_unpack_poses", "rs_build_local_window",
     "rs_image_create", "rs_image_destroy", "rs_image_levels", "rs_image_upload", "rs_image_upload_device", "rs_image_download",
     "rs_klt_track", "rs_track_features",
+    "rs_detector_create", "rs_detector_destroy", "rs_detect_features", "rs_corner_response", "rs_detector_stats",
     "rs_comm_get_unique_id", "rs_comm_init_rank", "rs_comm_destroy", "rs_comm_init_local", "rs_comm_count", "rs_prof_begin", "rs_prof_end", "rs_prof_counters", "rs_prof_empty_launch",
 ]
 
@@ -704,6 +705,32 @@ class Context:
                                                _dp(out["index"]), _dp(out["pts"]), _dp(out["count"])), "rs_track_features")
         return out
 
+    # -- GFTT (Tracker::track_features' replenishment)
+    def detector(self, width, height, max_corners=3000):
+        """rs_detector: the scratch of the corner detector for one image size (allocated once, reused across frames)."""
+        return Detector(self, width, height, max_corners)
+
+    def detect_features(self, det, img, d_mask=None, d_exclude_pt=None, d_exclude_count=None, exclude_radius=5,
+                        max_corners=3000, quality=0.005, min_distance=5.0, border=31, max_total=-1, out=None):
+        """rs_detect_features (src/Tracker.cpp:127-146): dict(pts [max_corners][2] f32, response [max_corners] f32,
+        counts [2] i32 = (detected, appended)), device tensors; the first counts[0] entries are the detected corners."""
+        t = self.torch
+        if out is None:
+            out = dict(pts=self.empty((max_corners, 2), t.float32), response=self.empty((max_corners,), t.float32),
+                       counts=self.empty((2,), t.int32))
+        self._check(self.lib.rs_detect_features(self.h, det.h, img.h, _dp(d_mask), _dp(d_exclude_pt), _dp(d_exclude_count),
+                                                int(exclude_radius), int(max_corners), C.c_double(quality),
+                                                C.c_double(min_distance), int(border), int(max_total), _dp(out["pts"]),
+                                                _dp(out["response"]), _dp(out["counts"])), "rs_detect_features")
+        return out
+
+    def corner_response(self, det, img, out=None):
+        """rs_corner_response: the min-eigenvalue map [height][width] f32 (device) before the threshold."""
+        if out is None:
+            out = self.empty((det.height, det.width), self.torch.float32)
+        self._check(self.lib.rs_corner_response(self.h, det.h, img.h, _dp(out)), "rs_corner_response")
+        return out
+
     def synchronize(self):
         self._check(self.lib.rs_context_synchronize(self.h), "rs_context_synchronize")
 
@@ -746,6 +773,27 @@ class Image:
     def close(self):
         if self.h:
             self.ctx.lib.rs_image_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+class Detector:
+    """rs_detector: the corner detector's device scratch for one image size."""
+
+    def __init__(self, ctx, width, height, max_corners=3000):
+        self.ctx, self.width, self.height, self.max_corners = ctx, int(width), int(height), int(max_corners)
+        self.h = C.c_void_p()
+        ctx._check(ctx.lib.rs_detector_create(ctx.h, self.width, self.height, self.max_corners, 3, 3, C.byref(self.h)),
+                   "rs_detector_create")
+
+    def stats(self):
+        """Diagnostic of the last detect_features: dict(candidates, accepted, rounds, finisher_rounds, capped)."""
+        s = (C.c_int32 * 5)()
+        self.ctx._check(self.ctx.lib.rs_detector_stats(self.ctx.h, self.h, s), "rs_detector_stats")
+        return dict(zip(("candidates", "accepted", "rounds", "finisher_rounds", "capped"), list(s)))
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.rs_detector_destroy(self.h)
             self.h = C.c_void_p()
 
 

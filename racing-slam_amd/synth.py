@@ -514,3 +514,23 @@ def make_klt_pair(config_id=2, seed=0, n_points=2000):
         return np.ascontiguousarray(np.stack([b, np.clip(g, 0, 255), r], -1).astype(np.uint8))
     return dict(img1=img1, img2=img2, bgr1=bgr(img1), bgr2=bgr(img2), pts=pts, label=label, truth=truth, mask=mask,
                 width=W, height=H, motion=dict(theta=theta, scale=s, t=t, centre=c), flat=flat, occluder=occ)
+
+
+def make_corner_scene(width=640, height=480, seed=0, side=16, spacing=48, band=(0.70, 0.80)):
+    """A grey frame with known corners for the corner detector (Tracker::track_features' replenishment, GFTT): bright
+    axis-aligned squares of `side` px on a grid of `spacing` px (each jittered by a few px) over a dark noise floor
+    (0 .. 2 grey levels).  A square covering pixels [x0, x0 + side) x [y0, y0 + side) has its corners at the pixel
+    boundaries (x0 - 0.5, y0 - 0.5) ... (x0 + side - 0.5, y0 + side - 0.5).  `mask` is all-255 except a zeroed
+    horizontal band (rows band[0] .. band[1] of the height).  Returns dict(img, mask, corners [n][2] f64)."""
+    rng = np.random.default_rng(1000 + int(seed))
+    img = 60 + rng.integers(0, 3, (height, width))
+    corners = []
+    for gy in range(spacing // 2, height - side - spacing // 2, spacing):
+        for gx in range(spacing // 2, width - side - spacing // 2, spacing):
+            x0, y0 = gx + int(rng.integers(-4, 5)), gy + int(rng.integers(-4, 5))
+            img[y0:y0 + side, x0:x0 + side] = 190 + int(rng.integers(0, 40))
+            corners += [(x0 - 0.5, y0 - 0.5), (x0 + side - 0.5, y0 - 0.5), (x0 - 0.5, y0 + side - 0.5),
+                        (x0 + side - 0.5, y0 + side - 0.5)]
+    mask = np.full((height, width), 255, np.uint8)
+    mask[int(band[0] * height):int(band[1] * height)] = 0
+    return dict(img=img.astype(np.uint8), mask=mask, corners=np.array(corners), width=width, height=height)

@@ -1,0 +1,163 @@
+"""Pins the CPU restatement of the corner detector (tests/gftt_ref.py: goodFeaturesToTrack + the replenishment around it,
+reference src/Tracker.cpp:127-146) independently of the device: Sobel and the tensor box sum against scipy correlation,
+the min-eigenvalue against a textbook f64 eigen-solver, the round-based greedy against a literal transcription of OpenCV's
+cell-grid walk, the circle loop against the disc, and a synthetic scene with known corners."""
+import importlib
+
+import numpy as np
+import pytest
+from scipy import ndimage
+
+import gftt_ref as G
+
+
+def _synth():
+    return importlib.import_module("racing-slam_amd").synth
+
+
+@pytest.mark.parametrize("shape", [(37, 53), (2, 9), (64, 3), (120, 160)])
+def test_sobel_and_box_sum_against_scipy(shape):
+    rng = np.random.default_rng(shape[0] * 100 + shape[1])
+    img = rng.integers(0, 256, shape, dtype=np.uint8)
+    dx, dy = G.sobel(img)
+    f = img.astype(np.int64)
+    kx = np.array([[-1, 0, 1], [-2, 0, 2], [-1, 0, 1]])
+    assert np.array_equal(dx, ndimage.correlate(f, kx, mode="mirror"))
+    assert np.array_equal(dy, ndimage.correlate(f, kx.T, mode="mirror"))
+    sxx, sxy, syy = G.tensor(img)
+    box = np.ones((3, 3), np.int64)
+    # the box sum reflects the tensor image, not the source
+    assert np.array_equal(sxx, ndimage.correlate(dx * dx, box, mode="mirror"))
+    assert np.array_equal(sxy, ndimage.correlate(dx * dy, box, mode="mirror"))
+    assert np.array_equal(syy, ndimage.correlate(dy * dy, box, mode="mirror"))
+    assert max(sxx.max(), syy.max(), np.abs(sxy).max()) < 1 << 24
+
+
+def test_tensor_border_rule_at_row_and_column_zero():
+    """Sxy(-1) = Sxy(1): on a diagonal ramp dx * dy changes sign under a reflected SOURCE but not under a reflected
+    tensor image, so the two rules differ at column 0."""
+    y, x = np.mgrid[0:16, 0:16]
+    img = ((x * 7 + y * 3) % 256).astype(np.uint8)
+    dx, dy = G.sobel(img)
+    sxx, sxy, syy = G.tensor(img)
+    p = dx * dy
+    assert sxy[5, 0] == p[4:7, [1, 0, 1]].sum()
+    assert sxy[0, 5] == p[[1, 0, 1], 4:7].sum()
+    # a Sobel on the reflected source would give dx(-1) = -dx(1), dy(-1) = dy(1): the column -1 term changes sign
+    src_rule = p[4:7, 0].sum() + p[4:7, 1].sum() - p[4:7, 1].sum()
+    assert p[4:7, 1].sum() != 0 and src_rule != sxy[5, 0]
+
+
+def test_min_eig_against_eigvalsh():
+    rng = np.random.default_rng(7)
+    img = rng.integers(0, 256, (60, 80), dtype=np.uint8)
+    sxx, sxy, syy = G.tensor(img)
+    eig = G.min_eig(sxx, sxy, syy)
+    assert eig.dtype == np.float32
+    M = np.stack([np.stack([sxx, sxy], -1), np.stack([sxy, syy], -1)], -2).astype(np.float64)
+    lam = np.linalg.eigvalsh(M)[..., 0]                       # the smaller eigenvalue of [[Sxx, Sxy], [Sxy, Syy]]
+    got = eig.astype(np.float64) / float(G.EIG_SCALE)
+    scale = np.maximum(sxx, syy).astype(np.float64)           # f32 cancellation error scales with the larger entry
+    assert np.all(np.abs(got - lam) <= 4e-7 * scale + 1e-3)
+    assert np.array_equal(G.corner_response(img), eig)
+
+
+def test_threshold_and_candidates():
+    rng = np.random.default_rng(3)
+    img = rng.integers(0, 256, (50, 70), dtype=np.uint8)
+    eig = G.corner_response(img)
+    mask = np.full(img.shape, 255, np.uint8)
+    mask[:, :35] = 0
+    thr, offs = G.candidates(eig, mask, 0.01)
+    assert thr == np.float32(float(eig[:, 35:].max()) * 0.01)
+    y, x = np.divmod(offs, 70)
+    assert (x >= 35).all() and (x <= 68).all() and (y >= 1).all() and (y <= 48).all()
+    for o in offs:
+        yy, xx = divmod(int(o), 70)
+        assert eig[yy, xx] > thr and eig[yy, xx] == eig[yy - 1:yy + 2, xx - 1:xx + 2].max()
+    _, none = G.candidates(eig, np.zeros_like(mask), 0.01)
+    assert len(none) == 0
+
+
+def _heavy_ties(rng, h, w, levels):
+    """a response map with few distinct values (many exact ties) and a random candidate set"""
+    eig = rng.integers(1, levels + 1, (h, w)).astype(np.float32)
+    offs = np.flatnonzero(rng.random(h * w) < 0.3)
+    return eig, offs
+
+
+@pytest.mark.parametrize("seed", range(6))
+@pytest.mark.parametrize("md", [0.0, 1.0, 1.5, 3.0, 5.0, 7.3])
+def test_round_greedy_equals_the_cell_grid_walk(seed, md):
+    rng = np.random.default_rng(seed)
+    h, w = 40 + seed * 7, 60 + seed * 5
+    eig, offs = _heavy_ties(rng, h, w, 3 if seed % 2 else 50)
+    for cap in (5, 40, 100000):
+        want = G.select_grid(G.order(eig, offs), w, h, md, cap)
+        got, rounds = G.select_rounds(eig, offs, md, cap)
+        assert np.array_equal(got, want), (md, cap)
+        assert (rounds == 0) == (md < 1)
+
+
+def test_order_breaks_ties_by_the_larger_offset():
+    eig = np.array([[1, 2, 2], [2, 1, 3]], np.float32)
+    offs = np.arange(6)
+    assert G.order(eig, offs).tolist() == [5, 3, 2, 1, 4, 0]
+
+
+def test_circle_radius_5_is_the_81_pixel_disc():
+    m = np.full((21, 21), 255, np.uint8)
+    G.stamp_circles(m, [(10.0, 10.0)], 5)
+    y, x = np.mgrid[0:21, 0:21]
+    disc = (x - 10) ** 2 + (y - 10) ** 2 <= 25
+    assert np.array_equal(m == 0, disc) and disc.sum() == 81
+
+
+@pytest.mark.parametrize("r", [0, 1, 2, 3, 7, 16])
+def test_circle_loop_is_symmetric_and_inside_the_radius(r):
+    hw = G.circle_half_widths(r)
+    assert hw[0] == r and (hw >= 0).all() and all(hw[i] >= hw[i + 1] for i in range(r))
+    assert all(d * d + hw[d] * hw[d] <= r * r + r for d in range(r + 1))
+
+
+def test_circles_clip_at_the_corners_and_round_half_to_even():
+    m = np.full((12, 14), 255, np.uint8)
+    G.stamp_circles(m, [(0.0, 0.0), (13.0, 11.0), (6.5, 5.5)], 5)   # cvRound(6.5) = 6, cvRound(5.5) = 6
+    y, x = np.mgrid[0:12, 0:14]
+    want = ((x ** 2 + y ** 2) <= 25) | (((x - 13) ** 2 + (y - 11) ** 2) <= 25) | (((x - 6) ** 2 + (y - 6) ** 2) <= 25)
+    assert np.array_equal(m == 0, want)
+    n = np.full((12, 14), 255, np.uint8)
+    G.stamp_circles(n, [(np.nan, 3.0), (1e9, 5.0), (-40.0, 5.0)], 5)
+    assert (n == 255).all()
+
+
+def test_detect_features_border_and_budget():
+    rng = np.random.default_rng(11)
+    img = rng.integers(0, 256, (160, 200), dtype=np.uint8)
+    full = G.detect_features(img, max_corners=200, border=0)
+    r = G.detect_features(img, max_corners=200)
+    inside = (full["pts"][:, 0] >= 31) & (full["pts"][:, 0] < 169) & (full["pts"][:, 1] >= 31) & (full["pts"][:, 1] < 129)
+    assert np.array_equal(r["pts"], full["pts"][inside]) and full["detected"] == 200
+    assert r["appended"] == r["detected"] and r["detected"] < 200
+    ex = rng.uniform(0, 200, (30, 2)).astype(np.float32)
+    b = G.detect_features(img, exclude_pts=ex, max_corners=200, max_total=40)
+    assert b["appended"] == min(b["detected"], 10)
+    assert G.detect_features(img, exclude_pts=ex, max_corners=200, max_total=20)["appended"] == 0
+    d = np.sqrt(((b["pts"][:, None, :] - np.rint(ex)[None]) ** 2).sum(-1))
+    assert (d > 5).all()                                   # nothing inside an exclusion disc
+
+
+def test_known_corners_of_the_synthetic_scene():
+    d = _synth().make_corner_scene()
+    r = G.detect_features(d["img"], d["mask"])
+    pts, C = r["pts"].astype(np.float64), d["corners"]
+    dist = np.sqrt(((pts[:, None, :] - C[None]) ** 2).sum(-1))
+    assert (dist.min(1) <= 1.0).all()                      # every corner found is a true corner
+    assert (d["mask"][pts[:, 1].astype(int), pts[:, 0].astype(int)] != 0).all()
+    pd = np.sqrt(((pts[:, None, :] - pts[None]) ** 2).sum(-1)) + np.eye(len(pts)) * 1e9
+    assert pd.min() >= 5.0
+    W, H = d["width"], d["height"]
+    far = (C[:, 0] > 34) & (C[:, 0] < W - 35) & (C[:, 1] > 34) & (C[:, 1] < H - 35)
+    far &= (d["mask"][np.clip(np.rint(C[:, 1] - 2).astype(int), 0, H - 1), np.clip(C[:, 0].astype(int), 0, W - 1)] != 0)
+    far &= (d["mask"][np.clip(np.rint(C[:, 1] + 2).astype(int), 0, H - 1), np.clip(C[:, 0].astype(int), 0, W - 1)] != 0)
+    assert (dist.min(0)[far] <= 1.0).all() and far.sum() > 250   # and every true corner clear of border and band is found
