@@ -104,7 +104,10 @@ int rs_context_fork(rs_context* ctx, rs_context* const* others, int n);
  * "k2_mode": rs_reproj_match — 0 (default) eight lanes per map point where the frame's KD-tree fits in LDS
  * (<= 6144 keypoints), 1 always one lane per point; the outputs are identical.
  * "ba_batch_mode": how rs_bundle_adjust_batch runs its windows — 0 (default) one launch sequence for all of them
- * where the windows allow it, 1 always the lanes. */
+ * where the windows allow it, 1 always the lanes.
+ * "gftt_round_launches": rs_detect_features — how many launches of the parallel minimum-distance round (0 .. 12,
+ * default 12) run before the single-workgroup finisher decides what they left undecided; 0 leaves every decision to
+ * the finisher.  The detected corners do not depend on it, only the launches and rs_detector_stats' round counts do. */
 int rs_context_set_int(rs_context* ctx, const char* name, int value);
 const char* rs_last_error(const rs_context* ctx);
 

@@ -119,6 +119,7 @@ extern "C" int rs_context_fork(rs_context* ctx, rs_context* const* others, int n
 }
 
 #define BA_MAXSETS_KNOB 5        /* = BA_MAXSETS (ba_common.h) */
+#define GFTT_ROUNDS_KNOB 12      /* = GFTT_ROUNDS (gftt.hip) */
 extern "C" int rs_context_set_int(rs_context* ctx, const char* name, int value)
 {
     if (!ctx || !name) return RS_ERR_INVALID;
@@ -170,6 +171,11 @@ extern "C" int rs_context_set_int(rs_context* ctx, const char* name, int value)
     if (strcmp(name, "ba_batch_mode") == 0) {
         if (value < 0 || value > 1) return rs_fail(ctx, RS_ERR_INVALID, "ba_batch_mode must be 0 (grid where possible) or 1 (lanes)");
         ctx->ba_batch_mode = value;
+        return RS_OK;
+    }
+    if (strcmp(name, "gftt_round_launches") == 0) {
+        if (value < 0 || value > GFTT_ROUNDS_KNOB) return rs_fail(ctx, RS_ERR_INVALID, "gftt_round_launches must be 0 .. 12 (default 12)");
+        ctx->gftt_round_launches = value;
         return RS_OK;
     }
     return rs_fail(ctx, RS_ERR_INVALID, "unknown option %s", name);

@@ -17,7 +17,8 @@
 //   gftt_candidates  threshold, 3x3 dilate, mask: a per-pixel state image and an (unordered) list of candidates
 //   gftt_round x R   one round of the parallel greedy walk (gftt_ref.select_rounds); exits at once when a previous
 //                    round left nothing undecided
-//   gftt_finish      one workgroup: further rounds until nothing is undecided (correctness never depends on R)
+//   gftt_finish      one workgroup: further rounds until nothing is undecided (correctness never depends on R; R = 0
+//                    leaves every decision to it)
 //   gftt_output      one workgroup: radix select of the top max_corners accepted keys (eig, offset), LDS bitonic sort,
 //                    border filter, budget, the ordered output
 // A priority key is (ordered eig bits) << 32 | raster offset: larger = earlier in OpenCV's order, ties by the larger
@@ -28,7 +29,8 @@
 #include "common.h"
 #include "klt.h"
 
-#define GFTT_ROUNDS 12              // round launches before the single-workgroup finisher
+#define GFTT_ROUNDS 12              // round launches before the single-workgroup finisher; at most
+                                    // this many, fewer with rs_context_set_int "gftt_round_launches"
 #define GFTT_MAX_CORNERS 8192
 #define GFTT_MAX_EXCLUDE 8192
 #define GFTT_MAX_RADIUS 16
@@ -59,6 +61,7 @@ struct rs_detector {
     unsigned long long* d_work = nullptr;   // radix-select working set (same capacity; ping-pong with d_acc)
     uint32_t* d_ctr = nullptr;
     bool filtered = false;          // the last call ran the distance filter
+    int round_launches = 0;         // gftt_round launches of the last call (0 .. GFTT_ROUNDS)
 };
 
 struct GfttCircle { int r, hw[GFTT_MAX_RADIUS + 1]; };
@@ -309,12 +312,13 @@ __global__ __launch_bounds__(256) void gftt_round(const float* __restrict__ eig,
     }
 }
 
-// one workgroup: rounds until nothing is undecided
+// one workgroup: rounds until nothing is undecided; `launched` = the gftt_round launches before it (0: it decides all).
+// It keys on the last round launched, as gftt_round keys on the one before it.
 __global__ __launch_bounds__(1024) void gftt_finish(const float* __restrict__ eig, uint8_t* state, const int32_t* __restrict__ cand,
-                                                    int W, int H, GfttDist d, unsigned long long* __restrict__ acc,
+                                                    int W, int H, GfttDist d, int launched, unsigned long long* __restrict__ acc,
                                                     uint32_t* __restrict__ ctr)
 {
-    if (ctr[C_ROUND + GFTT_ROUNDS - 1] == 0) return;
+    if (ctr[launched == 0 ? C_CANDIDATES : C_ROUND + launched - 1] == 0) return;     // nothing is undecided
     __shared__ uint32_t s_und;
     const int n = (int)ctr[C_CANDIDATES];
     int rounds = 0;
@@ -558,7 +562,9 @@ extern "C" int rs_detect_features(rs_context* ctx, rs_detector* det, const rs_im
     RS_HIP(ctx, hipSetDevice(ctx->device));
     const int W = det->width, H = det->height, n = W * H;
     const bool filter = min_distance >= 1.0;
+    const int launches = ctx->gftt_round_launches;
     det->filtered = filter;
+    det->round_launches = launches;
     GfttDist dist{0, 0};
     if (filter) {
         dist.d2max = (int)std::ceil(min_distance * min_distance) - 1;            // dx^2 + dy^2 < minDistance^2, integers
@@ -579,11 +585,11 @@ extern "C" int rs_detect_features(rs_context* ctx, rs_detector* det, const rs_im
     }
     if (filter) {
         rs_prof_scope ps(ctx, "GFTT4_rounds");
-        for (int r = 0; r < GFTT_ROUNDS; r++)
+        for (int r = 0; r < launches; r++)
             hipLaunchKernelGGL(gftt_round, dim3(GFTT_ROUND_BLOCKS), dim3(256), 0, ctx->stream, det->d_eig, det->d_state, det->d_cand,
                                W, H, dist, r, det->d_acc, det->d_ctr);
         hipLaunchKernelGGL(gftt_finish, dim3(1), dim3(1024), 0, ctx->stream, det->d_eig, det->d_state, det->d_cand, W, H, dist,
-                           det->d_acc, det->d_ctr);
+                           launches, det->d_acc, det->d_ctr);
     }
     {
         rs_prof_scope ps(ctx, "GFTT5_output");
@@ -604,8 +610,8 @@ extern "C" int rs_detector_stats(rs_context* ctx, const rs_detector* det, int32_
     RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     int rounds = 0;
     if (det->filtered && c[C_CANDIDATES] > 0) {
-        rounds = GFTT_ROUNDS + (int)c[C_FINISH_ROUNDS];
-        for (int r = 0; r < GFTT_ROUNDS; r++)
+        rounds = det->round_launches + (int)c[C_FINISH_ROUNDS];
+        for (int r = 0; r < det->round_launches; r++)
             if (c[C_ROUND + r] == 0) { rounds = r + 1; break; }
     }
     h_stats[0] = (int32_t)c[C_CANDIDATES];

@@ -745,13 +745,22 @@ class Image:
                    "rs_image_create")
 
     def upload(self, frame):
+        """grey [h][w] or BGR [h][w][3] u8, numpy or a device tensor.  Rows may lie further apart than w * channels bytes
+        (a view into a wider buffer, as a cv::Mat ROI hands over): that row stride is passed as the pitch."""
         ch = 1 if frame.ndim == 2 else int(frame.shape[2])
+        inner, row = ((1,) if frame.ndim == 2 else (ch, 1)), int(frame.shape[1]) * ch
         if isinstance(frame, np.ndarray):
-            a = np.ascontiguousarray(frame, np.uint8)
-            self.ctx._check(self.ctx.lib.rs_image_upload(self.ctx.h, self.h, a.ctypes.data_as(C.c_void_p), a.shape[1] * ch, ch),
+            a = frame
+            if a.dtype != np.uint8 or a.strides[1:] != inner or a.strides[0] < row:
+                a = np.ascontiguousarray(a, np.uint8)
+            self.ctx._check(self.ctx.lib.rs_image_upload(self.ctx.h, self.h, a.ctypes.data_as(C.c_void_p), a.strides[0], ch),
                             "rs_image_upload")
         else:
-            self.ctx._check(self.ctx.lib.rs_image_upload_device(self.ctx.h, self.h, _dp(frame), int(frame.shape[1]) * ch, ch),
+            t = frame
+            if tuple(t.stride()[1:]) != inner or t.stride(0) < row:
+                t = t.contiguous()
+            assert t.is_cuda and t.dtype == self.ctx.torch.uint8
+            self.ctx._check(self.ctx.lib.rs_image_upload_device(self.ctx.h, self.h, C.c_void_p(t.data_ptr()), int(t.stride(0)), ch),
                             "rs_image_upload_device")
         return self
 

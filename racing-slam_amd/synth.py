@@ -534,3 +534,22 @@ def make_corner_scene(width=640, height=480, seed=0, side=16, spacing=48, band=(
     mask = np.full((height, width), 255, np.uint8)
     mask[int(band[0] * height):int(band[1] * height)] = 0
     return dict(img=img.astype(np.uint8), mask=mask, corners=np.array(corners), width=width, height=height)
+
+
+def make_dot_chain(n=30, spacing=3, direction=(1, 0), width=320, height=240, base=250, step=2, background=40):
+    """A grey frame that makes the corner detector's minimum-distance walk long (its rounds, csrc/gftt.hip): a chain of
+    `n` bright 2x2 dots on a flat background, dot i at start + i * spacing * direction with grey level base - step * i,
+    so the response falls along the chain.  With spacing 3 (4 along an axis, or 3 diagonally) and min_distance 5,
+    consecutive dots lie closer than the distance and every second dot does not: each dot's fate waits for the one
+    before it, and the synchronous rounds grow with n.  The chain is centred in the frame.  Returns dict(img, dots
+    [n][2] int (x, y) of each dot's top-left pixel)."""
+    dx, dy = direction
+    assert base - step * (n - 1) > background + 16, "contrast must stay well above the background"
+    ext_x, ext_y = (n - 1) * spacing * dx, (n - 1) * spacing * dy
+    x0, y0 = (width - 2 - ext_x) // 2, (height - 2 - ext_y) // 2
+    dots = np.array([(x0 + i * spacing * dx, y0 + i * spacing * dy) for i in range(n)], np.int64)
+    assert (dots.min(0) >= 8).all() and (dots[:, 0].max() < width - 9) and (dots[:, 1].max() < height - 9), "chain leaves the frame"
+    img = np.full((height, width), background, np.uint8)
+    for i, (x, y) in enumerate(dots):
+        img[y:y + 2, x:x + 2] = base - step * i
+    return dict(img=img, dots=dots, width=width, height=height)

@@ -128,6 +128,43 @@ def _in_window(fx, fy, cols, rows, win):
     return (fx >= -win) & (fx < cols) & (fy >= -win) & (fy < rows)
 
 
+def _template(I, prev, win, pad):
+    """The window of level I at the level positions `prev` (f32 [n][2]): -> (ok = the window test, idx = its passing
+    points, and for those the template tI, tX, tY [m][win*win], the f32 matrix A11, A12, A22, its determinant D and
+    minimum eigenvalue mine [m])."""
+    prev = prev - F32((win - 1) * 0.5)
+    fx, fy = np.floor(prev[:, 0]), np.floor(prev[:, 1])
+    ok = _in_window(fx, fy, I["w"], I["h"], win)
+    idx = np.nonzero(ok)[0]
+    ix, iy = fx[idx].astype(np.int64), fy[idx].astype(np.int64)
+    a, b = prev[idx, 0] - fx[idx], prev[idx, 1] - fy[idx]
+    w00, w01, w10, w11 = (w[:, None] for w in _weights(a, b))
+    c = _gather(I["pad"], ix, iy, win, pad)
+    tI = _descale(c[0] * w00 + c[1] * w01 + c[2] * w10 + c[3] * w11, W_BITS - 5)
+    c = _gather(I["dx"], ix, iy, win, pad)
+    tX = _descale(c[0] * w00 + c[1] * w01 + c[2] * w10 + c[3] * w11, W_BITS)
+    c = _gather(I["dy"], ix, iy, win, pad)
+    tY = _descale(c[0] * w00 + c[1] * w01 + c[2] * w10 + c[3] * w11, W_BITS)
+    A11 = (tX * tX).sum(1).astype(np.float32) * FLT_SCALE
+    A12 = (tX * tY).sum(1).astype(np.float32) * FLT_SCALE
+    A22 = (tY * tY).sum(1).astype(np.float32) * FLT_SCALE
+    D = A11 * A22 - A12 * A12
+    d = A11 - A22
+    mine = (A22 + A11 - np.sqrt(d * d + F32(4) * A12 * A12)) / F32(2 * win * win)
+    return ok, idx, tI, tX, tY, A11, A12, A22, D, mine
+
+
+def min_eigenvalues(pyr, pts, win=21, level=0):
+    """The minEig that lk compares with min_eig at `level` for each point of `pts` (level-0 coordinates): f32 [n], NaN
+    where the window test fails there."""
+    pts = np.asarray(pts, np.float32).reshape(-1, 2)
+    pad = pyr[0]["pad"].shape[0] - pyr[0]["h"] >> 1
+    ok, idx, *_, mine = _template(pyr[level], pts * F32(1.0 / (1 << level)), win, pad)
+    out = np.full(len(pts), np.nan, np.float32)
+    out[idx] = mine
+    return out
+
+
 def lk(prev_pyr, next_pyr, pts, guess=None, win=21, max_level=4, max_iter=30, eps=0.01, min_eig=1e-4):
     """calcOpticalFlowPyrLK(prev, next, pts, guess) -> (next_pts [n][2] f32, status [n] u8)."""
     pts = np.asarray(pts, np.float32).reshape(-1, 2)
@@ -141,35 +178,16 @@ def lk(prev_pyr, next_pyr, pts, guess=None, win=21, max_level=4, max_iter=30, ep
     eps2 = float(eps) * float(eps)
     for lvl in range(top, -1, -1):
         I, J = prev_pyr[lvl], next_pyr[lvl]
-        cols, rows = I["w"], I["h"]
         prev = pts * F32(1.0 / (1 << lvl))
         if lvl == top:
             nxt = prev.copy() if guess is None else np.asarray(guess, np.float32).reshape(-1, 2) * F32(1.0 / (1 << lvl))
         else:
             nxt = nxt * F32(2)
-        prev = prev - half
-        fx, fy = np.floor(prev[:, 0]), np.floor(prev[:, 1])
-        ok = _in_window(fx, fy, cols, rows, win)
-        idx = np.nonzero(ok)[0]
+        ok, idx, tI, tX, tY, A11, A12, A22, D, mine = _template(I, prev, win, pad)
         if lvl == 0:
             status[~ok] = 0
         if len(idx) == 0:
             continue
-        ix, iy = fx[idx].astype(np.int64), fy[idx].astype(np.int64)
-        a, b = prev[idx, 0] - fx[idx], prev[idx, 1] - fy[idx]
-        w00, w01, w10, w11 = (w[:, None] for w in _weights(a, b))
-        c = _gather(I["pad"], ix, iy, win, pad)
-        tI = _descale(c[0] * w00 + c[1] * w01 + c[2] * w10 + c[3] * w11, W_BITS - 5)
-        c = _gather(I["dx"], ix, iy, win, pad)
-        tX = _descale(c[0] * w00 + c[1] * w01 + c[2] * w10 + c[3] * w11, W_BITS)
-        c = _gather(I["dy"], ix, iy, win, pad)
-        tY = _descale(c[0] * w00 + c[1] * w01 + c[2] * w10 + c[3] * w11, W_BITS)
-        A11 = (tX * tX).sum(1).astype(np.float32) * FLT_SCALE
-        A12 = (tX * tY).sum(1).astype(np.float32) * FLT_SCALE
-        A22 = (tY * tY).sum(1).astype(np.float32) * FLT_SCALE
-        D = A11 * A22 - A12 * A12
-        d = A11 - A22
-        mine = (A22 + A11 - np.sqrt(d * d + F32(4) * A12 * A12)) / F32(2 * win * win)
         bad = (mine.astype(np.float64) < min_eig) | (D < FLT_EPSILON)
         if lvl == 0:
             status[idx[bad]] = 0

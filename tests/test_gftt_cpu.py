@@ -161,3 +161,21 @@ def test_known_corners_of_the_synthetic_scene():
     far &= (d["mask"][np.clip(np.rint(C[:, 1] - 2).astype(int), 0, H - 1), np.clip(C[:, 0].astype(int), 0, W - 1)] != 0)
     far &= (d["mask"][np.clip(np.rint(C[:, 1] + 2).astype(int), 0, H - 1), np.clip(C[:, 0].astype(int), 0, W - 1)] != 0)
     assert (dist.min(0)[far] <= 1.0).all() and far.sum() > 250   # and every true corner clear of border and band is found
+
+
+CHAINS = [dict(n=30), dict(n=60), dict(n=60, direction=(0, 1)), dict(n=30, spacing=4), dict(n=60, direction=(1, 1)),
+          dict(n=60, direction=(1, -1))]
+
+
+@pytest.mark.parametrize("kw", CHAINS, ids=lambda kw: "-".join(f"{k}{v}" for k, v in kw.items()))
+def test_dot_chains_need_many_synchronous_rounds(kw):
+    """synth.make_dot_chain: the scenes that make the device's finisher work (tests/test_gpu_gftt_envelope.py) need
+    well over the 12 round launches, and the round-based walk still equals the cell-grid walk on them."""
+    d = _synth().make_dot_chain(**kw)
+    img = d["img"]
+    h, w = img.shape
+    eig = G.corner_response(img)
+    _, offs = G.candidates(eig, None, 0.005)
+    acc, rounds = G.select_rounds(eig, offs, 5.0, 3000)
+    assert rounds >= 20 and rounds >= kw["n"] // 2
+    assert np.array_equal(acc, G.select_grid(G.order(eig, offs), w, h, 5.0, 3000))
