@@ -520,6 +520,15 @@ int rs_map_bundle_adjust(rs_context* ctx, rs_map* map, const int32_t* h_kfs, con
                          const float h_intrinsics[4], const rs_ba_options* options, rs_ba_summary* h_summary,
                          float* h_out_poses, int32_t* h_out_points, float* h_out_xyz, int capacity, int* h_n_points);
 
+/* The problem rs_map_bundle_adjust would solve for the same window, built by the same kernels and copied out without
+ * solving: h_points [cap_points] free slots (ascending), h_xyz [cap_points][3] their f64 positions, h_obs_ptr
+ * [cap_points + 1] CSR by point, h_obs_cam [cap_obs] list index of the observing key frame (list order within a point),
+ * h_obs_uv [cap_obs][2] keypoints.  *h_n_points / *h_n_obs = the full sizes; nothing is copied unless both fit.  For
+ * tests and diagnostics: it neither solves nor changes the map. */
+int rs_map_window(rs_context* ctx, rs_map* map, const int32_t* h_kfs, const uint8_t* h_free, int n_kfs,
+                  int32_t* h_points, double* h_xyz, int32_t* h_obs_ptr, int32_t* h_obs_cam, float* h_obs_uv,
+                  int cap_points, int cap_obs, int* h_n_points, int* h_n_obs);
+
 /* Throughput mode: B INDEPENDENT windows (several sessions / maps served by one GPU) in one call.  A local-window
  * solve is a chain of small dependent launches that leaves most of the 256 CUs idle.
  *   grid mode (default)  every kernel of the solve runs ONCE for all windows (grid z = window, per-window arguments in a

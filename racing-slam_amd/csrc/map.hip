@@ -592,25 +592,29 @@ __global__ __launch_bounds__(256) void k_win_writeback(int n_free, const int32_t
     }
 }
 
-extern "C" int rs_map_bundle_adjust(rs_context* ctx, rs_map* m, const int32_t* h_kfs, const uint8_t* h_free, int n_kfs,
-                                    const float h_intrinsics[4], const rs_ba_options* options, rs_ba_summary* h_summary,
-                                    float* h_out_poses, int32_t* h_out_points, float* h_out_xyz, int capacity, int* h_n_points)
+// list index | free << 16 per key frame (-1: not listed), refusing unknown and repeated key frames
+static int window_of_kf(rs_context* ctx, const rs_map* m, const int32_t* h_kfs, const uint8_t* h_free, size_t C, std::vector<int32_t>* win)
 {
-    if (!ctx || !m || m->ctx != ctx || !h_kfs || !h_free || n_kfs < 0 || !h_intrinsics || !h_summary || !h_n_points) return RS_ERR_INVALID;
-    *h_n_points = 0;
-    memset(h_summary, 0, sizeof *h_summary);
-    const size_t C = (size_t)n_kfs, KF = m->kfs.size(), P = m->alive.size();
+    const size_t KF = m->kfs.size();
     if (C > 65535) return rs_fail(ctx, RS_ERR_UNSUPPORTED, "more than 65535 frames in a window");
-    std::vector<int32_t> win(KF ? KF : 1, -1);
+    win->assign(KF ? KF : 1, -1);
     for (size_t c = 0; c < C; c++) {
         if (h_kfs[c] < 0 || h_kfs[c] >= (int)KF) return rs_fail(ctx, RS_ERR_INVALID, "unknown key frame");
-        if (win[(size_t)h_kfs[c]] >= 0) return rs_fail(ctx, RS_ERR_INVALID, "key frame %d listed twice", h_kfs[c]);
-        win[(size_t)h_kfs[c]] = (int32_t)c | (h_free[c] ? 1 << 16 : 0);
+        if ((*win)[(size_t)h_kfs[c]] >= 0) return rs_fail(ctx, RS_ERR_INVALID, "key frame %d listed twice", h_kfs[c]);
+        (*win)[(size_t)h_kfs[c]] = (int32_t)c | (h_free[c] ? 1 << 16 : 0);
     }
-    auto keep_poses = [&]() {
-        if (h_out_poses) for (size_t c = 0; c < C; c++) memcpy(h_out_poses + 16 * c, m->kfs[(size_t)h_kfs[c]].pose, sizeof(float) * 16);
-    };
-    if (P == 0 || C == 0) { h_summary->termination = RS_BA_FAILURE; keep_poses(); return RS_OK; }
+    return RS_OK;
+}
+
+// The window's problem in staging memory (valid until the next rs_stage_begin); Pf == 0 or M == 0: nothing was filled.
+struct MapWindow {
+    size_t Pf = 0, M = 0;
+    double* pts = nullptr; int32_t *ptr = nullptr, *cam = nullptr, *list = nullptr; float* uv = nullptr;
+};
+
+static int map_window_build(rs_context* ctx, rs_map* m, const std::vector<int32_t>& win, size_t C, MapWindow* w)
+{
+    const size_t P = m->alive.size();
     RS_HIP(ctx, hipSetDevice(ctx->device));
     int rc = map_sync_device(m);
     if (rc) return rc;
@@ -632,34 +636,57 @@ extern "C" int rs_map_bundle_adjust(rs_context* ctx, rs_map* m, const int32_t* h
     int32_t tot[2] = {0, 0};
     if ((rc = rs_stage_download(ctx, d_tot, sizeof tot, tot))) return rc;
     if ((rc = rs_stage_sync(ctx))) return rc;
-    const size_t Pf = (size_t)tot[0], M = (size_t)tot[1];
-    if (Pf == 0 || M == 0) { h_summary->termination = RS_BA_FAILURE; keep_poses(); return RS_OK; }
-    std::vector<double> cams(6 * C);
-    for (size_t c = 0; c < C; c++) rs_pack_pose(m->kfs[(size_t)h_kfs[c]].pose, &cams[6 * c]);
-    double *d_cams = nullptr, *d_pts = nullptr;
-    int32_t *d_ptr = nullptr, *d_cam = nullptr, *d_list = nullptr;
-    float *d_uv = nullptr, *d_oxyz = nullptr;
-    if ((rc = rs_stage_upload(ctx, cams.data(), sizeof(double) * 6 * C, (void**)&d_cams))) return rc;
-    if ((rc = rs_stage_alloc(ctx, sizeof(double) * 3 * Pf, (void**)&d_pts))) return rc;
-    if ((rc = rs_stage_alloc(ctx, sizeof(int32_t) * (Pf + 1), (void**)&d_ptr))) return rc;
-    if ((rc = rs_stage_alloc(ctx, sizeof(int32_t) * M, (void**)&d_cam))) return rc;
-    if ((rc = rs_stage_alloc(ctx, sizeof(float) * 2 * M, (void**)&d_uv))) return rc;
-    if ((rc = rs_stage_alloc(ctx, sizeof(int32_t) * Pf, (void**)&d_list))) return rc;
-    if ((rc = rs_stage_alloc(ctx, sizeof(float) * 3 * Pf, (void**)&d_oxyz))) return rc;
+    w->Pf = (size_t)tot[0];
+    w->M = (size_t)tot[1];
+    if (w->Pf == 0 || w->M == 0) return RS_OK;
+    if ((rc = rs_stage_alloc(ctx, sizeof(double) * 3 * w->Pf, (void**)&w->pts))) return rc;
+    if ((rc = rs_stage_alloc(ctx, sizeof(int32_t) * (w->Pf + 1), (void**)&w->ptr))) return rc;
+    if ((rc = rs_stage_alloc(ctx, sizeof(int32_t) * w->M, (void**)&w->cam))) return rc;
+    if ((rc = rs_stage_alloc(ctx, sizeof(float) * 2 * w->M, (void**)&w->uv))) return rc;
+    if ((rc = rs_stage_alloc(ctx, sizeof(int32_t) * w->Pf, (void**)&w->list))) return rc;
     {
         rs_prof_scope ps(ctx, "K9_window_build");
         hipLaunchKernelGGL(k_win_fill, dim3(pb), dim3(256), 0, s, (int)P, (int)C, d_pid, d_off, m->d_obs_ptr, m->d_obs_kf, m->d_obs_desc, d_winkf,
-                           m->d_pos, (const float2*)m->d_kp_pool, d_pts, d_list, d_ptr, d_cam, (float2*)d_uv, (int)Pf, (int)M);
+                           m->d_pos, (const float2*)m->d_kp_pool, w->pts, w->list, w->ptr, w->cam, (float2*)w->uv, (int)w->Pf, (int)w->M);
     }
-    rc = rs_bundle_adjust(ctx, (int)C, (int)Pf, (int)M, d_cams, h_free, d_pts, d_ptr, d_cam, d_uv, h_intrinsics, options, h_summary);
+    return RS_OK;
+}
+
+extern "C" int rs_map_bundle_adjust(rs_context* ctx, rs_map* m, const int32_t* h_kfs, const uint8_t* h_free, int n_kfs,
+                                    const float h_intrinsics[4], const rs_ba_options* options, rs_ba_summary* h_summary,
+                                    float* h_out_poses, int32_t* h_out_points, float* h_out_xyz, int capacity, int* h_n_points)
+{
+    if (!ctx || !m || m->ctx != ctx || !h_kfs || !h_free || n_kfs < 0 || !h_intrinsics || !h_summary || !h_n_points) return RS_ERR_INVALID;
+    *h_n_points = 0;
+    memset(h_summary, 0, sizeof *h_summary);
+    const size_t C = (size_t)n_kfs, P = m->alive.size();
+    std::vector<int32_t> win;
+    int rc = window_of_kf(ctx, m, h_kfs, h_free, C, &win);
+    if (rc) return rc;
+    auto keep_poses = [&]() {
+        if (h_out_poses) for (size_t c = 0; c < C; c++) memcpy(h_out_poses + 16 * c, m->kfs[(size_t)h_kfs[c]].pose, sizeof(float) * 16);
+    };
+    if (P == 0 || C == 0) { h_summary->termination = RS_BA_FAILURE; keep_poses(); return RS_OK; }
+    MapWindow w;
+    if ((rc = map_window_build(ctx, m, win, C, &w))) return rc;
+    const size_t Pf = w.Pf, M = w.M;
+    if (Pf == 0 || M == 0) { h_summary->termination = RS_BA_FAILURE; keep_poses(); return RS_OK; }
+    hipStream_t s = ctx->stream;
+    std::vector<double> cams(6 * C);
+    for (size_t c = 0; c < C; c++) rs_pack_pose(m->kfs[(size_t)h_kfs[c]].pose, &cams[6 * c]);
+    double* d_cams = nullptr;
+    float* d_oxyz = nullptr;
+    if ((rc = rs_stage_upload(ctx, cams.data(), sizeof(double) * 6 * C, (void**)&d_cams))) return rc;
+    if ((rc = rs_stage_alloc(ctx, sizeof(float) * 3 * Pf, (void**)&d_oxyz))) return rc;
+    rc = rs_bundle_adjust(ctx, (int)C, (int)Pf, (int)M, d_cams, h_free, w.pts, w.ptr, w.cam, w.uv, h_intrinsics, options, h_summary);
     if (rc) return rc;
     if (!h_summary->usable) { keep_poses(); return RS_OK; }
     rc = rs_ba_get_cameras(ctx, cams.data(), (int)C);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_win_writeback, dim3((int)((Pf + 255) / 256)), dim3(256), 0, s, (int)Pf, d_list, d_pts, m->d_pos, d_oxyz);
+    hipLaunchKernelGGL(k_win_writeback, dim3((int)((Pf + 255) / 256)), dim3(256), 0, s, (int)Pf, w.list, w.pts, m->d_pos, d_oxyz);
     std::vector<int32_t> list(Pf);
     std::vector<float> xyz(3 * Pf);
-    if ((rc = rs_stage_download(ctx, d_list, sizeof(int32_t) * Pf, list.data()))) return rc;
+    if ((rc = rs_stage_download(ctx, w.list, sizeof(int32_t) * Pf, list.data()))) return rc;
     if ((rc = rs_stage_download(ctx, d_oxyz, sizeof(float) * 3 * Pf, xyz.data()))) return rc;
     if ((rc = rs_stage_sync(ctx))) return rc;
     for (size_t c = 0; c < C; c++) {
@@ -674,6 +701,36 @@ extern "C" int rs_map_bundle_adjust(rs_context* ctx, rs_map* m, const int32_t* h
         memcpy(h_out_xyz, xyz.data(), sizeof(float) * 3 * nout);
     }
     *h_n_points = (int)Pf;
+    return RS_OK;
+}
+
+// The problem rs_map_bundle_adjust would solve for this window, built by the same kernels and copied out unsolved.
+extern "C" int rs_map_window(rs_context* ctx, rs_map* m, const int32_t* h_kfs, const uint8_t* h_free, int n_kfs,
+                             int32_t* h_points, double* h_xyz, int32_t* h_obs_ptr, int32_t* h_obs_cam, float* h_obs_uv,
+                             int cap_points, int cap_obs, int* h_n_points, int* h_n_obs)
+{
+    if (!ctx || !m || m->ctx != ctx || !h_kfs || !h_free || n_kfs < 0 || !h_n_points || !h_n_obs) return RS_ERR_INVALID;
+    *h_n_points = 0;
+    *h_n_obs = 0;
+    const size_t C = (size_t)n_kfs;
+    std::vector<int32_t> win;
+    int rc = window_of_kf(ctx, m, h_kfs, h_free, C, &win);
+    if (rc) return rc;
+    if (m->alive.empty() || C == 0) return RS_OK;
+    MapWindow w;
+    if ((rc = map_window_build(ctx, m, win, C, &w))) return rc;
+    if (w.Pf == 0 || w.M == 0) return RS_OK;
+    if (w.Pf <= (size_t)(cap_points > 0 ? cap_points : 0) && w.M <= (size_t)(cap_obs > 0 ? cap_obs : 0)) {
+        if (!h_points || !h_xyz || !h_obs_ptr || !h_obs_cam || !h_obs_uv) return rs_fail(ctx, RS_ERR_INVALID, "null output");
+        if ((rc = rs_stage_download(ctx, w.list, sizeof(int32_t) * w.Pf, h_points))) return rc;
+        if ((rc = rs_stage_download(ctx, w.pts, sizeof(double) * 3 * w.Pf, h_xyz))) return rc;
+        if ((rc = rs_stage_download(ctx, w.ptr, sizeof(int32_t) * (w.Pf + 1), h_obs_ptr))) return rc;
+        if ((rc = rs_stage_download(ctx, w.cam, sizeof(int32_t) * w.M, h_obs_cam))) return rc;
+        if ((rc = rs_stage_download(ctx, w.uv, sizeof(float) * 2 * w.M, h_obs_uv))) return rc;
+    }
+    if ((rc = rs_stage_sync(ctx))) return rc;
+    *h_n_points = (int)w.Pf;
+    *h_n_obs = (int)w.M;
     return RS_OK;
 }
 

@@ -19,7 +19,7 @@ EXPORTS = [
     "rs_context_synchronize", "rs_context_set_int", "rs_stage_begin", "rs_stage_alloc", "rs_stage_upload", "rs_stage_download", "rs_stage_sync", "rs_last_error", "rs_hamming_knn2", "rs_match_descriptors",
     "rs_kdtree_build", "rs_kdtree_pack", "rs_reproj_match", "rs_reproj_match_sharded", "rs_map_create", "rs_map_destroy", "rs_frame_create", "rs_frame_destroy",
     "rs_map_add_keyframe", "rs_map_set_keyframe_pose", "rs_map_add_point", "rs_map_set_position", "rs_map_remove_point",
-    "rs_map_add_observation", "rs_map_remove_observation", "rs_map_counts", "rs_map_get_positions", "rs_map_match", "rs_map_pose_graph", "rs_pose_graph", "rs_pose_relative", "rs_transform_points", "rs_map_bundle_adjust", "rs_triangulate", "rs_triangulate_host", "rs_triangulate_matches", "rs_triangulate_matches_batch", "rs_triangulate_tracks", "rs_parallax_requirements", "rs_point_errors", "rs_ba_default_options",
+    "rs_map_add_observation", "rs_map_remove_observation", "rs_map_counts", "rs_map_get_positions", "rs_map_match", "rs_map_pose_graph", "rs_pose_graph", "rs_pose_relative", "rs_transform_points", "rs_map_bundle_adjust", "rs_map_window", "rs_triangulate", "rs_triangulate_host", "rs_triangulate_matches", "rs_triangulate_matches_batch", "rs_triangulate_tracks", "rs_parallax_requirements", "rs_point_errors", "rs_ba_default_options",
     "rs_bundle_adjust", "rs_bundle_adjust_batch", "rs_ba_get_trace", "rs_ba_get_stats", "rs_ba_get_cameras", "rs_reanchor_points", "rs_reanchor_points_host_poses", "rs_refine_pose", "rs_bundle_adjust_inertial", "rs_refine_pose_inertial", "rs_pack_pose", "rs_unpack_pose", "rs_pack_poses", "rs_unpack_poses", "rs_build_local_window",
     "rs_image_create", "rs_image_destroy", "rs_image_levels", "rs_image_upload", "rs_image_upload_device", "rs_image_download",
     "rs_klt_track", "rs_track_features",
@@ -903,12 +903,15 @@ class ResidentMap:
                                                    rot.ctypes.data_as(C.c_void_p), C.byref(s)), "rs_map_pose_graph")
         return s.as_dict(), poses[:n].reshape(-1, 4, 4), rot[:n].reshape(-1, 3, 3)
 
-    def bundle_adjust(self, kfs, free, K, options=None):
+    def bundle_adjust(self, kfs, free, K, options=None, capacity=None):
+        """Returns (summary, poses [n][16], free point slots, their positions).  `capacity` is the room given to the
+        library for free points (default: every slot); summary["n_points"] is the full count it reports, the slots and
+        positions returned are the first min(n_points, capacity)."""
         kfs = np.ascontiguousarray(kfs, np.int32)
         free = np.ascontiguousarray(free, np.uint8)
         Kc = (C.c_float * 4)(*[float(v) for v in K])
         s = BaSummary()
-        cap = self.counts()["slots"]
+        cap = self.counts()["slots"] if capacity is None else int(capacity)
         poses = np.zeros((len(kfs), 16), np.float32)
         pts, xyz = np.zeros(max(cap, 1), np.int32), np.zeros((max(cap, 1), 3), np.float32)
         n = C.c_int(0)
@@ -916,4 +919,23 @@ class ResidentMap:
             self.ctx.h, self.h, kfs.ctypes.data_as(C.c_void_p), free.ctypes.data_as(C.c_void_p), len(kfs), Kc,
             None if options is None else C.byref(options), C.byref(s), poses.ctypes.data_as(C.c_void_p),
             pts.ctypes.data_as(C.c_void_p), xyz.ctypes.data_as(C.c_void_p), cap, C.byref(n)), "rs_map_bundle_adjust")
-        return s.as_dict(), poses, pts[:n.value].copy(), xyz[:n.value].copy()
+        k = min(n.value, max(cap, 0))
+        return dict(s.as_dict(), n_points=n.value), poses, pts[:k].copy(), xyz[:k].copy()
+
+    def window(self, kfs, free):
+        """rs_map_window: the problem bundle_adjust would solve, unsolved: dict(points, positions f64, obs_ptr, obs_cam,
+        obs_uv).  Asks once for the sizes, then once more with room for them."""
+        kfs = np.ascontiguousarray(kfs, np.int32)
+        free = np.ascontiguousarray(free, np.uint8)
+        n, m = C.c_int(0), C.c_int(0)
+        cap_p, cap_o = 0, 0
+        while True:
+            pts, xyz = np.zeros(max(cap_p, 1), np.int32), np.zeros((max(cap_p, 1), 3))
+            ptr, cam, uv = np.zeros(cap_p + 1, np.int32), np.zeros(max(cap_o, 1), np.int32), np.zeros((max(cap_o, 1), 2), np.float32)
+            self.ctx._check(self.lib.rs_map_window(
+                self.ctx.h, self.h, kfs.ctypes.data_as(C.c_void_p), free.ctypes.data_as(C.c_void_p), len(kfs),
+                *[a.ctypes.data_as(C.c_void_p) for a in (pts, xyz, ptr, cam, uv)], cap_p, cap_o, C.byref(n), C.byref(m)), "rs_map_window")
+            if n.value <= cap_p and m.value <= cap_o:
+                return dict(points=pts[:n.value].copy(), positions=xyz[:n.value].copy(), obs_ptr=ptr[:n.value + 1].copy(),
+                            obs_cam=cam[:m.value].copy(), obs_uv=uv[:m.value].copy())
+            cap_p, cap_o = n.value, m.value
