@@ -798,6 +798,43 @@ int rs_corner_response(rs_context* ctx, rs_detector* det, const rs_image* img, f
  * finisher (0 when the fixed round launches sufficed), corners kept by the cap. */
 int rs_detector_stats(rs_context* ctx, const rs_detector* det, int32_t* h_stats);
 
+/* ------------------------------------------------- ORB: keypoint description */
+
+/* The description stage of Tracker::track_features: OrbFeatureExtractor::refresh_descriptors
+ * (features/OrbFeatureExtractor.cpp:29-61, called at src/Tracker.cpp:150), cv::ORB::compute with the ORB::create()
+ * defaults (patch 31, WTA_K 2, one level) on keypoints of octave 0 and angle -1, on level 0 of an rs_image; with no
+ * carried rows it is extract_features' compute (OrbFeatureExtractor.cpp:24; Initialization.cpp:47, :105).  The
+ * specification is tests/orb_ref.py: GaussianBlur(7x7, sigma 2, reflect-101) in sepFilter2D's f32 form, the border
+ * filter runByImageBorder(border) with cvRound'ed positions, and the 256 tests of OpenCV's bit_pattern_31_ at
+ * (cvRound(x), cvRound(y)), bit k of byte i = test 8 i + k.  Results are bit-identical to it.  IC-angle orientation and
+ * multi-octave keypoints are not implemented (the reference never uses them).
+ *
+ * rs_describer holds the blurred plane of one image size (allocated once; no allocation per call).  Envelope: width,
+ * height 1 .. 4096 (an rs_image of the same size), max_points 1 .. 8192.  Outside it: RS_ERR_UNSUPPORTED. */
+typedef struct rs_describer rs_describer;
+int rs_describer_create(rs_context* ctx, int width, int height, int max_points, rs_describer** out_desc);
+int rs_describer_destroy(rs_describer* d);
+/* refresh_descriptors over list a followed by list b, in one pass on the context stream with no host synchronisation:
+ *   list a   d_pt_a [][2] f32 and its count d_count_a[0] (DEVICE pointers, exactly rs_track_features' d_kept_pt /
+ *            d_count); point i carries row d_carry_desc[d_carry_index[i]] (rs_track_features' d_kept_index and the
+ *            previous frame's rows, :130), or row i when d_carry_index is NULL; n_carry = rows of d_carry_desc (an
+ *            index outside [0, n_carry) carries zeros); d_carry_desc NULL (n_carry 0) = list a carries zeros.
+ *   list b   d_pt_b [][2] f32 and its count d_count_b[0] (rs_detect_features' d_pt and d_counts + 1: the appended
+ *            corners); they carry zeros (the zero rows of the caller edit, :142).
+ *   Either list may be NULL (points and count together).  Counts are clamped: n_a = clamp(d_count_a[0], 0, max_points),
+ *   n_b = clamp(d_count_b[0], 0, max_points - n_a); the caller's arrays hold at least that many points.
+ * Outputs (device): d_desc [max_points][32] u8: row i < n_a + n_b is the fresh descriptor of point i (a_0 .. a_{n_a-1},
+ * b_0 ..) when border <= cvRound(x) <= W-1-border and likewise for y (cvRound: half to even; non-finite points are
+ * never kept), else the carried row; d_fresh [max_points] u8 (NULL = not written) = 1 for a fresh row; d_n[0] (NULL =
+ * not written) = n_a + n_b.  Rows from n_a + n_b on are not written.  border: 31 in the reference (ORB's
+ * edgeThreshold); envelope border >= 16 (the pattern's 13 px plus the blur's 3: no sample depends on the image
+ * border's rule). */
+int rs_describe_features(rs_context* ctx, rs_describer* d, const rs_image* img, const float* d_pt_a, const int32_t* d_count_a,
+                         const int32_t* d_carry_index, const uint8_t* d_carry_desc, int n_carry, const float* d_pt_b,
+                         const int32_t* d_count_b, int border, uint8_t* d_desc, uint8_t* d_fresh, int32_t* d_n);
+/* Diagnostic: the blurred level 0 the descriptors sample, d_blur [height][width] u8 (device). */
+int rs_orb_blur(rs_context* ctx, rs_describer* d, const rs_image* img, uint8_t* d_blur);
+
 /* ------------------------------------------------------------- multi-GPU */
 
 #define RS_COMM_ID_BYTES 128

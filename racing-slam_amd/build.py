@@ -25,6 +25,7 @@ SOURCES = [
     ("tracks.hip", ["-ffp-contract=off"]),
     ("klt.hip", ["-ffp-contract=off"]),
     ("gftt.hip", ["-ffp-contract=off"]),
+    ("orb.hip", ["-ffp-contract=off"]),
     ("ba.hip", ["-munsafe-fp-atomics"]),
     ("ba_solve.hip", ["-munsafe-fp-atomics"]),
     ("ba_solve_big.hip", ["-munsafe-fp-atomics"]),

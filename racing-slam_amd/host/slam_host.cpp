@@ -158,6 +158,8 @@ Session::~Session()
     for (rs_image* p : m_pyr) rs_image_destroy(p);
     rs_image_destroy(m_det_img);
     rs_detector_destroy(m_det);
+    rs_image_destroy(m_orb_img);
+    rs_describer_destroy(m_orb);
     rs_context_destroy(m_ctx);
 }
 Session& Session::get()
@@ -798,6 +800,60 @@ int Session::replenish_features(const Image& next, const Image& static_mask, Ext
         if (responses) responses->push_back(resp[(size_t)k]);
     }
     return counts[0];
+}
+
+std::vector<uint8_t> Session::refresh_descriptors(const Image& next, const ExtractedFeatures& features,
+                                                  const ExtractedFeatures& prev_features, const std::vector<FeatureMatch>& matches)
+{
+    constexpr int ORB_EDGE = 31, MAX_POINTS = 8192;              // ORB::create()'s edgeThreshold; rs_describer's envelope
+    const size_t n = features.keypoints.size(), m = matches.size();
+    if (n == 0 || features.descriptors.empty()) return features.descriptors;     // :32-34
+    const int W = next.width, H = next.height;
+    if (next.pixels.size() < (size_t)W * H * next.channels || n > (size_t)MAX_POINTS || m > n) {
+        std::printf("refresh_descriptors: bad frame, more than %d keypoints, or more matches than keypoints\n", MAX_POINTS);
+        return {};
+    }
+    if (m_orb_w != W || m_orb_h != H) {
+        rs_describer_destroy(m_orb);
+        rs_image_destroy(m_orb_img);
+        m_orb = nullptr;
+        m_orb_img = nullptr;
+        m_orb_w = m_orb_h = 0;
+        if (!rs_ok(rs_describer_create(m_ctx, W, H, MAX_POINTS, &m_orb), "rs_describer_create") ||
+            !rs_ok(rs_image_create(m_ctx, W, H, 0, 5, &m_orb_img), "rs_image_create"))
+            return {};
+        m_orb_w = W;
+        m_orb_h = H;
+    }
+    const rs_image* img = m_orb_img;
+    if (m_next_image == &next && m_next_data == next.pixels.data() && m_pyr_w == W && m_pyr_h == H) {
+        img = m_pyr[m_next];                                    // the frame track_features just uploaded
+    } else if (!rs_ok(rs_image_upload(m_ctx, m_orb_img, next.pixels.data(), W * next.channels, next.channels), "rs_image_upload")) {
+        return {};
+    }
+    // list a: the tracked keypoints with (previous index) from matches; list b: the appended ones
+    std::vector<float> pa(2 * std::max<size_t>(m, 1)), pb(2 * std::max<size_t>(n - m, 1));
+    std::vector<int32_t> carry_index(std::max<size_t>(m, 1));
+    for (size_t k = 0; k < n; k++) {
+        float* p = k < m ? &pa[2 * k] : &pb[2 * (k - m)];
+        p[0] = features.keypoints[k].pt.x;
+        p[1] = features.keypoints[k].pt.y;
+    }
+    for (size_t k = 0; k < m; k++) carry_index[k] = (int32_t)matches[k].train_index;
+    const size_t n_prev = prev_features.descriptors.size() / RS_DESC_BYTES;
+    StageScope scope;
+    DevBuf<float> d_pa(pa), d_pb(pb);
+    DevBuf<int32_t> d_carry_index(carry_index), d_counts(std::vector<int32_t>{(int32_t)m, (int32_t)(n - m)}), d_n(1);
+    std::unique_ptr<DevBuf<uint8_t>> d_prev;
+    if (n_prev) d_prev = std::make_unique<DevBuf<uint8_t>>(prev_features.descriptors);
+    DevBuf<uint8_t> d_desc((size_t)MAX_POINTS * RS_DESC_BYTES);
+    if (!rs_ok(rs_describe_features(m_ctx, m_orb, img, d_pa.get(), d_counts.get(), d_carry_index.get(),
+                                    d_prev ? d_prev->get() : nullptr, (int)n_prev, d_pb.get(), d_counts.get() + 1, ORB_EDGE,
+                                    d_desc.get(), nullptr, d_n.get()), "rs_describe_features"))
+        return {};
+    auto rows = d_desc.fetch(n * RS_DESC_BYTES);                // the one read-back: n x 32 bytes
+    stage_sync();
+    return rows;
 }
 
 }  // namespace slam

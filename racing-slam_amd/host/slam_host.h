@@ -246,6 +246,17 @@ class Session {
     // count), or -1 on failure.
     int replenish_features(const Image& next, const Image& static_mask, ExtractedFeatures& features, int max_total,
                            std::vector<float>* responses = nullptr);
+    // OrbFeatureExtractor::refresh_descriptors (features/OrbFeatureExtractor.cpp:29-61, called at src/Tracker.cpp:150)
+    // as ONE rs_describe_features call: the ORB descriptor (patch 31, angle -1, one level) of every keypoint of
+    // `features` inside ORB's 31-px border on `next`; a keypoint outside it keeps the row the frame carried.  The first
+    // matches.size() keypoints are the tracked ones of track_features (matches[k] = (previous index, k)) and carry
+    // prev_features' row at their previous index (:130); the rest are appended corners and carry zeros (the rows
+    // replenish_features appends).  Returns the N x 32 rows; `features` without keypoints or rows is returned as it
+    // is (the reference's early return), and an empty vector on failure.  `next` is reused as replenish_features
+    // reuses it: the device pyramid of the last track_features call when it is that call's `next`, else uploaded.
+    // Up to 8192 keypoints.
+    std::vector<uint8_t> refresh_descriptors(const Image& next, const ExtractedFeatures& features,
+                                             const ExtractedFeatures& prev_features, const std::vector<FeatureMatch>& matches);
 
   private:
     Session();
@@ -257,6 +268,9 @@ class Session {
     rs_detector* m_det = nullptr;               // replenish_features: detector scratch and a pyramid of its own
     rs_image* m_det_img = nullptr;              // (used when the frame is not the last tracked one)
     int m_det_w = 0, m_det_h = 0;
+    rs_describer* m_orb = nullptr;              // refresh_descriptors: describer plane and a pyramid of its own
+    rs_image* m_orb_img = nullptr;
+    int m_orb_w = 0, m_orb_h = 0;
 };
 
 }  // namespace slam

@@ -24,6 +24,7 @@ EXPORTS = [
     "rs_image_create", "rs_image_destroy", "rs_image_levels", "rs_image_upload", "rs_image_upload_device", "rs_image_download",
     "rs_klt_track", "rs_track_features",
     "rs_detector_create", "rs_detector_destroy", "rs_detect_features", "rs_corner_response", "rs_detector_stats",
+    "rs_describer_create", "rs_describer_destroy", "rs_describe_features", "rs_orb_blur",
     "rs_comm_get_unique_id", "rs_comm_init_rank", "rs_comm_destroy", "rs_comm_init_local", "rs_comm_count", "rs_prof_begin", "rs_prof_end", "rs_prof_counters", "rs_prof_empty_launch",
 ]
 
@@ -731,6 +732,31 @@ class Context:
         self._check(self.lib.rs_corner_response(self.h, det.h, img.h, _dp(out)), "rs_corner_response")
         return out
 
+    # -- ORB (Tracker::track_features' refresh_descriptors)
+    def describer(self, width, height, max_points=8192):
+        """rs_describer: the blurred plane of the ORB describer for one image size (allocated once, reused)."""
+        return Describer(self, width, height, max_points)
+
+    def describe_features(self, d, img, d_pt_a=None, d_count_a=None, d_carry_index=None, d_carry_desc=None, n_carry=0,
+                          d_pt_b=None, d_count_b=None, border=31, out=None):
+        """rs_describe_features (OrbFeatureExtractor::refresh_descriptors): dict(desc [max_points][32] u8,
+        fresh [max_points] u8, n [1] i32), device tensors; the first n rows are list a's points then list b's."""
+        t = self.torch
+        if out is None:
+            out = dict(desc=self.empty((d.max_points, 32), t.uint8), fresh=self.empty((d.max_points,), t.uint8),
+                       n=self.empty((1,), t.int32))
+        self._check(self.lib.rs_describe_features(self.h, d.h, img.h, _dp(d_pt_a), _dp(d_count_a), _dp(d_carry_index),
+                                                  _dp(d_carry_desc), int(n_carry), _dp(d_pt_b), _dp(d_count_b), int(border),
+                                                  _dp(out["desc"]), _dp(out["fresh"]), _dp(out["n"])), "rs_describe_features")
+        return out
+
+    def orb_blur(self, d, img, out=None):
+        """rs_orb_blur: the blurred level 0 [height][width] u8 (device) that the descriptors sample."""
+        if out is None:
+            out = self.empty((d.height, d.width), self.torch.uint8)
+        self._check(self.lib.rs_orb_blur(self.h, d.h, img.h, _dp(out)), "rs_orb_blur")
+        return out
+
     def synchronize(self):
         self._check(self.lib.rs_context_synchronize(self.h), "rs_context_synchronize")
 
@@ -803,6 +829,21 @@ class Detector:
     def close(self):
         if self.h:
             self.ctx.lib.rs_detector_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+class Describer:
+    """rs_describer: the ORB describer's device plane for one image size."""
+
+    def __init__(self, ctx, width, height, max_points=8192):
+        self.ctx, self.width, self.height, self.max_points = ctx, int(width), int(height), int(max_points)
+        self.h = C.c_void_p()
+        ctx._check(ctx.lib.rs_describer_create(ctx.h, self.width, self.height, self.max_points, C.byref(self.h)),
+                   "rs_describer_create")
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.rs_describer_destroy(self.h)
             self.h = C.c_void_p()
 
 
