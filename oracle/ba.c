@@ -239,8 +239,14 @@ static int n_extras(const problem* pr)
 }
 
 static int pose_col(const problem* pr, int c, int k) { return pr->cam_slot[c] >= 0 ? 6 * pr->cam_slot[c] + k : -1; }
-static int vel_col(const problem* pr, int c, int k) { return pr->inert_slot[c] >= 0 ? 6 * pr->Cf + 9 * pr->inert_slot[c] + k : -1; }
-static int bias_col(const problem* pr, int c, int k) { return pr->inert_slot[c] >= 0 ? 6 * pr->Cf + 9 * pr->inert_slot[c] + 3 + k : -1; }
+/* unknowns per inertial frame: velocity + bias, or the velocity alone in refine_pose's InertialDelta, whose bias is not a
+ * parameter block of the problem (src/Optimization.cpp:237-251) */
+static int inert_width(const problem* pr) { return pr->delta_only ? 3 : 9; }
+static int vel_col(const problem* pr, int c, int k) { return pr->inert_slot[c] >= 0 ? 6 * pr->Cf + inert_width(pr) * pr->inert_slot[c] + k : -1; }
+static int bias_col(const problem* pr, int c, int k)
+{
+    return (pr->inert_slot[c] >= 0 && !pr->delta_only) ? 6 * pr->Cf + 9 * pr->inert_slot[c] + 3 + k : -1;
+}
 
 /* residuals r[EX_RES] (+ Jacobian J[EX_RES][EX_PAR] when J != NULL) and the shape of extra block e at the given state */
 static void eval_extra(const problem* pr, int e, const double* cams, const double* vel, const double* bias,
@@ -398,7 +404,7 @@ static int lm_solve(problem* pr, double* cams, double* pts, double* vel, double*
     for (int c = 0; c < C; c++) pr->inert_slot[c] = cam_inert[c] ? pr->Ci++ : -1;
     free(cam_nobs); free(cam_inert);
     pr->n_extra = n_extras(pr);
-    const int Cf = pr->Cf, nc = 6 * Cf + 9 * pr->Ci, NE = pr->n_extra;
+    const int Cf = pr->Cf, nc = 6 * Cf + inert_width(pr) * pr->Ci, NE = pr->n_extra;
     pr->nc = nc;
     const int NP = pr->points_constant ? 0 : P;
     double zero9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -635,8 +641,8 @@ static int lm_solve(problem* pr, double* cams, double* pts, double* vel, double*
         for (int c = 0; c < C; c++) {
             const int q = pr->inert_slot[c];
             if (q < 0) continue;
-            for (int k = 0; k < 9; k++) {
-                const int col = 6 * Cf + 9 * q + k;
+            for (int k = 0; k < inert_width(pr); k++) {
+                const int col = 6 * Cf + inert_width(pr) * q + k;
                 double* xs = k < 3 ? &x_v[3 * c + k] : &x_b[6 * c + k - 3];
                 double* cs = k < 3 ? &cand_v[3 * c + k] : &cand_b[6 * c + k - 3];
                 *cs = *xs + step_c[col] * scale_c[col];

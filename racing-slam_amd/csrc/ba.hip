@@ -1498,8 +1498,9 @@ __global__ __launch_bounds__(RP_THREADS) void ba_refine_pose(BaDims d, BaOpt opt
 extern "C" int rs_refine_pose(rs_context* ctx, double h_camera[6], const double* d_points, const float* d_uv, int n,
                               const float h_intrinsics[4], const rs_ba_options* options, rs_ba_summary* h_summary)
 {
-    if (!ctx || !h_summary || !h_camera) return RS_ERR_INVALID;
-    memset(h_summary, 0, sizeof *h_summary);
+    if (!ctx || !h_summary) return RS_ERR_INVALID;
+    memset(h_summary, 0, sizeof *h_summary);     // a refused call leaves a zeroed summary too
+    if (!h_camera) return rs_fail(ctx, RS_ERR_INVALID, "null pointer");
     if (n < 0) return rs_fail(ctx, RS_ERR_INVALID, "negative n");
     if (n == 0) return RS_OK;   // "nothing to constrain", src/Optimization.cpp:227-229
     if (!d_points || !d_uv || !h_intrinsics) return rs_fail(ctx, RS_ERR_INVALID, "null pointer");
@@ -1778,13 +1779,14 @@ extern "C" int rs_refine_pose_inertial(rs_context* ctx, double h_camera[6], cons
                                        const rs_imu_factor* h_delta, const double h_gravity[3], double h_velocity[3],
                                        const rs_ba_options* options, rs_ba_summary* h_summary)
 {
-    if (!ctx || !h_summary || !h_camera) return RS_ERR_INVALID;
+    if (!ctx || !h_summary) return RS_ERR_INVALID;
+    memset(h_summary, 0, sizeof *h_summary);     // a refused call leaves a zeroed summary too
+    if (!h_camera) return rs_fail(ctx, RS_ERR_INVALID, "null pointer");
     if (kind < 0 || kind > 2) return rs_fail(ctx, RS_ERR_INVALID, "kind must be 0, 1 or 2");
     // RotationPrior::enabled / InertialDelta::enabled (src/Optimization.h:50-53,60-63): a disabled constraint is no constraint
     if (kind == 1 && (!h_predicted || !(sigma_radians > 0.0))) kind = 0;
     if (kind == 2 && (!h_delta || !(h_delta->duration > 0.0))) kind = 0;
     if (kind == 0) return rs_refine_pose(ctx, h_camera, d_points, d_uv, n, h_intrinsics, options, h_summary);
-    memset(h_summary, 0, sizeof *h_summary);
     if (n < 0) return rs_fail(ctx, RS_ERR_INVALID, "negative n");
     if (n == 0) return RS_OK;   // "nothing to constrain", src/Optimization.cpp:227-229 (checked before the inertial block is added)
     if (!d_points || !d_uv || !h_intrinsics) return rs_fail(ctx, RS_ERR_INVALID, "null pointer");

@@ -553,3 +553,65 @@ def make_dot_chain(n=30, spacing=3, direction=(1, 0), width=320, height=240, bas
     for i, (x, y) in enumerate(dots):
         img[y:y + 2, x:x + 2] = base - step * i
     return dict(img=img, dots=dots, width=width, height=height)
+
+
+def make_refine_problem(n=600, seed=0, outlier_frac=0.0, noise_px=0.0, rot0=None, rot_err=0.02, offset=0.0,
+                        trans_err=0.05, bad_depth_frac=0.0, imu=False, width=640, height=480):
+    """One frame's pose solve (optimization::refine_pose, reference src/Optimization.cpp:194-267): n world points with
+    their observations in the frame and a starting camera cam0 (angle-axis | centre, p = R(aa) (X - centre)).
+
+    rot0: the starting angle-axis, used bit for bit (None: a random rotation of 0.3 rad); the true rotation is
+    R(e) R(rot0) with |e| = rot_err, so a solve leaves rot0 on its first step.  offset: distance of the true centre from
+    the origin along a random direction (the points travel with it); trans_err: distance of cam0's centre from the true
+    one.  Observations are the true projections plus Gaussian noise of noise_px (f32); a fraction outlier_frac of them is
+    moved by 20..120 px in a random direction.  A fraction bad_depth_frac of the points lies near or behind the true
+    camera's image plane (camera-frame depth in [-2, 0.05], a few of them at |depth| <= 1e-4), observed at random
+    pixels.  imu=True adds a one-factor InertialDelta built by make_imu on the (previous, this) pair of true cameras:
+    delta = dict(imu, prev_pose, prev_velocity, prev_bias, velocity) as refine_pose_inertial takes it.
+    Returns dict(cam0, points [n][3] f64, uv [n][2] f32, K (f32 fx, fy, cx, cy), cam_true, outlier [n] bool,
+    bad_depth [n] bool, delta or None)."""
+    rng = np.random.default_rng([0x5EED7E00, int(seed)])
+    K = np.array([450.0, 445.0, width / 2.0, height / 2.0], np.float32)
+    fx, fy, cx, cy = [float(k) for k in K]
+    if rot0 is None:
+        d = rng.normal(size=3)
+        rot0 = 0.3 * d / np.linalg.norm(d)
+    rot0 = np.asarray(rot0, np.float64)
+    e = rng.normal(size=3)
+    e *= rot_err / np.linalg.norm(e)
+    R_true = rodrigues(e) @ rodrigues(rot0)
+    u = rng.normal(size=3)
+    c_true = float(offset) * u / np.linalg.norm(u)
+    t = rng.normal(size=3)
+    c0 = c_true + float(trans_err) * t / np.linalg.norm(t)
+    cam_true = np.concatenate([log_so3(R_true), c_true])
+    cam0 = np.concatenate([rot0, c0])
+    # points in the true camera's frame: in front (depth 2..30) or, for the bad fraction, near / behind the image plane
+    px = np.stack([rng.uniform(0, width, n), rng.uniform(0, height, n)], 1)
+    depth = rng.uniform(2.0, 30.0, n)
+    bad = rng.random(n) < bad_depth_frac
+    depth[bad] = rng.uniform(-2.0, 0.05, int(bad.sum()))
+    tiny = bad & (rng.random(n) < 0.2)
+    depth[tiny] = rng.uniform(-1e-4, 1e-4, int(tiny.sum()))
+    p = np.stack([(px[:, 0] - cx) / fx * depth, (px[:, 1] - cy) / fy * depth, depth], 1)
+    points = p @ R_true + c_true                       # X = R^T p + c
+    q = (points - c_true) @ R_true.T
+    with np.errstate(divide="ignore", invalid="ignore"):
+        uv = np.stack([fx * q[:, 0] / q[:, 2] + cx, fy * q[:, 1] / q[:, 2] + cy], 1)
+    uv[bad] = np.stack([rng.uniform(0, width, int(bad.sum())), rng.uniform(0, height, int(bad.sum()))], 1)
+    uv[~bad] += rng.normal(0.0, 1.0, (int((~bad).sum()), 2)) * noise_px
+    out = ~bad & (rng.random(n) < outlier_frac)
+    ang = rng.uniform(0, 2 * np.pi, int(out.sum()))
+    mag = rng.uniform(20.0, 120.0, int(out.sum()))
+    uv[out] += np.stack([np.cos(ang), np.sin(ang)], 1) * mag[:, None]
+    delta = None
+    if imu:
+        T = 0.5
+        prev_c = c_true - rng.normal(0.0, 0.5, 3)
+        prev_aa = log_so3(rodrigues(rng.normal(0.0, 0.02, 3)) @ R_true)
+        win = dict(cams_true=np.stack([np.concatenate([prev_aa, prev_c]), cam_true]), cam_free=np.ones(2, np.uint8))
+        f = make_imu(win, seed=int(seed), duration=T)
+        delta = dict(imu=f, prev_pose=win["cams_true"][0], prev_velocity=f["cam_velocity_true"][0],
+                     prev_bias=f["cam_bias"][0], velocity=f["cam_velocity"][1])
+    return dict(cam0=cam0, points=points, uv=uv.astype(np.float32), K=K, cam_true=cam_true, outlier=out,
+                bad_depth=bad, delta=delta)

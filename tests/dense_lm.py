@@ -125,7 +125,10 @@ def imu_preintegration(f, gravity, pose_i, vel_i, bias_i, pose_j, vel_j):
     sv = Ri @ (vel_j - vel_i - gravity * T)
     sp = Ri @ (pose_j[3:] - pose_i[3:] - vel_i * T - 0.5 * gravity * T * T)
     res = np.concatenate([matrix_to_aa(Rm.T @ Rs), sv - mvel, sp - mpos])
-    L = np.linalg.cholesky(f["covariance"].reshape(9, 9))
+    try:
+        L = np.linalg.cholesky(f["covariance"].reshape(9, 9))
+    except np.linalg.LinAlgError:           # not positive definite: identity whitener (src/ImuFactor.cpp:10-17)
+        return res
     return np.linalg.solve(L, res)
 
 
@@ -324,13 +327,14 @@ class Problem:
 
 
 def solve(prob, max_iter=10, r0=1e4, rmax=1e16, rmin=1e-32, min_rel=1e-3, dmin=1e-6, dmax=1e32,
-          ftol=1e-6, gtol=1e-10, ptol=1e-8, max_invalid=5):
-    """Returns (x, summary dict, trace list) with the fields of orc_ba_iteration."""
+          ftol=1e-6, gtol=1e-10, ptol=1e-8, max_invalid=5, jacobi=True):
+    """Returns (x, summary dict, trace list) with the fields of orc_ba_iteration.  jacobi=False: no Jacobi scaling
+    (rs_ba_options.jacobi_scaling = 0)."""
     x = prob.pack(prob.cams0, prob.pts0)
     r, J, x_cost = prob.linearize(x)
     summary = dict(initial_cost=x_cost, iterations=0, successful_steps=0, termination=0)
     trace = []
-    scale = 1.0 / (1.0 + np.sqrt(np.sum(J * J, axis=0)))
+    scale = 1.0 / (1.0 + np.sqrt(np.sum(J * J, axis=0))) if jacobi else np.ones(J.shape[1])
     radius, factor, invalid = r0, 2.0, 0
     best_x, best_cost = x.copy(), x_cost
     if not np.isfinite(x_cost):
