@@ -835,6 +835,60 @@ int rs_describe_features(rs_context* ctx, rs_describer* d, const rs_image* img, 
 /* Diagnostic: the blurred level 0 the descriptors sample, d_blur [height][width] u8 (device). */
 int rs_orb_blur(rs_context* ctx, rs_describer* d, const rs_image* img, uint8_t* d_blur);
 
+/* ------------------------------------------------- relative pose: essential-matrix RANSAC */
+
+/* Tracker::initial_pose_estimate's pose::estimate_pose (src/PoseEstimation.cpp:59-88, with recover_pose_from_essential
+ * :23-57; called at src/Tracker.cpp:162) and pose::estimate_pose_with_known_rotation (:110-227; Initialization.cpp:153).
+ * The reference runs cv::findEssentialMat(USAC_ACCURATE, 0.99, 1.0 px), which cannot be restated bit for bit; the
+ * specification is tests/essential_ref.py: hashed samples, Nister's five-point solver (Sturm bisection), integer
+ * inlier counts (squared Sampson distance < t^2, t = threshold_px / ((fx + fy) / 2)), the adaptive stop after each
+ * round of 256 hypotheses, up to 4 linear 8-point LO refits, decomposeEssentialMat on a one-sided Jacobi SVD and the
+ * reference's cheirality vote (triangulate_points over EVERY finite match, 0.9999, 2.0 px; the first strict maximum).
+ * Agreement with OpenCV's USAC is not claimed.  No nonlinear polish.
+ *
+ * rs_pose_estimator holds the scratch (allocated once; no allocation per call).  Envelope: max_points 1 .. 8192,
+ * max_hypotheses 1 .. 4096.  Outside it: RS_ERR_UNSUPPORTED.  Creation synchronises the context stream only. */
+typedef struct rs_pose_estimator rs_pose_estimator;
+int rs_pose_estimator_create(rs_context* ctx, int max_points, int max_hypotheses, rs_pose_estimator** out_est);
+int rs_pose_estimator_destroy(rs_pose_estimator* est);
+/* One stream-ordered chain with no host synchronisation.  Inputs (device): the "from" pixels d_pts_from [][2] f32, read
+ * as d_pts_from[d_from_index[i]] (rs_track_features' d_kept_index over the previous frame's points; a negative index
+ * is a non-finite point; indices must lie inside the caller's array) or d_pts_from[i] when d_from_index is NULL; the
+ * "to" pixels d_pts_to [][2] (rs_track_features' d_kept_pt); the count n = clamp(d_count[0], 0, max_n), read on the
+ * device.  h_intrinsics = fx, fy, cx, cy.  Hypotheses h = 0 .. max_hypotheses-1 (<= the estimator's) in rounds of 256;
+ * seed selects the samples.  Outputs (device): d_pose [16] f32 row-major (X_to = R X_from + t, |t| = 1),
+ * d_inlier [max_n] u8 (entries from n on are 0), d_inlier_index [max_n] (ascending), d_inlier_count [1],
+ * d_status [1]: 0 = ok, 1 = fewer than 5 points, 2 = no model with >= 5 inliers (both: identity pose, no inliers; the
+ * reference would throw inside OpenCV).  A point with a non-finite coordinate is never sampled, never an inlier and
+ * not triangulated. */
+int rs_estimate_pose(rs_context* ctx, rs_pose_estimator* est, const float* d_pts_from, const int32_t* d_from_index,
+                     const float* d_pts_to, const int32_t* d_count, int max_n, const float* h_intrinsics, double threshold_px,
+                     double confidence, int max_hypotheses, uint64_t seed, float* d_pose, uint8_t* d_inlier,
+                     int32_t* d_inlier_index, int32_t* d_inlier_count, int32_t* d_status);
+/* estimate_pose_with_known_rotation (:110-227) in f32 with the same outputs: n points (host count), h_rotation [9]
+ * row-major, d_pairs [n_iter][2] (the reference draws 200 with std::mt19937(0) and uniform_int_distribution<size_t>;
+ * a pair with i == j, or an index outside [0, n), is skipped), max_epipolar_px (2.0 in the reference), focal = fx.
+ * Status 1 = fewer than 8 points, 2 = best support below 8; both leave the pose [R | 0].  The refit takes the smallest
+ * eigenvector of the f64 normal matrix of the inlier constraints (the reference: JacobiSVD of the stack).  n_iter
+ * 1 .. the estimator's max_hypotheses. */
+int rs_estimate_pose_known_rotation(rs_context* ctx, rs_pose_estimator* est, const float* d_pts_from, const int32_t* d_from_index,
+                                    const float* d_pts_to, int n, const float* h_intrinsics, const float* h_rotation,
+                                    const int32_t* d_pairs, int n_iter, float max_epipolar_px, float* d_pose, uint8_t* d_inlier,
+                                    int32_t* d_inlier_index, int32_t* d_inlier_count, int32_t* d_status);
+/* Diagnostic of the last call (synchronises the stream): h_stats[14] = hypotheses drawn, models scored, best index
+ * (10 h + m; the pair index after the known-rotation form), best count, LO refits kept, the four cheirality counts
+ * (known rotation: +t, -t, 0, 0), chosen candidate, status, inlier count, n, known-rotation flag; h_E [9] the final
+ * E (f64, unit norm); h_candidates [4][16] f32 the decomposition's poses.  Any pointer may be NULL. */
+int rs_pose_estimator_stats(rs_context* ctx, const rs_pose_estimator* est, int32_t* h_stats, double* h_E, float* h_candidates);
+/* Diagnostic (synchronises) of the last call, over the estimator's whole table h < max_hypotheses (every call resets
+ * it: nothing of an earlier call survives): h_samples [][5] (-1: not drawn, or a sample that could not find 5 distinct
+ * finite points), h_nmodels [] (-1: not drawn), h_models [][10][9] f64 (row m valid for m < nmodels[h]) and
+ * h_scores [][10] (0 past nmodels[h]).  After the known-rotation form: samples[h][0..1] = the pair (-1 past n_iter),
+ * nmodels 1 = scored, 0 = skipped, -1 = past n_iter; the translation in models[h][0][0..2] when scored; the support
+ * in scores[h][0] (-1: skipped or past n_iter).  Any pointer may be NULL. */
+int rs_pose_hypotheses(rs_context* ctx, const rs_pose_estimator* est, int32_t* h_samples, int32_t* h_nmodels, double* h_models,
+                       int32_t* h_scores);
+
 /* ------------------------------------------------------------- multi-GPU */
 
 #define RS_COMM_ID_BYTES 128

@@ -19,7 +19,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(ROOT, "integration", "reference_shim")
-UNITS = ("MapMatcher.cpp", "Triangulation.cpp", "Optimization.cpp", "LocalWindow.cpp")
+UNITS = ("MapMatcher.cpp", "Triangulation.cpp", "Optimization.cpp", "LocalWindow.cpp", "PoseEstimation.cpp")
 
 
 def flags(upstream_src):

@@ -26,6 +26,7 @@ SOURCES = [
     ("klt.hip", ["-ffp-contract=off"]),
     ("gftt.hip", ["-ffp-contract=off"]),
     ("orb.hip", ["-ffp-contract=off"]),
+    ("pose.hip", ["-ffp-contract=off"]),
     ("ba.hip", ["-munsafe-fp-atomics"]),
     ("ba_solve.hip", ["-munsafe-fp-atomics"]),
     ("ba_solve_big.hip", ["-munsafe-fp-atomics"]),

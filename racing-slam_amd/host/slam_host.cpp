@@ -9,6 +9,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <cstdint>
+#include <random>
 #include <unordered_map>
 
 namespace slam {
@@ -160,6 +161,7 @@ Session::~Session()
     rs_detector_destroy(m_det);
     rs_image_destroy(m_orb_img);
     rs_describer_destroy(m_orb);
+    rs_pose_estimator_destroy(m_pose);
     rs_context_destroy(m_ctx);
 }
 Session& Session::get()
@@ -855,5 +857,119 @@ std::vector<uint8_t> Session::refresh_descriptors(const Image& next, const Extra
     stage_sync();
     return rows;
 }
+
+rs_pose_estimator* Session::pose_estimator()
+{
+    if (!m_pose && !rs_ok(rs_pose_estimator_create(m_ctx, 8192, 1000, &m_pose), "rs_pose_estimator_create")) m_pose = nullptr;
+    return m_pose;
+}
+
+// ------------------------------------------------------------------------ pose (src/PoseEstimation.cpp)
+namespace pose {
+
+namespace {
+
+constexpr int POSE_MAX_POINTS = 8192;
+
+// the matched pixels (prev keypoint of train_index, keypoint of query_index), PoseEstimation.cpp:64-68
+void matched_pixels(const ExtractedFeatures& prev_features, const ExtractedFeatures& features,
+                    const std::vector<FeatureMatch>& matches, std::vector<float>& from, std::vector<float>& to)
+{
+    const size_t n = matches.size();
+    from.assign(2 * std::max<size_t>(n, 1), 0.f);
+    to.assign(2 * std::max<size_t>(n, 1), 0.f);
+    for (size_t k = 0; k < n; k++) {
+        const Vec2f a = prev_features.keypoints[matches[k].train_index].pt, b = features.keypoints[matches[k].query_index].pt;
+        from[2 * k] = a.x; from[2 * k + 1] = a.y;
+        to[2 * k] = b.x; to[2 * k + 1] = b.y;
+    }
+}
+
+PoseEstimate collect(const std::vector<FeatureMatch>& matches, const std::vector<float>& pose, const std::vector<int32_t>& index,
+                     const std::vector<int32_t>& count, const std::vector<int32_t>& status)
+{
+    PoseEstimate e;
+    for (int k = 0; k < 16; k++) e.pose[k] = pose[k];
+    for (int32_t k = 0; k < count[0]; k++) e.inlier_matches.push_back(matches[index[k]]);
+    e.status = status[0];
+    return e;
+}
+
+}  // namespace
+
+std::vector<int32_t> known_rotation_pairs(size_t n)
+{
+    std::vector<int32_t> pairs(400, 0);
+    if (n == 0) return pairs;
+    std::mt19937 generator(0);
+    std::uniform_int_distribution<size_t> pick(0, n - 1);
+    for (size_t it = 0; it < 200; it++) {
+        const size_t i = pick(generator);
+        const size_t j = pick(generator);
+        pairs[2 * it] = (int32_t)i;
+        pairs[2 * it + 1] = (int32_t)j;
+    }
+    return pairs;
+}
+
+PoseEstimate estimate_pose(const ExtractedFeatures& prev_features, const ExtractedFeatures& features,
+                           const std::vector<FeatureMatch>& matches, const Camera& camera)
+{
+    const size_t n = matches.size();
+    rs_pose_estimator* est = Session::get().pose_estimator();
+    if (!est || n > (size_t)POSE_MAX_POINTS) {
+        std::printf("estimate_pose: no estimator, or more than %d matches\n", POSE_MAX_POINTS);
+        return {};
+    }
+    std::vector<float> from, to;
+    matched_pixels(prev_features, features, matches, from, to);
+    const float K[4] = {camera.fx(), camera.fy(), camera.cx(), camera.cy()};
+    StageScope scope;
+    DevBuf<float> d_from(from), d_to(to), d_pose(16);
+    DevBuf<int32_t> d_count(std::vector<int32_t>{(int32_t)n}), d_index(std::max<size_t>(n, 1)), d_cnt(1), d_status(1);
+    DevBuf<uint8_t> d_inlier(std::max<size_t>(n, 1));
+    if (!rs_ok(rs_estimate_pose(Session::get().ctx(), est, d_from.get(), nullptr, d_to.get(), d_count.get(), (int)n, K, 1.0, 0.99,
+                                1000, 0, d_pose.get(), d_inlier.get(), d_index.get(), d_cnt.get(), d_status.get()),
+               "rs_estimate_pose"))
+        return {};
+    auto pose = d_pose.fetch(16);
+    auto index = d_index.fetch(n);
+    auto count = d_cnt.fetch(1);
+    auto status = d_status.fetch(1);
+    stage_sync();
+    return collect(matches, pose, index, count, status);
+}
+
+PoseEstimate estimate_pose_with_known_rotation(const ExtractedFeatures& prev_features, const ExtractedFeatures& features,
+                                               const std::vector<FeatureMatch>& matches, const Camera& camera,
+                                               const std::array<float, 9>& rotation)
+{
+    const size_t n = matches.size();
+    rs_pose_estimator* est = Session::get().pose_estimator();
+    if (!est || n > (size_t)POSE_MAX_POINTS) {
+        std::printf("estimate_pose_with_known_rotation: no estimator, or more than %d matches\n", POSE_MAX_POINTS);
+        return {};
+    }
+    std::vector<float> from, to;
+    matched_pixels(prev_features, features, matches, from, to);
+    const float K[4] = {camera.fx(), camera.fy(), camera.cx(), camera.cy()};
+    StageScope scope;
+    DevBuf<float> d_from(from), d_to(to), d_pose(16);
+    DevBuf<int32_t> d_pairs(known_rotation_pairs(n)), d_index(std::max<size_t>(n, 1)), d_cnt(1), d_status(1);
+    DevBuf<uint8_t> d_inlier(std::max<size_t>(n, 1));
+    if (!rs_ok(rs_estimate_pose_known_rotation(Session::get().ctx(), est, d_from.get(), nullptr, d_to.get(), (int)n, K,
+                                               rotation.data(), d_pairs.get(), 200, 2.0f, d_pose.get(), d_inlier.get(),
+                                               d_index.get(), d_cnt.get(), d_status.get()),
+               "rs_estimate_pose_known_rotation"))
+        return {};
+    auto pose = d_pose.fetch(16);
+    auto index = d_index.fetch(n);
+    auto count = d_cnt.fetch(1);
+    auto status = d_status.fetch(1);
+    stage_sync();
+    return collect(matches, pose, index, count, status);
+}
+
+}  // namespace pose
 
 }  // namespace slam

@@ -257,6 +257,8 @@ class Session {
     // Up to 8192 keypoints.
     std::vector<uint8_t> refresh_descriptors(const Image& next, const ExtractedFeatures& features,
                                              const ExtractedFeatures& prev_features, const std::vector<FeatureMatch>& matches);
+    // the relative-pose scratch of pose::estimate_pose* (8192 points, 1000 hypotheses), created on first use
+    rs_pose_estimator* pose_estimator();
 
   private:
     Session();
@@ -271,6 +273,32 @@ class Session {
     rs_describer* m_orb = nullptr;              // refresh_descriptors: describer plane and a pyramid of its own
     rs_image* m_orb_img = nullptr;
     int m_orb_w = 0, m_orb_h = 0;
+    rs_pose_estimator* m_pose = nullptr;
 };
+
+// src/PoseEstimation.h: the relative pose from prev_features to features (X = R X_prev + t, |t| = 1), Tracker.cpp:162
+// and Initialization.cpp:153.  Each is ONE C-ABI call on the device (include/rsgpu.h: rs_estimate_pose /
+// rs_estimate_pose_known_rotation) and one read-back.  Up to 8192 matches.
+namespace pose {
+
+struct PoseEstimate {
+    Mat4f pose = identity4();                    // row-major
+    std::vector<FeatureMatch> inlier_matches;    // matches used for the estimate
+    int status = -1;                             // rs_estimate_pose's status; -1 = the call failed (logged)
+};
+
+// findEssentialMat(USAC_ACCURATE, 0.99, 1.0 px) + recover_pose_from_essential (PoseEstimation.cpp:23-88), as specified
+// by tests/essential_ref.py: 1000 hypotheses, seed 0.  Fewer than 5 matches or no model: identity, no inliers.
+PoseEstimate estimate_pose(const ExtractedFeatures& prev_features, const ExtractedFeatures& features,
+                           const std::vector<FeatureMatch>& matches, const Camera& camera);
+// estimate_pose_with_known_rotation (PoseEstimation.cpp:110-227); rotation row-major.  The 200 (i, j) pairs are the
+// reference's draws, known_rotation_pairs(matches.size()).
+PoseEstimate estimate_pose_with_known_rotation(const ExtractedFeatures& prev_features, const ExtractedFeatures& features,
+                                               const std::vector<FeatureMatch>& matches, const Camera& camera,
+                                               const std::array<float, 9>& rotation);
+// std::mt19937(0) and std::uniform_int_distribution<size_t>(0, n - 1), i then j, 200 times (:137-143); [200][2]
+std::vector<int32_t> known_rotation_pairs(size_t n);
+
+}  // namespace pose
 
 }  // namespace slam

@@ -25,6 +25,8 @@ EXPORTS = [
     "rs_klt_track", "rs_track_features",
     "rs_detector_create", "rs_detector_destroy", "rs_detect_features", "rs_corner_response", "rs_detector_stats",
     "rs_describer_create", "rs_describer_destroy", "rs_describe_features", "rs_orb_blur",
+    "rs_pose_estimator_create", "rs_pose_estimator_destroy", "rs_estimate_pose", "rs_estimate_pose_known_rotation",
+    "rs_pose_estimator_stats", "rs_pose_hypotheses",
     "rs_comm_get_unique_id", "rs_comm_init_rank", "rs_comm_destroy", "rs_comm_init_local", "rs_comm_count", "rs_prof_begin", "rs_prof_end", "rs_prof_counters", "rs_prof_empty_launch",
 ]
 
@@ -757,6 +759,45 @@ class Context:
         self._check(self.lib.rs_orb_blur(self.h, d.h, img.h, _dp(out)), "rs_orb_blur")
         return out
 
+    # -- relative pose (Tracker::initial_pose_estimate)
+    def pose_estimator(self, max_points=8192, max_hypotheses=1000):
+        """rs_pose_estimator: the scratch of the relative-pose RANSAC (allocated once, reused)."""
+        return PoseEstimator(self, max_points, max_hypotheses)
+
+    def _pose_out(self, max_n, out):
+        t = self.torch
+        if out is None:
+            m = max(int(max_n), 1)
+            out = dict(pose=self.empty((4, 4), t.float32), inlier=self.empty((m,), t.uint8),
+                       inlier_index=self.empty((m,), t.int32), inlier_count=self.empty((1,), t.int32),
+                       status=self.empty((1,), t.int32))
+        return out
+
+    def estimate_pose(self, est, d_from, d_to, d_count, max_n, K, d_from_index=None, threshold_px=1.0, confidence=0.99,
+                      max_hypotheses=1000, seed=0, out=None):
+        """rs_estimate_pose (pose::estimate_pose): dict(pose [4][4] f32, inlier [max_n] u8, inlier_index [max_n] i32,
+        inlier_count [1], status [1]), device tensors; d_count is a device [1] i32."""
+        out = self._pose_out(max_n, out)
+        Kc = (C.c_float * 4)(*[float(v) for v in K])
+        self._check(self.lib.rs_estimate_pose(self.h, est.h, _dp(d_from), _dp(d_from_index), _dp(d_to), _dp(d_count),
+                                              int(max_n), Kc, C.c_double(threshold_px), C.c_double(confidence),
+                                              int(max_hypotheses), C.c_uint64(int(seed) & (2 ** 64 - 1)), _dp(out["pose"]),
+                                              _dp(out["inlier"]), _dp(out["inlier_index"]), _dp(out["inlier_count"]),
+                                              _dp(out["status"])), "rs_estimate_pose")
+        return out
+
+    def estimate_pose_known_rotation(self, est, d_from, d_to, n, K, R, d_pairs, n_iter, d_from_index=None,
+                                     max_epipolar_px=2.0, out=None):
+        """rs_estimate_pose_known_rotation (pose::estimate_pose_with_known_rotation); outputs as estimate_pose."""
+        out = self._pose_out(n, out)
+        Kc = (C.c_float * 4)(*[float(v) for v in K])
+        Rc = (C.c_float * 9)(*[float(v) for v in np.asarray(R, np.float32).ravel()])
+        self._check(self.lib.rs_estimate_pose_known_rotation(
+            self.h, est.h, _dp(d_from), _dp(d_from_index), _dp(d_to), int(n), Kc, Rc, _dp(d_pairs), int(n_iter),
+            C.c_float(max_epipolar_px), _dp(out["pose"]), _dp(out["inlier"]), _dp(out["inlier_index"]),
+            _dp(out["inlier_count"]), _dp(out["status"])), "rs_estimate_pose_known_rotation")
+        return out
+
     def synchronize(self):
         self._check(self.lib.rs_context_synchronize(self.h), "rs_context_synchronize")
 
@@ -844,6 +885,46 @@ class Describer:
     def close(self):
         if self.h:
             self.ctx.lib.rs_describer_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+class PoseEstimator:
+    """rs_pose_estimator: the relative-pose RANSAC's device scratch."""
+
+    STATS = ("drawn", "scored", "best_index", "best_count", "lo_kept", "cheir0", "cheir1", "cheir2", "cheir3", "chosen",
+             "status", "inliers", "n", "known")
+
+    def __init__(self, ctx, max_points=8192, max_hypotheses=1000):
+        self.ctx, self.max_points, self.max_hypotheses = ctx, int(max_points), int(max_hypotheses)
+        self.h = C.c_void_p()
+        ctx._check(ctx.lib.rs_pose_estimator_create(ctx.h, self.max_points, self.max_hypotheses, C.byref(self.h)),
+                   "rs_pose_estimator_create")
+
+    def stats(self):
+        """Diagnostic of the last call: dict of STATS, cheir [4], E [9] f64, candidates [4][4][4] f32."""
+        s = np.zeros(14, np.int32)
+        E = np.zeros(9, np.float64)
+        cand = np.zeros((4, 4, 4), np.float32)
+        self.ctx._check(self.ctx.lib.rs_pose_estimator_stats(self.ctx.h, self.h, s.ctypes.data_as(C.c_void_p),
+                                                             E.ctypes.data_as(C.c_void_p), cand.ctypes.data_as(C.c_void_p)),
+                        "rs_pose_estimator_stats")
+        d = {k: int(v) for k, v in zip(self.STATS, s)}
+        d.update(cheir=[d["cheir0"], d["cheir1"], d["cheir2"], d["cheir3"]], E=E, candidates=cand)
+        return d
+
+    def hypotheses(self):
+        """Diagnostic of the last call: dict(samples [H][5], nmodels [H], models [H][10][9] f64, scores [H][10])."""
+        H = self.max_hypotheses
+        out = dict(samples=np.zeros((H, 5), np.int32), nmodels=np.zeros(H, np.int32), models=np.zeros((H, 10, 9)),
+                   scores=np.zeros((H, 10), np.int32))
+        self.ctx._check(self.ctx.lib.rs_pose_hypotheses(self.ctx.h, self.h, *[out[k].ctypes.data_as(C.c_void_p) for k in
+                                                                              ("samples", "nmodels", "models", "scores")]),
+                        "rs_pose_hypotheses")
+        return out
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.rs_pose_estimator_destroy(self.h)
             self.h = C.c_void_p()
 
 

@@ -615,3 +615,52 @@ def make_refine_problem(n=600, seed=0, outlier_frac=0.0, noise_px=0.0, rot0=None
                      prev_bias=f["cam_bias"][0], velocity=f["cam_velocity"][1])
     return dict(cam0=cam0, points=points, uv=uv.astype(np.float32), K=K, cam_true=cam_true, outlier=out,
                 bad_depth=bad, delta=delta)
+
+
+POSE_MOTIONS = ("forward", "sideways", "small", "rotation", "planar")
+
+
+def make_pose_pair(seed=0, n=2000, outlier_frac=0.3, noise_px=0.5, motion="forward", width=1280, height=720):
+    """Matched pixels of two views for the relative-pose stage (pose::estimate_pose, src/PoseEstimation.cpp:59-88) with a
+    known motion X2 = R X1 + t.  motion: "forward" (the dash-cam case: t mostly along the optical axis, the epipole
+    inside the image), "sideways", "small" (a baseline of 2 cm against depths of 4 .. 40 m), "rotation" (3 degrees with a
+    baseline of 1 mm) or "planar" (every point on one tilted plane).  Inliers are the true projections plus Gaussian
+    noise of noise_px; a fraction outlier_frac of the points is moved to a random pixel of the second image.
+    Returns dict(pts_from, pts_to [n][2] f32, K (f32 fx, fy, cx, cy), R [3][3], t [3] (unit), inlier [n] bool)."""
+    rng = np.random.default_rng([0x905E, POSE_MOTIONS.index(motion), int(seed)])
+    K = np.array([700.0, 700.0, width / 2.0, height / 2.0], np.float32)
+    fx, fy, cx, cy = (float(k) for k in K)
+    aa = {"forward": (0.0, 0.02, 0.0), "sideways": (0.0, 0.035, 0.005), "small": (0.01, 0.01, 0.0),
+          "rotation": (0.01, 0.05, 0.0), "planar": (0.01, -0.02, 0.005)}[motion]
+    tv = {"forward": (0.05, 0.02, 1.0), "sideways": (1.0, 0.05, 0.1), "small": (0.3, 0.1, 1.0),
+          "rotation": (0.6, 0.2, 0.4), "planar": (0.3, 0.05, 1.0)}[motion]
+    scale = {"small": 0.02, "rotation": 0.001}.get(motion, 1.0)
+    R = rodrigues(np.array(aa) + rng.normal(0, 0.002, 3))
+    t = np.array(tv) + rng.normal(0, 0.02, 3)
+    t /= np.linalg.norm(t)
+    pf, pt, X = [], [], 0
+    while X < n:
+        m = 2 * n
+        u = np.stack([rng.uniform(0, width, m), rng.uniform(0, height, m)], 1)
+        ray = np.stack([(u[:, 0] - cx) / fx, (u[:, 1] - cy) / fy, np.ones(m)], 1)
+        if motion == "planar":                        # plane n . X = 12 with n tilted towards the camera
+            nrm = np.array([0.1, -0.3, 1.0])
+            depth = 12.0 / (ray @ nrm)
+        else:
+            depth = rng.uniform(4.0, 40.0, m)
+        P1 = ray * depth[:, None]
+        P2 = P1 @ R.T + scale * t
+        ok = (depth > 0.5) & (P2[:, 2] > 0.5)
+        u2 = np.stack([fx * P2[:, 0] / P2[:, 2] + cx, fy * P2[:, 1] / P2[:, 2] + cy], 1)
+        ok &= (u2[:, 0] >= 0) & (u2[:, 0] < width) & (u2[:, 1] >= 0) & (u2[:, 1] < height)
+        pf.append(u[ok])
+        pt.append(u2[ok])
+        X += int(ok.sum())
+    pf, pt = np.concatenate(pf)[:n], np.concatenate(pt)[:n]
+    pf = pf + rng.normal(0, noise_px, pf.shape)
+    pt = pt + rng.normal(0, noise_px, pt.shape)
+    inlier = rng.random(n) >= outlier_frac
+    bad = ~inlier
+    pt[bad] = np.stack([rng.uniform(0, width, bad.sum()), rng.uniform(0, height, bad.sum())], 1)
+    return dict(pts_from=pf.astype(np.float32), pts_to=pt.astype(np.float32), K=K, R=R, t=t, inlier=inlier,
+                width=width, height=height)

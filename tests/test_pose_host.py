@@ -1,0 +1,100 @@
+"""slam::pose::estimate_pose and estimate_pose_with_known_rotation (racing-slam_amd/host/slam_host.cpp) — the C++ host
+mirror of the reference's src/PoseEstimation.h — built against librsgpu and checked against the restatement
+tests/essential_ref.py, including the reference's std::mt19937(0) pairs of the known-rotation form."""
+import importlib
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import essential_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "tests", "host_cpp", "test_pose_host.bin")
+
+
+def build_pose_host(rs):
+    rs.load()
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    srcs = [os.path.join(ROOT, "tests", "host_cpp", "test_pose_host.cpp"), os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.cpp")]
+    deps = srcs + [os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.h"), os.path.join(ROOT, "include", "rsgpu.h"),
+                   os.path.join(ROOT, "racing-slam_amd", "librsgpu.so")]
+    if os.path.exists(BIN) and all(os.path.getmtime(d) <= os.path.getmtime(BIN) for d in deps):
+        return BIN
+    subprocess.check_call([hipcc, "-O2", "-std=c++17", "-Wall", "-o", BIN] + srcs + [
+        "-L" + os.path.join(ROOT, "racing-slam_amd"), "-lrsgpu", "-Wl,-rpath," + os.path.join(ROOT, "racing-slam_amd"), "-lm"])
+    return BIN
+
+
+def mt19937_pairs(n, iterations=200):
+    """std::mt19937(0) with libstdc++'s uniform_int_distribution<size_t>(0, n - 1) (GCC 11 and later: Lemire's
+    nearly divisionless downscaling of the 32-bit outputs), i then j per iteration — an independent statement of what
+    the mirror draws.  numpy's MT19937 with the legacy seeding is std::mt19937's init_genrand."""
+    bg = np.random.MT19937()
+    bg._legacy_seeding(0)
+    rng = n
+
+    def pick():
+        product = int(bg.random_raw()) * rng
+        low = product & 0xFFFFFFFF
+        if low < rng:
+            threshold = ((1 << 32) - rng) % rng
+            while low < threshold:
+                product = int(bg.random_raw()) * rng
+                low = product & 0xFFFFFFFF
+        return product >> 32
+
+    out = []
+    for _ in range(iterations):
+        i = pick()
+        j = pick()
+        out += [i, j]
+    return np.array(out, np.int64)
+
+
+def test_pose_host_mirror_compiles(rs):
+    assert os.path.exists(build_pose_host(rs))
+
+
+def _parse(lines):
+    status, count = (int(v) for v in lines[0].split())
+    pose = np.array([int(v, 16) for v in lines[1].split()], np.uint32).view(np.float32).reshape(4, 4)
+    idx = np.array([int(v) for v in lines[2].split()], np.int64)
+    assert len(idx) == count
+    return status, pose, idx
+
+
+@pytest.mark.gpu
+def test_host_pose_matches_the_restatement(rs, tmp_path):
+    exe = build_pose_host(rs)
+    synth = importlib.import_module("racing-slam_amd").synth
+    d = synth.make_pose_pair(5, 1500, 0.3, 0.5, "forward")
+    n, K = len(d["pts_from"]), d["K"]
+    Rm = d["R"].astype(np.float32)
+    (tmp_path / "meta.txt").write_text(f"{n} " + " ".join(repr(float(k)) for k in K) + "\n")
+    for name, arr in [("from.f32", d["pts_from"]), ("to.f32", d["pts_to"]), ("rot.f32", Rm)]:
+        np.ascontiguousarray(arr, np.float32).tofile(str(tmp_path / name))
+    r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    lines = (tmp_path / "out.txt").read_text().split("\n")
+    # estimate_pose: 1000 hypotheses, seed 0, 1 px, 0.99
+    status, pose, idx = _parse(lines[0:3])
+    ref = R.estimate_pose(d["pts_from"], d["pts_to"], K)
+    assert status == ref["status"] == 0
+    assert np.allclose(pose, ref["pose"], atol=1e-5)
+    x1, y1 = R.normalise(d["pts_from"], K)
+    x2, y2 = R.normalise(d["pts_to"], K)
+    near = np.abs(R.sampson(ref["E"], x1, y1, x2, y2) - ref["thr2"]) <= 1e-9 * ref["thr2"]
+    mask = np.zeros(n, bool)
+    mask[idx] = True
+    assert np.array_equal(mask[~near], ref["inlier"].astype(bool)[~near]) and np.all(np.diff(idx) > 0)
+    # the reference's pairs, then the known-rotation form on them
+    pairs = np.array([int(v) for v in lines[6].split()], np.int64)
+    assert np.array_equal(pairs, mt19937_pairs(n))
+    status, pose, idx = _parse(lines[3:6])
+    ref = R.estimate_pose_known_rotation(d["pts_from"], d["pts_to"], K, Rm, pairs.reshape(-1, 2))
+    assert status == ref["status"] == 0
+    assert np.allclose(pose, ref["pose"], atol=2e-6) and np.array_equal(pose[:3, :3], Rm)
+    assert np.array_equal(idx, np.flatnonzero(ref["inlier"]))
