@@ -868,7 +868,8 @@ int rs_estimate_pose(rs_context* ctx, rs_pose_estimator* est, const float* d_pts
 /* estimate_pose_with_known_rotation (:110-227) in f32 with the same outputs: n points (host count), h_rotation [9]
  * row-major, d_pairs [n_iter][2] (the reference draws 200 with std::mt19937(0) and uniform_int_distribution<size_t>;
  * a pair with i == j, or an index outside [0, n), is skipped), max_epipolar_px (2.0 in the reference), focal = fx.
- * Status 1 = fewer than 8 points, 2 = best support below 8; both leave the pose [R | 0].  The refit takes the smallest
+ * Status 1 = fewer than 8 points, 2 = best support below 8; both leave the pose [R | 0].  With fewer than 8 points no
+ * pair is evaluated: rs_pose_estimator_stats reports drawn = 0 and rs_pose_hypotheses an all -1 table.  The refit takes the smallest
  * eigenvector of the f64 normal matrix of the inlier constraints (the reference: JacobiSVD of the stack).  n_iter
  * 1 .. the estimator's max_hypotheses. */
 int rs_estimate_pose_known_rotation(rs_context* ctx, rs_pose_estimator* est, const float* d_pts_from, const int32_t* d_from_index,

@@ -19,6 +19,7 @@
 // rs_estimate_pose_known_rotation: kr_prep, kr_support (one workgroup per pair), kr_final (one workgroup).
 // No float atomics: two calls with the same inputs write the same bytes.
 #include <algorithm>
+#include <climits>
 #include <cmath>
 
 #include "common.h"
@@ -29,10 +30,15 @@
 #define POSE_ROUND 256
 #define POSE_MAX_DRAWS 64
 #define POSE_PIVOT_EPS 1e-12
-#define POSE_TRIM_EPS 1e-12
-#define POSE_REM_EPS 1e-14
-#define POSE_STURM_ITERS 100
+// The real roots of the degree-10 determinant (tests/essential_ref.real_roots): a leading coefficient below
+// POSE_TRIM_EPS of the largest is dropped (roots beyond ~1e30); the roots of p's derivatives isolate those of p, level by
+// level, and each isolated root takes POSE_BISECT_ITERS halvings of its interval's ordered 64-bit keys (any f64 interval
+// closes to two adjacent doubles, whatever the root's magnitude), then POSE_NEWTON guarded Newton steps.  A model is
+// kept only if its unit-norm E satisfies max |2 E E^T E - tr(E E^T) E| <= POSE_ESS_EPS.
+#define POSE_TRIM_EPS 1e-30
+#define POSE_BISECT_ITERS 64
 #define POSE_NEWTON 3
+#define POSE_ESS_EPS 1e-6
 #define POSE_LO_ROUNDS 4
 #define POSE_SWEEPS 16
 #define POSE_JACOBI_TOL 1e-30       // a sweep starts only while sum(off-diagonal^2) > 1e-30 sum(diagonal^2)
@@ -171,21 +177,24 @@ __device__ __forceinline__ void pmul(const double* a, int na, const double* b, i
         for (int j = 0; j < nb; j++) out[i + j] = out[i + j] + a[i] * b[j];
 }
 
-// sign changes of the Sturm sequence seq [nseq][11] (lengths len[]) at x
-__device__ __forceinline__ int sturm_changes(const double* seq, const int* len, int nseq, double x)
+// the sign of the degree-j polynomial c (ascending) at x
+__device__ __forceinline__ int poly_sign(const double* c, int j, double x)
 {
-    int cnt = 0, prev = 0;
-    for (int i = 0; i < nseq; i++) {
-        const double* s = seq + 11 * i;
-        double v = s[len[i] - 1];
-        for (int k = len[i] - 2; k >= 0; k--) v = v * x + s[k];
-        const int sg = (v > 0.0) - (v < 0.0);
-        if (sg != 0) {
-            if (prev != 0 && sg != prev) cnt++;
-            prev = sg;
-        }
-    }
-    return cnt;
+    double v = c[j];
+    for (int k = j - 1; k >= 0; k--) v = v * x + c[k];
+    return (v > 0.0) - (v < 0.0);
+}
+
+// f64 <-> int64 keys in the order of the values (+0 and -0 both 0)
+__device__ __forceinline__ long long dkey(double x)
+{
+    const long long i = __double_as_longlong(x);
+    return i < 0 ? LLONG_MIN - i : i;
+}
+
+__device__ __forceinline__ double dunkey(long long k)
+{
+    return __longlong_as_double(k < 0 ? LLONG_MIN - k : k);
 }
 
 __device__ __forceinline__ double horner_up(const double* c, int n, double z)
@@ -405,10 +414,10 @@ struct HypLds {
     double EE[6][10];
     double minor[3][10];
     double bx[3][4], by[3][4], b1[3][5];
-    double seq[11 * 11];
-    int len[11];
+    double D[11 * 11];                  // D[r] = the r-th derivative of the scaled determinant, ascending
+    double rt[2][10];                   // the roots of the level below / of this level
     double bound;
-    int nseq, nroot, ok;
+    int deg, ok;
     int idx[5];
 };
 
@@ -511,8 +520,7 @@ __global__ __launch_bounds__(64) void pose_hyp(int round, int max_hyp, unsigned 
         good = wave_gauss_jordan(L.A, 10, 20, 10, lane);
     }
     if (lane == 0) {
-        L.nroot = 0;
-        L.nseq = 0;
+        L.deg = 0;
         if (good) {
             // B(z): rows (4, 5), (6, 7), (8, 9) of the reduced system
             for (int q = 0; q < 3; q++) {
@@ -532,71 +540,63 @@ __global__ __launch_bounds__(64) void pose_hyp(int round, int max_hyp, unsigned 
             for (int k = 0; k < 7; k++) c2[k] = t0[k] - t1[k];
             pmul(L.bx[0], 4, c0, 8, u0); pmul(L.by[0], 4, c1, 8, u1); pmul(L.b1[0], 5, c2, 7, u2);
             for (int k = 0; k < 11; k++) p[k] = (u0[k] - u1[k]) + u2[k];
-            // the Sturm sequence (tests/essential_ref.sturm_sequence)
+            // scaled, trimmed; the derivative table and the root bound (tests/essential_ref.real_roots)
             double m = 0.0;
             for (int k = 0; k < 11; k++) m = fmax(m, fabs(p[k]));
-            int d = -1;
             if (m > 0.0 && isfinite(m)) {
                 for (int k = 0; k < 11; k++) p[k] = p[k] / m;
-                d = 10;
+                int d = 10;
                 while (d > 0 && fabs(p[d]) < POSE_TRIM_EPS) d--;
-            }
-            for (int k = 0; k < 121; k++) L.seq[k] = 0.0;
-            if (d > 0) {
-                for (int k = 0; k <= d; k++) L.seq[k] = p[k];
-                L.len[0] = d + 1;
-                double mm = 0.0;
-                for (int k = 0; k < d; k++) mm = fmax(mm, fabs((double)(k + 1) * p[k + 1]));
-                for (int k = 0; k < d; k++) L.seq[11 + k] = (double)(k + 1) * p[k + 1] / mm;
-                L.len[1] = d;
-                int ns = 2;
-                while (L.len[ns - 1] > 1 && ns < 11) {
-                    const double* a = L.seq + 11 * (ns - 2);
-                    const double* b = L.seq + 11 * (ns - 1);
-                    const int la = L.len[ns - 2], db = L.len[ns - 1] - 1;
-                    double r[11];
-                    for (int k = 0; k < la; k++) r[k] = a[k];
-                    for (int k = la - 1 - db; k >= 0; k--) {
-                        const double qq = r[db + k] / b[db];
-                        for (int j = 0; j <= db; j++) r[j + k] = r[j + k] - qq * b[j];
-                    }
-                    double rm = 0.0;
-                    for (int k = 0; k < db; k++) rm = fmax(rm, fabs(r[k]));
-                    if (!(rm > POSE_REM_EPS)) break;
-                    int lr = db;
-                    for (int k = 0; k < db; k++) r[k] = -r[k] / rm;
-                    while (lr > 1 && fabs(r[lr - 1]) < POSE_REM_EPS) lr--;
-                    for (int k = 0; k < lr; k++) L.seq[11 * ns + k] = r[k];
-                    L.len[ns] = lr;
-                    ns++;
+                for (int k = d + 1; k < 11; k++) p[k] = 0.0;
+                for (int k = 0; k < 11; k++) L.D[k] = p[k];
+                for (int r = 0; r < 10; r++) {
+                    for (int k = 0; k < 10; k++) L.D[11 * (r + 1) + k] = (double)(k + 1) * L.D[11 * r + k + 1];
+                    L.D[11 * (r + 1) + 10] = 0.0;
                 }
-                L.nseq = ns;
                 double bnd = 0.0;
                 for (int k = 0; k < d; k++) bnd = fmax(bnd, fabs(p[k] / p[d]));
                 L.bound = 1.0 + bnd;
-                const int nr = sturm_changes(L.seq, L.len, ns, -L.bound) - sturm_changes(L.seq, L.len, ns, L.bound);
-                L.nroot = min(max(nr, 0), 10);
+                L.deg = d;
             }
         }
     }
     __syncthreads();
-    const int nroot = L.nroot;
+    // level j = 1 .. d: the roots of D[d - j] (degree j), one lane per interval between the roots of the level below
+    const int deg = L.deg;
+    const double B = L.bound;
+    int nroot = 0;
+    for (int j = 1; j <= deg; j++) {
+        const double* q = L.D + 11 * (deg - j);
+        const double* rt = L.rt[(j - 1) & 1];
+        bool has = false;
+        double z = 0.0;
+        if (lane <= nroot) {
+            const double a = lane == 0 ? -B : rt[lane - 1], b = lane == nroot ? B : rt[lane];
+            const int sa = poly_sign(q, j, a), sb = poly_sign(q, j, b);
+            if (sa != 0 && sb != sa) {
+                has = true;
+                long long lo = dkey(a), hi = dkey(b);
+                for (int it = 0; it < POSE_BISECT_ITERS; it++) {
+                    const long long mid = ((lo >> 1) + (hi >> 1)) + (lo & hi & 1ll);
+                    if (poly_sign(q, j, dunkey(mid)) == sa) lo = mid; else hi = mid;
+                }
+                z = dunkey(hi);
+            }
+        }
+        const unsigned long long hb = __ballot(has);
+        if (has) L.rt[j & 1][__popcll(hb & ((1ull << lane) - 1ull))] = z;
+        nroot = __popcll(hb);
+        __syncthreads();
+    }
     bool valid = false;
     double e[9];
     if (lane < nroot) {                               // one lane per root: the (lane + 1)-th smallest
-        const double B = L.bound;
-        const int vlo = sturm_changes(L.seq, L.len, L.nseq, -B);
-        double lo = -B, hi = B;
-        for (int it = 0; it < POSE_STURM_ITERS; it++) {
-            const double mid = 0.5 * (lo + hi);
-            if (vlo - sturm_changes(L.seq, L.len, L.nseq, mid) >= lane + 1) hi = mid; else lo = mid;
-        }
-        double z = 0.5 * (lo + hi);
+        double z = L.rt[deg & 1][lane];
         for (int it = 0; it < POSE_NEWTON; it++) {
             double v = 0.0, dv = 0.0;
             for (int c = 10; c >= 0; c--) {
                 dv = dv * z + v;
-                v = v * z + L.seq[c];
+                v = v * z + L.D[c];
             }
             const double zn = z - v / dv;
             if (dv != 0.0 && isfinite(zn) && fabs(zn - z) <= 1e-6 * (1.0 + fabs(z))) z = zn;
@@ -624,8 +624,18 @@ __global__ __launch_bounds__(64) void pose_hyp(int round, int max_hyp, unsigned 
             }
             nn = sqrt(nn);
             if (nn > 0.0 && isfinite(nn)) {
-                valid = true;
                 for (int i = 0; i < 9; i++) e[i] = e[i] / nn;
+                // the essential-matrix identity (tests/essential_ref.essential_residual): a model that fails it is dropped
+                double EE[9], res = 0.0;
+                for (int a = 0; a < 3; a++)
+                    for (int b = 0; b < 3; b++) EE[3 * a + b] = (e[3 * a] * e[3 * b] + e[3 * a + 1] * e[3 * b + 1]) + e[3 * a + 2] * e[3 * b + 2];
+                const double tr = (EE[0] + EE[4]) + EE[8];
+                for (int a = 0; a < 3; a++)
+                    for (int b = 0; b < 3; b++) {
+                        const double v = ((EE[3 * a] * e[b] + EE[3 * a + 1] * e[3 + b]) + EE[3 * a + 2] * e[6 + b]) * 2.0 - tr * e[3 * a + b];
+                        res = fmax(res, fabs(v));
+                    }
+                valid = res <= POSE_ESS_EPS;
             }
         }
     }

@@ -620,22 +620,27 @@ def make_refine_problem(n=600, seed=0, outlier_frac=0.0, noise_px=0.0, rot0=None
 POSE_MOTIONS = ("forward", "sideways", "small", "rotation", "planar")
 
 
-def make_pose_pair(seed=0, n=2000, outlier_frac=0.3, noise_px=0.5, motion="forward", width=1280, height=720):
+def make_pose_pair(seed=0, n=2000, outlier_frac=0.3, noise_px=0.5, motion="forward", width=1280, height=720, K=None,
+                   rotvec=None, epipole_points=0):
     """Matched pixels of two views for the relative-pose stage (pose::estimate_pose, src/PoseEstimation.cpp:59-88) with a
     known motion X2 = R X1 + t.  motion: "forward" (the dash-cam case: t mostly along the optical axis, the epipole
     inside the image), "sideways", "small" (a baseline of 2 cm against depths of 4 .. 40 m), "rotation" (3 degrees with a
     baseline of 1 mm) or "planar" (every point on one tilted plane).  Inliers are the true projections plus Gaussian
     noise of noise_px; a fraction outlier_frac of the points is moved to a random pixel of the second image.
+    Knobs (the defaults give the arrays of the plain call): K = (fx, fy, cx, cy) replaces the intrinsics (700, 700, centre);
+    rotvec replaces the motion's axis-angle rotation (radians, before the same jitter); epipole_points > 0 puts the last
+    epipole_points matches exactly on the epipoles (the other camera's centre seen from each view, noise-free, inliers),
+    where E x1 = E^T x2 = 0 and the Sampson denominator vanishes.
     Returns dict(pts_from, pts_to [n][2] f32, K (f32 fx, fy, cx, cy), R [3][3], t [3] (unit), inlier [n] bool)."""
     rng = np.random.default_rng([0x905E, POSE_MOTIONS.index(motion), int(seed)])
-    K = np.array([700.0, 700.0, width / 2.0, height / 2.0], np.float32)
+    K = np.array([700.0, 700.0, width / 2.0, height / 2.0] if K is None else K, np.float32)
     fx, fy, cx, cy = (float(k) for k in K)
     aa = {"forward": (0.0, 0.02, 0.0), "sideways": (0.0, 0.035, 0.005), "small": (0.01, 0.01, 0.0),
           "rotation": (0.01, 0.05, 0.0), "planar": (0.01, -0.02, 0.005)}[motion]
     tv = {"forward": (0.05, 0.02, 1.0), "sideways": (1.0, 0.05, 0.1), "small": (0.3, 0.1, 1.0),
           "rotation": (0.6, 0.2, 0.4), "planar": (0.3, 0.05, 1.0)}[motion]
     scale = {"small": 0.02, "rotation": 0.001}.get(motion, 1.0)
-    R = rodrigues(np.array(aa) + rng.normal(0, 0.002, 3))
+    R = rodrigues(np.array(aa if rotvec is None else rotvec, np.float64) + rng.normal(0, 0.002, 3))
     t = np.array(tv) + rng.normal(0, 0.02, 3)
     t /= np.linalg.norm(t)
     pf, pt, X = [], [], 0
@@ -662,5 +667,11 @@ def make_pose_pair(seed=0, n=2000, outlier_frac=0.3, noise_px=0.5, motion="forwa
     inlier = rng.random(n) >= outlier_frac
     bad = ~inlier
     pt[bad] = np.stack([rng.uniform(0, width, bad.sum()), rng.uniform(0, height, bad.sum())], 1)
+    if epipole_points:
+        c1 = -R.T @ t                                 # camera 2's centre in camera 1, and camera 1's in camera 2 (= t)
+        k = int(epipole_points)
+        pf[-k:] = (fx * c1[0] / c1[2] + cx, fy * c1[1] / c1[2] + cy)
+        pt[-k:] = (fx * t[0] / t[2] + cx, fy * t[1] / t[2] + cy)
+        inlier[-k:] = True
     return dict(pts_from=pf.astype(np.float32), pts_to=pt.astype(np.float32), K=K, R=R, t=t, inlier=inlier,
                 width=width, height=height)

@@ -15,9 +15,11 @@ from OpenCV:
               with fewer than 5 indices after MAX_DRAWS draws yields no model.
   solver      Nister's five-point method: the 5 x 9 system's null space by Gauss-Jordan with partial pivoting, the
               10 x 20 cubic constraints (det E = 0, 2 E E^T E - tr(E E^T) E = 0) in Nister's monomial order,
-              Gauss-Jordan again, the 3 x 3 matrix B(z) and its degree-10 determinant; the real roots by Sturm
-              sequences and bisection (STURM_ITERS halvings), then NEWTON_STEPS guarded Newton steps; x, y from the
-              largest cross product of two rows of B(z).  Up to 10 models per sample, each of unit Frobenius norm.
+              Gauss-Jordan again, the 3 x 3 matrix B(z) and its degree-10 determinant; the real roots
+              isolated by the roots of its derivatives and found by bisection of 64-bit keys (real_roots), then
+              NEWTON_STEPS guarded Newton steps; x, y from the largest cross product of two rows of B(z).  Up to 10
+              models per sample, each of unit Frobenius norm; a model whose max |2 E E^T E - tr(E E^T) E| exceeds
+              ESS_EPS is dropped (an ill-conditioned elimination, e.g. a near-pure rotation).
               A rank-deficient sample (a pivot <= PIVOT_EPS * max |entry|) or a polynomial with no real roots yields
               0 models.
   score       the integer inlier count.  The best model has the highest count, ties to the lowest index
@@ -44,10 +46,10 @@ import numpy as np
 
 MAX_DRAWS = 64
 PIVOT_EPS = 1e-12
-TRIM_EPS = 1e-12
-REM_EPS = 1e-14
-STURM_ITERS = 100
+TRIM_EPS = 1e-30            # a leading coefficient below TRIM_EPS * max |coefficient| is dropped
+BISECT_ITERS = 64           # halvings of 64-bit keys: any f64 interval closes to two adjacent doubles
 NEWTON_STEPS = 3
+ESS_EPS = 1e-6              # a unit-norm model is kept only if max |2 E E^T E - tr(E E^T) E| <= ESS_EPS
 ROUND = 256
 LO_ROUNDS = 4
 JACOBI_SWEEPS = 16
@@ -56,6 +58,7 @@ THREADS = 256               # pose_final's workgroup: the reduction order of the
 STATUS_OK, STATUS_FEW_POINTS, STATUS_FAILED = 0, 1, 2
 
 M64 = (1 << 64) - 1
+I64_MIN = np.int64(-(1 << 63))
 
 # ------------------------------------------------------------------------------------------------ monomials
 B1 = [(1, 0, 0), (0, 1, 0), (0, 0, 1), (0, 0, 0)]                                   # x, y, z, 1
@@ -238,113 +241,114 @@ def det_poly(bx, by, b1):
     return (_pmul(bx[0], c0) - _pmul(by[0], c1)) + _pmul(b1[0], c2)
 
 
-def sturm_sequence(p):
-    """One sample (python floats): the Sturm sequence of p (11 coefficients ascending) as [11][11] zero-padded rows,
-    each scaled by its largest |coefficient|, and the trimmed degree of p (-1: no usable polynomial)."""
-    S = np.zeros((11, 11))
-    p = [float(v) for v in p]
-    m = 0.0
-    for v in p:
-        m = max(m, abs(v))
-    if not (m > 0.0 and math.isfinite(m)):
-        return S, -1
-    p = [v / m for v in p]
-    d = 10
-    while d > 0 and abs(p[d]) < TRIM_EPS:
-        d -= 1
-    if d == 0:
-        return S, 0
-    seq = [p[:d + 1]]
-    dp = [(k + 1) * p[k + 1] for k in range(d)]
-    m = 0.0
-    for v in dp:
-        m = max(m, abs(v))
-    seq.append([v / m for v in dp])
-    while len(seq[-1]) > 1 and len(seq) < 11:
-        a, b = seq[-2], seq[-1]
-        r = list(a)
-        db = len(b) - 1
-        for k in range(len(a) - 1 - db, -1, -1):
-            q = r[db + k] / b[db]
-            for j in range(db + 1):
-                r[j + k] = r[j + k] - q * b[j]
-        r = r[:db]
-        m = 0.0
-        for v in r:
-            m = max(m, abs(v))
-        if not (m > REM_EPS):
-            break
-        r = [-v / m for v in r]
-        while len(r) > 1 and abs(r[-1]) < REM_EPS:
-            r.pop()
-        seq.append(r)
-    for i, s in enumerate(seq):
-        S[i, :len(s)] = s
-    return S, d
+def _key(x):
+    """f64 -> int64 keys in the order of the values (+0 and -0 both 0): halving an interval of keys halves the number
+    of doubles in it, whatever their magnitude."""
+    i = np.asarray(x, np.float64).view(np.int64)
+    return np.where(i < 0, I64_MIN - i, i)
 
 
-def _horner(S, x):
-    """S [..., 11] coefficients ascending, x broadcast; top-down Horner over all 11 (zero padding is exact)."""
-    v = np.zeros(np.broadcast_shapes(S.shape[:-1], np.shape(x)))
+def _unkey(k):
+    k = np.asarray(k, np.int64)
+    return np.where(k < 0, I64_MIN - k, k).view(np.float64)
+
+
+def _horner(c, x):
+    """c [..., 11] coefficients ascending, x [...]; top-down Horner over all 11 (zero padding is exact)."""
+    v = np.zeros(np.shape(x))
     for k in range(10, -1, -1):
-        v = v * x + S[..., k]
+        v = v * x + c[..., k]
     return v
 
 
-def _changes(S, x):
-    """Sign changes of the Sturm sequence S [..., 11 members, 11] at x [...]: zeros are skipped."""
-    vals = _horner(S, x[..., None])
-    sg = np.sign(vals)
-    cnt = np.zeros(x.shape, np.int64)
-    prev = np.zeros(x.shape)
-    for i in range(S.shape[-2]):
-        s = sg[..., i]
-        cnt += ((s != 0) & (prev != 0) & (s != prev)).astype(np.int64)
-        prev = np.where(s != 0, s, prev)
-    return cnt
-
-
 def real_roots(polys):
-    """polys [S][11] -> roots [S][10] (ascending, NaN-padded), count [S]."""
+    """polys [S][11] -> roots [S][10] (ascending, NaN-padded), count [S].
+
+    p is scaled by its largest |coefficient|; leading coefficients below TRIM_EPS are dropped (roots beyond ~1 / TRIM_EPS)
+    and B = 1 + max |p_k / p_d| bounds every real root of p and of its derivatives (Gauss-Lucas).  The roots of the
+    derivatives isolate those of p: level j = 1 .. d takes D = p^(d - j), of degree j; the roots of the level below
+    (ascending) and -B, B cut [-B, B] into intervals on which D is monotonic, and an interval whose left end has a
+    non-zero sign and whose right end has another sign (or zero) holds exactly one root.  It is found by BISECT_ITERS
+    halvings of the interval's ordered-integer keys (the right end: the first double whose sign differs from the left
+    end's).  The roots of p then take NEWTON_STEPS guarded Newton steps."""
+    polys = np.asarray(polys, np.float64)
     S = len(polys)
-    seqs = np.zeros((S, 11, 11))
+    m = np.abs(polys).max(axis=1)
+    good = (m > 0.0) & np.isfinite(m)
+    p = polys / np.where(good, m, 1.0)[:, None]
+    p[~good] = 0.0
+    d = np.full(S, 10)
+    for _ in range(10):
+        trim = (d > 0) & (np.abs(p[np.arange(S), d]) < TRIM_EPS)
+        d = np.where(trim, d - 1, d)
+    p[np.arange(11)[None, :] > d[:, None]] = 0.0
+    d[~good] = 0
     bound = np.zeros(S)
     for s in range(S):
-        seqs[s], d = sturm_sequence(polys[s])
-        if d > 0:
-            p = seqs[s, 0]
-            b = 0.0
-            for k in range(d):
-                b = max(b, abs(p[k] / p[d]))
-            bound[s] = 1.0 + b
-    lo0 = -bound
-    v_lo = _changes(seqs, lo0)
-    nroot = np.clip(v_lo - _changes(seqs, bound), 0, 10)
-    nroot[bound == 0] = 0
-    k = np.arange(10)[None, :]
-    lo = np.repeat(lo0[:, None], 10, 1)
-    hi = np.repeat(bound[:, None], 10, 1)
-    sq = np.repeat(seqs[:, None], 10, 1)
-    vl = v_lo[:, None]
-    for _ in range(STURM_ITERS):
-        mid = 0.5 * (lo + hi)
-        up = (vl - _changes(sq, mid)) >= k + 1
-        hi = np.where(up, mid, hi)
-        lo = np.where(up, lo, mid)
-    z = 0.5 * (lo + hi)
-    p = seqs[:, None, 0, :]
+        if d[s] > 0:
+            bound[s] = 1.0 + np.abs(p[s, :d[s]] / p[s, d[s]]).max()
+    D = np.zeros((S, 11, 11))                        # D[s, r] = the r-th derivative of p, ascending
+    D[:, 0] = p
+    for r in range(10):
+        for k in range(10):
+            D[:, r + 1, k] = float(k + 1) * D[:, r, k + 1]
+    roots = np.full((S, 10), np.nan)
+    nroot = np.zeros(S, np.int64)
+    ar = np.arange(S)
+    icol = np.arange(10)[None, :]
+    for j in range(1, 11):
+        act = d >= j
+        q = D[ar, np.maximum(d - j, 0)]                                          # [S][11]
+        ends = np.full((S, 11), np.nan)
+        ends[:, 0] = -bound
+        ends[:, 1:] = roots
+        ends[ar, nroot + 1] = bound
+        a, b = ends[:, :10], ends[:, 1:]
+        live = act[:, None] & (icol <= nroot[:, None])
+        a, b = np.where(live, a, 0.0), np.where(live, b, 0.0)
+        qb = q[:, None, :]
+        sa, sb = np.sign(_horner(qb, a)), np.sign(_horner(qb, b))
+        has = live & (sa != 0) & (sb != sa)
+        lo, hi = _key(a), _key(b)
+        for _ in range(BISECT_ITERS):
+            mid = ((lo >> 1) + (hi >> 1)) + (lo & hi & 1)
+            same = np.sign(_horner(qb, _unkey(mid))) == sa
+            lo = np.where(same, mid, lo)
+            hi = np.where(same, hi, mid)
+        z = np.where(has, _unkey(hi), np.nan)
+        order = np.argsort(~has, axis=1, kind="stable")
+        nz = np.take_along_axis(z, order, 1)
+        nz[icol >= has.sum(1)[:, None]] = np.nan
+        roots = np.where(act[:, None], nz, roots)
+        nroot = np.where(act, has.sum(1), nroot)
+    z = np.where(np.isnan(roots), 0.0, roots)
+    pc = p[:, None, :]
     for _ in range(NEWTON_STEPS):
         v = np.zeros(z.shape)
         dv = np.zeros(z.shape)
         for c in range(10, -1, -1):
             dv = dv * z + v
-            v = v * z + p[..., c]
+            v = v * z + pc[..., c]
         with np.errstate(divide="ignore", invalid="ignore"):
             zn = z - v / dv
         ok = (dv != 0) & np.isfinite(zn) & (np.abs(zn - z) <= 1e-6 * (1.0 + np.abs(z)))
         z = np.where(ok, zn, z)
-    z = np.where(k < nroot[:, None], z, np.nan)
+    z = np.where(icol < nroot[:, None], z, np.nan)
     return z, nroot
+
+
+def essential_residual(e):
+    """max |2 E E^T E - tr(E E^T) E| of a row-major E [9] (python floats), in pose_hyp's order of operations.  Zero
+    exactly when E's singular values are (s, s, 0): the cubic implies det E = 0."""
+    EE = [[(e[3 * i] * e[3 * j] + e[3 * i + 1] * e[3 * j + 1]) + e[3 * i + 2] * e[3 * j + 2] for j in range(3)]
+          for i in range(3)]
+    tr = (EE[0][0] + EE[1][1]) + EE[2][2]
+    r = 0.0
+    for i in range(3):
+        for j in range(3):
+            v = ((EE[i][0] * e[j] + EE[i][1] * e[3 + j]) + EE[i][2] * e[6 + j]) * 2.0 - tr * e[3 * i + j]
+            r = max(r, abs(v))
+    return r
 
 
 def five_point(x1, y1, x2, y2):
@@ -382,7 +386,10 @@ def five_point(x1, y1, x2, y2):
             nn = math.sqrt(nn)
             if not (nn > 0.0 and math.isfinite(nn)):
                 continue
-            models[s, count[s]] = [v / nn for v in e]
+            e = [v / nn for v in e]
+            if not (essential_residual(e) <= ESS_EPS):
+                continue
+            models[s, count[s]] = e
             count[s] += 1
     return models, count
 
@@ -735,7 +742,7 @@ def estimate_pose_known_rotation(pix_from, pix_to, K, R, pairs, max_epipolar_px=
     cons = _cross_f32(_matvec_f32(R, fr), to)
     best_t, best_s, best_it = np.array([0, 0, 1], np.float32), 0, -1
     for it, (i, j) in enumerate(pairs):
-        if i == j:
+        if i == j or not (0 <= i < n and 0 <= j < n):               # out of range: skipped, as the kernel does
             continue
         tr = _cross_f32(cons[i], cons[j])
         nrm = np.sqrt(np.float32((tr[0] * tr[0] + tr[1] * tr[1]) + tr[2] * tr[2]))

@@ -76,7 +76,7 @@ def test_sturm_roots_match_np_roots():
         if len(rr) == len(mine) and np.allclose(mine, rr, rtol=1e-6, atol=1e-9):
             agree += 1
     assert not bad.any() and not bad2.any()
-    assert agree >= 95                                      # np.roots' companion eigenvalues blur near-double roots
+    assert agree == 100                                     # recorded: 100 (95 before the derivative cascade)
 
 
 def test_sampler_is_deterministic_distinct_and_uniform():
