@@ -130,8 +130,18 @@ __global__ __launch_bounds__(64) void ba_imu_factors(BaDims d, BaBufs b)
 
 // ---------------------------------------------------------------------------------------------- K6b
 #define KCH 84                  // z rows per staged chunk (a multiple of 4: MFMA k-steps): two passes for 18 cameras
-#define KLD 116                 // row stride of a staged chunk (>= 16 * tiles per side; n + 1 <= 112)
-#define KTW 4                   // output tiles per wave (28 upper-triangular tiles of 16 x 16 over 8 waves)
+#define KLD 144                 // row stride of a staged chunk (>= 16 * tiles per side: n + 1 <= 127, 8 tiles; an odd
+                                // multiple of 16 doubles, so that the rows of lane quarters 0 / 1 lie 32 banks apart)
+#define KTW 5                   // output tiles per wave (36 upper-triangular tiles of 16 x 16 over 8 waves at n = 126)
+#define KT16 ((BA_MAX_LDS_N + 1 + 15) / 16)                    // tiles per side of the largest pose system
+static_assert(KLD >= 16 * KT16, "a staged row must hold every column an MFMA tile reads");
+static_assert(16 * KT16 <= KI_THREADS / 4, "the staging threads (column tid & 127) cover every column a tile reads");
+static_assert(8 * KTW >= KT16 * (KT16 + 1) / 2, "the eight waves' tile slots must cover the upper triangle of tiles");
+static_assert(KCH % 4 == 0 && KCH % 28 == 0, "KCH: whole MFMA k-steps, staged as 4 row groups x 7 loads");
+static_assert(6 * IMU_MAXCI <= BA_MAX_LDS_N, "inertial cameras are optimised cameras of a window the LDS K7 takes");
+// K6b's static LDS: Hd, Ho, gz, dinv, st, s_red, s_fail (+ up to 8 B of alignment per array)
+#define K6B_STATIC_LDS (sizeof(double) * ((2 * 81 + 18) * IMU_MAXCI + KI_THREADS / 64) + sizeof(BaState) + sizeof(int) + 7 * 8)
+static_assert(sizeof(double) * KCH * KLD + K6B_STATIC_LDS <= 160 * 1024, "K6b's LDS: the staged chunk and the static arrays");
 __global__ __launch_bounds__(KI_THREADS) void ba_imu_eliminate(BaDims d, BaBufs b, BaOpt opt)
 {
     extern __shared__ __attribute__((aligned(16))) double dyn[];      // [KCH][KLD]: chunk of W
@@ -249,7 +259,7 @@ __global__ __launch_bounds__(KI_THREADS) void ba_imu_eliminate(BaDims d, BaBufs 
         typedef __attribute__((ext_vector_type(4))) double d4;
         double* Wc = dyn;
         const int lr = lane & 15, lq = lane >> 4;
-        const int nt16 = (n + 1 + 15) / 16;                 // tiles per side (n = 108: 7)
+        const int nt16 = (n + 1 + 15) / 16;                 // tiles per side (n = 108: 7; n = 114 .. 126: 8)
         // this wave's tiles: t = wave, wave + 8, ... over the (tr <= tc) list
         int tr[KTW], tc[KTW];
         bool tv[KTW];

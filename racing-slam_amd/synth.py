@@ -194,7 +194,9 @@ def make_ba_window(n_kf=20, n_points=10000, config_id=3, seed_stream=0, n_fixed=
                 run_len=run_len.astype(np.int32))
 
 
-def make_imu(window, seed=11, duration=0.5, sigma_rot=2e-3, sigma_vel=2e-2, sigma_pos=1e-2, skip=()):
+def make_imu(window, seed=11, duration=0.5, sigma_rot=2e-3, sigma_vel=2e-2, sigma_pos=1e-2, skip=(), pairs=None,
+             durations=None, shuffle=None, cov_scale=1.0, cov_cond=None, gyro_bias_sigma=2.78e-5, accel_bias_sigma=2.79e-3,
+             zero_bias_jacobian=False):
     """Synthetic IMU factor pairs for a BA window (reference src/Optimization.cpp:317-346): one per pair of consecutive
     FREE cameras (pairs listed in `skip` are left out, like a gap with fewer than two samples), consistent with the
     ground-truth trajectory up to noise:
@@ -202,7 +204,16 @@ def make_imu(window, seed=11, duration=0.5, sigma_rot=2e-3, sigma_vel=2e-2, sigm
     (R = world -> camera; the residual of src/ImuFactor.cpp:66-69 vanishes on them).  Covariances are random SPD
     matrices of realistic scale, the bias Jacobians random, and the current bias estimates differ slightly from the
     biases used at preintegration so that the first-order bias correction (:49-61) is exercised.  Also returns the
-    perturbed initial velocities / biases per camera (cam_velocity [C][3], cam_bias [C][6]) and gravity."""
+    perturbed initial velocities / biases per camera (cam_velocity [C][3], cam_bias [C][6]) and gravity.
+    Envelope knobs (the defaults reproduce the original output bit for bit):
+      pairs               explicit (cam_i, cam_j) list instead of the consecutive free pairs: any two cameras, either
+                          order, repeats allowed (`skip` is not applied)
+      durations           per-factor preintegration time (one per factor; default `duration` for all)
+      shuffle             seed of a permutation of the factor order (velocities / biases are those of the unshuffled list)
+      cov_scale, cov_cond the covariance times cov_scale; cov_cond: its eigenvalues respread geometrically over that
+                          condition number below the largest one (eigenvectors and their order kept)
+      gyro_bias_sigma, accel_bias_sigma  the bias random-walk densities
+      zero_bias_jacobian  all bias Jacobians zero (no first-order bias correction)"""
     rng = np.random.default_rng(0x1A2B0000 + seed)
     cams_true = window["cams_true"]
     C = len(cams_true)
@@ -218,15 +229,27 @@ def make_imu(window, seed=11, duration=0.5, sigma_rot=2e-3, sigma_vel=2e-2, sigm
     free = np.flatnonzero(window["cam_free"])
     fac = dict(cam_i=[], cam_j=[], duration=[], rotation=[], velocity=[], position=[], covariance=[], bias_gyro=[],
                bias_accel=[], bias_jacobian=[])
-    for a, b in zip(free[:-1], free[1:]):
-        if b != a + 1 or (int(a), int(b)) in skip:
-            continue
+    if pairs is None:
+        pairs = [(int(a), int(b)) for a, b in zip(free[:-1], free[1:]) if b == a + 1 and (int(a), int(b)) not in skip]
+    if durations is not None and len(durations) != len(pairs):
+        raise ValueError("one duration per factor")
+    for f, (a, b) in enumerate(pairs):
+        T = float(duration) if durations is None else float(durations[f])
         dR = Rcw[a] @ Rcw[b].T @ rodrigues(rng.normal(0, sigma_rot, 3))
         dv = Rcw[a] @ (v_true[b] - v_true[a] - g * T) + rng.normal(0, sigma_vel, 3)
         dp = Rcw[a] @ (ctr[b] - ctr[a] - v_true[a] * T - 0.5 * g * T * T) + rng.normal(0, sigma_pos, 3)
         A = rng.normal(0, 1, (9, 9)) * np.array([sigma_rot] * 3 + [sigma_vel] * 3 + [sigma_pos] * 3)[:, None] * 0.3
         cov = A @ A.T + np.diag(np.array([sigma_rot] * 3 + [sigma_vel] * 3 + [sigma_pos] * 3) ** 2)
+        if cov_scale != 1.0:
+            cov = cov * cov_scale
+        if cov_cond is not None:
+            ev, Q = np.linalg.eigh(cov)
+            spread = ev[-1] * np.geomspace(1.0 / float(cov_cond), 1.0, 9)      # ascending like eigh's eigenvalues
+            cov = (Q * spread) @ Q.T
+            cov = 0.5 * (cov + cov.T)
         bj = rng.normal(0, 1, (9, 6)) * np.array([T] * 3 + [T] * 3 + [T * T] * 3)[:, None] * 0.5
+        if zero_bias_jacobian:
+            bj = np.zeros_like(bj)
         fac["cam_i"].append(a); fac["cam_j"].append(b); fac["duration"].append(T)
         fac["rotation"].append(dR.reshape(9)); fac["velocity"].append(dv); fac["position"].append(dp)
         fac["covariance"].append(cov.reshape(81)); fac["bias_gyro"].append(rng.normal(0, 1e-3, 3))
@@ -241,7 +264,11 @@ def make_imu(window, seed=11, duration=0.5, sigma_rot=2e-3, sigma_vel=2e-2, sigm
     if nF:
         bias[out["cam_j"][-1]] = bias[out["cam_i"][-1]] + rng.normal(0, 1e-4, 6)
     out.update(cam_velocity=v_true + rng.normal(0, 0.05, (C, 3)), cam_bias=bias, gravity=g, cam_velocity_true=v_true,
-               gyro_bias_sigma=2.78e-5, accel_bias_sigma=2.79e-3)      # imu::NoiseDensity defaults, src/Imu.h:42-49
+               gyro_bias_sigma=gyro_bias_sigma, accel_bias_sigma=accel_bias_sigma)      # defaults: imu::NoiseDensity, src/Imu.h:42-49
+    if shuffle is not None and nF:
+        perm = np.random.default_rng(0x5EED0000 + int(shuffle)).permutation(nF)
+        for k in fac:
+            out[k] = out[k][perm]
     return out
 
 
