@@ -141,7 +141,8 @@ int rs_stage_sync(rs_context* ctx);
  *   d_idx1/d_dist1 = second nearest (idx1 = -1, dist1 = -1 when nt == 1).
  * Ties: the lower train index is the nearer neighbour (OpenCV batchDistance
  * inserts with strict compares).  Bit-exact integer results.
- * nq == 0 or nt == 0 is valid: nothing is written. */
+ * nq == 0 or nt == 0 is valid: nothing is written.  nt must be below 2^20 (the train index is
+ * packed into 20 bits): nt >= 2^20 returns RS_ERR_UNSUPPORTED and leaves the context usable.  nq, batch: any. */
 int rs_hamming_knn2(rs_context* ctx,
                     const uint8_t* d_query, int nq,
                     const uint8_t* d_train, int nt, int batch,
@@ -232,7 +233,10 @@ typedef struct rs_map_view {
  *   d_match_kp / d_match_point [N] + d_match_count[1]: accepted_matches()
  *   (src/MapMatcher.cpp:34-43), ascending keypoint index.
  * Integer outputs are bit-exact against the oracle; the f32 gates follow the
- * operation order documented in oracle/reproj_match.c. */
+ * operation order documented in oracle/reproj_match.c.
+ * Up to 6144 keypoints (K2_MAX_LDS_NODES) K2 stages the frame's KD-tree in LDS; beyond that it walks the tree in
+ * global memory (one lane per point, whatever k2_mode says): same outputs, any n_keypoints below 2^30.
+ * max_distance may be any int; a point proposes only at a distance strictly below it, so <= 0 proposes nothing. */
 int rs_reproj_match(rs_context* ctx, const rs_frame_view* frame,
                     const rs_map_view* map, int replace, int max_distance,
                     int32_t* d_point_kp, int32_t* d_point_dist,
