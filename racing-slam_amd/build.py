@@ -39,7 +39,7 @@ SOURCES = [
     ("pose_graph.cpp", ["-ffp-contract=off"]),
 ]
 STAMPS = ["-DRS_STAMPS=1"] if os.environ.get("RS_STAMPS") else []
-# A/B builds: RS_VARIANT=<name> RS_DEFS="-DK7_V2=0 ..." -> librsgpu_<name>.so from objects of its own (tools/ab_time.py
+# A/B builds: RS_VARIANT=<name> RS_DEFS="-D<SWITCH>=<value> ..." -> librsgpu_<name>.so from objects of its own (tools/ab_time.py
 # loads it through RS_LIB); never the product library
 VARIANT = os.environ.get("RS_VARIANT", "")
 STAMPS = STAMPS + os.environ.get("RS_DEFS", "").split() if VARIANT else STAMPS

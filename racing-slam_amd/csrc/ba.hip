@@ -403,9 +403,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_backsub_cost(BaDims d, BaBufs b
 }
 
 // -------------------------------------------------------------------- finalize
-#ifndef BA_FINALIZE_WGS
 #define BA_FINALIZE_WGS 32
-#endif
 static __device__ __forceinline__ void ba_finalize_body(const BaDims& d, const BaBufs& b, const BaOpt& opt, int it, double* __restrict__ cams_out,
                                                         const uint8_t* __restrict__ cam_free, double* __restrict__ pts_out, BaState* host_st,
                                                         BaTrace* host_trace, double* __restrict__ host_cams, double* __restrict__ host_vb,

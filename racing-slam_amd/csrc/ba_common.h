@@ -20,11 +20,10 @@
 #define BA_DBG_WORDS 96
 #define BA_MAX_LDS_N 126      // largest reduced system kept in LDS by K7
 #define BA_DEFAULT_SREP 1      // replicas of S on the local-window path (BaBufs::srep)
-#define BA_DEFAULT_SETS (BA_MAXSETS < 5 ? BA_MAXSETS : 5)      // default number of speculative radii a round MAY evaluate on the local-window path (ba_round_sets below)
+#define BA_DEFAULT_SETS 5      // default number of speculative radii a round MAY evaluate on the local-window path (ba_round_sets below)
 #define BA_CALIBRATED_SETS 3   // ... once the trust-region radius is calibrated
-#ifndef BA_MAXSETS
 #define BA_MAXSETS 5          // speculative trust-region radii evaluated per round (see "Speculative radii" below)
-#endif
+static_assert(BA_MAXSETS == 5, "the range of the ba_speculative_sets knob (BA_MAXSETS_KNOB, context.hip) repeats this value");
 
 struct BaState {
     double radius, decrease_factor, x_cost, initial_cost;

@@ -21,9 +21,6 @@ __host__ __device__ __forceinline__ int sch_tile_doubles(int it_l)
     const int a = 3 * it_l * YT_STRIDE4, b8 = 3 * (it_l / 2) * YT_STRIDE8;
     return ((a > b8 ? a : b8) + 1) & ~1;
 }
-#ifndef K5_ALLSETS
-#define K5_ALLSETS 1            // every speculative radius in one pass over the tile (syrk_tiles_sets); 0: set by set, the tile transformed in place
-#endif
 #define SCH_PRE 3               // observation rounds prefetched per lane (covers 12 observations per landmark)
 #define SCH_MAXC_LDS 64         // cameras staged in LDS when the window has at most this many
 
@@ -520,7 +517,7 @@ static __device__ __forceinline__ void ba_schur_body(const BaDims& d, const BaBu
     double* Mt = (double*)(gslot + 32);                       // [it_l][6] behind the slot table ([2][it_l][6] as Gt)
     int set_first = 0;
     // ---- several radii, compact 4x4-tile item: every set in ONE pass over the tile (syrk_tiles_sets above)
-    if (K5_ALLSETS && st.nact > 1 && ns > 0 && ns <= 10) {
+    if (st.nact > 1 && ns > 0 && ns <= 10) {
         double Li0[6] = {0, 0, 0, 0, 0, 0}, L0[6] = {0, 0, 0, 0, 0, 0};
         // damped block of one set: damping, Cholesky, inverse; false when the block is not positive definite
         auto damped = [&](int set, double lam[3], double Li[6], double I[6], double Lc[6]) -> bool {

@@ -484,9 +484,6 @@ __global__ __launch_bounds__(256) void ba_big_update(BaDims d, BaBufs b, BigBufs
 // the stores of the factor with the factorisation
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-#ifndef BAND_DIAG
-#define BAND_DIAG 0           // timing diagnostics (wrong results): 1 no factor stores, 2 the whole fetch at the end of the block, 4 no tile updates
-#endif
 // ---- the panel of one block column, 8 columns per step, with the chain kept off the matrix cores (the form of ba_solve.hip's
 // K7 on a window in LDS).  The first 8 waves of the workgroup have ROLES (512 threads: 256 registers per lane, where 1024
 // threads leave 128 and the chain's 36-entry triangle + row state spills; waves w, w + 4 share a SIMD; f64 MFMA and f64 VALU
@@ -507,19 +504,10 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // that factors the next sub-block one step ahead (a single wave's 8 x 8 factorisation takes as long as the chain's whole step),
 // the chain waves on two SIMDs.  Rows above the step's sub-block are finished and idle; identity padding needs no masks.
 #define BAND_TS 10
-#ifndef BAND_CHAIN_X
-#define BAND_CHAIN_X 4          // the chain waves are dw and dw ^ BAND_CHAIN_X: 1 = on two SIMDs (each has the FP64 pipe to itself in the
-#endif                          // factorisation), 4 = on one SIMD (no tile wave's MFMAs next to the chain)
 #define BAND_NT 5               // tile waves (waves beyond the first eight of a larger workgroup only keep the barriers)
-#if BAND_CHAIN_X == 1
-#define BAND_RHS_WAVE 2
-#define band_is_tile(wave) ((wave) >= 3 && (wave) < 8)
-#define band_tile_index(wave) ((wave) - 3)                                   // 0 .. 4
-#else
 #define BAND_RHS_WAVE 5         // (SIMD 1: its factorisation runs while the tile waves of that SIMD wait for the step's multipliers)
 #define band_is_tile(wave) ((wave) < 8 && ((wave) & 3) != 0 && (wave) != BAND_RHS_WAVE)
 #define band_tile_index(wave) ((wave) < 4 ? (wave) - 1 : (wave) - 3)         // 0 .. 4
-#endif
 // live tiles of a step by lo = (c + 8) / 16: tile rows lo .. 7 x tile columns lo .. min(row, 3), the triangle of the D rows first, then
 // the P rows' rectangle; entry = 4 * tile row + tile column
 __device__ static const unsigned char BAND_TILES[4][26] = {
@@ -550,7 +538,7 @@ static __device__ __forceinline__ void band_block8(const BandWin& W, const int s
 #define BLOCK_STAMP(i) do { } while (0)
 #endif
     const int lr = lane & 15, lk = lane >> 4;
-    const bool chain_d = wave == dw, chain_p = has_p && wave == (dw ^ BAND_CHAIN_X), rhs = wave == BAND_RHS_WAVE;
+    const bool chain_d = wave == dw, chain_p = has_p && wave == (dw ^ 4), rhs = wave == BAND_RHS_WAVE;
     const bool chain = chain_d || chain_p, tile = band_is_tile(wave);
     const int tw = band_tile_index(wave);
     double* const rp = chain_p ? W.Pp + lane * WBS : W.Dm + lane * WBS;     // chain: this lane's panel row
@@ -675,7 +663,7 @@ static __device__ __forceinline__ void band_block8(const BandWin& W, const int s
                 for (int k = 0; k < 8; k++) cur[k] = W.y[c + 8 + k];
             }
         }
-        if ((tile || rhs) && !(BAND_DIAG & 4)) {                                 // (the right-hand side's wave joins as sixth tile wave)
+        if (tile || rhs) {                                                       // (the right-hand side's wave joins as sixth tile wave)
             // tile q of the step's list (BAND_TILES; without P rows only its triangle) -> tile wave q % 6
             const int pdiff = has_p ? (int)(W.Pp - W.Dm) : 0;                   // (P rows: the same LDS allocation as D)
             const int lo = (c + 8) >> 4, nlo = 4 - lo, tri = (nlo * (nlo + 1)) >> 1, ntile = tri + (has_p ? 4 * nlo : 0);
@@ -859,16 +847,10 @@ __global__ __launch_bounds__(BAND_THREADS) void ba_band_factor(BaDims d, BaBufs 
         band_block8(W, s_first, dw, has_p, bad, [&](int, int c) {
             if (!tile) return;
             // (the fetched values first: waiting for them behind this step's stores would wait for the stores as well)
-#if !(BAND_DIAG & 2)
             if (pending) place(chunk - 1);
-#endif
-#if !(BAND_DIAG & 1)
             store_cols(c);
-#endif
-#if !(BAND_DIAG & 2)
             pending = chunk < NCHUNK;
             if (pending) request(chunk++);
-#endif
         }, RS_STAMPS ? (unsigned long long*)b.dbg + (blockIdx.x == 0 ? 0 : 8) : nullptr);
         if (tile) {                                                             // (a short first block of side 1: the rest, waiting)
             if (pending) place(chunk - 1);
@@ -905,7 +887,7 @@ __global__ __launch_bounds__(BAND_THREADS) void ba_band_factor(BaDims d, BaBufs 
         }
         // ---- shift the window by swapping buffers: T becomes D, the fetched P the panel's; the chain waves swap their rows
         { double* t_ = Dm; Dm = Tm; Tm = t_; t_ = Pp; Pp = Pn; Pn = t_; }
-        dw ^= BAND_CHAIN_X;
+        dw ^= 4;                    // (the chain waves share one SIMD: no tile wave's MFMAs next to the chain)
     }
     if (__any(bad) && lane == 0) *g.fail = 1;
 #if RS_STAMPS

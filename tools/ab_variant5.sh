@@ -1,4 +1,4 @@
-# A/B of a variant library on the banded (cfg 5) path: BA tests on the variant, then both timed. usage: bash tools/ab_variant5.sh librsgpu_<name>.so
+# A/B of a variant library on the banded (cfg 5) path: BA tests on the variant, then both timed. usage: bash tools/ab_variant5.sh librsgpu_<name>.so  (csrc/ holds no compile-time variant switch at present: RS_DEFS has to name one that a change under test adds)
 set -e
 V=$1
 mkdir -p gpurun_out/ab
