@@ -275,6 +275,31 @@ int rs_map_destroy(rs_map* map);
 int rs_frame_create(rs_context* ctx, const float* h_keypoints /*[n][2]*/, const uint8_t* h_descriptors /*[n][32]*/, int n,
                     rs_frame** out_frame);                                        /* Frame::Frame, src/Frame.cpp:8-15 */
 int rs_frame_destroy(rs_frame* frame);
+/* A reusable frame (re)filled FROM DEVICE ARRAYS: what rs_track_features, rs_detect_features and rs_describe_features
+ * leave on the device becomes an rs_frame without a host pass.  rs_frame_create_device allocates once for max_points
+ * keypoints (envelope 1 .. 8192, the describer's and the detector's; outside it RS_ERR_UNSUPPORTED) and leaves n = 0.
+ * rs_frame_assign_device gathers list a then list b with rs_describe_features' rule, read on the device —
+ * n_a = clamp(d_count_a[0], 0, max_points), n_b = clamp(d_count_b[0], 0, max_points - n_a); either list may be NULL
+ * (points and count together) — copies the first n = n_a + n_b rows of d_desc [>= n][32] and builds the KD-tree and its
+ * packed form (rs_kdtree_pack's layout) on the device, byte for byte what rs_frame_create builds from the same arrays
+ * (finite coordinates; with NaN the tree is still a permutation of the keypoints, but rs_kdtree_build's comparator is no
+ * ordering then and nothing is promised about equality).  Stream-ordered on the context stream, no allocation per call;
+ * it may be called again and again on one frame (nothing of the previous contents shows through; a key frame added from
+ * it keeps its own copy of the rows).  ONE host synchronisation per call, to read n (4 bytes): rs_map_match sizes its
+ * launches and outputs and rs_map_add_keyframe books pool rows by the host-side n; removing that read means device-side
+ * n in the matching kernels and is not done here.  h_n (NULL = not wanted) receives n.
+ * A frame from rs_frame_create has no capacity and is refused (RS_ERR_INVALID), as is a frame of another context.
+ * rs_map_match, rs_map_add_keyframe and rs_frame_destroy take both kinds of frame. */
+int rs_frame_create_device(rs_context* ctx, int max_points, rs_frame** out_frame);
+int rs_frame_assign_device(rs_context* ctx, rs_frame* frame,
+                           const float* d_pt_a, const int32_t* d_count_a,     /* rs_track_features' d_kept_pt / d_count */
+                           const float* d_pt_b, const int32_t* d_count_b,     /* rs_detect_features' d_pt / d_counts + 1 */
+                           const uint8_t* d_desc,                            /* rs_describe_features' d_desc */
+                           int* h_n);
+/* Diagnostic (synchronises): what a frame of either kind holds on the device.  Any pointer may be NULL.
+ * h_kp [n][2], h_desc [n][32], h_kd [3][n] = node_kp | left | right, h_root [1], h_packed 20 n bytes. */
+int rs_frame_download(rs_context* ctx, const rs_frame* frame, int* h_n, float* h_kp, uint8_t* h_desc,
+                      int32_t* h_kd, int32_t* h_root, void* h_packed);
 int rs_map_add_keyframe(rs_map* map, const rs_frame* frame, const float h_pose[16], int* out_kf);
 int rs_map_set_keyframe_pose(rs_map* map, int kf, const float h_pose[16]);      /* Frame::set_pose */
 int rs_map_add_point(rs_map* map, const float h_xyz[3], int* out_point);        /* Map::add_point / create_point */

@@ -35,6 +35,7 @@ SOURCES = [
     ("ba_update.hip", ["-munsafe-fp-atomics"]),
     ("ba_round.hip", ["-munsafe-fp-atomics"]),
     ("map.hip", []),
+    ("frame.hip", ["-ffp-contract=off"]),
     ("host.cpp", ["-ffp-contract=off"]),
     ("pose_graph.cpp", ["-ffp-contract=off"]),
 ]

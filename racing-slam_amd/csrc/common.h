@@ -91,6 +91,23 @@ struct rs_context {
     size_t k1_top_cap = 0;
 };
 
+// A frame's keypoints, descriptors and flattened KD-tree on the device (map.hip: built on the host and uploaded by
+// rs_frame_create; frame.hip: filled from device arrays by rs_frame_assign_device).
+struct rs_frame {
+    rs_context* ctx = nullptr;
+    int n = 0;
+    float* d_kp = nullptr; uint8_t* d_desc = nullptr; int32_t* d_kd = nullptr;   // node_kp | left | right, stride n
+    uint8_t* d_matched = nullptr;
+    void* d_packed = nullptr;           // {x, y, left, right}[n] + keypoint[n]: what K2 stages in LDS (rs_kdtree_pack layout)
+    int kd_root = -1;
+    std::vector<float> kp;              // host copy of the keypoints (rs_frame_create only; nothing reads it)
+    // rs_frame_create_device: every buffer above holds `cap` keypoints and is refilled by rs_frame_assign_device
+    int cap = 0;                        // 0 = built by rs_frame_create: exactly n, not assignable
+    uint32_t* d_rank = nullptr;         // [cap] rank_x | rank_y << 16 of the last assign
+    int32_t* d_n = nullptr;             // [1] n of the last assign
+    int32_t* h_n = nullptr;             // pinned word the one read-back per assign lands in
+};
+
 int rs_fail(rs_context* ctx, int code, const char* fmt, ...);
 
 #define RS_HIP(ctx, call)                                                                  \

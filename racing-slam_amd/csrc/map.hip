@@ -60,15 +60,7 @@ struct rs_map {
     std::vector<float> h_centres;
 };
 
-struct rs_frame {
-    rs_context* ctx = nullptr;
-    int n = 0;
-    float* d_kp = nullptr; uint8_t* d_desc = nullptr; int32_t* d_kd = nullptr;   // node_kp | left | right
-    uint8_t* d_matched = nullptr;
-    void* d_packed = nullptr;           // {x, y, left, right}[n] + keypoint[n]: what K2 stages in LDS (rs_kdtree_pack layout)
-    int kd_root = -1;
-    std::vector<float> kp;
-};
+// (struct rs_frame: common.h — frame.hip fills one from device arrays)
 
 template <typename T>
 static int grow(rs_context* ctx, T** p, size_t* cap, size_t need, size_t keep_bytes)
@@ -154,8 +146,9 @@ extern "C" int rs_frame_destroy(rs_frame* f)
     if (!f) return RS_OK;
     (void)hipSetDevice(f->ctx->device);
     (void)hipStreamSynchronize(f->ctx->stream);
-    for (void* p : {(void*)f->d_kp, (void*)f->d_desc, (void*)f->d_kd, (void*)f->d_matched, f->d_packed})
+    for (void* p : {(void*)f->d_kp, (void*)f->d_desc, (void*)f->d_kd, (void*)f->d_matched, f->d_packed, (void*)f->d_rank, (void*)f->d_n})
         if (p) (void)hipFree(p);
+    if (f->h_n) (void)hipHostFree(f->h_n);
     delete f;
     return RS_OK;
 }

@@ -162,6 +162,7 @@ Session::~Session()
     rs_image_destroy(m_orb_img);
     rs_describer_destroy(m_orb);
     rs_pose_estimator_destroy(m_pose);
+    rs_frame_destroy(m_frame);
     rs_context_destroy(m_ctx);
 }
 Session& Session::get()
@@ -805,8 +806,10 @@ int Session::replenish_features(const Image& next, const Image& static_mask, Ext
 }
 
 std::vector<uint8_t> Session::refresh_descriptors(const Image& next, const ExtractedFeatures& features,
-                                                  const ExtractedFeatures& prev_features, const std::vector<FeatureMatch>& matches)
+                                                  const ExtractedFeatures& prev_features, const std::vector<FeatureMatch>& matches,
+                                                  rs_frame** out_frame)
 {
+    if (out_frame) *out_frame = nullptr;
     constexpr int ORB_EDGE = 31, MAX_POINTS = 8192;              // ORB::create()'s edgeThreshold; rs_describer's envelope
     const size_t n = features.keypoints.size(), m = matches.size();
     if (n == 0 || features.descriptors.empty()) return features.descriptors;     // :32-34
@@ -854,6 +857,16 @@ std::vector<uint8_t> Session::refresh_descriptors(const Image& next, const Extra
                                     d_desc.get(), nullptr, d_n.get()), "rs_describe_features"))
         return {};
     auto rows = d_desc.fetch(n * RS_DESC_BYTES);                // the one read-back: n x 32 bytes
+    if (out_frame) {
+        // the frame of rs_map_match / rs_map_add_keyframe from the same device lists and rows: no host pass, KD-tree built
+        // on the device (csrc/frame.hip).  One frame per session, allocated once, refilled per video frame.
+        int n_frame = -1;
+        if ((!m_frame && !rs_ok(rs_frame_create_device(m_ctx, MAX_POINTS, &m_frame), "rs_frame_create_device")) ||
+            !rs_ok(rs_frame_assign_device(m_ctx, m_frame, d_pa.get(), d_counts.get(), d_pb.get(), d_counts.get() + 1, d_desc.get(),
+                                          &n_frame), "rs_frame_assign_device") || n_frame != (int)n)
+            return {};
+        *out_frame = m_frame;
+    }
     stage_sync();
     return rows;
 }

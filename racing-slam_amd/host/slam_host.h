@@ -255,8 +255,13 @@ class Session {
     // is (the reference's early return), and an empty vector on failure.  `next` is reused as replenish_features
     // reuses it: the device pyramid of the last track_features call when it is that call's `next`, else uploaded.
     // Up to 8192 keypoints.
+    // With `out_frame`, the same device lists and rows also fill the session's rs_frame (rs_frame_assign_device: KD-tree
+    // built on the device, no host pass) in the same chain, and *out_frame is that frame: what rs_map_match and
+    // rs_map_add_keyframe take, byte for byte the frame rs_frame_create makes from `features` and the returned rows.  It
+    // belongs to the session and is refilled by the next such call; nullptr on failure or on the early return.
     std::vector<uint8_t> refresh_descriptors(const Image& next, const ExtractedFeatures& features,
-                                             const ExtractedFeatures& prev_features, const std::vector<FeatureMatch>& matches);
+                                             const ExtractedFeatures& prev_features, const std::vector<FeatureMatch>& matches,
+                                             rs_frame** out_frame = nullptr);
     // the relative-pose scratch of pose::estimate_pose* (8192 points, 1000 hypotheses), created on first use
     rs_pose_estimator* pose_estimator();
 
@@ -274,6 +279,7 @@ class Session {
     rs_image* m_orb_img = nullptr;
     int m_orb_w = 0, m_orb_h = 0;
     rs_pose_estimator* m_pose = nullptr;
+    rs_frame* m_frame = nullptr;                // refresh_descriptors' device-built frame (8192 keypoints), created on first use
 };
 
 // src/PoseEstimation.h: the relative pose from prev_features to features (X = R X_prev + t, |t| = 1), Tracker.cpp:162

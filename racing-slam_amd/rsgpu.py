@@ -18,6 +18,7 @@ EXPORTS = [
     "rs_abi_version", "rs_context_create", "rs_context_destroy", "rs_context_set_stream", "rs_context_wait_for", "rs_context_fork",
     "rs_context_synchronize", "rs_context_set_int", "rs_stage_begin", "rs_stage_alloc", "rs_stage_upload", "rs_stage_download", "rs_stage_sync", "rs_last_error", "rs_hamming_knn2", "rs_match_descriptors",
     "rs_kdtree_build", "rs_kdtree_pack", "rs_reproj_match", "rs_reproj_match_sharded", "rs_map_create", "rs_map_destroy", "rs_frame_create", "rs_frame_destroy",
+    "rs_frame_create_device", "rs_frame_assign_device", "rs_frame_download",
     "rs_map_add_keyframe", "rs_map_set_keyframe_pose", "rs_map_add_point", "rs_map_set_position", "rs_map_remove_point",
     "rs_map_add_observation", "rs_map_remove_observation", "rs_map_counts", "rs_map_get_positions", "rs_map_match", "rs_map_pose_graph", "rs_pose_graph", "rs_pose_relative", "rs_transform_points", "rs_map_bundle_adjust", "rs_map_window", "rs_triangulate", "rs_triangulate_host", "rs_triangulate_matches", "rs_triangulate_matches_batch", "rs_triangulate_tracks", "rs_parallax_requirements", "rs_point_errors", "rs_ba_default_options",
     "rs_bundle_adjust", "rs_bundle_adjust_batch", "rs_ba_get_trace", "rs_ba_get_stats", "rs_ba_get_cameras", "rs_reanchor_points", "rs_reanchor_points_host_poses", "rs_refine_pose", "rs_bundle_adjust_inertial", "rs_refine_pose_inertial", "rs_pack_pose", "rs_unpack_pose", "rs_pack_poses", "rs_unpack_poses", "rs_build_local_window",
@@ -937,6 +938,52 @@ class ResidentFrame:
         self.n = len(kp)
         self.h = C.c_void_p()
         ctx._check(ctx.lib.rs_frame_create(ctx.h, kp.ctypes.data_as(C.c_void_p), de.ctypes.data_as(C.c_void_p), self.n, C.byref(self.h)), "rs_frame_create")
+
+    def download(self):
+        return frame_download(self.ctx, self)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.rs_frame_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+def frame_download(ctx, frame):
+    """rs_frame_download of a ResidentFrame or a DeviceFrame (synchronises): dict(n, kp [n][2] f32, desc [n][32] u8,
+    kd [3][n] i32 = node_kp | left | right, root, packed u8 [20 n])."""
+    n = C.c_int(0)
+    ctx._check(ctx.lib.rs_frame_download(ctx.h, frame.h, C.byref(n), None, None, None, None, None), "rs_frame_download")
+    m = max(n.value, 1)
+    kp, desc, kd = np.zeros((m, 2), np.float32), np.zeros((m, 32), np.uint8), np.zeros((3, m), np.int32)
+    packed, root = np.zeros(20 * m, np.uint8), C.c_int32(0)
+    ctx._check(ctx.lib.rs_frame_download(ctx.h, frame.h, C.byref(n), kp.ctypes.data_as(C.c_void_p), desc.ctypes.data_as(C.c_void_p),
+                                         kd.ctypes.data_as(C.c_void_p), C.byref(root), packed.ctypes.data_as(C.c_void_p)),
+               "rs_frame_download")
+    k = n.value
+    return dict(n=k, kp=kp[:k], desc=desc[:k], kd=kd[:, :k] if k else np.zeros((3, 0), np.int32), root=root.value,
+                packed=packed[:20 * k])
+
+
+class DeviceFrame:
+    """rs_frame filled from device arrays (rs_frame_create_device / rs_frame_assign_device): allocated once for
+    max_points keypoints, reassigned every video frame; usable wherever ResidentMap takes a frame."""
+
+    def __init__(self, ctx, max_points=8192):
+        self.ctx, self.max_points, self.n = ctx, int(max_points), 0
+        self.h = C.c_void_p()
+        ctx._check(ctx.lib.rs_frame_create_device(ctx.h, self.max_points, C.byref(self.h)), "rs_frame_create_device")
+
+    def assign(self, d_desc, d_pt_a=None, d_count_a=None, d_pt_b=None, d_count_b=None):
+        """List a (rs_track_features' pts / count) then list b (rs_detect_features' pts / counts[1:]) and the first n rows
+        of d_desc (rs_describe_features' desc), all device tensors; one 4-byte read-back.  Returns n."""
+        n = C.c_int(0)
+        self.ctx._check(self.ctx.lib.rs_frame_assign_device(self.ctx.h, self.h, _dp(d_pt_a), _dp(d_count_a), _dp(d_pt_b),
+                                                            _dp(d_count_b), _dp(d_desc), C.byref(n)), "rs_frame_assign_device")
+        self.n = n.value
+        return self.n
+
+    def download(self):
+        return frame_download(self.ctx, self)
 
     def close(self):
         if self.h:
