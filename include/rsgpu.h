@@ -919,6 +919,48 @@ int rs_pose_estimator_stats(rs_context* ctx, const rs_pose_estimator* est, int32
 int rs_pose_hypotheses(rs_context* ctx, const rs_pose_estimator* est, int32_t* h_samples, int32_t* h_nmodels, double* h_models,
                        int32_t* h_scores);
 
+/* ------------------------------------------------- absolute pose: P3P RANSAC with an EPnP refit */
+
+/* The two cv::solvePnPRansac(..., 200, threshold, 0.99, inliers, cv::SOLVEPNP_EPNP) calls of the reference: LoopDetector's
+ * verify_pnp (src/LoopDetector.cpp:176-229) and Initialization's third-view check (src/Initialization.cpp:188-228, 2.0 px).
+ * OpenCV's RNG and RANSAC internals cannot be restated bit for bit; the specification is tests/pnp_ref.py: hashed
+ * samples of 4, Grunert's P3P on the first three (the quartic's real roots by bisection between the roots of its
+ * derivatives; R, t from the orthonormal frames of the two triangles), every model scored by its integer count of
+ * points with positive depth and squared reprojection error < threshold_px^2, the adaptive stop after each round of
+ * 256 hypotheses (sample size 4), and one EPnP refit (normalised coordinates; beta cases N = 1, 2, 3 with 5
+ * Gauss-Newton steps each) over the best model's inliers when there are >= 6, kept iff its count over all points is
+ * >= the minimal model's.  Agreement with cv::solvePnPRansac is not claimed.
+ *
+ * rs_pnp_estimator holds the scratch (allocated once; no allocation per call).  Envelope: max_points 1 .. 8192,
+ * max_hypotheses 1 .. 4096.  Outside it: RS_ERR_UNSUPPORTED.  Creation synchronises the context stream only. */
+typedef struct rs_pnp_estimator rs_pnp_estimator;
+int rs_pnp_estimator_create(rs_context* ctx, int max_points, int max_hypotheses, rs_pnp_estimator** out_est);
+int rs_pnp_estimator_destroy(rs_pnp_estimator* est);
+/* One stream-ordered chain with no host synchronisation.  Inputs (device): correspondence i pairs the object point
+ * d_object[d_object_index[i]] ([][3] f32, world) with the pixel d_pixels[d_pixel_index[i]] ([][2] f32); either index
+ * array may be NULL (then i itself).  rs_match_descriptors' d_match_train / d_match_query / d_match_count serve as
+ * d_object_index / d_pixel_index / d_count.  A negative index is a non-finite correspondence; indices must lie inside
+ * the caller's arrays.  n = clamp(d_count[0], 0, max_n), read on the device.  h_intrinsics = fx, fy, cx, cy.
+ * Hypotheses h = 0 .. max_hypotheses-1 (<= the estimator's; the reference passes 200) in rounds of 256; seed selects
+ * the samples.  Outputs (device): d_pose [16] f32 row-major world -> camera (X_cam = R X + t), d_inlier [max_n] u8
+ * (entries from n on are 0), d_inlier_index [max_n] (ascending), d_inlier_count [1], d_status [1]: 0 = ok, 1 = fewer
+ * than 4 finite correspondences, 2 = no model with >= 4 inliers (both: identity pose, no inliers; the reference gets
+ * solved == false).  A correspondence with a non-finite coordinate is never sampled, never an inlier, never refitted. */
+int rs_estimate_pose_pnp(rs_context* ctx, rs_pnp_estimator* est, const float* d_object, const int32_t* d_object_index,
+                         const float* d_pixels, const int32_t* d_pixel_index, const int32_t* d_count, int max_n,
+                         const float* h_intrinsics, double threshold_px, double confidence, int max_hypotheses, uint64_t seed,
+                         float* d_pose, uint8_t* d_inlier, int32_t* d_inlier_index, int32_t* d_inlier_count, int32_t* d_status);
+/* Diagnostic of the last call (synchronises the stream): h_stats[9] = hypotheses drawn, models scored, best index
+ * (4 h + m), best count, refit kept (0 / 1), the refit's beta case (1 .. 3; 0 = none), status, inlier count, n;
+ * h_pose [12] the final [R | t] (f64, row-major 3 x 4; the identity unless status is 0).  Any pointer may be NULL. */
+int rs_pnp_estimator_stats(rs_context* ctx, const rs_pnp_estimator* est, int32_t* h_stats, double* h_pose);
+/* Diagnostic (synchronises) of the last call, over the estimator's whole table h < max_hypotheses (every call resets
+ * it): h_samples [][4] (-1: not drawn, or a sample that could not find 4 distinct finite correspondences), h_nmodels []
+ * (-1: not drawn), h_models [][4][12] f64 ([R | t]; row m valid for m < nmodels[h]) and h_scores [][4] (0 past
+ * nmodels[h]).  Any pointer may be NULL. */
+int rs_pnp_hypotheses(rs_context* ctx, const rs_pnp_estimator* est, int32_t* h_samples, int32_t* h_nmodels, double* h_models,
+                      int32_t* h_scores);
+
 /* ------------------------------------------------------------- multi-GPU */
 
 #define RS_COMM_ID_BYTES 128

@@ -27,6 +27,7 @@ SOURCES = [
     ("gftt.hip", ["-ffp-contract=off"]),
     ("orb.hip", ["-ffp-contract=off"]),
     ("pose.hip", ["-ffp-contract=off"]),
+    ("pnp.hip", ["-ffp-contract=off"]),
     ("ba.hip", ["-munsafe-fp-atomics"]),
     ("ba_solve.hip", ["-munsafe-fp-atomics"]),
     ("ba_solve_big.hip", ["-munsafe-fp-atomics"]),

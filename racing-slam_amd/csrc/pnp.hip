@@ -1,0 +1,790 @@
+// pnp.hip — the absolute-pose stage: P3P RANSAC with an EPnP refit.
+//
+// Replaces the two cv::solvePnPRansac(..., 200, threshold, 0.99, inliers, cv::SOLVEPNP_EPNP) calls of the reference
+// (LoopDetector's verify_pnp, src/LoopDetector.cpp:176-229; Initialization's third-view check,
+// src/Initialization.cpp:188-228).  The specification is tests/pnp_ref.py; this file follows it operation by operation
+// (-ffp-contract=off), so sampling, model sets and scores agree with it to rounding.
+//
+// rs_estimate_pose_pnp: one stream-ordered chain, no host synchronisation, no allocation; the count is read on the device.
+//   pnp_prep      gather through the two optional index arrays, normalise into f64 SoA scratch, count the finite
+//                 correspondences, reset the state and the hypothesis table
+//   pnp_hyp       one lane per hypothesis (4 wave64 workgroups per round of 256): the hashed sample, Grunert's quartic,
+//                 its real roots by the bisection of ordered 64-bit keys between the roots of the derivatives (serial
+//                 per lane), up to 4 models [R | t] from the orthonormal frames of the two triangles
+//   pnp_score     one workgroup per hypothesis: every point is loaded once and tested against all of its models;
+//                 integer counts; a packed 64-bit atomicMax of (count, ~(4 h + m)) keeps the best
+//   pnp_stop      the adaptive stop after each round of 256; later rounds exit at entry
+//   pnp_final     one workgroup: the best model's mask, the EPnP sums in a fixed order, the 12 x 12 cyclic Jacobi with the
+//                 whole workgroup, the three beta cases with Gauss-Newton (lane 0), their summed errors, the keep /
+//                 discard decision, the mask and its ordered compaction
+// No float atomics: two calls with the same inputs write the same bytes.
+#include <algorithm>
+
+#include "pose_shared.h"
+#include "tri_core.h"
+
+#define PNP_MAX_POINTS 8192
+#define PNP_MAX_HYP 4096
+#define PNP_ROUND 256
+#define PNP_MAX_DRAWS 64
+#define PNP_P3P_EPS 1e-6            // relative residual of each cosine law that a model may have
+#define PNP_COLLINEAR_EPS 1e-6      // |(P2 - P1) x (P3 - P1)| must exceed this times |P2 - P1| |P3 - P1|
+#define PNP_SOLVE_EPS 1e-13
+#define PNP_GN_STEPS 5
+#define PNP_MIN_REFIT 6
+#define PNP_STATUS_OK 0
+#define PNP_STATUS_FEW 1
+#define PNP_STATUS_FAILED 2
+
+struct PnpState {
+    unsigned long long best_key;
+    int stop, drawn, n, status, refit_kept, beta_case, inliers, scored, best_index, best_count;
+    int nfin;               // finite correspondences of the last call
+    int nfin_acc;           // pnp_prep's atomic counter: zero between calls (pnp_final clears it)
+    double Rt[12];
+};
+
+struct rs_pnp_estimator {
+    rs_context* ctx = nullptr;
+    int max_points = 0, max_hyp = 0;
+    double* x = nullptr;            // [5][max_points] X, Y, Z, x, y
+    uint8_t* fin = nullptr;         // [max_points]
+    uint8_t* mask = nullptr;        // [2][max_points] the minimal model's mask, the refit's
+    int32_t* samples = nullptr;     // [max_hyp][4]
+    int32_t* nmod = nullptr;        // [max_hyp]
+    double* models = nullptr;       // [max_hyp][4][12]
+    int32_t* scores = nullptr;      // [max_hyp][4]
+    PnpState* st = nullptr;
+};
+
+struct PnpScratch {
+    double *X, *Y, *Z, *x, *y;
+    uint8_t* fin;
+    int32_t *samples, *nmod, *scores;
+    double* models;
+    PnpState* st;
+};
+
+static PnpScratch scratch_of(const rs_pnp_estimator* e)
+{
+    const size_t m = e->max_points;
+    return PnpScratch{e->x, e->x + m, e->x + 2 * m, e->x + 3 * m, e->x + 4 * m, e->fin, e->samples, e->nmod, e->scores,
+                      e->models, e->st};
+}
+
+// ------------------------------------------------------------------------------------------------ helpers
+__device__ __forceinline__ double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+__device__ __forceinline__ void sub3(const double* a, const double* b, double* o)
+{
+    o[0] = a[0] - b[0]; o[1] = a[1] - b[1]; o[2] = a[2] - b[2];
+}
+
+// depth and squared reprojection error in pixels of model m [12] (tests/pnp_ref.reproj2)
+__device__ __forceinline__ double reproj2(const double* m, double X, double Y, double Z, double x, double y, double fx, double fy,
+                                          double* depth)
+{
+    const double xc = ((m[0] * X + m[1] * Y) + m[2] * Z) + m[3];
+    const double yc = ((m[4] * X + m[5] * Y) + m[6] * Z) + m[7];
+    const double zc = ((m[8] * X + m[9] * Y) + m[10] * Z) + m[11];
+    const double ex = fx * (xc / zc - x), ey = fy * (yc / zc - y);
+    *depth = zc;
+    return ex * ex + ey * ey;
+}
+
+// the real roots of a quartic (5 coefficients ascending), ascending: tests/essential_ref.real_roots on one lane
+__device__ int quartic_roots(const double* pin, double* z)
+{
+    double p[5], m = 0.0;
+    for (int k = 0; k < 5; k++) m = fmax(m, fabs(pin[k]));
+    if (!(m > 0.0 && isfinite(m))) return 0;
+    for (int k = 0; k < 5; k++) p[k] = pin[k] / m;
+    int d = 4;
+    while (d > 0 && fabs(p[d]) < POSE_TRIM_EPS) d--;
+    for (int k = d + 1; k < 5; k++) p[k] = 0.0;
+    if (d == 0) return 0;
+    double bnd = 0.0;
+    for (int k = 0; k < d; k++) bnd = fmax(bnd, fabs(p[k] / p[d]));
+    const double B = 1.0 + bnd;
+    double D[5][5];                                   // D[r] = the r-th derivative, ascending
+    for (int k = 0; k < 5; k++) D[0][k] = p[k];
+    for (int r = 0; r < 4; r++) {
+        for (int k = 0; k < 4; k++) D[r + 1][k] = (double)(k + 1) * D[r][k + 1];
+        D[r + 1][4] = 0.0;
+    }
+    double rt[2][4];
+    int nroot = 0;
+    for (int j = 1; j <= d; j++) {                    // level j: the roots of D[d - j] (degree j)
+        const double* q = D[d - j];
+        const double* prev = rt[(j - 1) & 1];
+        double* cur = rt[j & 1];
+        int nn = 0;
+        for (int iv = 0; iv <= nroot; iv++) {
+            const double a = iv == 0 ? -B : prev[iv - 1], b = iv == nroot ? B : prev[iv];
+            const int sa = poly_sign(q, j, a), sb = poly_sign(q, j, b);
+            if (sa != 0 && sb != sa) {
+                long long lo = dkey(a), hi = dkey(b);
+                for (int it = 0; it < POSE_BISECT_ITERS; it++) {
+                    const long long mid = ((lo >> 1) + (hi >> 1)) + (lo & hi & 1ll);
+                    if (poly_sign(q, j, dunkey(mid)) == sa) lo = mid; else hi = mid;
+                }
+                cur[nn++] = dunkey(hi);
+            }
+        }
+        nroot = nn;
+    }
+    for (int r = 0; r < nroot; r++) {
+        double zz = rt[d & 1][r];
+        for (int it = 0; it < POSE_NEWTON; it++) {
+            double v = 0.0, dv = 0.0;
+            for (int c = 4; c >= 0; c--) {
+                dv = dv * zz + v;
+                v = v * zz + p[c];
+            }
+            const double zn = zz - v / dv;
+            if (dv != 0.0 && isfinite(zn) && fabs(zn - zz) <= 1e-6 * (1.0 + fabs(zz))) zz = zn;
+        }
+        z[r] = zz;
+    }
+    return nroot;
+}
+
+// orthonormal frame of a triangle (rows e1, e2, e3 of F); false when degenerate
+__device__ bool tri_frame(const double* p0, const double* p1, const double* p2, double* F)
+{
+    double d1[3], d2[3], nv[3];
+    sub3(p1, p0, d1);
+    sub3(p2, p0, d2);
+    const double n1 = sqrt(dot3(d1, d1));
+    if (!(n1 > 0.0)) return false;
+    for (int i = 0; i < 3; i++) F[i] = d1[i] / n1;
+    cross3(F, d2, nv);
+    const double n3 = sqrt(dot3(nv, nv));
+    if (!(n3 > 0.0)) return false;
+    for (int i = 0; i < 3; i++) F[6 + i] = nv[i] / n3;
+    cross3(F + 6, F, F + 3);
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------ kernels
+__global__ __launch_bounds__(256) void pnp_prep(const float* __restrict__ object, const int32_t* __restrict__ object_index,
+                                                const float2* __restrict__ pixels, const int32_t* __restrict__ pixel_index,
+                                                const int32_t* __restrict__ d_count, int max_n, double fx, double fy, double cx,
+                                                double cy, int table_hyp, PnpScratch s)
+{
+    __shared__ int red[4];
+    const int n = min(max(*d_count, 0), max_n);
+    const int tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    int c = 0;
+    for (int i = tid; i < n; i += stride) {
+        const int oi = object_index ? object_index[i] : i, pi = pixel_index ? pixel_index[i] : i;
+        float o[3] = {NAN, NAN, NAN};
+        if (oi >= 0) { o[0] = object[3 * (size_t)oi]; o[1] = object[3 * (size_t)oi + 1]; o[2] = object[3 * (size_t)oi + 2]; }
+        const float2 p = pi >= 0 ? pixels[pi] : make_float2(NAN, NAN);
+        const double X = (double)o[0], Y = (double)o[1], Z = (double)o[2];
+        const double x = ((double)p.x - cx) / fx, y = ((double)p.y - cy) / fy;
+        const bool f = isfinite(X) && isfinite(Y) && isfinite(Z) && isfinite(x) && isfinite(y);
+        s.X[i] = f ? X : 0.0; s.Y[i] = f ? Y : 0.0; s.Z[i] = f ? Z : 0.0; s.x[i] = f ? x : 0.0; s.y[i] = f ? y : 0.0;
+        s.fin[i] = f ? 1 : 0;
+        c += f ? 1 : 0;
+    }
+    c = block_sum_int(c, red);
+    if (threadIdx.x == 0 && c) atomicAdd(&s.st->nfin_acc, c);
+    for (int h = tid; h < table_hyp; h += stride) {     // the estimator's whole table: no entry outlives its call
+        s.nmod[h] = -1;
+#pragma unroll
+        for (int k = 0; k < 4; k++) { s.samples[4 * h + k] = -1; s.scores[4 * h + k] = 0; }
+    }
+    if (tid == 0) {
+        PnpState* st = s.st;
+        st->best_key = 0ull;
+        st->stop = 0; st->drawn = 0; st->n = n; st->status = PNP_STATUS_FAILED;
+        st->refit_kept = 0; st->beta_case = 0; st->inliers = 0; st->scored = 0;
+        st->best_index = -1; st->best_count = 0;
+    }
+}
+
+__global__ __launch_bounds__(64) void pnp_hyp(int round, int max_hyp, unsigned long long seed_hash, PnpScratch s)
+{
+    const int h = round * PNP_ROUND + blockIdx.x * 64 + threadIdx.x;
+    if (s.st->stop || s.st->nfin_acc < 4 || h >= max_hyp) return;
+    const int n = s.st->n;
+    int idx[4], k = 0;
+    for (int j = 0; j < PNP_MAX_DRAWS && k < 4; j++) {
+        const unsigned long long u = splitmix64(seed_hash + (((unsigned long long)h << 16) | (unsigned long long)j));
+        const int i = (int)(((u >> 32) * (unsigned long long)n) >> 32);
+        bool dup = !s.fin[i];
+        for (int q = 0; q < k; q++) dup |= idx[q] == i;
+        if (!dup) idx[k++] = i;
+    }
+    if (k < 4) { s.nmod[h] = 0; return; }
+    for (int q = 0; q < 4; q++) s.samples[4 * h + q] = idx[q];
+    double P[3][3], jv[3][3];
+    for (int q = 0; q < 3; q++) {
+        const int i = idx[q];
+        P[q][0] = s.X[i]; P[q][1] = s.Y[i]; P[q][2] = s.Z[i];
+        const double x = s.x[i], y = s.y[i];
+        const double nrm = sqrt((x * x + y * y) + 1.0);
+        jv[q][0] = x / nrm; jv[q][1] = y / nrm; jv[q][2] = 1.0 / nrm;
+    }
+    double d21[3], d31[3], d32[3], cr[3];
+    sub3(P[1], P[0], d21); sub3(P[2], P[0], d31); sub3(P[2], P[1], d32);
+    const double a2 = dot3(d32, d32), b2 = dot3(d31, d31), c2 = dot3(d21, d21);
+    cross3(d21, d31, cr);
+    if (!(dot3(cr, cr) > (PNP_COLLINEAR_EPS * PNP_COLLINEAR_EPS) * (b2 * c2))) { s.nmod[h] = 0; return; }
+    const double ca = dot3(jv[1], jv[2]), cb = dot3(jv[0], jv[2]), cg = dot3(jv[0], jv[1]);
+    const double q1 = (a2 - c2) / b2, r = c2 / b2;
+    const double N[3] = {1.0 + q1, -2.0 * q1 * cb, q1 - 1.0}, D[2] = {2.0 * cg, -2.0 * ca}, W[3] = {1.0, -2.0 * cb, 1.0};
+    double NN[5], ND[4], DD[3], GD[5], poly[5], z[4];
+    pmul(N, 3, N, 3, NN); pmul(N, 3, D, 2, ND); pmul(D, 2, D, 2, DD);
+    const double G[3] = {1.0 - r * W[0], -(r * W[1]), -(r * W[2])};
+    pmul(G, 3, DD, 3, GD);
+    for (int q = 0; q < 5; q++) poly[q] = (NN[q] - (2.0 * cg) * (q < 4 ? ND[q] : 0.0)) + GD[q];
+    const int nroot = quartic_roots(poly, z);
+    double Fw[9];
+    const bool wok = tri_frame(P[0], P[1], P[2], Fw);
+    int nm = 0;
+    for (int q = 0; q < nroot && wok; q++) {
+        const double v = z[q];
+        if (!(v > 0.0)) continue;
+        const double Dv = D[1] * v + D[0];
+        if (Dv == 0.0) continue;
+        const double u = ((N[2] * v + N[1]) * v + N[0]) / Dv;
+        const double den = (v * v - (2.0 * cb) * v) + 1.0;
+        if (!(u > 0.0 && den > 0.0)) continue;
+        const double s1 = sqrt(b2 / den), s2 = u * s1, s3 = v * s1;
+        const double r1 = ((s2 * s2 + s3 * s3) - ((2.0 * s2) * s3) * ca) - a2;
+        const double r2 = ((s1 * s1 + s3 * s3) - ((2.0 * s1) * s3) * cb) - b2;
+        const double r3 = ((s1 * s1 + s2 * s2) - ((2.0 * s1) * s2) * cg) - c2;
+        if (!(fabs(r1) <= PNP_P3P_EPS * a2 && fabs(r2) <= PNP_P3P_EPS * b2 && fabs(r3) <= PNP_P3P_EPS * c2)) continue;
+        double C[3][3], Fc[9], m[12];
+        for (int i = 0; i < 3; i++) { C[0][i] = s1 * jv[0][i]; C[1][i] = s2 * jv[1][i]; C[2][i] = s3 * jv[2][i]; }
+        if (!tri_frame(C[0], C[1], C[2], Fc)) continue;
+        bool fin = true;
+        for (int i = 0; i < 3; i++) {
+            for (int c = 0; c < 3; c++) m[4 * i + c] = (Fc[i] * Fw[c] + Fc[3 + i] * Fw[3 + c]) + Fc[6 + i] * Fw[6 + c];
+            m[4 * i + 3] = C[0][i] - dot3(m + 4 * i, P[0]);
+        }
+        for (int i = 0; i < 12; i++) fin = fin && isfinite(m[i]);
+        if (!fin) continue;
+        double* out = s.models + 48 * (size_t)h + 12 * nm;
+        for (int i = 0; i < 12; i++) out[i] = m[i];
+        nm++;
+    }
+    s.nmod[h] = nm;
+}
+
+__global__ __launch_bounds__(256) void pnp_score(int round, int max_hyp, double fx, double fy, double thr2, PnpScratch s)
+{
+    __shared__ int red[4];
+    const int h = round * PNP_ROUND + blockIdx.x;
+    if (s.st->stop || s.st->nfin_acc < 4 || h >= max_hyp) return;
+    const int nm = s.nmod[h], n = s.st->n;
+    if (nm <= 0) return;                                 // uniform per workgroup
+    double m[4][12];
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+#pragma unroll
+        for (int i = 0; i < 12; i++) m[q][i] = q < nm ? s.models[48 * (size_t)h + 12 * q + i] : 0.0;
+    int c[4] = {0, 0, 0, 0};
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        if (!s.fin[i]) continue;
+        const double X = s.X[i], Y = s.Y[i], Z = s.Z[i], x = s.x[i], y = s.y[i];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            if (q < nm) {
+                double zc;
+                const double e2 = reproj2(m[q], X, Y, Z, x, y, fx, fy, &zc);
+                c[q] += (zc > 0.0 && e2 < thr2) ? 1 : 0;
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        if (q >= nm) break;                              // uniform
+        const int t = block_sum_int(c[q], red);
+        if (threadIdx.x == 0) {
+            s.scores[4 * h + q] = t;
+            atomicMax(&s.st->best_key, ((unsigned long long)t << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)(4 * h + q)));
+            atomicAdd(&s.st->scored, 1);
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void pnp_stop_k(int round, int max_hyp, double log1mconf, PnpState* st)
+{
+    if (threadIdx.x != 0 || st->stop) return;
+    if (st->nfin_acc < 4) { st->stop = 1; return; }
+    const int drawn = min((round + 1) * PNP_ROUND, max_hyp);
+    st->drawn = drawn;
+    const int cnt = (int)(st->best_key >> 32), n = st->n;
+    double needed = INFINITY;
+    if (n > 0 && cnt > 0) {
+        const double w = (double)cnt / (double)n, w4 = w * w * w * w;
+        if (w4 >= 1.0) needed = 0.0;
+        else {
+            const double d = log(1.0 - w4);
+            if (d < 0.0) needed = log1mconf / d;
+        }
+    }
+    if ((double)drawn >= needed || drawn >= max_hyp) st->stop = 1;
+}
+
+struct PnpFinalLds {
+    double A[144], V[144];
+    double part[4][40], sum[40];
+    double Rt[12], cand[3][12];
+    double c0[3], sig[3], V3[9];
+    int red[4];
+    int fail, valid[3], best;
+};
+
+// column sums in a fixed order (tests/pnp_ref.ordered_sum): each thread's points in turn, a wave64 butterfly, then the
+// four waves as ((w0 + w1) + w2) + w3 into L.sum
+template <int K>
+__device__ __forceinline__ void ordered_sum(double* acc, PnpFinalLds& L)
+{
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < K; k++) acc[k] = wave_sum_f64(acc[k]);
+    __syncthreads();
+    if ((tid & 63) == 0)
+        for (int k = 0; k < K; k++) L.part[tid >> 6][k] = acc[k];
+    __syncthreads();
+    if (tid < K) L.sum[tid] = ((L.part[0][tid] + L.part[1][tid]) + L.part[2][tid]) + L.part[3][tid];
+    __syncthreads();
+}
+
+__device__ __forceinline__ int pnp_score_mask(const double* m, const PnpScratch& s, int n, double fx, double fy, double thr2,
+                                              uint8_t* mask, int* red)
+{
+    int c = 0;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        double zc;
+        const double e2 = reproj2(m, s.X[i], s.Y[i], s.Z[i], s.x[i], s.y[i], fx, fy, &zc);
+        const bool in = s.fin[i] && zc > 0.0 && e2 < thr2;
+        mask[i] = in ? 1 : 0;
+        c += in ? 1 : 0;
+    }
+    return block_sum_int(c, red);
+}
+
+// Gaussian elimination with partial pivoting of the n x n system in A [6][7] (augmented, row stride 7), n <= 6
+// (tests/pnp_ref.solve_small)
+__device__ bool solve_small(double (*A)[7], int n, double* d)
+{
+    double mmax = 0.0;
+    for (int r = 0; r < n; r++)
+        for (int c = 0; c < n; c++) {
+            if (!isfinite(A[r][c])) return false;
+            mmax = fmax(mmax, fabs(A[r][c]));
+        }
+    if (!(mmax > 0.0)) return false;
+    for (int c = 0; c < n; c++) {
+        int p = c;
+        for (int r = c + 1; r < n; r++)
+            if (fabs(A[r][c]) > fabs(A[p][c])) p = r;
+        if (p != c)
+            for (int k = 0; k <= n; k++) { const double t = A[c][k]; A[c][k] = A[p][k]; A[p][k] = t; }
+        const double piv = A[c][c];
+        if (!(fabs(piv) > PNP_SOLVE_EPS * mmax)) return false;
+        for (int r = c + 1; r < n; r++) {
+            const double f = A[r][c] / piv;
+            for (int k = c; k <= n; k++) A[r][k] = A[r][k] - f * A[c][k];
+        }
+    }
+    for (int c = n - 1; c >= 0; c--) {
+        double sacc = A[c][n];
+        for (int k = c + 1; k < n; k++) sacc = sacc - A[c][k] * d[k];
+        d[c] = sacc / A[c][c];
+    }
+    for (int c = 0; c < n; c++)
+        if (!isfinite(d[c])) return false;
+    return true;
+}
+
+// (L^T L | L^T r) of the 6-row L [6][6] (n columns used) into the augmented A
+__device__ void normal6(const double (*Lm)[6], const double* r, int n, double (*A)[7])
+{
+    for (int a = 0; a < n; a++) {
+        for (int b = 0; b < n; b++) {
+            double sacc = 0.0;
+            for (int p = 0; p < 6; p++) sacc = sacc + Lm[p][a] * Lm[p][b];
+            A[a][b] = sacc;
+        }
+        double sacc = 0.0;
+        for (int p = 0; p < 6; p++) sacc = sacc + Lm[p][a] * r[p];
+        A[a][n] = sacc;
+    }
+}
+
+// lane 0 of pnp_final: the three beta cases from the eigenvectors in L.A / L.V (tests/pnp_ref.epnp)
+__device__ void epnp_candidates(PnpFinalLds& L)
+{
+    const int PA[6] = {0, 0, 0, 1, 1, 2}, PB[6] = {1, 2, 3, 2, 3, 3};
+    const int MK[6] = {0, 0, 1, 0, 1, 2}, ML[6] = {0, 1, 1, 2, 2, 2};
+    int order[12];
+    for (int i = 0; i < 12; i++) order[i] = i;
+    for (int i = 0; i < 3; i++)
+        for (int j = i + 1; j < 12; j++)
+            if (L.A[13 * order[j]] < L.A[13 * order[i]]) { const int t = order[i]; order[i] = order[j]; order[j] = t; }
+    double v[3][12], C[4][3], rho[6], dv[3][6][3];
+    for (int k = 0; k < 3; k++)
+        for (int r = 0; r < 12; r++) v[k][r] = L.V[12 * r + order[k]];
+    for (int i = 0; i < 3; i++) {
+        C[0][i] = L.c0[i];
+        for (int j = 0; j < 3; j++) C[j + 1][i] = L.c0[i] + L.sig[j] * L.V3[3 * i + j];
+    }
+    for (int p = 0; p < 6; p++) {
+        double d[3];
+        sub3(C[PA[p]], C[PB[p]], d);
+        rho[p] = dot3(d, d);
+        for (int k = 0; k < 3; k++)
+            for (int i = 0; i < 3; i++) dv[k][p][i] = v[k][3 * PA[p] + i] - v[k][3 * PB[p] + i];
+    }
+    for (int N = 1; N <= 3; N++) {
+        L.valid[N - 1] = 0;
+        const int nm = N == 1 ? 1 : (N == 2 ? 3 : 6);
+        double Lm[6][6], Aug[6][7], b[6] = {0, 0, 0, 0, 0, 0};
+        for (int p = 0; p < 6; p++)
+            for (int q = 0; q < nm; q++) Lm[p][q] = dot3(dv[MK[q]][p], dv[ML[q]][p]) * (MK[q] == ML[q] ? 1.0 : 2.0);
+        normal6(Lm, rho, nm, Aug);
+        if (!solve_small(Aug, nm, b)) continue;
+        if (b[0] < 0.0)
+            for (int q = 0; q < 6; q++) b[q] = -b[q];
+        double beta[3] = {sqrt(b[0]), sqrt(fmax(b[2], 0.0)), sqrt(fmax(b[5], 0.0))};
+        if (b[1] < 0.0) beta[1] = -beta[1];
+        if (b[3] < 0.0) beta[2] = -beta[2];
+        for (int it = 0; it < PNP_GN_STEPS; it++) {
+            double res[6], dl[6];
+            for (int p = 0; p < 6; p++) {
+                double cvec[3] = {0.0, 0.0, 0.0};
+                for (int k = 0; k < N; k++)
+                    for (int i = 0; i < 3; i++) cvec[i] = cvec[i] + beta[k] * dv[k][p][i];
+                res[p] = dot3(cvec, cvec) - rho[p];
+                for (int k = 0; k < N; k++) Lm[p][k] = 2.0 * dot3(dv[k][p], cvec);
+            }
+            normal6(Lm, res, N, Aug);
+            if (!solve_small(Aug, N, dl)) break;
+            for (int k = 0; k < N; k++) beta[k] = beta[k] - dl[k];
+        }
+        double cc[4][3];
+        for (int j = 0; j < 4; j++)
+            for (int i = 0; i < 3; i++) {
+                double a = 0.0;
+                for (int k = 0; k < N; k++) a = a + beta[k] * v[k][3 * j + i];
+                cc[j][i] = a;
+            }
+        if (cc[0][2] < 0.0)
+            for (int j = 0; j < 4; j++)
+                for (int i = 0; i < 3; i++) cc[j][i] = -cc[j][i];
+        double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, U[9], Vs[9];
+        for (int j = 1; j < 4; j++) {
+            double dc[3], dw[3];
+            sub3(cc[j], cc[0], dc);
+            sub3(C[j], C[0], dw);
+            for (int a = 0; a < 3; a++)
+                for (int c = 0; c < 3; c++) H[3 * a + c] = H[3 * a + c] + dc[a] * dw[c];
+        }
+        svd3(H, U, Vs);
+        double* m = L.cand[N - 1];
+        bool fin = true;
+        for (int i = 0; i < 3; i++) {
+            for (int c = 0; c < 3; c++) m[4 * i + c] = (U[3 * i] * Vs[3 * c] + U[3 * i + 1] * Vs[3 * c + 1]) + U[3 * i + 2] * Vs[3 * c + 2];
+            m[4 * i + 3] = cc[0][i] - dot3(m + 4 * i, C[0]);
+        }
+        for (int i = 0; i < 12; i++) fin = fin && isfinite(m[i]);
+        L.valid[N - 1] = fin ? 1 : 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void pnp_final(int max_n, double fx, double fy, double thr2, PnpScratch s,
+                                                 uint8_t* __restrict__ mask0, uint8_t* __restrict__ mask1,
+                                                 float* __restrict__ d_pose, uint8_t* __restrict__ d_inlier,
+                                                 int32_t* __restrict__ d_inlier_index, int32_t* __restrict__ d_inlier_count,
+                                                 int32_t* __restrict__ d_status)
+{
+    __shared__ PnpFinalLds L;
+    PnpState* st = s.st;
+    const int n = st->n, nfin = st->nfin_acc, tid = threadIdx.x;
+    const unsigned long long key = st->best_key;
+    const int best_count = (int)(key >> 32);
+    const bool ok = nfin >= 4 && best_count >= 4;
+    uint8_t* cur = mask0;
+    int count = 0, kept = 0, beta_case = 0;
+    if (tid < 12) L.Rt[tid] = (tid == 0 || tid == 5 || tid == 10) ? 1.0 : 0.0;
+    __syncthreads();
+    if (ok) {
+        const int bi = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+        if (tid < 12) L.Rt[tid] = s.models[48 * (size_t)(bi / 4) + 12 * (bi % 4) + tid];
+        if (tid == 0) { st->best_index = bi; st->best_count = best_count; L.fail = 0; }
+        __syncthreads();
+        count = pnp_score_mask(L.Rt, s, n, fx, fy, thr2, mask0, L.red);
+        if (count >= PNP_MIN_REFIT) {                    // uniform
+            const double fm = (double)count;
+            double acc[40];
+            // the centroid
+            for (int k = 0; k < 3; k++) acc[k] = 0.0;
+            for (int i = tid; i < n; i += blockDim.x) {
+                if (!mask0[i]) continue;
+                acc[0] += s.X[i]; acc[1] += s.Y[i]; acc[2] += s.Z[i];
+            }
+            ordered_sum<3>(acc, L);
+            if (tid < 3) L.c0[tid] = L.sum[tid] / fm;
+            __syncthreads();
+            const double c0x = L.c0[0], c0y = L.c0[1], c0z = L.c0[2];
+            // the covariance, its principal axes (lane 0), the control points' scales
+            for (int k = 0; k < 6; k++) acc[k] = 0.0;
+            for (int i = tid; i < n; i += blockDim.x) {
+                if (!mask0[i]) continue;
+                const double dx = s.X[i] - c0x, dy = s.Y[i] - c0y, dz = s.Z[i] - c0z;
+                acc[0] += dx * dx; acc[1] += dx * dy; acc[2] += dx * dz; acc[3] += dy * dy; acc[4] += dy * dz; acc[5] += dz * dz;
+            }
+            ordered_sum<6>(acc, L);
+            if (tid == 0) {
+                double cov[9] = {L.sum[0], L.sum[1], L.sum[2], L.sum[1], L.sum[3], L.sum[4], L.sum[2], L.sum[4], L.sum[5]};
+                jacobi_eigen(cov, L.V3, 3);
+                for (int j = 0; j < 3; j++) {
+                    const double q = cov[4 * j] / fm;
+                    if (!(q > 0.0)) L.fail = 1;
+                    L.sig[j] = sqrt(q);
+                }
+            }
+            __syncthreads();
+            if (!L.fail) {                               // uniform
+                // the 40 sums of alpha_j alpha_k {1, x, y, x^2 + y^2}, j <= k
+                for (int k = 0; k < 40; k++) acc[k] = 0.0;
+                for (int i = tid; i < n; i += blockDim.x) {
+                    if (!mask0[i]) continue;
+                    const double dx = s.X[i] - c0x, dy = s.Y[i] - c0y, dz = s.Z[i] - c0z, x = s.x[i], y = s.y[i];
+                    double al[4];
+#pragma unroll
+                    for (int j = 0; j < 3; j++) al[j + 1] = ((L.V3[j] * dx + L.V3[3 + j] * dy) + L.V3[6 + j] * dz) / L.sig[j];
+                    al[0] = ((1.0 - al[1]) - al[2]) - al[3];
+                    const double rr = x * x + y * y;
+                    int q = 0;
+#pragma unroll
+                    for (int j = 0; j < 4; j++)
+#pragma unroll
+                        for (int k = j; k < 4; k++) {
+                            const double w = al[j] * al[k];
+                            acc[q] += w; acc[q + 1] += w * x; acc[q + 2] += w * y; acc[q + 3] += w * rr;
+                            q += 4;
+                        }
+                }
+                ordered_sum<40>(acc, L);
+                for (int i = tid; i < 144; i += blockDim.x) L.A[i] = 0.0;
+                __syncthreads();
+                if (tid == 0) {
+                    int q = 0;
+                    for (int j = 0; j < 4; j++)
+                        for (int k = j; k < 4; k++, q++) {
+                            const double s1 = L.sum[4 * q], sx = L.sum[4 * q + 1], sy = L.sum[4 * q + 2], sr = L.sum[4 * q + 3];
+                            for (int w = 0; w < 2; w++) {
+                                const int a = w ? k : j, b = w ? j : k;
+                                L.A[12 * (3 * a) + 3 * b] = s1;
+                                L.A[12 * (3 * a + 1) + 3 * b + 1] = s1;
+                                L.A[12 * (3 * a) + 3 * b + 2] = -sx;
+                                L.A[12 * (3 * a + 2) + 3 * b] = -sx;
+                                L.A[12 * (3 * a + 1) + 3 * b + 2] = -sy;
+                                L.A[12 * (3 * a + 2) + 3 * b + 1] = -sy;
+                                L.A[12 * (3 * a + 2) + 3 * b + 2] = sr;
+                            }
+                        }
+                }
+                __syncthreads();
+                jacobi_eigen_block(L.A, L.V, 12);
+                __syncthreads();
+                if (tid == 0) epnp_candidates(L);
+                __syncthreads();
+                // the summed squared reprojection error of each candidate over the inliers
+                for (int k = 0; k < 3; k++) acc[k] = 0.0;
+                for (int i = tid; i < n; i += blockDim.x) {
+                    if (!mask0[i]) continue;
+                    for (int k = 0; k < 3; k++) {
+                        if (!L.valid[k]) continue;
+                        double zc;
+                        const double e2 = reproj2(L.cand[k], s.X[i], s.Y[i], s.Z[i], s.x[i], s.y[i], fx, fy, &zc);
+                        acc[k] += zc > 0.0 ? e2 : INFINITY;
+                    }
+                }
+                ordered_sum<3>(acc, L);
+                if (tid == 0) {
+                    int best = 0;
+                    double be = INFINITY;
+                    for (int k = 0; k < 3; k++)
+                        if (L.valid[k] && L.sum[k] < be) { best = k + 1; be = L.sum[k]; }
+                    L.best = best;
+                }
+                __syncthreads();
+                const int best = L.best;
+                if (best) {                              // uniform
+                    const int cn = pnp_score_mask(L.cand[best - 1], s, n, fx, fy, thr2, mask1, L.red);
+                    if (cn >= count) {
+                        count = cn; kept = 1; beta_case = best; cur = mask1;
+                        if (tid < 12) L.Rt[tid] = L.cand[best - 1][tid];
+                    }
+                    __syncthreads();
+                }
+            }
+        }
+    }
+    // the inlier mask and its ordered compaction
+    int base = 0;
+    for (int c0 = 0; c0 < max_n; c0 += blockDim.x) {
+        const int i = c0 + tid;
+        const int f = (ok && i < n && cur[i]) ? 1 : 0;
+        if (i < max_n) d_inlier[i] = (uint8_t)f;
+        int tot;
+        const int off = rs_block_exclusive_scan(f, &tot);
+        if (f) d_inlier_index[base + off] = i;
+        base += tot;
+    }
+    if (tid < 16) {
+        const int r = tid >> 2, c = tid & 3;
+        d_pose[tid] = r < 3 ? (float)L.Rt[4 * r + c] : (c == 3 ? 1.f : 0.f);
+    }
+    if (tid < 12) st->Rt[tid] = L.Rt[tid];
+    if (tid == 0) {
+        const int status = nfin < 4 ? PNP_STATUS_FEW : (ok ? PNP_STATUS_OK : PNP_STATUS_FAILED);
+        *d_inlier_count = base;
+        *d_status = status;
+        st->status = status; st->refit_kept = kept; st->beta_case = beta_case; st->inliers = base;
+        st->nfin = nfin;
+        st->nfin_acc = 0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ C-ABI
+extern "C" int rs_pnp_estimator_create(rs_context* ctx, int max_points, int max_hypotheses, rs_pnp_estimator** out)
+{
+    if (!ctx || !out) return RS_ERR_INVALID;
+    *out = nullptr;
+    if (max_points < 1 || max_points > PNP_MAX_POINTS) return rs_fail(ctx, RS_ERR_UNSUPPORTED, "max_points 1 .. %d", PNP_MAX_POINTS);
+    if (max_hypotheses < 1 || max_hypotheses > PNP_MAX_HYP)
+        return rs_fail(ctx, RS_ERR_UNSUPPORTED, "max_hypotheses 1 .. %d", PNP_MAX_HYP);
+    RS_HIP(ctx, hipSetDevice(ctx->device));
+    rs_pnp_estimator* e = new rs_pnp_estimator();
+    e->ctx = ctx;
+    e->max_points = max_points;
+    e->max_hyp = max_hypotheses;
+    const size_t m = max_points, H = max_hypotheses;
+    bool okm = hipMalloc(&e->x, 5 * m * sizeof(double)) == hipSuccess && hipMalloc(&e->fin, m) == hipSuccess &&
+               hipMalloc(&e->mask, 2 * m) == hipSuccess && hipMalloc(&e->samples, 4 * H * sizeof(int32_t)) == hipSuccess &&
+               hipMalloc(&e->nmod, H * sizeof(int32_t)) == hipSuccess && hipMalloc(&e->models, 48 * H * sizeof(double)) == hipSuccess &&
+               hipMalloc(&e->scores, 4 * H * sizeof(int32_t)) == hipSuccess && hipMalloc(&e->st, sizeof(PnpState)) == hipSuccess;
+    if (okm) okm = hipMemsetAsync(e->st, 0, sizeof(PnpState), ctx->stream) == hipSuccess &&
+                   hipMemsetAsync(e->samples, 0xFF, 4 * H * sizeof(int32_t), ctx->stream) == hipSuccess &&
+                   hipMemsetAsync(e->nmod, 0xFF, H * sizeof(int32_t), ctx->stream) == hipSuccess &&
+                   hipMemsetAsync(e->scores, 0, 4 * H * sizeof(int32_t), ctx->stream) == hipSuccess &&
+                   hipMemsetAsync(e->models, 0, 48 * H * sizeof(double), ctx->stream) == hipSuccess &&
+                   hipStreamSynchronize(ctx->stream) == hipSuccess;
+    if (!okm) {
+        rs_pnp_estimator_destroy(e);
+        return rs_fail(ctx, RS_ERR_NOMEM, "pnp estimator scratch for %d points, %d hypotheses", max_points, max_hypotheses);
+    }
+    *out = e;
+    return RS_OK;
+}
+
+extern "C" int rs_pnp_estimator_destroy(rs_pnp_estimator* e)
+{
+    if (!e) return RS_OK;
+    (void)hipSetDevice(e->ctx->device);
+    (void)hipStreamSynchronize(e->ctx->stream);
+    void* p[] = {e->x, e->fin, e->mask, e->samples, e->nmod, e->models, e->scores, e->st};
+    for (void* q : p)
+        if (q) (void)hipFree(q);
+    delete e;
+    return RS_OK;
+}
+
+extern "C" int rs_estimate_pose_pnp(rs_context* ctx, rs_pnp_estimator* e, const float* d_object, const int32_t* d_object_index,
+                                    const float* d_pixels, const int32_t* d_pixel_index, const int32_t* d_count, int max_n,
+                                    const float* h_intrinsics, double threshold_px, double confidence, int max_hypotheses,
+                                    uint64_t seed, float* d_pose, uint8_t* d_inlier, int32_t* d_inlier_index,
+                                    int32_t* d_inlier_count, int32_t* d_status)
+{
+    if (!ctx) return RS_ERR_INVALID;
+    if (!e || !h_intrinsics) return rs_fail(ctx, RS_ERR_INVALID, "null estimator / intrinsics");
+    if (!d_pose || !d_inlier || !d_inlier_index || !d_inlier_count || !d_status) return rs_fail(ctx, RS_ERR_INVALID, "null output");
+    if (!d_count) return rs_fail(ctx, RS_ERR_INVALID, "null count");
+    if (max_n < 0) return rs_fail(ctx, RS_ERR_INVALID, "negative point count");
+    if (max_n > e->max_points) return rs_fail(ctx, RS_ERR_UNSUPPORTED, "points 0 .. %d (the estimator's max_points)", e->max_points);
+    if (max_n > 0 && (!d_object || !d_pixels)) return rs_fail(ctx, RS_ERR_INVALID, "null points");
+    const float* K = h_intrinsics;
+    if (!(K[0] > 0.f) || !(K[1] > 0.f) || !std::isfinite(K[2]) || !std::isfinite(K[3]))
+        return rs_fail(ctx, RS_ERR_INVALID, "intrinsics fx, fy > 0, finite cx, cy");
+    if (max_hypotheses < 1 || max_hypotheses > e->max_hyp)
+        return rs_fail(ctx, RS_ERR_UNSUPPORTED, "max_hypotheses 1 .. %d (the estimator's)", e->max_hyp);
+    if (!(threshold_px > 0.0) || !(confidence > 0.0 && confidence < 1.0))
+        return rs_fail(ctx, RS_ERR_INVALID, "threshold_px > 0, confidence in (0, 1)");
+    RS_HIP(ctx, hipSetDevice(ctx->device));
+    const double fx = K[0], fy = K[1], cx = K[2], cy = K[3], thr2 = threshold_px * threshold_px;
+    const PnpScratch s = scratch_of(e);
+    hipStream_t st = ctx->stream;
+    const int blocks = std::max(1, std::min((std::max(max_n, e->max_hyp) + 255) / 256, 64));
+    {
+        rs_prof_scope ps(ctx, "PNP0_prep");
+        hipLaunchKernelGGL(pnp_prep, dim3(blocks), dim3(256), 0, st, d_object, d_object_index, (const float2*)d_pixels,
+                           d_pixel_index, d_count, max_n, fx, fy, cx, cy, e->max_hyp, s);
+    }
+    const unsigned long long seed_hash = [](unsigned long long x) {
+        x += 0x9E3779B97F4A7C15ull;
+        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+        return x ^ (x >> 31);
+    }(seed);
+    const double log1mconf = std::log(1.0 - confidence);
+    const int rounds = (max_hypotheses + PNP_ROUND - 1) / PNP_ROUND;
+    for (int r = 0; r < rounds; r++) {
+        const int nh = std::min(PNP_ROUND, max_hypotheses - r * PNP_ROUND);
+        {
+            rs_prof_scope ps(ctx, "PNP1_hyp");
+            hipLaunchKernelGGL(pnp_hyp, dim3((nh + 63) / 64), dim3(64), 0, st, r, max_hypotheses, seed_hash, s);
+        }
+        {
+            rs_prof_scope ps(ctx, "PNP2_score");
+            hipLaunchKernelGGL(pnp_score, dim3(nh), dim3(256), 0, st, r, max_hypotheses, fx, fy, thr2, s);
+        }
+        hipLaunchKernelGGL(pnp_stop_k, dim3(1), dim3(64), 0, st, r, max_hypotheses, log1mconf, e->st);
+    }
+    {
+        rs_prof_scope ps(ctx, "PNP3_final");
+        hipLaunchKernelGGL(pnp_final, dim3(1), dim3(256), 0, st, max_n, fx, fy, thr2, s, e->mask, e->mask + e->max_points, d_pose,
+                           d_inlier, d_inlier_index, d_inlier_count, d_status);
+    }
+    RS_HIP(ctx, hipGetLastError());
+    return RS_OK;
+}
+
+extern "C" int rs_pnp_estimator_stats(rs_context* ctx, const rs_pnp_estimator* e, int32_t* h_stats, double* h_pose)
+{
+    if (!ctx) return RS_ERR_INVALID;
+    if (!e) return rs_fail(ctx, RS_ERR_INVALID, "null estimator");
+    RS_HIP(ctx, hipSetDevice(ctx->device));
+    PnpState st;
+    RS_HIP(ctx, hipMemcpyAsync(&st, e->st, sizeof(PnpState), hipMemcpyDeviceToHost, ctx->stream));
+    RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (h_stats) {
+        const int v[9] = {st.drawn, st.scored, st.best_index, st.best_count, st.refit_kept, st.beta_case, st.status, st.inliers, st.n};
+        memcpy(h_stats, v, sizeof(v));
+    }
+    if (h_pose) memcpy(h_pose, st.Rt, sizeof(st.Rt));
+    return RS_OK;
+}
+
+extern "C" int rs_pnp_hypotheses(rs_context* ctx, const rs_pnp_estimator* e, int32_t* h_samples, int32_t* h_nmodels,
+                                 double* h_models, int32_t* h_scores)
+{
+    if (!ctx) return RS_ERR_INVALID;
+    if (!e) return rs_fail(ctx, RS_ERR_INVALID, "null estimator");
+    RS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t H = e->max_hyp;
+    if (h_samples) RS_HIP(ctx, hipMemcpyAsync(h_samples, e->samples, 4 * H * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (h_nmodels) RS_HIP(ctx, hipMemcpyAsync(h_nmodels, e->nmod, H * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (h_models) RS_HIP(ctx, hipMemcpyAsync(h_models, e->models, 48 * H * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (h_scores) RS_HIP(ctx, hipMemcpyAsync(h_scores, e->scores, 4 * H * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RS_OK;
+}

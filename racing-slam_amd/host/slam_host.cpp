@@ -162,6 +162,7 @@ Session::~Session()
     rs_image_destroy(m_orb_img);
     rs_describer_destroy(m_orb);
     rs_pose_estimator_destroy(m_pose);
+    rs_pnp_estimator_destroy(m_pnp);
     rs_frame_destroy(m_frame);
     rs_context_destroy(m_ctx);
 }
@@ -877,6 +878,12 @@ rs_pose_estimator* Session::pose_estimator()
     return m_pose;
 }
 
+rs_pnp_estimator* Session::pnp_estimator()
+{
+    if (!m_pnp && !rs_ok(rs_pnp_estimator_create(m_ctx, 8192, 1000, &m_pnp), "rs_pnp_estimator_create")) m_pnp = nullptr;
+    return m_pnp;
+}
+
 // ------------------------------------------------------------------------ pose (src/PoseEstimation.cpp)
 namespace pose {
 
@@ -981,6 +988,42 @@ PoseEstimate estimate_pose_with_known_rotation(const ExtractedFeatures& prev_fea
     auto status = d_status.fetch(1);
     stage_sync();
     return collect(matches, pose, index, count, status);
+}
+
+PnpEstimate estimate_pose_pnp(const std::vector<Vec3f>& object_points, const std::vector<Vec2f>& pixels, const Camera& camera,
+                              double threshold_px)
+{
+    const size_t n = std::min(object_points.size(), pixels.size());
+    rs_pnp_estimator* est = Session::get().pnp_estimator();
+    if (!est || n > (size_t)POSE_MAX_POINTS) {
+        std::printf("estimate_pose_pnp: no estimator, or more than %d correspondences\n", POSE_MAX_POINTS);
+        return {};
+    }
+    std::vector<float> obj(3 * std::max<size_t>(n, 1), 0.f), pix(2 * std::max<size_t>(n, 1), 0.f);
+    for (size_t k = 0; k < n; k++) {
+        obj[3 * k] = object_points[k].x; obj[3 * k + 1] = object_points[k].y; obj[3 * k + 2] = object_points[k].z;
+        pix[2 * k] = pixels[k].x; pix[2 * k + 1] = pixels[k].y;
+    }
+    const float K[4] = {camera.fx(), camera.fy(), camera.cx(), camera.cy()};
+    StageScope scope;
+    DevBuf<float> d_obj(obj), d_pix(pix), d_pose(16);
+    DevBuf<int32_t> d_count(std::vector<int32_t>{(int32_t)n}), d_index(std::max<size_t>(n, 1)), d_cnt(1), d_status(1);
+    DevBuf<uint8_t> d_inlier(std::max<size_t>(n, 1));
+    if (!rs_ok(rs_estimate_pose_pnp(Session::get().ctx(), est, d_obj.get(), nullptr, d_pix.get(), nullptr, d_count.get(), (int)n, K,
+                                    threshold_px, 0.99, 200, 0, d_pose.get(), d_inlier.get(), d_index.get(), d_cnt.get(),
+                                    d_status.get()),
+               "rs_estimate_pose_pnp"))
+        return {};
+    auto pose = d_pose.fetch(16);
+    auto index = d_index.fetch(n);
+    auto count = d_cnt.fetch(1);
+    auto status = d_status.fetch(1);
+    stage_sync();
+    PnpEstimate e;
+    for (int k = 0; k < 16; k++) e.pose[k] = pose[k];
+    for (int32_t k = 0; k < count[0]; k++) e.inliers.push_back((size_t)index[k]);
+    e.status = status[0];
+    return e;
 }
 
 }  // namespace pose

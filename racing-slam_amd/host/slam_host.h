@@ -264,6 +264,8 @@ class Session {
                                              rs_frame** out_frame = nullptr);
     // the relative-pose scratch of pose::estimate_pose* (8192 points, 1000 hypotheses), created on first use
     rs_pose_estimator* pose_estimator();
+    // the absolute-pose scratch of pose::estimate_pose_pnp (8192 correspondences, 1000 hypotheses), created on first use
+    rs_pnp_estimator* pnp_estimator();
 
   private:
     Session();
@@ -279,6 +281,7 @@ class Session {
     rs_image* m_orb_img = nullptr;
     int m_orb_w = 0, m_orb_h = 0;
     rs_pose_estimator* m_pose = nullptr;
+    rs_pnp_estimator* m_pnp = nullptr;
     rs_frame* m_frame = nullptr;                // refresh_descriptors' device-built frame (8192 keypoints), created on first use
 };
 
@@ -304,6 +307,18 @@ PoseEstimate estimate_pose_with_known_rotation(const ExtractedFeatures& prev_fea
                                                const std::array<float, 9>& rotation);
 // std::mt19937(0) and std::uniform_int_distribution<size_t>(0, n - 1), i then j, 200 times (:137-143); [200][2]
 std::vector<int32_t> known_rotation_pairs(size_t n);
+
+// cv::solvePnPRansac(object_points, pixels, K, {}, rvec, tvec, false, 200, threshold_px, 0.99, inliers, SOLVEPNP_EPNP) as
+// LoopDetector's verify_pnp (src/LoopDetector.cpp:176-229) and Initialization's third-view check
+// (src/Initialization.cpp:188-228, 2.0 px) call it, as specified by tests/pnp_ref.py: 200 hypotheses, seed 0.  ONE C-ABI
+// call on the device (rs_estimate_pose_pnp) and one read-back.  Up to 8192 correspondences.
+struct PnpEstimate {
+    Mat4f pose = identity4();                    // row-major, world -> camera
+    std::vector<size_t> inliers;                 // indices of the inlier correspondences, ascending
+    int status = -1;                             // rs_estimate_pose_pnp's status (0 = solved); -1 = the call failed (logged)
+};
+PnpEstimate estimate_pose_pnp(const std::vector<Vec3f>& object_points, const std::vector<Vec2f>& pixels, const Camera& camera,
+                              double threshold_px);
 
 }  // namespace pose
 

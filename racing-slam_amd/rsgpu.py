@@ -28,6 +28,7 @@ EXPORTS = [
     "rs_describer_create", "rs_describer_destroy", "rs_describe_features", "rs_orb_blur",
     "rs_pose_estimator_create", "rs_pose_estimator_destroy", "rs_estimate_pose", "rs_estimate_pose_known_rotation",
     "rs_pose_estimator_stats", "rs_pose_hypotheses",
+    "rs_pnp_estimator_create", "rs_pnp_estimator_destroy", "rs_estimate_pose_pnp", "rs_pnp_estimator_stats", "rs_pnp_hypotheses",
     "rs_comm_get_unique_id", "rs_comm_init_rank", "rs_comm_destroy", "rs_comm_init_local", "rs_comm_count", "rs_prof_begin", "rs_prof_end", "rs_prof_counters", "rs_prof_empty_launch",
 ]
 
@@ -799,6 +800,25 @@ class Context:
             _dp(out["inlier_count"]), _dp(out["status"])), "rs_estimate_pose_known_rotation")
         return out
 
+    # -- absolute pose (LoopDetector's verify_pnp, Initialization's third-view check)
+    def pnp_estimator(self, max_points=8192, max_hypotheses=1000):
+        """rs_pnp_estimator: the scratch of the absolute-pose RANSAC (allocated once, reused)."""
+        return PnpEstimator(self, max_points, max_hypotheses)
+
+    def estimate_pose_pnp(self, est, d_object, d_pixels, d_count, max_n, K, d_object_index=None, d_pixel_index=None,
+                          threshold_px=2.0, confidence=0.99, max_hypotheses=200, seed=0, out=None):
+        """rs_estimate_pose_pnp: dict(pose [4][4] f32 world -> camera, inlier [max_n] u8, inlier_index [max_n] i32,
+        inlier_count [1], status [1]), device tensors; d_count is a device [1] i32."""
+        out = self._pose_out(max_n, out)
+        Kc = (C.c_float * 4)(*[float(v) for v in K])
+        self._check(self.lib.rs_estimate_pose_pnp(self.h, est.h, _dp(d_object), _dp(d_object_index), _dp(d_pixels),
+                                                  _dp(d_pixel_index), _dp(d_count), int(max_n), Kc, C.c_double(threshold_px),
+                                                  C.c_double(confidence), int(max_hypotheses),
+                                                  C.c_uint64(int(seed) & (2 ** 64 - 1)), _dp(out["pose"]), _dp(out["inlier"]),
+                                                  _dp(out["inlier_index"]), _dp(out["inlier_count"]), _dp(out["status"])),
+                    "rs_estimate_pose_pnp")
+        return out
+
     def synchronize(self):
         self._check(self.lib.rs_context_synchronize(self.h), "rs_context_synchronize")
 
@@ -926,6 +946,43 @@ class PoseEstimator:
     def close(self):
         if self.h:
             self.ctx.lib.rs_pose_estimator_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+class PnpEstimator:
+    """rs_pnp_estimator: the absolute-pose RANSAC's device scratch."""
+
+    STATS = ("drawn", "scored", "best_index", "best_count", "refit_kept", "beta_case", "status", "inliers", "n")
+
+    def __init__(self, ctx, max_points=8192, max_hypotheses=1000):
+        self.ctx, self.max_points, self.max_hypotheses = ctx, int(max_points), int(max_hypotheses)
+        self.h = C.c_void_p()
+        ctx._check(ctx.lib.rs_pnp_estimator_create(ctx.h, self.max_points, self.max_hypotheses, C.byref(self.h)),
+                   "rs_pnp_estimator_create")
+
+    def stats(self):
+        """Diagnostic of the last call: dict of STATS and Rt [12] f64, the final [R | t]."""
+        s = np.zeros(9, np.int32)
+        Rt = np.zeros(12, np.float64)
+        self.ctx._check(self.ctx.lib.rs_pnp_estimator_stats(self.ctx.h, self.h, s.ctypes.data_as(C.c_void_p),
+                                                            Rt.ctypes.data_as(C.c_void_p)), "rs_pnp_estimator_stats")
+        d = {k: int(v) for k, v in zip(self.STATS, s)}
+        d.update(Rt=Rt)
+        return d
+
+    def hypotheses(self):
+        """Diagnostic of the last call: dict(samples [H][4], nmodels [H], models [H][4][12] f64, scores [H][4])."""
+        H = self.max_hypotheses
+        out = dict(samples=np.zeros((H, 4), np.int32), nmodels=np.zeros(H, np.int32), models=np.zeros((H, 4, 12)),
+                   scores=np.zeros((H, 4), np.int32))
+        self.ctx._check(self.ctx.lib.rs_pnp_hypotheses(self.ctx.h, self.h, *[out[k].ctypes.data_as(C.c_void_p) for k in
+                                                                             ("samples", "nmodels", "models", "scores")]),
+                        "rs_pnp_hypotheses")
+        return out
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.rs_pnp_estimator_destroy(self.h)
             self.h = C.c_void_p()
 
 

@@ -702,3 +702,53 @@ def make_pose_pair(seed=0, n=2000, outlier_frac=0.3, noise_px=0.5, motion="forwa
         inlier[-k:] = True
     return dict(pts_from=pf.astype(np.float32), pts_to=pt.astype(np.float32), K=K, R=R, t=t, inlier=inlier,
                 width=width, height=height)
+
+
+PNP_LAYOUTS = ("volume", "far", "near_planar", "narrow")
+
+
+def make_pnp_scene(seed=0, n=2000, outlier_frac=0.3, noise_px=0.5, layout="volume", width=1280, height=720,
+                   descriptors=False):
+    """Object points and their pixels for the absolute-pose stage (the cv::solvePnPRansac calls of LoopDetector's
+    verify_pnp and Initialization's third-view check) under a known world -> camera pose.  layout: "volume" (depths of
+    4 .. 40 m over the whole image), "far" (60 .. 200 m), "near_planar" (a tilted plane 12 m away, 2 cm thick) or
+    "narrow" (the central 15 % of the image, 10 .. 30 m).  Inlier pixels are the projections of the f32 points plus
+    Gaussian noise of noise_px; a fraction outlier_frac of the pixels is displaced by 20 .. 200 px in a random direction,
+    so the true inlier set is unambiguous at a 2 px gate.
+    Returns dict(points [n][3] f32, pixels [n][2] f32, K (f32 fx, fy, cx, cy), pose [4][4] f64 world -> camera,
+    inlier [n] bool).  With descriptors=True the pixels are permuted and the dict also holds desc_points [n][32] u8
+    (random_descriptors), desc_pixels [n][32] u8 (flip_bits of the point's row; random rows for outliers) and
+    pixel_point [n] (the object point of each pixel); inlier then follows the pixels' order."""
+    rng = np.random.default_rng([0x9A9, PNP_LAYOUTS.index(layout), int(seed)])
+    K = np.array([700.0, 700.0, width / 2.0, height / 2.0], np.float32)
+    fx, fy, cx, cy = (float(k) for k in K)
+    R = rodrigues(np.array([0.2, -0.4, 0.1]) + rng.normal(0, 0.05, 3))
+    t = np.array([0.5, -0.3, 2.0]) + rng.normal(0, 0.2, 3)
+    span = 0.15 if layout == "narrow" else 1.0
+    u = np.stack([cx + span * rng.uniform(-0.5, 0.5, n) * width, cy + span * rng.uniform(-0.5, 0.5, n) * height], 1)
+    ray = np.stack([(u[:, 0] - cx) / fx, (u[:, 1] - cy) / fy, np.ones(n)], 1)
+    if layout == "near_planar":
+        depth = 12.0 / (ray @ np.array([0.1, -0.3, 1.0])) + rng.uniform(-0.01, 0.01, n)
+    else:
+        lo, hi = {"volume": (4.0, 40.0), "far": (60.0, 200.0), "narrow": (10.0, 30.0)}[layout]
+        depth = rng.uniform(lo, hi, n)
+    Xc = ray * depth[:, None]
+    Xw = ((Xc - t) @ R).astype(np.float32)            # R^T (Xc - t)
+    Xf = Xw.astype(np.float64) @ R.T + t
+    pix = np.stack([fx * Xf[:, 0] / Xf[:, 2] + cx, fy * Xf[:, 1] / Xf[:, 2] + cy], 1)
+    pix = pix + rng.normal(0, noise_px, pix.shape)
+    inlier = rng.random(n) >= outlier_frac
+    bad = np.flatnonzero(~inlier)
+    ang, mag = rng.uniform(0, 2 * np.pi, len(bad)), rng.uniform(20.0, 200.0, len(bad))
+    pix[bad] += np.stack([mag * np.cos(ang), mag * np.sin(ang)], 1)
+    pose = np.eye(4)
+    pose[:3, :3], pose[:3, 3] = R, t
+    out = dict(points=Xw, pixels=pix.astype(np.float32), K=K, pose=pose, inlier=inlier, width=width, height=height)
+    if descriptors:
+        dp = random_descriptors(rng, n)
+        dq = flip_bits(rng, dp)
+        dq[bad] = random_descriptors(rng, len(bad))
+        perm = rng.permutation(n)
+        out.update(pixels=out["pixels"][perm], inlier=inlier[perm], desc_points=dp, desc_pixels=np.ascontiguousarray(dq[perm]),
+                   pixel_point=perm.astype(np.int32))
+    return out

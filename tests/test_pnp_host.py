@@ -1,0 +1,81 @@
+"""slam::pose::estimate_pose_pnp (racing-slam_amd/host/slam_host.cpp) — the C++ host-side form of the reference's
+cv::solvePnPRansac calls — built against librsgpu and checked against the restatement tests/pnp_ref.py; and the new
+symbols of the C ABI without a GPU."""
+import ctypes as C
+import importlib
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import pnp_ref as P
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "tests", "host_cpp", "test_pnp_host.bin")
+SYMBOLS = ("rs_pnp_estimator_create", "rs_pnp_estimator_destroy", "rs_estimate_pose_pnp", "rs_pnp_estimator_stats",
+           "rs_pnp_hypotheses")
+
+
+def build_pnp_host(rs):
+    rs.load()
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    srcs = [os.path.join(ROOT, "tests", "host_cpp", "test_pnp_host.cpp"), os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.cpp")]
+    deps = srcs + [os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.h"), os.path.join(ROOT, "include", "rsgpu.h"),
+                   os.path.join(ROOT, "racing-slam_amd", "librsgpu.so")]
+    if os.path.exists(BIN) and all(os.path.getmtime(d) <= os.path.getmtime(BIN) for d in deps):
+        return BIN
+    subprocess.check_call([hipcc, "-O2", "-std=c++17", "-Wall", "-o", BIN] + srcs + [
+        "-L" + os.path.join(ROOT, "racing-slam_amd"), "-lrsgpu", "-Wl,-rpath," + os.path.join(ROOT, "racing-slam_amd"), "-lm"])
+    return BIN
+
+
+def test_library_exports_the_pnp_symbols(rs):
+    lib = rs.load()
+    missing = [s for s in SYMBOLS if not hasattr(lib, s)]
+    assert not missing, missing
+    assert set(SYMBOLS) <= set(rs.EXPORTS)
+    assert hasattr(rs.Context, "pnp_estimator") and hasattr(rs.Context, "estimate_pose_pnp")
+    assert hasattr(rs.PnpEstimator, "stats") and hasattr(rs.PnpEstimator, "hypotheses")
+
+
+def test_no_estimator_without_a_context(rs):
+    lib = rs.load()
+    h = C.c_void_p()
+    rc = lib.rs_pnp_estimator_create(None, 100, 10, C.byref(h))
+    assert rc == 1 and not h.value                   # RS_ERR_INVALID, no estimator
+    assert lib.rs_pnp_estimator_destroy(None) == 0
+    assert lib.rs_estimate_pose_pnp(None, None, None, None, None, None, None, 0, None, C.c_double(2.0), C.c_double(0.99), 200,
+                                    C.c_uint64(0), None, None, None, None, None) == 1
+
+
+def test_pnp_host_mirror_compiles(rs):
+    assert os.path.exists(build_pnp_host(rs))
+
+
+@pytest.mark.gpu
+def test_host_pnp_matches_the_restatement(rs, tmp_path):
+    exe = build_pnp_host(rs)
+    synth = importlib.import_module("racing-slam_amd").synth
+    d = synth.make_pnp_scene(5, 1500, 0.3, 0.5, "volume")
+    n, K = len(d["points"]), d["K"]
+    (tmp_path / "meta.txt").write_text(f"{n} " + " ".join(repr(float(k)) for k in K) + " 2.0\n")
+    d["points"].tofile(str(tmp_path / "object.f32"))
+    d["pixels"].tofile(str(tmp_path / "pixels.f32"))
+    r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    lines = (tmp_path / "out.txt").read_text().split("\n")
+    status, count = (int(v) for v in lines[0].split())
+    pose = np.array([int(v, 16) for v in lines[1].split()], np.uint32).view(np.float32).reshape(4, 4)
+    idx = np.array([int(v) for v in lines[2].split()], np.int64)
+    ref = P.estimate_pose_pnp(d["points"], d["pixels"], K, 2.0, 0.99, 200, seed=0)          # the reference's arguments
+    assert status == ref["status"] == 0 and len(idx) == count
+    assert np.allclose(pose, ref["pose"], atol=1e-5)
+    X, Y, Z, x, y, fin = P.prepare(d["points"], d["pixels"], K)
+    _, e2 = P.reproj2(ref["Rt"], X, Y, Z, x, y, float(K[0]), float(K[1]))
+    near = np.abs(e2 - ref["thr2"]) <= 1e-9 * ref["thr2"]
+    mask = np.zeros(n, bool)
+    mask[idx] = True
+    assert np.array_equal(mask[~near], ref["mask"].astype(bool)[~near]) and np.all(np.diff(idx) > 0)
+    assert not mask[~d["inlier"]].any()
