@@ -6,70 +6,55 @@
 // (-ffp-contract=off), so sampling, model sets and scores agree with it to rounding.
 //
 // rs_estimate_pose_pnp: one stream-ordered chain, no host synchronisation, no allocation; the count is read on the device.
+// The RANSAC frame (draw, table, key, stop, inlier compaction) is ransac.h's with S = 4, M = 4, D = 12; this file adds:
 //   pnp_prep      gather through the two optional index arrays, normalise into f64 SoA scratch, count the finite
-//                 correspondences, reset the state and the hypothesis table
-//   pnp_hyp       one lane per hypothesis (4 wave64 workgroups per round of 256): the hashed sample, Grunert's quartic,
-//                 its real roots by the bisection of ordered 64-bit keys between the roots of the derivatives (serial
-//                 per lane), up to 4 models [R | t] from the orthonormal frames of the two triangles
+//                 correspondences, reset the state and the table
+//   pnp_hyp       one lane per hypothesis (4 wave64 workgroups per round of 256): the sample (every lane, in registers),
+//                 Grunert's quartic, its real roots by the bisection of ordered 64-bit keys between the roots of the
+//                 derivatives (serial per lane), up to 4 models [R | t] from the orthonormal frames of the two triangles
 //   pnp_score     one workgroup per hypothesis: every point is loaded once and tested against all of its models;
-//                 integer counts; a packed 64-bit atomicMax of (count, ~(4 h + m)) keeps the best
-//   pnp_stop      the adaptive stop after each round of 256; later rounds exit at entry
+//                 integer counts, the key's atomicMax
+//   pnp_stop_k    the adaptive stop after each round of 256 (at once with fewer than 4 finite correspondences); later
+//                 rounds exit at entry
 //   pnp_final     one workgroup: the best model's mask, the EPnP sums in a fixed order, the 12 x 12 cyclic Jacobi with the
 //                 whole workgroup, the three beta cases with Gauss-Newton (lane 0), their summed errors, the keep /
-//                 discard decision, the mask and its ordered compaction
+//                 discard decision, the final inlier mask
 // No float atomics: two calls with the same inputs write the same bytes.
-#include <algorithm>
-
 #include "pose_shared.h"
 #include "tri_core.h"
 
-#define PNP_MAX_POINTS 8192
-#define PNP_MAX_HYP 4096
-#define PNP_ROUND 256
-#define PNP_MAX_DRAWS 64
 #define PNP_P3P_EPS 1e-6            // relative residual of each cosine law that a model may have
 #define PNP_COLLINEAR_EPS 1e-6      // |(P2 - P1) x (P3 - P1)| must exceed this times |P2 - P1| |P3 - P1|
 #define PNP_SOLVE_EPS 1e-13
 #define PNP_GN_STEPS 5
 #define PNP_MIN_REFIT 6
-#define PNP_STATUS_OK 0
-#define PNP_STATUS_FEW 1
-#define PNP_STATUS_FAILED 2
 
 struct PnpState {
-    unsigned long long best_key;
-    int stop, drawn, n, status, refit_kept, beta_case, inliers, scored, best_index, best_count;
+    RansacState r;
+    int status, refit_kept, beta_case, inliers;
     int nfin;               // finite correspondences of the last call
     int nfin_acc;           // pnp_prep's atomic counter: zero between calls (pnp_final clears it)
     double Rt[12];
 };
 
-struct rs_pnp_estimator {
-    rs_context* ctx = nullptr;
-    int max_points = 0, max_hyp = 0;
+struct rs_pnp_estimator : RansacEstimator {          // t: samples [max_hyp][4], models [max_hyp][4][12], scores [max_hyp][4]
     double* x = nullptr;            // [5][max_points] X, Y, Z, x, y
     uint8_t* fin = nullptr;         // [max_points]
     uint8_t* mask = nullptr;        // [2][max_points] the minimal model's mask, the refit's
-    int32_t* samples = nullptr;     // [max_hyp][4]
-    int32_t* nmod = nullptr;        // [max_hyp]
-    double* models = nullptr;       // [max_hyp][4][12]
-    int32_t* scores = nullptr;      // [max_hyp][4]
     PnpState* st = nullptr;
 };
 
 struct PnpScratch {
     double *X, *Y, *Z, *x, *y;
     uint8_t* fin;
-    int32_t *samples, *nmod, *scores;
-    double* models;
+    RansacTable t;
     PnpState* st;
 };
 
 static PnpScratch scratch_of(const rs_pnp_estimator* e)
 {
     const size_t m = e->max_points;
-    return PnpScratch{e->x, e->x + m, e->x + 2 * m, e->x + 3 * m, e->x + 4 * m, e->fin, e->samples, e->nmod, e->scores,
-                      e->models, e->st};
+    return PnpScratch{e->x, e->x + m, e->x + 2 * m, e->x + 3 * m, e->x + 4 * m, e->fin, e->t, e->st};
 }
 
 // ------------------------------------------------------------------------------------------------ helpers
@@ -190,35 +175,22 @@ __global__ __launch_bounds__(256) void pnp_prep(const float* __restrict__ object
     }
     c = block_sum_int(c, red);
     if (threadIdx.x == 0 && c) atomicAdd(&s.st->nfin_acc, c);
-    for (int h = tid; h < table_hyp; h += stride) {     // the estimator's whole table: no entry outlives its call
-        s.nmod[h] = -1;
-#pragma unroll
-        for (int k = 0; k < 4; k++) { s.samples[4 * h + k] = -1; s.scores[4 * h + k] = 0; }
-    }
+    ransac_reset_table<4, 4>(s.t, table_hyp);
     if (tid == 0) {
         PnpState* st = s.st;
-        st->best_key = 0ull;
-        st->stop = 0; st->drawn = 0; st->n = n; st->status = PNP_STATUS_FAILED;
-        st->refit_kept = 0; st->beta_case = 0; st->inliers = 0; st->scored = 0;
-        st->best_index = -1; st->best_count = 0;
+        st->r = RansacState{0ull, 0, 0, n, 0, -1, 0};
+        st->status = RANSAC_STATUS_FAILED;
+        st->refit_kept = 0; st->beta_case = 0; st->inliers = 0;
     }
 }
 
 __global__ __launch_bounds__(64) void pnp_hyp(int round, int max_hyp, unsigned long long seed_hash, PnpScratch s)
 {
-    const int h = round * PNP_ROUND + blockIdx.x * 64 + threadIdx.x;
-    if (s.st->stop || s.st->nfin_acc < 4 || h >= max_hyp) return;
-    const int n = s.st->n;
-    int idx[4], k = 0;
-    for (int j = 0; j < PNP_MAX_DRAWS && k < 4; j++) {
-        const unsigned long long u = splitmix64(seed_hash + (((unsigned long long)h << 16) | (unsigned long long)j));
-        const int i = (int)(((u >> 32) * (unsigned long long)n) >> 32);
-        bool dup = !s.fin[i];
-        for (int q = 0; q < k; q++) dup |= idx[q] == i;
-        if (!dup) idx[k++] = i;
-    }
-    if (k < 4) { s.nmod[h] = 0; return; }
-    for (int q = 0; q < 4; q++) s.samples[4 * h + q] = idx[q];
+    const int h = round * RANSAC_ROUND + blockIdx.x * 64 + threadIdx.x;
+    if (s.st->r.stop || s.st->nfin_acc < 4 || h >= max_hyp) return;
+    int idx[4];
+    if (!ransac_draw<4>(seed_hash, h, s.st->r.n, s.fin, idx)) { s.t.nmod[h] = 0; return; }
+    for (int q = 0; q < 4; q++) s.t.samples[4 * h + q] = idx[q];
     double P[3][3], jv[3][3];
     for (int q = 0; q < 3; q++) {
         const int i = idx[q];
@@ -231,7 +203,7 @@ __global__ __launch_bounds__(64) void pnp_hyp(int round, int max_hyp, unsigned l
     sub3(P[1], P[0], d21); sub3(P[2], P[0], d31); sub3(P[2], P[1], d32);
     const double a2 = dot3(d32, d32), b2 = dot3(d31, d31), c2 = dot3(d21, d21);
     cross3(d21, d31, cr);
-    if (!(dot3(cr, cr) > (PNP_COLLINEAR_EPS * PNP_COLLINEAR_EPS) * (b2 * c2))) { s.nmod[h] = 0; return; }
+    if (!(dot3(cr, cr) > (PNP_COLLINEAR_EPS * PNP_COLLINEAR_EPS) * (b2 * c2))) { s.t.nmod[h] = 0; return; }
     const double ca = dot3(jv[1], jv[2]), cb = dot3(jv[0], jv[2]), cg = dot3(jv[0], jv[1]);
     const double q1 = (a2 - c2) / b2, r = c2 / b2;
     const double N[3] = {1.0 + q1, -2.0 * q1 * cb, q1 - 1.0}, D[2] = {2.0 * cg, -2.0 * ca}, W[3] = {1.0, -2.0 * cb, 1.0};
@@ -267,25 +239,25 @@ __global__ __launch_bounds__(64) void pnp_hyp(int round, int max_hyp, unsigned l
         }
         for (int i = 0; i < 12; i++) fin = fin && isfinite(m[i]);
         if (!fin) continue;
-        double* out = s.models + 48 * (size_t)h + 12 * nm;
+        double* out = s.t.models + 48 * (size_t)h + 12 * nm;
         for (int i = 0; i < 12; i++) out[i] = m[i];
         nm++;
     }
-    s.nmod[h] = nm;
+    s.t.nmod[h] = nm;
 }
 
 __global__ __launch_bounds__(256) void pnp_score(int round, int max_hyp, double fx, double fy, double thr2, PnpScratch s)
 {
     __shared__ int red[4];
-    const int h = round * PNP_ROUND + blockIdx.x;
-    if (s.st->stop || s.st->nfin_acc < 4 || h >= max_hyp) return;
-    const int nm = s.nmod[h], n = s.st->n;
+    const int h = round * RANSAC_ROUND + blockIdx.x;
+    if (s.st->r.stop || s.st->nfin_acc < 4 || h >= max_hyp) return;
+    const int nm = s.t.nmod[h], n = s.st->r.n;
     if (nm <= 0) return;                                 // uniform per workgroup
     double m[4][12];
 #pragma unroll
     for (int q = 0; q < 4; q++)
 #pragma unroll
-        for (int i = 0; i < 12; i++) m[q][i] = q < nm ? s.models[48 * (size_t)h + 12 * q + i] : 0.0;
+        for (int i = 0; i < 12; i++) m[q][i] = q < nm ? s.t.models[48 * (size_t)h + 12 * q + i] : 0.0;
     int c[4] = {0, 0, 0, 0};
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         if (!s.fin[i]) continue;
@@ -304,30 +276,18 @@ __global__ __launch_bounds__(256) void pnp_score(int round, int max_hyp, double 
         if (q >= nm) break;                              // uniform
         const int t = block_sum_int(c[q], red);
         if (threadIdx.x == 0) {
-            s.scores[4 * h + q] = t;
-            atomicMax(&s.st->best_key, ((unsigned long long)t << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)(4 * h + q)));
-            atomicAdd(&s.st->scored, 1);
+            s.t.scores[4 * h + q] = t;
+            atomicMax(&s.st->r.best_key, ransac_key(t, 4 * h + q));
+            atomicAdd(&s.st->r.scored, 1);
         }
     }
 }
 
 __global__ __launch_bounds__(64) void pnp_stop_k(int round, int max_hyp, double log1mconf, PnpState* st)
 {
-    if (threadIdx.x != 0 || st->stop) return;
-    if (st->nfin_acc < 4) { st->stop = 1; return; }
-    const int drawn = min((round + 1) * PNP_ROUND, max_hyp);
-    st->drawn = drawn;
-    const int cnt = (int)(st->best_key >> 32), n = st->n;
-    double needed = INFINITY;
-    if (n > 0 && cnt > 0) {
-        const double w = (double)cnt / (double)n, w4 = w * w * w * w;
-        if (w4 >= 1.0) needed = 0.0;
-        else {
-            const double d = log(1.0 - w4);
-            if (d < 0.0) needed = log1mconf / d;
-        }
-    }
-    if ((double)drawn >= needed || drawn >= max_hyp) st->stop = 1;
+    if (threadIdx.x != 0 || st->r.stop) return;
+    if (st->nfin_acc < 4) { st->r.stop = 1; return; }
+    ransac_stop<4>(&st->r, round, max_hyp, log1mconf);
 }
 
 struct PnpFinalLds {
@@ -506,18 +466,18 @@ __global__ __launch_bounds__(256) void pnp_final(int max_n, double fx, double fy
 {
     __shared__ PnpFinalLds L;
     PnpState* st = s.st;
-    const int n = st->n, nfin = st->nfin_acc, tid = threadIdx.x;
-    const unsigned long long key = st->best_key;
-    const int best_count = (int)(key >> 32);
+    const int n = st->r.n, nfin = st->nfin_acc, tid = threadIdx.x;
+    const unsigned long long key = st->r.best_key;
+    const int best_count = ransac_key_count(key);
     const bool ok = nfin >= 4 && best_count >= 4;
     uint8_t* cur = mask0;
     int count = 0, kept = 0, beta_case = 0;
     if (tid < 12) L.Rt[tid] = (tid == 0 || tid == 5 || tid == 10) ? 1.0 : 0.0;
     __syncthreads();
     if (ok) {
-        const int bi = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
-        if (tid < 12) L.Rt[tid] = s.models[48 * (size_t)(bi / 4) + 12 * (bi % 4) + tid];
-        if (tid == 0) { st->best_index = bi; st->best_count = best_count; L.fail = 0; }
+        const int bi = ransac_key_slot(key);
+        if (tid < 12) L.Rt[tid] = s.t.models[48 * (size_t)(bi / 4) + 12 * (bi % 4) + tid];
+        if (tid == 0) { st->r.best_index = bi; st->r.best_count = best_count; L.fail = 0; }
         __syncthreads();
         count = pnp_score_mask(L.Rt, s, n, fx, fy, thr2, mask0, L.red);
         if (count >= PNP_MIN_REFIT) {                    // uniform
@@ -629,24 +589,14 @@ __global__ __launch_bounds__(256) void pnp_final(int max_n, double fx, double fy
             }
         }
     }
-    // the inlier mask and its ordered compaction
-    int base = 0;
-    for (int c0 = 0; c0 < max_n; c0 += blockDim.x) {
-        const int i = c0 + tid;
-        const int f = (ok && i < n && cur[i]) ? 1 : 0;
-        if (i < max_n) d_inlier[i] = (uint8_t)f;
-        int tot;
-        const int off = rs_block_exclusive_scan(f, &tot);
-        if (f) d_inlier_index[base + off] = i;
-        base += tot;
-    }
+    const int base = write_inliers(ok, n, max_n, cur, d_inlier, d_inlier_index);
     if (tid < 16) {
         const int r = tid >> 2, c = tid & 3;
         d_pose[tid] = r < 3 ? (float)L.Rt[4 * r + c] : (c == 3 ? 1.f : 0.f);
     }
     if (tid < 12) st->Rt[tid] = L.Rt[tid];
     if (tid == 0) {
-        const int status = nfin < 4 ? PNP_STATUS_FEW : (ok ? PNP_STATUS_OK : PNP_STATUS_FAILED);
+        const int status = nfin < 4 ? RANSAC_STATUS_FEW : (ok ? RANSAC_STATUS_OK : RANSAC_STATUS_FAILED);
         *d_inlier_count = base;
         *d_status = status;
         st->status = status; st->refit_kept = kept; st->beta_case = beta_case; st->inliers = base;
@@ -656,47 +606,21 @@ __global__ __launch_bounds__(256) void pnp_final(int max_n, double fx, double fy
 }
 
 // ------------------------------------------------------------------------------------------------ C-ABI
+static bool pnp_alloc(rs_pnp_estimator* e, size_t m, hipStream_t stream)
+{
+    return hipMalloc(&e->x, 5 * m * sizeof(double)) == hipSuccess && hipMalloc(&e->fin, m) == hipSuccess &&
+           hipMalloc(&e->mask, 2 * m) == hipSuccess && hipMalloc(&e->st, sizeof(PnpState)) == hipSuccess &&
+           hipMemsetAsync(e->st, 0, sizeof(PnpState), stream) == hipSuccess;
+}
+
 extern "C" int rs_pnp_estimator_create(rs_context* ctx, int max_points, int max_hypotheses, rs_pnp_estimator** out)
 {
-    if (!ctx || !out) return RS_ERR_INVALID;
-    *out = nullptr;
-    if (max_points < 1 || max_points > PNP_MAX_POINTS) return rs_fail(ctx, RS_ERR_UNSUPPORTED, "max_points 1 .. %d", PNP_MAX_POINTS);
-    if (max_hypotheses < 1 || max_hypotheses > PNP_MAX_HYP)
-        return rs_fail(ctx, RS_ERR_UNSUPPORTED, "max_hypotheses 1 .. %d", PNP_MAX_HYP);
-    RS_HIP(ctx, hipSetDevice(ctx->device));
-    rs_pnp_estimator* e = new rs_pnp_estimator();
-    e->ctx = ctx;
-    e->max_points = max_points;
-    e->max_hyp = max_hypotheses;
-    const size_t m = max_points, H = max_hypotheses;
-    bool okm = hipMalloc(&e->x, 5 * m * sizeof(double)) == hipSuccess && hipMalloc(&e->fin, m) == hipSuccess &&
-               hipMalloc(&e->mask, 2 * m) == hipSuccess && hipMalloc(&e->samples, 4 * H * sizeof(int32_t)) == hipSuccess &&
-               hipMalloc(&e->nmod, H * sizeof(int32_t)) == hipSuccess && hipMalloc(&e->models, 48 * H * sizeof(double)) == hipSuccess &&
-               hipMalloc(&e->scores, 4 * H * sizeof(int32_t)) == hipSuccess && hipMalloc(&e->st, sizeof(PnpState)) == hipSuccess;
-    if (okm) okm = hipMemsetAsync(e->st, 0, sizeof(PnpState), ctx->stream) == hipSuccess &&
-                   hipMemsetAsync(e->samples, 0xFF, 4 * H * sizeof(int32_t), ctx->stream) == hipSuccess &&
-                   hipMemsetAsync(e->nmod, 0xFF, H * sizeof(int32_t), ctx->stream) == hipSuccess &&
-                   hipMemsetAsync(e->scores, 0, 4 * H * sizeof(int32_t), ctx->stream) == hipSuccess &&
-                   hipMemsetAsync(e->models, 0, 48 * H * sizeof(double), ctx->stream) == hipSuccess &&
-                   hipStreamSynchronize(ctx->stream) == hipSuccess;
-    if (!okm) {
-        rs_pnp_estimator_destroy(e);
-        return rs_fail(ctx, RS_ERR_NOMEM, "pnp estimator scratch for %d points, %d hypotheses", max_points, max_hypotheses);
-    }
-    *out = e;
-    return RS_OK;
+    return ransac_create(ctx, max_points, max_hypotheses, out, 4, 4, 12, "pnp", pnp_alloc, rs_pnp_estimator_destroy);
 }
 
 extern "C" int rs_pnp_estimator_destroy(rs_pnp_estimator* e)
 {
-    if (!e) return RS_OK;
-    (void)hipSetDevice(e->ctx->device);
-    (void)hipStreamSynchronize(e->ctx->stream);
-    void* p[] = {e->x, e->fin, e->mask, e->samples, e->nmod, e->models, e->scores, e->st};
-    for (void* q : p)
-        if (q) (void)hipFree(q);
-    delete e;
-    return RS_OK;
+    return e ? ransac_destroy(e, {e->x, e->fin, e->mask, e->st}) : RS_OK;
 }
 
 extern "C" int rs_estimate_pose_pnp(rs_context* ctx, rs_pnp_estimator* e, const float* d_object, const int32_t* d_object_index,
@@ -705,40 +629,26 @@ extern "C" int rs_estimate_pose_pnp(rs_context* ctx, rs_pnp_estimator* e, const 
                                     uint64_t seed, float* d_pose, uint8_t* d_inlier, int32_t* d_inlier_index,
                                     int32_t* d_inlier_count, int32_t* d_status)
 {
-    if (!ctx) return RS_ERR_INVALID;
-    if (!e || !h_intrinsics) return rs_fail(ctx, RS_ERR_INVALID, "null estimator / intrinsics");
-    if (!d_pose || !d_inlier || !d_inlier_index || !d_inlier_count || !d_status) return rs_fail(ctx, RS_ERR_INVALID, "null output");
-    if (!d_count) return rs_fail(ctx, RS_ERR_INVALID, "null count");
-    if (max_n < 0) return rs_fail(ctx, RS_ERR_INVALID, "negative point count");
-    if (max_n > e->max_points) return rs_fail(ctx, RS_ERR_UNSUPPORTED, "points 0 .. %d (the estimator's max_points)", e->max_points);
-    if (max_n > 0 && (!d_object || !d_pixels)) return rs_fail(ctx, RS_ERR_INVALID, "null points");
-    const float* K = h_intrinsics;
-    if (!(K[0] > 0.f) || !(K[1] > 0.f) || !std::isfinite(K[2]) || !std::isfinite(K[3]))
-        return rs_fail(ctx, RS_ERR_INVALID, "intrinsics fx, fy > 0, finite cx, cy");
-    if (max_hypotheses < 1 || max_hypotheses > e->max_hyp)
-        return rs_fail(ctx, RS_ERR_UNSUPPORTED, "max_hypotheses 1 .. %d (the estimator's)", e->max_hyp);
-    if (!(threshold_px > 0.0) || !(confidence > 0.0 && confidence < 1.0))
-        return rs_fail(ctx, RS_ERR_INVALID, "threshold_px > 0, confidence in (0, 1)");
+    int rc = ransac_check_call(ctx, e, d_object, d_pixels, max_n, h_intrinsics, d_pose, d_inlier, d_inlier_index, d_inlier_count,
+                               d_status);
+    if (!rc) rc = ransac_check_options(ctx, e, d_count, max_hypotheses, threshold_px, confidence);
+    if (rc) return rc;
     RS_HIP(ctx, hipSetDevice(ctx->device));
+    const float* K = h_intrinsics;
     const double fx = K[0], fy = K[1], cx = K[2], cy = K[3], thr2 = threshold_px * threshold_px;
     const PnpScratch s = scratch_of(e);
     hipStream_t st = ctx->stream;
-    const int blocks = std::max(1, std::min((std::max(max_n, e->max_hyp) + 255) / 256, 64));
+    const int blocks = ransac_blocks(max_n, e->max_hyp);
     {
         rs_prof_scope ps(ctx, "PNP0_prep");
         hipLaunchKernelGGL(pnp_prep, dim3(blocks), dim3(256), 0, st, d_object, d_object_index, (const float2*)d_pixels,
                            d_pixel_index, d_count, max_n, fx, fy, cx, cy, e->max_hyp, s);
     }
-    const unsigned long long seed_hash = [](unsigned long long x) {
-        x += 0x9E3779B97F4A7C15ull;
-        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-        return x ^ (x >> 31);
-    }(seed);
+    const unsigned long long seed_hash = splitmix64(seed);
     const double log1mconf = std::log(1.0 - confidence);
-    const int rounds = (max_hypotheses + PNP_ROUND - 1) / PNP_ROUND;
+    const int rounds = (max_hypotheses + RANSAC_ROUND - 1) / RANSAC_ROUND;
     for (int r = 0; r < rounds; r++) {
-        const int nh = std::min(PNP_ROUND, max_hypotheses - r * PNP_ROUND);
+        const int nh = std::min(RANSAC_ROUND, max_hypotheses - r * RANSAC_ROUND);
         {
             rs_prof_scope ps(ctx, "PNP1_hyp");
             hipLaunchKernelGGL(pnp_hyp, dim3((nh + 63) / 64), dim3(64), 0, st, r, max_hypotheses, seed_hash, s);
@@ -767,7 +677,8 @@ extern "C" int rs_pnp_estimator_stats(rs_context* ctx, const rs_pnp_estimator* e
     RS_HIP(ctx, hipMemcpyAsync(&st, e->st, sizeof(PnpState), hipMemcpyDeviceToHost, ctx->stream));
     RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (h_stats) {
-        const int v[9] = {st.drawn, st.scored, st.best_index, st.best_count, st.refit_kept, st.beta_case, st.status, st.inliers, st.n};
+        const int v[9] = {st.r.drawn, st.r.scored, st.r.best_index, st.r.best_count, st.refit_kept, st.beta_case, st.status, st.inliers,
+                          st.r.n};
         memcpy(h_stats, v, sizeof(v));
     }
     if (h_pose) memcpy(h_pose, st.Rt, sizeof(st.Rt));
@@ -777,14 +688,5 @@ extern "C" int rs_pnp_estimator_stats(rs_context* ctx, const rs_pnp_estimator* e
 extern "C" int rs_pnp_hypotheses(rs_context* ctx, const rs_pnp_estimator* e, int32_t* h_samples, int32_t* h_nmodels,
                                  double* h_models, int32_t* h_scores)
 {
-    if (!ctx) return RS_ERR_INVALID;
-    if (!e) return rs_fail(ctx, RS_ERR_INVALID, "null estimator");
-    RS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t H = e->max_hyp;
-    if (h_samples) RS_HIP(ctx, hipMemcpyAsync(h_samples, e->samples, 4 * H * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (h_nmodels) RS_HIP(ctx, hipMemcpyAsync(h_nmodels, e->nmod, H * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (h_models) RS_HIP(ctx, hipMemcpyAsync(h_models, e->models, 48 * H * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (h_scores) RS_HIP(ctx, hipMemcpyAsync(h_scores, e->scores, 4 * H * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return RS_OK;
+    return ransac_table_download(ctx, e, 4, 4, 12, h_samples, h_nmodels, h_models, h_scores);
 }

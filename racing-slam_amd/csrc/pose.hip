@@ -4,32 +4,23 @@
 // pose::estimate_pose_with_known_rotation (:110-227).  The specification is tests/essential_ref.py; this file follows
 // it operation by operation (-ffp-contract=off), so sampling, model sets and scores agree with it to rounding.
 //
-// rs_estimate_pose: one stream-ordered chain, no host synchronisation; the point count is read on the device.
-//   pose_prep     gather (through an optional index) + normalise into f64 SoA scratch; reset the state
-//   pose_hyp      one wave64 workgroup per hypothesis: the hashed sample, the 5 x 9 null space (Gauss-Jordan, lanes
-//                 per row, Gram-Schmidt), the 10 x 20 cubic constraints (lanes per row), Gauss-Jordan, B(z) and its
-//                 degree-10 determinant and Sturm sequence (lane 0), bisection and Newton (one lane per root), models
-//   pose_score    one workgroup per hypothesis: integer inlier counts of its models; a packed 64-bit atomicMax of
-//                 (count, ~(10 h + m)) keeps the best
-//   pose_stop     the adaptive stop after each round of 256; later rounds exit at entry
+// rs_estimate_pose: one stream-ordered chain, no host synchronisation; the point count is read on the device.  The
+// RANSAC frame (draw, table, key, stop, inlier compaction) is ransac.h's with S = 5, M = 10, D = 9; this file adds:
+//   pose_prep     gather (through an optional index) + normalise into f64 SoA scratch; reset the state and the table
+//   pose_hyp      one wave64 workgroup per hypothesis: the sample (lane 0, into LDS), the 5 x 9 null space (Gauss-Jordan,
+//                 lanes per row, Gram-Schmidt), the 10 x 20 cubic constraints (lanes per row), Gauss-Jordan, B(z) and its
+//                 degree-10 determinant and derivative table (lane 0), bisection and Newton (one lane per root), models
+//   pose_score    one workgroup per hypothesis: integer Sampson inlier counts of its models, the key's atomicMax
+//   pose_stop_k   the adaptive stop after each round of 256; later rounds exit at entry
 //   pose_final    one workgroup: LO (8-point refits with a fixed reduction order), decomposition, the final inlier mask
-//                 and its ordered compaction
 //   pose_cheir    4 candidates x point chunks: tri_core.h's DLT and gates, integer counts
 //   pose_choose   the first strict maximum; the f32 pose
-// rs_estimate_pose_known_rotation: kr_prep, kr_support (one workgroup per pair), kr_final (one workgroup).
+// rs_estimate_pose_known_rotation: kr_prep, kr_support (one workgroup per pair), kr_final (one workgroup), on the same
+// table (slot = the pair's number) with the same key and compaction; its pairs come from the caller, so no draw, no stop.
 // No float atomics: two calls with the same inputs write the same bytes.
-#include <algorithm>
-#include <climits>
-#include <cmath>
-
-#include "common.h"
 #include "pose_shared.h"
 #include "tri_core.h"
 
-#define POSE_MAX_POINTS 8192
-#define POSE_MAX_HYP 4096
-#define POSE_ROUND 256
-#define POSE_MAX_DRAWS 64
 #define POSE_PIVOT_EPS 1e-12
 // The real roots of the degree-10 determinant (tests/essential_ref.real_roots): a leading coefficient below
 // POSE_TRIM_EPS of the largest is dropped (roots beyond ~1e30); the roots of p's derivatives isolate those of p, level by
@@ -38,32 +29,23 @@
 // kept only if its unit-norm E satisfies max |2 E E^T E - tr(E E^T) E| <= POSE_ESS_EPS.
 #define POSE_ESS_EPS 1e-6
 #define POSE_LO_ROUNDS 4
-#define POSE_STATUS_OK 0
-#define POSE_STATUS_FEW 1
-#define POSE_STATUS_FAILED 2
 
 struct PoseState {
-    unsigned long long best_key;
-    int stop, drawn, n, status, lo_kept, chosen, inliers, scored;
+    RansacState r;
+    int status, lo_kept, chosen, inliers;
     int cheir[4];
-    int best_index, best_count, known;     // known = 1 after rs_estimate_pose_known_rotation
+    int known;                             // 1 after rs_estimate_pose_known_rotation
     double E[9];
     float cand[4][16];
     float pose[16];
 };
 
-struct rs_pose_estimator {
-    rs_context* ctx = nullptr;
-    int max_points = 0, max_hyp = 0;
+struct rs_pose_estimator : RansacEstimator {         // t: samples [max_hyp][5], models [max_hyp][10][9], scores [max_hyp][10]
     double* x = nullptr;            // [4][max_points] x1, y1, x2, y2
     float2* pix = nullptr;          // [2][max_points] gathered from / to pixels
     uint8_t* fin = nullptr;         // [max_points]
     uint8_t* mask = nullptr;        // [2][max_points] LO masks
     float* rays = nullptr;          // [9][max_points] known rotation: from, to, constraint
-    int32_t* samples = nullptr;     // [max_hyp][5]
-    int32_t* nmod = nullptr;        // [max_hyp]
-    double* models = nullptr;       // [max_hyp][10][9]
-    int32_t* scores = nullptr;      // [max_hyp][10]
     PoseState* st = nullptr;
 };
 
@@ -149,16 +131,14 @@ struct PoseScratch {
     double *x1, *y1, *x2, *y2;
     float2 *pf, *pt;
     uint8_t* fin;
-    int32_t *samples, *nmod, *scores;
-    double* models;
+    RansacTable t;
     PoseState* st;
 };
 
 static PoseScratch scratch_of(const rs_pose_estimator* e)
 {
     const size_t m = e->max_points;
-    return PoseScratch{e->x, e->x + m, e->x + 2 * m, e->x + 3 * m, e->pix, e->pix + m, e->fin,
-                       e->samples, e->nmod, e->scores, e->models, e->st};
+    return PoseScratch{e->x, e->x + m, e->x + 2 * m, e->x + 3 * m, e->pix, e->pix + m, e->fin, e->t, e->st};
 }
 
 __global__ __launch_bounds__(256) void pose_prep(const float2* __restrict__ from, const int32_t* __restrict__ from_index,
@@ -177,21 +157,14 @@ __global__ __launch_bounds__(256) void pose_prep(const float2* __restrict__ from
         s.pf[i] = a; s.pt[i] = b;
         s.fin[i] = f ? 1 : 0;
     }
-    for (int h = tid; h < table_hyp; h += stride) {     // the estimator's whole table: no entry outlives its call
-        s.nmod[h] = -1;
-#pragma unroll
-        for (int k = 0; k < 5; k++) s.samples[5 * h + k] = -1;
-#pragma unroll
-        for (int k = 0; k < 10; k++) s.scores[10 * h + k] = 0;
-    }
+    ransac_reset_table<5, 10>(s.t, table_hyp);
     if (tid == 0) {
         PoseState* st = s.st;
-        st->best_key = 0ull;
-        st->stop = n < 5 ? 1 : 0;
-        st->drawn = 0; st->n = n; st->status = n < 5 ? POSE_STATUS_FEW : POSE_STATUS_FAILED;
-        st->lo_kept = 0; st->chosen = -1; st->inliers = 0; st->scored = 0;
+        st->r = RansacState{0ull, n < 5 ? 1 : 0, 0, n, 0, -1, 0};
+        st->status = n < 5 ? RANSAC_STATUS_FEW : RANSAC_STATUS_FAILED;
+        st->lo_kept = 0; st->chosen = -1; st->inliers = 0;
         st->cheir[0] = st->cheir[1] = st->cheir[2] = st->cheir[3] = 0;
-        st->best_index = -1; st->best_count = 0; st->known = 0;
+        st->known = 0;
         for (int k = 0; k < 9; k++) st->E[k] = 0.0;
     }
 }
@@ -214,26 +187,15 @@ __global__ __launch_bounds__(64) void pose_hyp(int round, int max_hyp, unsigned 
 {
     __shared__ HypLds L;
     const int lane = threadIdx.x;
-    const int h = round * POSE_ROUND + blockIdx.x;
-    if (s.st->stop || h >= max_hyp) return;
-    const int n = s.st->n;
-    if (lane == 0) {                                  // the hashed sample
-        int k = 0;
-        for (int j = 0; j < POSE_MAX_DRAWS && k < 5; j++) {
-            const unsigned long long u = splitmix64(seed_hash + (((unsigned long long)h << 16) | (unsigned long long)j));
-            const int i = (int)(((u >> 32) * (unsigned long long)n) >> 32);
-            bool dup = !s.fin[i];
-            for (int q = 0; q < k; q++) dup |= L.idx[q] == i;
-            if (!dup) L.idx[k++] = i;
-        }
-        L.ok = k == 5;
-    }
+    const int h = round * RANSAC_ROUND + blockIdx.x;
+    if (s.st->r.stop || h >= max_hyp) return;
+    if (lane == 0) L.ok = ransac_draw<5>(seed_hash, h, s.st->r.n, s.fin, L.idx);
     __syncthreads();
     if (!L.ok) {
-        if (lane == 0) s.nmod[h] = 0;
+        if (lane == 0) s.t.nmod[h] = 0;
         return;
     }
-    if (lane < 5) s.samples[5 * h + lane] = L.idx[lane];
+    if (lane < 5) s.t.samples[5 * h + lane] = L.idx[lane];
     if (lane < 45) {                                  // Q [5][9]
         const int r = lane / 9, c = lane - 9 * r, i = L.idx[r];
         const double x1 = s.x1[i], y1 = s.y1[i], x2 = s.x2[i], y2 = s.y2[i];
@@ -431,21 +393,21 @@ __global__ __launch_bounds__(64) void pose_hyp(int round, int max_hyp, unsigned 
     const unsigned long long bal = __ballot(valid);
     if (valid) {
         const int slot = __popcll(bal & ((1ull << lane) - 1ull));
-        double* out = s.models + 90 * (size_t)h + 9 * slot;
+        double* out = s.t.models + 90 * (size_t)h + 9 * slot;
         for (int i = 0; i < 9; i++) out[i] = e[i];
     }
-    if (lane == 0) s.nmod[h] = __popcll(bal);
+    if (lane == 0) s.t.nmod[h] = __popcll(bal);
 }
 
 __global__ __launch_bounds__(256) void pose_score(int round, int max_hyp, double thr2, PoseScratch s)
 {
     __shared__ int red[4];
-    const int h = round * POSE_ROUND + blockIdx.x;
-    if (s.st->stop || h >= max_hyp) return;
-    const int nm = s.nmod[h], n = s.st->n;
+    const int h = round * RANSAC_ROUND + blockIdx.x;
+    if (s.st->r.stop || h >= max_hyp) return;
+    const int nm = s.t.nmod[h], n = s.st->r.n;
     for (int m = 0; m < nm; m++) {
         double e[9];
-        const double* src = s.models + 90 * (size_t)h + 9 * m;
+        const double* src = s.t.models + 90 * (size_t)h + 9 * m;
 #pragma unroll
         for (int i = 0; i < 9; i++) e[i] = src[i];
         int c = 0;
@@ -453,29 +415,17 @@ __global__ __launch_bounds__(256) void pose_score(int round, int max_hyp, double
             c += (s.fin[i] && sampson2(e, s.x1[i], s.y1[i], s.x2[i], s.y2[i]) < thr2) ? 1 : 0;
         c = block_sum_int(c, red);
         if (threadIdx.x == 0) {
-            s.scores[10 * h + m] = c;
-            atomicMax(&s.st->best_key, ((unsigned long long)c << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)(10 * h + m)));
-            atomicAdd(&s.st->scored, 1);
+            s.t.scores[10 * h + m] = c;
+            atomicMax(&s.st->r.best_key, ransac_key(c, 10 * h + m));
+            atomicAdd(&s.st->r.scored, 1);
         }
     }
 }
 
 __global__ __launch_bounds__(64) void pose_stop_k(int round, int max_hyp, double log1mconf, PoseState* st)
 {
-    if (threadIdx.x != 0 || st->stop) return;
-    const int drawn = min((round + 1) * POSE_ROUND, max_hyp);
-    st->drawn = drawn;
-    const int cnt = (int)(st->best_key >> 32), n = st->n;
-    double needed = INFINITY;
-    if (n > 0 && cnt > 0) {
-        const double w = (double)cnt / (double)n, w5 = w * w * w * w * w;
-        if (w5 >= 1.0) needed = 0.0;
-        else {
-            const double d = log(1.0 - w5);
-            if (d < 0.0) needed = log1mconf / d;
-        }
-    }
-    if ((double)drawn >= needed || drawn >= max_hyp) st->stop = 1;
+    if (threadIdx.x != 0 || st->r.stop) return;
+    ransac_stop<5>(&st->r, round, max_hyp, log1mconf);
 }
 
 // score E into mask (for i < n), returns the count (all threads)
@@ -504,17 +454,17 @@ __global__ __launch_bounds__(256) void pose_final(int max_n, double thr2, PoseSc
 {
     __shared__ FinalLds L;
     PoseState* st = s.st;
-    const int n = st->n, tid = threadIdx.x;
-    const unsigned long long key = st->best_key;
-    const int best_count = (int)(key >> 32);
+    const int n = st->r.n, tid = threadIdx.x;
+    const unsigned long long key = st->r.best_key;
+    const int best_count = ransac_key_count(key);
     const bool ok = n >= 5 && best_count >= 5;
     uint8_t* cur = mask0;
     uint8_t* nxt = mask1;
     int count = 0;
     if (ok) {
-        const int bi = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
-        if (tid < 9) L.E[tid] = s.models[90 * (size_t)(bi / 10) + 9 * (bi % 10) + tid];
-        if (tid == 0) { st->best_index = bi; st->best_count = best_count; }
+        const int bi = ransac_key_slot(key);
+        if (tid < 9) L.E[tid] = s.t.models[90 * (size_t)(bi / 10) + 9 * (bi % 10) + tid];
+        if (tid == 0) { st->r.best_index = bi; st->r.best_count = best_count; }
         __syncthreads();
         count = score_mask(L.E, s, n, thr2, cur, L.red);
         int kept = 0;
@@ -598,21 +548,11 @@ __global__ __launch_bounds__(256) void pose_final(int max_n, double thr2, PoseSc
                 P[12] = 0.f; P[13] = 0.f; P[14] = 0.f; P[15] = 1.f;
             }
             for (int i = 0; i < 9; i++) st->E[i] = L.E[i];
-            st->status = POSE_STATUS_OK;
+            st->status = RANSAC_STATUS_OK;
             st->inliers = count;
         }
     }
-    // the inlier mask and its ordered compaction
-    int base = 0;
-    for (int c0 = 0; c0 < max_n; c0 += blockDim.x) {
-        const int i = c0 + tid;
-        const int f = (ok && i < n && cur[i]) ? 1 : 0;
-        if (i < max_n) d_inlier[i] = (uint8_t)f;
-        int tot;
-        const int off = rs_block_exclusive_scan(f, &tot);
-        if (f) d_inlier_index[base + off] = i;
-        base += tot;
-    }
+    const int base = write_inliers(ok, n, max_n, cur, d_inlier, d_inlier_index);
     if (tid == 0) *d_inlier_count = base;
 }
 
@@ -620,8 +560,8 @@ __global__ __launch_bounds__(256) void pose_cheir(TriParams prm, PoseScratch s)
 {
     __shared__ int red[4];
     const PoseState* st = s.st;
-    if (st->status != POSE_STATUS_OK) return;
-    const int n = st->n, c = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (st->status != RANSAC_STATUS_OK) return;
+    const int n = st->r.n, c = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
     if (blockIdx.x * blockDim.x >= n) return;         // uniform per workgroup
     const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     float T[16];
@@ -640,7 +580,7 @@ __global__ void pose_choose(PoseState* st, float* __restrict__ d_pose, int32_t* 
 {
     if (threadIdx.x != 0) return;
     float P[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    if (st->status == POSE_STATUS_OK) {
+    if (st->status == RANSAC_STATUS_OK) {
         int best = 0, most = 0;
         for (int c = 0; c < 4; c++)
             if (st->cheir[c] > most) { most = st->cheir[c]; best = c; }
@@ -655,8 +595,7 @@ __global__ void pose_choose(PoseState* st, float* __restrict__ d_pose, int32_t* 
 struct KrScratch {
     float *fr, *to, *cons;          // [n][3] each
     float2 *pf, *pt;
-    int32_t *samples, *nmod, *scores;
-    double* models;
+    RansacTable t;
     PoseState* st;
 };
 
@@ -714,20 +653,14 @@ __global__ __launch_bounds__(256) void kr_prep(const float2* __restrict__ from, 
         s.pf[i] = a;
         s.pt[i] = b;
     }
-    for (int h = tid; h < table_hyp; h += stride) {     // the estimator's whole table: no entry outlives its call
-        s.nmod[h] = -1;
-#pragma unroll
-        for (int k = 0; k < 5; k++) s.samples[5 * h + k] = -1;
-#pragma unroll
-        for (int k = 0; k < 10; k++) s.scores[10 * h + k] = k == 0 ? -1 : 0;
-    }
+    ransac_reset_table<5, 10>(s.t, table_hyp);
+    for (int h = tid; h < table_hyp; h += stride) s.t.scores[10 * h] = -1;      // a pair's one score: -1 until it is counted
     if (tid == 0) {
         PoseState* st = s.st;
-        st->best_key = 0ull;
-        st->n = n; st->status = n < 8 ? POSE_STATUS_FEW : POSE_STATUS_FAILED; st->known = 1;
-        st->drawn = 0; st->stop = 1; st->lo_kept = 0; st->chosen = -1; st->inliers = 0; st->scored = 0;
+        st->r = RansacState{0ull, 1, 0, n, 0, -1, 0};
+        st->status = n < 8 ? RANSAC_STATUS_FEW : RANSAC_STATUS_FAILED; st->known = 1;
+        st->lo_kept = 0; st->chosen = -1; st->inliers = 0;
         st->cheir[0] = st->cheir[1] = st->cheir[2] = st->cheir[3] = 0;
-        st->best_index = -1; st->best_count = 0;
         for (int k = 0; k < 9; k++) st->E[k] = 0.0;
     }
 }
@@ -739,10 +672,10 @@ __global__ __launch_bounds__(256) void kr_support(const int32_t* __restrict__ pa
     if (n < 8) return;
     const int it = blockIdx.x;
     const int i = pairs[2 * it], j = pairs[2 * it + 1];
-    if (threadIdx.x < 2) s.samples[5 * it + threadIdx.x] = threadIdx.x ? j : i;
+    if (threadIdx.x < 2) s.t.samples[5 * it + threadIdx.x] = threadIdx.x ? j : i;
     if (threadIdx.x == 0) {
-        s.nmod[it] = 0;
-        atomicAdd(&s.st->drawn, 1);
+        s.t.nmod[it] = 0;
+        atomicAdd(&s.st->r.drawn, 1);
     }
     if (i == j || i < 0 || j < 0 || i >= n || j >= n) return;
     float ci[3], cj[3], tr[3];
@@ -759,10 +692,10 @@ __global__ __launch_bounds__(256) void kr_support(const int32_t* __restrict__ pa
         c += epipolar_error_f(E, s.fr + 3 * k, s.to + 3 * k, focal) < max_err ? 1 : 0;
     c = block_sum_int(c, red);
     if (threadIdx.x == 0) {
-        s.scores[10 * it] = c;
-        s.nmod[it] = 1;
-        for (int k = 0; k < 3; k++) s.models[90 * (size_t)it + k] = (double)tr[k];
-        if (c > 0) atomicMax(&s.st->best_key, ((unsigned long long)c << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)it));
+        s.t.scores[10 * it] = c;
+        s.t.nmod[it] = 1;
+        for (int k = 0; k < 3; k++) s.t.models[90 * (size_t)it + k] = (double)tr[k];
+        if (c > 0) atomicMax(&s.st->r.best_key, ransac_key(c, it));
     }
 }
 
@@ -780,15 +713,15 @@ __global__ __launch_bounds__(256) void kr_final(int max_n, Rot9 R, float focal, 
 {
     __shared__ KrLds L;
     PoseState* st = s.st;
-    const int n = st->n, tid = threadIdx.x;
-    const unsigned long long key = st->best_key;
-    const int best_s = (int)(key >> 32);
+    const int n = st->r.n, tid = threadIdx.x;
+    const unsigned long long key = st->r.best_key;
+    const int best_s = ransac_key_count(key);
     const bool ok = n >= 8 && best_s >= 8;
     float P[16] = {R.r[0], R.r[1], R.r[2], 0.f, R.r[3], R.r[4], R.r[5], 0.f, R.r[6], R.r[7], R.r[8], 0.f, 0.f, 0.f, 0.f, 1.f};
     if (ok) {
-        const int bi = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+        const int bi = ransac_key_slot(key);
         float bt[3], E[9];
-        for (int k = 0; k < 3; k++) bt[k] = (float)s.models[90 * (size_t)bi + k];
+        for (int k = 0; k < 3; k++) bt[k] = (float)s.t.models[90 * (size_t)bi + k];
         essential_tr(bt, R.r, E);
         double acc[6] = {0, 0, 0, 0, 0, 0};
         for (int k = tid; k < n; k += blockDim.x) {
@@ -814,8 +747,8 @@ __global__ __launch_bounds__(256) void kr_final(int max_n, Rot9 R, float focal, 
             float t[3] = {(float)L.V[j], (float)L.V[3 + j], (float)L.V[6 + j]};
             if ((t[0] * bt[0] + t[1] * bt[1]) + t[2] * bt[2] < 0.0f) { t[0] = -t[0]; t[1] = -t[1]; t[2] = -t[2]; }
             L.t[0] = t[0]; L.t[1] = t[1]; L.t[2] = t[2];
-            st->best_index = bi;
-            st->best_count = best_s;
+            st->r.best_index = bi;
+            st->r.best_count = best_s;
         }
         __syncthreads();
         const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -837,83 +770,34 @@ __global__ __launch_bounds__(256) void kr_final(int max_n, Rot9 R, float focal, 
         for (int a = 0; a < 3; a++) P[4 * a + 3] = sg * L.t[a];
         if (tid == 0) {
             st->cheir[0] = fp; st->cheir[1] = fm; st->chosen = fm > fp ? 1 : 0;
-            st->status = POSE_STATUS_OK; st->inliers = cnt;
+            st->status = RANSAC_STATUS_OK; st->inliers = cnt;
         }
     }
-    int base = 0;
-    for (int c0 = 0; c0 < max_n; c0 += blockDim.x) {
-        const int i = c0 + tid;
-        const int f = (ok && i < n && mask[i]) ? 1 : 0;
-        if (i < max_n) d_inlier[i] = (uint8_t)f;
-        int tot;
-        const int off = rs_block_exclusive_scan(f, &tot);
-        if (f) d_inlier_index[base + off] = i;
-        base += tot;
-    }
+    const int base = write_inliers(ok, n, max_n, mask, d_inlier, d_inlier_index);
     if (tid == 0) {
         *d_inlier_count = base;
         for (int k = 0; k < 16; k++) { d_pose[k] = P[k]; st->pose[k] = P[k]; }
-        *d_status = ok ? POSE_STATUS_OK : (n < 8 ? POSE_STATUS_FEW : POSE_STATUS_FAILED);
+        *d_status = ok ? RANSAC_STATUS_OK : (n < 8 ? RANSAC_STATUS_FEW : RANSAC_STATUS_FAILED);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ C-ABI
+static bool pose_alloc(rs_pose_estimator* e, size_t m, hipStream_t stream)
+{
+    return hipMalloc(&e->x, 4 * m * sizeof(double)) == hipSuccess && hipMalloc(&e->pix, 2 * m * sizeof(float2)) == hipSuccess &&
+           hipMalloc(&e->fin, m) == hipSuccess && hipMalloc(&e->mask, 2 * m) == hipSuccess &&
+           hipMalloc(&e->rays, 9 * m * sizeof(float)) == hipSuccess && hipMalloc(&e->st, sizeof(PoseState)) == hipSuccess &&
+           hipMemsetAsync(e->st, 0, sizeof(PoseState), stream) == hipSuccess;
+}
+
 extern "C" int rs_pose_estimator_create(rs_context* ctx, int max_points, int max_hypotheses, rs_pose_estimator** out)
 {
-    if (!ctx || !out) return RS_ERR_INVALID;
-    *out = nullptr;
-    if (max_points < 1 || max_points > POSE_MAX_POINTS) return rs_fail(ctx, RS_ERR_UNSUPPORTED, "max_points 1 .. %d", POSE_MAX_POINTS);
-    if (max_hypotheses < 1 || max_hypotheses > POSE_MAX_HYP)
-        return rs_fail(ctx, RS_ERR_UNSUPPORTED, "max_hypotheses 1 .. %d", POSE_MAX_HYP);
-    RS_HIP(ctx, hipSetDevice(ctx->device));
-    rs_pose_estimator* e = new rs_pose_estimator();
-    e->ctx = ctx;
-    e->max_points = max_points;
-    e->max_hyp = max_hypotheses;
-    const size_t m = max_points, H = max_hypotheses;
-    bool okm = hipMalloc(&e->x, 4 * m * sizeof(double)) == hipSuccess && hipMalloc(&e->pix, 2 * m * sizeof(float2)) == hipSuccess &&
-               hipMalloc(&e->fin, m) == hipSuccess && hipMalloc(&e->mask, 2 * m) == hipSuccess &&
-               hipMalloc(&e->rays, 9 * m * sizeof(float)) == hipSuccess && hipMalloc(&e->samples, 5 * H * sizeof(int32_t)) == hipSuccess &&
-               hipMalloc(&e->nmod, H * sizeof(int32_t)) == hipSuccess && hipMalloc(&e->models, 90 * H * sizeof(double)) == hipSuccess &&
-               hipMalloc(&e->scores, 10 * H * sizeof(int32_t)) == hipSuccess && hipMalloc(&e->st, sizeof(PoseState)) == hipSuccess;
-    if (okm) okm = hipMemsetAsync(e->st, 0, sizeof(PoseState), ctx->stream) == hipSuccess &&
-                   hipMemsetAsync(e->samples, 0xFF, 5 * H * sizeof(int32_t), ctx->stream) == hipSuccess &&
-                   hipMemsetAsync(e->nmod, 0xFF, H * sizeof(int32_t), ctx->stream) == hipSuccess &&
-                   hipMemsetAsync(e->scores, 0, 10 * H * sizeof(int32_t), ctx->stream) == hipSuccess &&
-                   hipMemsetAsync(e->models, 0, 90 * H * sizeof(double), ctx->stream) == hipSuccess &&
-                   hipStreamSynchronize(ctx->stream) == hipSuccess;
-    if (!okm) {
-        rs_pose_estimator_destroy(e);
-        return rs_fail(ctx, RS_ERR_NOMEM, "pose estimator scratch for %d points, %d hypotheses", max_points, max_hypotheses);
-    }
-    *out = e;
-    return RS_OK;
+    return ransac_create(ctx, max_points, max_hypotheses, out, 5, 10, 9, "pose", pose_alloc, rs_pose_estimator_destroy);
 }
 
 extern "C" int rs_pose_estimator_destroy(rs_pose_estimator* e)
 {
-    if (!e) return RS_OK;
-    (void)hipSetDevice(e->ctx->device);
-    (void)hipStreamSynchronize(e->ctx->stream);
-    void* p[] = {e->x, e->pix, e->fin, e->mask, e->rays, e->samples, e->nmod, e->models, e->scores, e->st};
-    for (void* q : p)
-        if (q) (void)hipFree(q);
-    delete e;
-    return RS_OK;
-}
-
-static int pose_check(rs_context* ctx, const rs_pose_estimator* e, const float* from, const float* to, int max_n,
-                      const float* K, float* d_pose, uint8_t* d_inlier, int32_t* d_index, int32_t* d_cnt, int32_t* d_status)
-{
-    if (!ctx) return RS_ERR_INVALID;
-    if (!e || !K) return rs_fail(ctx, RS_ERR_INVALID, "null estimator / intrinsics");
-    if (!d_pose || !d_inlier || !d_index || !d_cnt || !d_status) return rs_fail(ctx, RS_ERR_INVALID, "null output");
-    if (max_n < 0) return rs_fail(ctx, RS_ERR_INVALID, "negative point count");
-    if (max_n > e->max_points) return rs_fail(ctx, RS_ERR_UNSUPPORTED, "points 0 .. %d (the estimator's max_points)", e->max_points);
-    if (max_n > 0 && (!from || !to)) return rs_fail(ctx, RS_ERR_INVALID, "null points");
-    if (!(K[0] > 0.f) || !(K[1] > 0.f) || !std::isfinite(K[2]) || !std::isfinite(K[3]))
-        return rs_fail(ctx, RS_ERR_INVALID, "intrinsics fx, fy > 0, finite cx, cy");
-    return RS_OK;
+    return e ? ransac_destroy(e, {e->x, e->pix, e->fin, e->mask, e->rays, e->st}) : RS_OK;
 }
 
 extern "C" int rs_estimate_pose(rs_context* ctx, rs_pose_estimator* e, const float* d_pts_from, const int32_t* d_from_index,
@@ -921,34 +805,26 @@ extern "C" int rs_estimate_pose(rs_context* ctx, rs_pose_estimator* e, const flo
                                 double threshold_px, double confidence, int max_hypotheses, uint64_t seed, float* d_pose,
                                 uint8_t* d_inlier, int32_t* d_inlier_index, int32_t* d_inlier_count, int32_t* d_status)
 {
-    int rc = pose_check(ctx, e, d_pts_from, d_pts_to, max_n, h_intrinsics, d_pose, d_inlier, d_inlier_index, d_inlier_count, d_status);
+    int rc = ransac_check_call(ctx, e, d_pts_from, d_pts_to, max_n, h_intrinsics, d_pose, d_inlier, d_inlier_index, d_inlier_count,
+                               d_status);
+    if (!rc) rc = ransac_check_options(ctx, e, d_count, max_hypotheses, threshold_px, confidence);
     if (rc) return rc;
-    if (!d_count) return rs_fail(ctx, RS_ERR_INVALID, "null count");
-    if (max_hypotheses < 1 || max_hypotheses > e->max_hyp)
-        return rs_fail(ctx, RS_ERR_UNSUPPORTED, "max_hypotheses 1 .. %d (the estimator's)", e->max_hyp);
-    if (!(threshold_px > 0.0) || !(confidence > 0.0 && confidence < 1.0))
-        return rs_fail(ctx, RS_ERR_INVALID, "threshold_px > 0, confidence in (0, 1)");
     RS_HIP(ctx, hipSetDevice(ctx->device));
     const double fx = h_intrinsics[0], fy = h_intrinsics[1], cx = h_intrinsics[2], cy = h_intrinsics[3];
     const double t = threshold_px / ((fx + fy) / 2.0), thr2 = t * t;
     const PoseScratch s = scratch_of(e);
     hipStream_t st = ctx->stream;
-    const int pts_blocks = std::max(1, std::min((std::max(max_n, e->max_hyp) + 255) / 256, 64));
+    const int pts_blocks = ransac_blocks(max_n, e->max_hyp);
     {
         rs_prof_scope ps(ctx, "POSE0_prep");
         hipLaunchKernelGGL(pose_prep, dim3(pts_blocks), dim3(256), 0, st, (const float2*)d_pts_from, d_from_index,
                            (const float2*)d_pts_to, d_count, max_n, fx, fy, cx, cy, e->max_hyp, s);
     }
-    const unsigned long long seed_hash = [](unsigned long long x) {
-        x += 0x9E3779B97F4A7C15ull;
-        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-        return x ^ (x >> 31);
-    }(seed);
+    const unsigned long long seed_hash = splitmix64(seed);
     const double log1mconf = std::log(1.0 - confidence);
-    const int rounds = (max_hypotheses + POSE_ROUND - 1) / POSE_ROUND;
+    const int rounds = (max_hypotheses + RANSAC_ROUND - 1) / RANSAC_ROUND;
     for (int r = 0; r < rounds; r++) {
-        const int nh = std::min(POSE_ROUND, max_hypotheses - r * POSE_ROUND);
+        const int nh = std::min(RANSAC_ROUND, max_hypotheses - r * RANSAC_ROUND);
         {
             rs_prof_scope ps(ctx, "POSE1_hyp");
             hipLaunchKernelGGL(pose_hyp, dim3(nh), dim3(64), 0, st, r, max_hypotheses, seed_hash, s);
@@ -981,7 +857,7 @@ extern "C" int rs_estimate_pose_known_rotation(rs_context* ctx, rs_pose_estimato
                                                int n_iter, float max_epipolar_px, float* d_pose, uint8_t* d_inlier,
                                                int32_t* d_inlier_index, int32_t* d_inlier_count, int32_t* d_status)
 {
-    int rc = pose_check(ctx, e, d_pts_from, d_pts_to, n, h_intrinsics, d_pose, d_inlier, d_inlier_index, d_inlier_count, d_status);
+    int rc = ransac_check_call(ctx, e, d_pts_from, d_pts_to, n, h_intrinsics, d_pose, d_inlier, d_inlier_index, d_inlier_count, d_status);
     if (rc) return rc;
     if (!h_rotation || !d_pairs) return rs_fail(ctx, RS_ERR_INVALID, "null rotation / pairs");
     if (n_iter < 1 || n_iter > e->max_hyp) return rs_fail(ctx, RS_ERR_UNSUPPORTED, "n_iter 1 .. %d (the estimator's max_hypotheses)", e->max_hyp);
@@ -990,10 +866,10 @@ extern "C" int rs_estimate_pose_known_rotation(rs_context* ctx, rs_pose_estimato
     Rot9 R;
     for (int k = 0; k < 9; k++) R.r[k] = h_rotation[k];
     const size_t m = e->max_points;
-    const KrScratch s{e->rays, e->rays + 3 * m, e->rays + 6 * m, e->pix, e->pix + m, e->samples, e->nmod, e->scores, e->models, e->st};
+    const KrScratch s{e->rays, e->rays + 3 * m, e->rays + 6 * m, e->pix, e->pix + m, e->t, e->st};
     hipStream_t st = ctx->stream;
     const float fx = h_intrinsics[0], fy = h_intrinsics[1], cx = h_intrinsics[2], cy = h_intrinsics[3];
-    const int blocks = std::max(1, std::min((std::max(n, e->max_hyp) + 255) / 256, 64));
+    const int blocks = ransac_blocks(n, e->max_hyp);
     {
         rs_prof_scope ps(ctx, "POSEK0_prep");
         hipLaunchKernelGGL(kr_prep, dim3(blocks), dim3(256), 0, st, (const float2*)d_pts_from, d_from_index, (const float2*)d_pts_to,
@@ -1022,8 +898,8 @@ extern "C" int rs_pose_estimator_stats(rs_context* ctx, const rs_pose_estimator*
     RS_HIP(ctx, hipMemcpyAsync(&st, e->st, sizeof(PoseState), hipMemcpyDeviceToHost, ctx->stream));
     RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (h_stats) {
-        const int v[14] = {st.drawn, st.scored, st.best_index, st.best_count, st.lo_kept, st.cheir[0], st.cheir[1], st.cheir[2],
-                           st.cheir[3], st.chosen, st.status, st.inliers, st.n, st.known};
+        const int v[14] = {st.r.drawn, st.r.scored, st.r.best_index, st.r.best_count, st.lo_kept, st.cheir[0], st.cheir[1], st.cheir[2],
+                           st.cheir[3], st.chosen, st.status, st.inliers, st.r.n, st.known};
         memcpy(h_stats, v, sizeof(v));
     }
     if (h_E) memcpy(h_E, st.E, sizeof(st.E));
@@ -1034,14 +910,5 @@ extern "C" int rs_pose_estimator_stats(rs_context* ctx, const rs_pose_estimator*
 extern "C" int rs_pose_hypotheses(rs_context* ctx, const rs_pose_estimator* e, int32_t* h_samples, int32_t* h_nmodels,
                                   double* h_models, int32_t* h_scores)
 {
-    if (!ctx) return RS_ERR_INVALID;
-    if (!e) return rs_fail(ctx, RS_ERR_INVALID, "null estimator");
-    RS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t H = e->max_hyp;
-    if (h_samples) RS_HIP(ctx, hipMemcpyAsync(h_samples, e->samples, 5 * H * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (h_nmodels) RS_HIP(ctx, hipMemcpyAsync(h_nmodels, e->nmod, H * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (h_models) RS_HIP(ctx, hipMemcpyAsync(h_models, e->models, 90 * H * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (h_scores) RS_HIP(ctx, hipMemcpyAsync(h_scores, e->scores, 10 * H * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return RS_OK;
+    return ransac_table_download(ctx, e, 5, 10, 9, h_samples, h_nmodels, h_models, h_scores);
 }

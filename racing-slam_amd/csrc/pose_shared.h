@@ -1,26 +1,20 @@
-// pose_shared.h — what the relative-pose stage (pose.hip) and the absolute-pose stage (pnp.hip) share: the hashed draw's
-// mixer, the integer workgroup sum, polynomial helpers of the bisection root finders (ordered 64-bit keys), cyclic
-// Jacobi (serial and workgroup-wide) and the one-sided Jacobi 3 x 3 SVD.  Each follows tests/essential_ref.py operation
-// by operation; both stages are compiled with -ffp-contract=off.
+// pose_shared.h — what the relative-pose stage (pose.hip) and the absolute-pose stage (pnp.hip) share: the RANSAC frame
+// (ransac.h: the hashed draw, the hypothesis table, the best-model key, the adaptive stop, the inlier compaction and the
+// host side of an estimator) and the numeric helpers below: the integer workgroup sum, polynomial helpers of the bisection
+// root finders (ordered 64-bit keys), cyclic Jacobi (serial and workgroup-wide) and the one-sided Jacobi 3 x 3 SVD.
+// Each follows tests/essential_ref.py operation by operation; both stages are compiled with -ffp-contract=off.
 #pragma once
 #include <climits>
 #include <cmath>
 
 #include "common.h"
+#include "ransac.h"
 
 #define POSE_TRIM_EPS 1e-30
 #define POSE_BISECT_ITERS 64
 #define POSE_NEWTON 3
 #define POSE_SWEEPS 16
 #define POSE_JACOBI_TOL 1e-30       // a sweep starts only while sum(off-diagonal^2) > 1e-30 sum(diagonal^2)
-
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 
 __device__ __forceinline__ int block_sum_int(int v, int* red)
 {

@@ -909,17 +909,38 @@ class Describer:
             self.h = C.c_void_p()
 
 
-class PoseEstimator:
-    """rs_pose_estimator: the relative-pose RANSAC's device scratch."""
-
-    STATS = ("drawn", "scored", "best_index", "best_count", "lo_kept", "cheir0", "cheir1", "cheir2", "cheir3", "chosen",
-             "status", "inliers", "n", "known")
+class _RansacEstimator:
+    """The device scratch of a RANSAC stage.  PREFIX names its rs_<PREFIX>_estimator_* / rs_<PREFIX>_hypotheses exports;
+    SHAPE = (S, M, D): indices per sample, models per hypothesis, doubles per model."""
 
     def __init__(self, ctx, max_points=8192, max_hypotheses=1000):
         self.ctx, self.max_points, self.max_hypotheses = ctx, int(max_points), int(max_hypotheses)
         self.h = C.c_void_p()
-        ctx._check(ctx.lib.rs_pose_estimator_create(ctx.h, self.max_points, self.max_hypotheses, C.byref(self.h)),
-                   "rs_pose_estimator_create")
+        name = f"rs_{self.PREFIX}_estimator_create"
+        ctx._check(getattr(ctx.lib, name)(ctx.h, self.max_points, self.max_hypotheses, C.byref(self.h)), name)
+
+    def hypotheses(self):
+        """Diagnostic of the last call: dict(samples [H][S], nmodels [H], models [H][M][D] f64, scores [H][M])."""
+        H, (S, M, D) = self.max_hypotheses, self.SHAPE
+        out = dict(samples=np.zeros((H, S), np.int32), nmodels=np.zeros(H, np.int32), models=np.zeros((H, M, D)),
+                   scores=np.zeros((H, M), np.int32))
+        name = f"rs_{self.PREFIX}_hypotheses"
+        self.ctx._check(getattr(self.ctx.lib, name)(self.ctx.h, self.h, *[out[k].ctypes.data_as(C.c_void_p) for k in
+                                                                          ("samples", "nmodels", "models", "scores")]), name)
+        return out
+
+    def close(self):
+        if self.h:
+            getattr(self.ctx.lib, f"rs_{self.PREFIX}_estimator_destroy")(self.h)
+            self.h = C.c_void_p()
+
+
+class PoseEstimator(_RansacEstimator):
+    """rs_pose_estimator: the relative-pose RANSAC's device scratch; hypotheses(): samples [H][5], models [H][10][9]."""
+
+    PREFIX, SHAPE = "pose", (5, 10, 9)
+    STATS = ("drawn", "scored", "best_index", "best_count", "lo_kept", "cheir0", "cheir1", "cheir2", "cheir3", "chosen",
+             "status", "inliers", "n", "known")
 
     def stats(self):
         """Diagnostic of the last call: dict of STATS, cheir [4], E [9] f64, candidates [4][4][4] f32."""
@@ -933,32 +954,12 @@ class PoseEstimator:
         d.update(cheir=[d["cheir0"], d["cheir1"], d["cheir2"], d["cheir3"]], E=E, candidates=cand)
         return d
 
-    def hypotheses(self):
-        """Diagnostic of the last call: dict(samples [H][5], nmodels [H], models [H][10][9] f64, scores [H][10])."""
-        H = self.max_hypotheses
-        out = dict(samples=np.zeros((H, 5), np.int32), nmodels=np.zeros(H, np.int32), models=np.zeros((H, 10, 9)),
-                   scores=np.zeros((H, 10), np.int32))
-        self.ctx._check(self.ctx.lib.rs_pose_hypotheses(self.ctx.h, self.h, *[out[k].ctypes.data_as(C.c_void_p) for k in
-                                                                              ("samples", "nmodels", "models", "scores")]),
-                        "rs_pose_hypotheses")
-        return out
 
-    def close(self):
-        if self.h:
-            self.ctx.lib.rs_pose_estimator_destroy(self.h)
-            self.h = C.c_void_p()
+class PnpEstimator(_RansacEstimator):
+    """rs_pnp_estimator: the absolute-pose RANSAC's device scratch; hypotheses(): samples [H][4], models [H][4][12]."""
 
-
-class PnpEstimator:
-    """rs_pnp_estimator: the absolute-pose RANSAC's device scratch."""
-
+    PREFIX, SHAPE = "pnp", (4, 4, 12)
     STATS = ("drawn", "scored", "best_index", "best_count", "refit_kept", "beta_case", "status", "inliers", "n")
-
-    def __init__(self, ctx, max_points=8192, max_hypotheses=1000):
-        self.ctx, self.max_points, self.max_hypotheses = ctx, int(max_points), int(max_hypotheses)
-        self.h = C.c_void_p()
-        ctx._check(ctx.lib.rs_pnp_estimator_create(ctx.h, self.max_points, self.max_hypotheses, C.byref(self.h)),
-                   "rs_pnp_estimator_create")
 
     def stats(self):
         """Diagnostic of the last call: dict of STATS and Rt [12] f64, the final [R | t]."""
@@ -969,21 +970,6 @@ class PnpEstimator:
         d = {k: int(v) for k, v in zip(self.STATS, s)}
         d.update(Rt=Rt)
         return d
-
-    def hypotheses(self):
-        """Diagnostic of the last call: dict(samples [H][4], nmodels [H], models [H][4][12] f64, scores [H][4])."""
-        H = self.max_hypotheses
-        out = dict(samples=np.zeros((H, 4), np.int32), nmodels=np.zeros(H, np.int32), models=np.zeros((H, 4, 12)),
-                   scores=np.zeros((H, 4), np.int32))
-        self.ctx._check(self.ctx.lib.rs_pnp_hypotheses(self.ctx.h, self.h, *[out[k].ctypes.data_as(C.c_void_p) for k in
-                                                                             ("samples", "nmodels", "models", "scores")]),
-                        "rs_pnp_hypotheses")
-        return out
-
-    def close(self):
-        if self.h:
-            self.ctx.lib.rs_pnp_estimator_destroy(self.h)
-            self.h = C.c_void_p()
 
 
 # ---- §8(f) rank 4: the resident map (rs_map / rs_frame) -----------------------------------------------------

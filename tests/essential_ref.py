@@ -90,14 +90,14 @@ def draw(seed, h, j, n):
     return ((u >> 32) * int(n)) >> 32
 
 
-def sample(seed, h, n, finite):
-    """The 5 indices of hypothesis h (draw order), or None."""
+def sample(seed, h, n, finite, size=5):
+    """The `size` indices of hypothesis h (draw order), or None."""
     out = []
     for j in range(MAX_DRAWS):
         i = draw(seed, h, j, n)
         if finite[i] and i not in out:
             out.append(i)
-            if len(out) == 5:
+            if len(out) == size:
                 return out
     return None
 
@@ -124,15 +124,18 @@ def sampson(E, x1, y1, x2, y2):
         return num * num / den
 
 
-def needed_hypotheses(best_count, n, confidence):
-    """log(1 - confidence) / log(1 - w^5), w = best_count / n; inf when w^5 underflows to a no-op."""
+def needed_hypotheses(best_count, n, confidence, size=5):
+    """log(1 - confidence) / log(1 - w^size), w = best_count / n; inf when w^size underflows to a no-op.  The power is
+    formed by repeated left multiplication, (w * w) * w ..."""
     if n <= 0 or best_count <= 0:
         return math.inf
     w = best_count / n
-    w5 = w * w * w * w * w
-    if w5 >= 1.0:
+    ws = w
+    for _ in range(size - 1):
+        ws = ws * w
+    if ws >= 1.0:
         return 0.0
-    d = math.log(1.0 - w5)
+    d = math.log(1.0 - ws)
     if not d < 0.0:
         return math.inf
     return math.log(1.0 - confidence) / d

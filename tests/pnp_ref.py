@@ -20,8 +20,7 @@ so, as with the essential matrix (essential_ref.py), this file is the project's 
   score       the integer count of points with positive depth and squared reprojection error (pixels) < threshold^2.
               Every model of every hypothesis is scored; ties go to the lower 4 h + m.
   stopping    rounds of 256; stop once drawn >= log(1 - confidence) / log(1 - w^4), w = best count / n
-              (essential_ref.needed_hypotheses hard-codes the five-point sample size, so the same rule is restated
-              here with 4).
+              (essential_ref.needed_hypotheses with size 4).
   refit       EPnP (Lepetit, Moreno-Noguer, Fua 2009) in normalised coordinates over the best model's inliers, >= 6 of
               them: control points from the centroid and the principal axes; M^T M from 40 sums in the kernel's fixed
               order (ordered_sum); its 12 x 12 eigenvectors by essential_ref.jacobi_eigen; beta approximations N = 1, 2,
@@ -35,6 +34,7 @@ import math
 
 import numpy as np
 
+import essential_ref as E
 from essential_ref import MAX_DRAWS, ROUND, THREADS, draw, jacobi_eigen, real_roots, splitmix64, svd3  # noqa: F401
 
 P3P_EPS = 1e-6              # relative residual of each cosine law that a model may have
@@ -48,29 +48,11 @@ MONO = ((0, 0), (0, 1), (1, 1), (0, 2), (1, 2), (2, 2))                  # beta_
 
 
 def sample(seed, h, n, finite):
-    """The 4 indices of hypothesis h (draw order), or None."""
-    out = []
-    for j in range(MAX_DRAWS):
-        i = draw(seed, h, j, n)
-        if finite[i] and i not in out:
-            out.append(i)
-            if len(out) == 4:
-                return out
-    return None
+    return E.sample(seed, h, n, finite, 4)
 
 
 def needed_hypotheses(best_count, n, confidence):
-    """log(1 - confidence) / log(1 - w^4), w = best_count / n."""
-    if n <= 0 or best_count <= 0:
-        return math.inf
-    w = best_count / n
-    w4 = w * w * w * w
-    if w4 >= 1.0:
-        return 0.0
-    d = math.log(1.0 - w4)
-    if not d < 0.0:
-        return math.inf
-    return math.log(1.0 - confidence) / d
+    return E.needed_hypotheses(best_count, n, confidence, 4)
 
 
 # ------------------------------------------------------------------------------------------------ P3P

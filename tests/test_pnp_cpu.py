@@ -280,3 +280,21 @@ if __name__ == "__main__":
     for lay in LAYOUTS:
         print('    "%s": (%s),' % (lay, ", ".join("%.4f" % _epnp_ratio(lay, s)[0] for s in range(3))),
               "   # cases", [_epnp_ratio(lay, s)[1] for s in range(3)])
+
+
+# ------------------------------------------------------------------------------------------------ 5. the size-4 forms
+def test_size_4_sampling_and_stop_rule():
+    """sample and needed_hypotheses are essential_ref's with size 4; the values were recorded from the stand-alone
+    size-4 functions this file held before."""
+    inf = math.inf
+    for args, want in (((37, 100, 0.99), 243.4091819996546), ((1500, 2000, 0.99), 12.106397073668207),
+                       ((4, 2000, 0.999), 431735268364.0377), ((100, 100, 0.99), 0.0), ((0, 10, 0.99), inf),
+                       ((1, 10 ** 6, 0.99), inf)):
+        assert P.needed_hypotheses(*args) == want, args
+    fin = np.ones(1000, bool)
+    fin[::3] = False
+    assert P.sample(0, 0, 1000, fin) == [652, 166, 509, 370]
+    assert P.sample(7, 255, 1000, fin) == [461, 224, 839, 491]
+    assert P.sample((1 << 64) - 1, 4095, 1000, fin) == [524, 2, 515, 580]
+    assert P.sample(1 << 63, 17, 5, np.array([1, 1, 0, 1, 1], bool)) == [0, 4, 3, 1]
+    assert P.sample(3, 9, 5, np.array([1, 1, 0, 0, 1], bool)) is None
