@@ -1,12 +1,12 @@
 // ba.hip — local-window bundle adjustment (Levenberg-Marquardt with point-block
-// Schur elimination) and pose-only refinement, all in f64, with the whole LM
-// schedule resident on the device (no host round trip until the summary is
-// read): host orchestration, K0 init, K10 finalize, the generic (any size)
-// fallback kernels and refine_pose.  The fast paths live in ba_schur.hip (K5),
-// ba_solve.hip (K7) and ba_update.hip (K8).
+// Schur elimination), all in f64, with the whole LM schedule resident on the
+// device (no host round trip until the summary is read): host orchestration,
+// K0 init, K10 finalize and the generic (any size) fallback kernels.  The fast
+// paths live in ba_schur.hip (K5), ba_solve.hip (K7) and ba_update.hip (K8);
+// the pose solve of one frame (K11) follows the same schedule in refine_pose.hip.
 //
-// Replaces optimization::bundle_adjust / refine_pose's ceres::Solve
-// (reference src/Optimization.cpp:21-72,127-142,194-267,269-374).  The Ceres
+// Replaces optimization::bundle_adjust's ceres::Solve
+// (reference src/Optimization.cpp:21-72,127-142,269-374).  The Ceres
 // trust-region schedule restated here is documented in oracle/ba.c and
 // SURVEY.md §8 a11; this file works in UNSCALED parameters, which is
 // algebraically identical to Ceres' Jacobi-scaled solve:
@@ -542,7 +542,7 @@ struct BaInertialArgs {
 };
 
 // whitener of src/ImuFactor.cpp:10-17: L^-1 of the covariance's LLT, identity when it is not positive definite
-static void imu_whitener(const double cov[81], double W[81])
+void imu_whitener(const double cov[81], double W[81])
 {
     double L[81];
     memcpy(L, cov, sizeof L);
@@ -670,13 +670,7 @@ static int ba_solve_once(rs_context* ctx, int n_cameras, int n_points, int n_obs
     d.n = 6 * d.Cf;
     d.fx = h_intrinsics[0]; d.fy = h_intrinsics[1]; d.cx = h_intrinsics[2]; d.cy = h_intrinsics[3];
     d.huber_a = options->huber_delta;
-    BaOpt opt;
-    opt.max_iter = options->max_num_iterations; opt.max_invalid = options->max_num_consecutive_invalid_steps;
-    opt.jacobi = options->jacobi_scaling; opt.r0 = options->initial_trust_region_radius;
-    opt.rmax = options->max_trust_region_radius; opt.rmin = options->min_trust_region_radius;
-    opt.min_rel = options->min_relative_decrease; opt.dmin = options->min_lm_diagonal;
-    opt.dmax = options->max_lm_diagonal; opt.ftol = options->function_tolerance;
-    opt.gtol = options->gradient_tolerance; opt.ptol = options->parameter_tolerance;
+    const BaOpt opt = ba_opt_from(options);
     if (opt.max_iter < 0 || opt.max_iter > 1000) return rs_fail(ctx, RS_ERR_INVALID, "max_num_iterations out of range");
     // beyond 128 free cameras K5 is the generic kernel with its U / gc partial sums in LDS: 42 doubles per free camera of
     // the 160 KB a workgroup may hold
@@ -994,20 +988,10 @@ static int ba_solve_once(rs_context* ctx, int n_cameras, int n_points, int n_obs
         if (fused_setup) { ctx->grp_zero_ptr = zero_ptr; ctx->grp_zero_n = zero_n; }      // stream-ordered in front of the next solve
         // wait for the completion flag the last workgroup of ba_finalize raises in pinned memory (summary, trace, camera
         // mirror are then all there); fall back to the stream if it drains without the flag (a failed launch)
-        long spins = 0;
-        while (h_prog->pad != itf + 1) {
-            if ((++spins & 0x3FFFF) == 0 && hipStreamQuery(s) != hipErrorNotReady) break;
-        }
-        if (h_prog->pad != itf + 1) RS_HIP(ctx, hipStreamSynchronize(s));
+        RS_HIP(ctx, ba_wait_flag(s, &h_prog->pad, itf + 1));
     }
     RS_HIP(ctx, hipGetLastError());
-    h_summary->termination = h_st->termination;
-    h_summary->iterations = h_st->iter;
-    h_summary->successful_steps = h_st->successful;
-    h_summary->usable = h_st->usable;
-    h_summary->initial_cost = h_st->initial_cost;
-    h_summary->final_cost = h_st->x_cost;
-    h_summary->final_radius = h_st->radius;
+    ba_summary_from(*h_st, h_summary);
     ctx->ba_trace = h_trace;            // stays valid until the next call that uses the pinned block
     ctx->ba_trace_n = h_st->iter;
     ctx->ba_stats[0] = h_st->n_rounds; ctx->ba_stats[1] = h_st->n_fresh; ctx->ba_stats[2] = h_st->n_sets;
@@ -1095,13 +1079,7 @@ static int ba_solve_batch_grid(rs_context* ctx, int B, const rs_ba_problem* Q, c
     *rc_out = RS_OK;
     rs_ba_options def;
     if (!options) { rs_ba_default_options(&def); options = &def; }
-    BaOpt opt;
-    opt.max_iter = options->max_num_iterations; opt.max_invalid = options->max_num_consecutive_invalid_steps;
-    opt.jacobi = options->jacobi_scaling; opt.r0 = options->initial_trust_region_radius;
-    opt.rmax = options->max_trust_region_radius; opt.rmin = options->min_trust_region_radius;
-    opt.min_rel = options->min_relative_decrease; opt.dmin = options->min_lm_diagonal;
-    opt.dmax = options->max_lm_diagonal; opt.ftol = options->function_tolerance;
-    opt.gtol = options->gradient_tolerance; opt.ptol = options->parameter_tolerance;
+    const BaOpt opt = ba_opt_from(options);
     if (opt.max_iter < 1 || opt.max_iter > 1000) return 1;
     int ns = ctx->ba_sets > 0 ? ctx->ba_sets : BA_CALIBRATED_SETS;      // (throughput mode: extra radii are CU time other windows want)
     if (ns > BA_CALIBRATED_SETS) ns = BA_CALIBRATED_SETS;
@@ -1219,12 +1197,7 @@ static int ba_solve_batch_grid(rs_context* ctx, int B, const rs_ba_problem* Q, c
         hipLaunchKernelGGL(ba_finalize_batch, dim3(16, 1, B), dim3(256), 0, s, d_wins, opt, rounds);
     }
     if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) { *rc_out = rs_fail(ctx, RS_ERR_HIP, "batched bundle adjustment"); return 0; }
-    for (int i = 0; i < B; i++) {
-        const BaState* h = wins[(size_t)i].h_st;
-        rs_ba_summary& o = out[i];
-        o.termination = h->termination; o.iterations = h->iter; o.successful_steps = h->successful; o.usable = h->usable;
-        o.initial_cost = h->initial_cost; o.final_cost = h->x_cost; o.final_radius = h->radius;
-    }
+    for (int i = 0; i < B; i++) ba_summary_from(*wins[(size_t)i].h_st, &out[i]);
     ctx->ba_trace = nullptr; ctx->ba_trace_n = 0; ctx->ba_cams = nullptr; ctx->ba_cams_n = 0;
     ctx->ba_stats[0] = ctx->ba_stats[1] = ctx->ba_stats[2] = 0; ctx->ba_stats[3] = rounds;
     return 0;
@@ -1305,559 +1278,5 @@ extern "C" int rs_ba_get_stats(rs_context* ctx, int h_out[8])
 {
     if (!ctx || !h_out) return RS_ERR_INVALID;
     for (int i = 0; i < 8; i++) h_out[i] = ctx->ba_stats[i];
-    return RS_OK;
-}
-
-// ------------------------------------------------------------- refine_pose
-// optimization::refine_pose (src/Optimization.cpp:194-267), vision-only: one
-// camera block, points constant.  The whole LM loop runs inside ONE launch of
-// a single workgroup (6 unknowns; <= 2000 residual pairs): per iteration a
-// block reduction of the 6x6 normal equations, a register Cholesky on lane 0
-// and a second reduction for the candidate cost.
-#define RP_THREADS 512         // 2000 observations: four per thread; 256 VGPRs per thread keep the 28 accumulators in registers
-
-__device__ __forceinline__ void block_sum(double* vals, int count, double* scratch /*[RP_THREADS / 64 + 1][32]*/)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int k = 0; k < count; k++) {
-        const double v = wave_sum_lane63(vals[k]);
-        if (lane == 63) scratch[wave * 32 + k] = v;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < count) {                 // thread k folds the waves' partial sums of value k (fixed order)
-        double t = 0.0;
-        for (int w = 0; w < RP_THREADS / 64; w++) t += scratch[w * 32 + threadIdx.x];
-        scratch[(RP_THREADS / 64) * 32 + threadIdx.x] = t;
-    }
-    __syncthreads();
-    for (int k = 0; k < count; k++) vals[k] = scratch[(RP_THREADS / 64) * 32 + k];
-    __syncthreads();
-}
-
-__global__ __launch_bounds__(RP_THREADS) void ba_refine_pose(BaDims d, BaOpt opt, const double* __restrict__ pts,
-                                                            const float2* __restrict__ uv, int n,
-                                                            double* __restrict__ cam_io, BaState* __restrict__ st_out, volatile int* host_done)
-{
-    __shared__ double x[6], xn[6], prep[BA_PREP], prepn[BA_PREP], scratch[(RP_THREADS / 64 + 1) * 32];
-    __shared__ BaState st;
-    __shared__ double sc[6];
-    const int tid = threadIdx.x;
-    if (tid == 0) {
-        for (int k = 0; k < 6; k++) x[k] = cam_io[k];
-        cam_prepare(x, prep);
-        st.radius = opt.r0; st.decrease_factor = 2.0; st.x_cost = 0.0; st.initial_cost = 0.0;
-        st.iter = 0; st.successful = 0; st.invalid_steps = 0; st.done = 0; st.termination = 0; st.cur = 0;
-        st.have_scale = 0; st.solver_failed = 0; st.fresh = 1; st.usable = 0; st.consec_accepts = 0; st.nact = 1;
-        st.n_rounds = 0; st.n_fresh = 0; st.n_sets = 0; st.hand_lost = 0;
-    }
-    __syncthreads();
-    double acc[28];
-    while (true) {
-        // linearise at x (recomputed after a rejected step too: same values)
-        for (int k = 0; k < 28; k++) acc[k] = 0.0;
-        ObsLin o;
-        for (int i = tid; i < n; i += RP_THREADS) {
-            const double X[3] = {pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]};
-            obs_eval<true>(prep, X, uv[i], d, o);
-            int q = 0;
-#pragma unroll
-            for (int a = 0; a < 6; a++) {
-#pragma unroll
-                for (int e = a; e < 6; e++) acc[q++] += o.w * (o.jc[a] * o.jc[e] + o.jc[6 + a] * o.jc[6 + e]);
-            }
-#pragma unroll
-            for (int a = 0; a < 6; a++) acc[21 + a] += o.w * (o.jc[a] * o.r0 + o.jc[6 + a] * o.r1);
-            acc[27] += 0.5 * o.rho;
-        }
-        block_sum(acc, 28, scratch);
-        if (tid == 0) {
-            double H[6][6], g[6], lam[6], dlt[6];
-            int q = 0;
-            for (int a = 0; a < 6; a++)
-                for (int e = a; e < 6; e++) { H[a][e] = acc[q]; H[e][a] = acc[q]; q++; }
-            for (int a = 0; a < 6; a++) g[a] = acc[21 + a];
-            if (st.fresh) {
-                st.x_cost = acc[27];
-                if (st.iter == 0) st.initial_cost = st.x_cost;
-                if (!st.have_scale)
-                    for (int a = 0; a < 6; a++) sc[a] = opt.jacobi ? 1.0 / (1.0 + sqrt(H[a][a])) : 1.0;
-                double gm = 0.0;
-                for (int a = 0; a < 6; a++) gm = fmax(gm, fabs(g[a]));
-                if (!isfinite(st.x_cost)) { st.done = 1; st.termination = RS_BA_FAILURE; }
-                else if (gm <= opt.gtol) { st.done = 1; st.termination = RS_BA_CONVERGENCE_GRADIENT; }
-            }
-            if (!st.done && st.iter >= opt.max_iter) { st.done = 1; st.termination = RS_BA_NO_CONVERGENCE; }
-            if (!st.done) {
-                bool fail = false;
-                for (int a = 0; a < 6; a++) {
-                    const double s2 = sc[a] * sc[a];
-                    lam[a] = clampd(s2 * H[a][a], opt.dmin, opt.dmax) / (st.radius * s2);
-                    H[a][a] += lam[a];
-                }
-                // Cholesky 6x6 (one reciprocal per column instead of a division per entry: this is one lane's serial code)
-                double rdiag[6];
-                for (int j = 0; j < 6 && !fail; j++) {
-                    double dj = H[j][j];
-                    for (int k = 0; k < j; k++) dj -= H[j][k] * H[j][k];
-                    if (!(dj > 0.0) || !isfinite(dj)) { fail = true; break; }
-                    dj = sqrt(dj);
-                    H[j][j] = dj;
-                    rdiag[j] = 1.0 / dj;
-                    for (int i = j + 1; i < 6; i++) {
-                        double s = H[i][j];
-                        for (int k = 0; k < j; k++) s -= H[i][k] * H[j][k];
-                        H[i][j] = s * rdiag[j];
-                    }
-                }
-                if (!fail) {
-                    for (int i = 0; i < 6; i++) {
-                        double s = g[i];
-                        for (int k = 0; k < i; k++) s -= H[i][k] * dlt[k];
-                        dlt[i] = s * rdiag[i];
-                    }
-                    for (int i = 5; i >= 0; i--) {
-                        double s = dlt[i];
-                        for (int k = i + 1; k < 6; k++) s -= H[k][i] * dlt[k];
-                        dlt[i] = s * rdiag[i];
-                    }
-                    double mcc = 0.0, ssq = 0.0, xsq = 0.0;
-                    for (int a = 0; a < 6; a++) {
-                        dlt[a] = -dlt[a];
-                        if (!isfinite(dlt[a])) fail = true;
-                        mcc += 0.5 * (dlt[a] * dlt[a] * lam[a] - dlt[a] * g[a]);
-                        xn[a] = x[a] + dlt[a];
-                        ssq += (x[a] - xn[a]) * (x[a] - xn[a]);
-                        xsq += x[a] * x[a];
-                    }
-                    st.cam_scal[0] = mcc; st.cam_scal[1] = ssq; st.cam_scal[2] = xsq;
-                    cam_prepare(xn, prepn);
-                }
-                st.solver_failed = fail ? 1 : 0;
-            }
-        }
-        __syncthreads();
-        if (st.done) break;
-        double cc[1] = {0.0};
-        if (!st.solver_failed) {
-            for (int i = tid; i < n; i += RP_THREADS) {
-                const double X[3] = {pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]};
-                obs_eval<false>(prepn, X, uv[i], d, o);
-                cc[0] += 0.5 * o.rho;
-            }
-        }
-        block_sum(cc, 1, scratch);
-        if (tid == 0) {
-            st.iter++;
-            const double cand = cc[0], mcc = st.cam_scal[0];
-            st.fresh = 0;
-            if (st.solver_failed || !(mcc > 0.0)) {
-                if (++st.invalid_steps >= opt.max_invalid) { st.done = 1; st.termination = RS_BA_FAILURE; }
-                else { st.radius /= st.decrease_factor; st.decrease_factor *= 2.0; }
-            } else {
-                st.invalid_steps = 0;
-                const double step_norm = sqrt(st.cam_scal[1]), x_norm = sqrt(st.cam_scal[2]);
-                if (step_norm <= opt.ptol * (x_norm + opt.ptol)) { st.done = 1; st.termination = RS_BA_CONVERGENCE_PARAMETER; }
-                else if (fabs(st.x_cost - cand) <= opt.ftol * st.x_cost) { st.done = 1; st.termination = RS_BA_CONVERGENCE_FUNCTION; }
-                else {
-                    const double rel = (st.x_cost - cand) / mcc;
-                    if (rel > opt.min_rel && isfinite(cand)) {
-                        for (int a = 0; a < 6; a++) x[a] = xn[a];
-                        for (int a = 0; a < BA_PREP; a++) prep[a] = prepn[a];
-                        st.successful++;
-                        const double t = 2.0 * rel - 1.0;
-                        st.radius = fmin(opt.rmax, st.radius / fmax(1.0 / 3.0, 1.0 - t * t * t));
-                        st.decrease_factor = 2.0;
-                        st.fresh = 1;
-                        st.x_cost = cand;
-                    } else {
-                        st.radius /= st.decrease_factor;
-                        st.decrease_factor *= 2.0;
-                        if (st.radius < opt.rmin) { st.done = 1; st.termination = RS_BA_CONVERGENCE_RADIUS; }
-                    }
-                }
-            }
-            st.solver_failed = 0;
-            st.have_scale = 1;
-        }
-        __syncthreads();
-        if (st.done) break;
-    }
-    if (tid == 0) {
-        st.usable = (st.termination != RS_BA_FAILURE && isfinite(st.x_cost) && st.x_cost <= st.initial_cost) ? 1 : 0;
-        if (st.usable)
-            for (int k = 0; k < 6; k++) cam_io[k] = x[k];
-        *st_out = st;
-        __threadfence_system();           // cam_io / st_out are pinned host memory
-        *host_done = 1;                   // the host spins on this instead of synchronising the stream
-        __threadfence_system();
-    }
-}
-
-extern "C" int rs_refine_pose(rs_context* ctx, double h_camera[6], const double* d_points, const float* d_uv, int n,
-                              const float h_intrinsics[4], const rs_ba_options* options, rs_ba_summary* h_summary)
-{
-    if (!ctx || !h_summary) return RS_ERR_INVALID;
-    memset(h_summary, 0, sizeof *h_summary);     // a refused call leaves a zeroed summary too
-    if (!h_camera) return rs_fail(ctx, RS_ERR_INVALID, "null pointer");
-    if (n < 0) return rs_fail(ctx, RS_ERR_INVALID, "negative n");
-    if (n == 0) return RS_OK;   // "nothing to constrain", src/Optimization.cpp:227-229
-    if (!d_points || !d_uv || !h_intrinsics) return rs_fail(ctx, RS_ERR_INVALID, "null pointer");
-    rs_ba_options def;
-    if (!options) { rs_ba_default_options(&def); options = &def; }
-    RS_HIP(ctx, hipSetDevice(ctx->device));
-    BaDims d;
-    d.C = 1; d.Cf = 1; d.P = n; d.M = n; d.n = 6;
-    d.fx = h_intrinsics[0]; d.fy = h_intrinsics[1]; d.cx = h_intrinsics[2]; d.cy = h_intrinsics[3];
-    d.huber_a = options->huber_delta;
-    BaOpt opt;
-    opt.max_iter = options->max_num_iterations; opt.max_invalid = options->max_num_consecutive_invalid_steps;
-    opt.jacobi = options->jacobi_scaling; opt.r0 = options->initial_trust_region_radius;
-    opt.rmax = options->max_trust_region_radius; opt.rmin = options->min_trust_region_radius;
-    opt.min_rel = options->min_relative_decrease; opt.dmin = options->min_lm_diagonal;
-    opt.dmax = options->max_lm_diagonal; opt.ftol = options->function_tolerance;
-    opt.gtol = options->gradient_tolerance; opt.ptol = options->parameter_tolerance;
-    void* wsv = nullptr;
-    int rc = rs_workspace(ctx, 1024, &wsv);
-    if (rc) return rc;
-    (void)wsv;
-    void* pin = nullptr;
-    rc = rs_pinned(ctx, 512, &pin);
-    if (rc) return rc;
-    ctx->ba_trace_n = 0;                 // the pinned block is reused: the last BA's record is gone
-    ctx->ba_cams = nullptr;
-    ctx->ba_cams_n = 0;
-    double* h_cam = (double*)pin;
-    BaState* h_st = (BaState*)((char*)pin + 256);
-    memcpy(h_cam, h_camera, 6 * sizeof(double));
-    hipStream_t s = ctx->stream;
-    {
-        // the kernel reads the camera from and writes camera + state to the PINNED block itself: no copy launches around
-        // a 40 us kernel (three hipMemcpyAsync cost more than the solve)
-        rs_prof_scope ps(ctx, "K11_refine_pose");
-        volatile int* h_done = (volatile int*)((char*)pin + 448);
-        *h_done = 0;
-        hipLaunchKernelGGL(ba_refine_pose, dim3(1), dim3(RP_THREADS), 0, s, d, opt, d_points, (const float2*)d_uv, n, h_cam, h_st, h_done);
-        RS_HIP(ctx, hipGetLastError());
-        long spins = 0;
-        while (*h_done != 1)
-            if ((++spins & 0x3FFFF) == 0 && hipStreamQuery(s) != hipErrorNotReady) break;
-        if (*h_done != 1) RS_HIP(ctx, hipStreamSynchronize(s));
-    }
-    RS_HIP(ctx, hipGetLastError());
-    if (h_st->usable) memcpy(h_camera, h_cam, 6 * sizeof(double));
-    h_summary->termination = h_st->termination;
-    h_summary->iterations = h_st->iter;
-    h_summary->successful_steps = h_st->successful;
-    h_summary->usable = h_st->usable;
-    h_summary->initial_cost = h_st->initial_cost;
-    h_summary->final_cost = h_st->x_cost;
-    h_summary->final_radius = h_st->radius;
-    return RS_OK;
-}
-
-// ------------------------------------------------- refine_pose with an InertialConstraint
-// optimization::refine_pose (src/Optimization.cpp:194-267) with a RotationPrior (:252-258: 3 more residuals on the
-// pose block) or an InertialDelta (:237-251: the 9-residual preintegration block with the previous frame constant and
-// this frame's velocity as a second free block -> 9 unknowns).  Same single-launch LM as ba_refine_pose; thread 0
-// evaluates the one extra block with dual numbers and solves the nu x nu system (nu = 6 or 9).
-struct RpInertial {
-    int kind;                 // 1 rotation prior, 2 inertial delta
-    double predicted[9], sigma;
-    double prev_pose[6], prev_vel[3], prev_bias[6], gravity[3];
-    ImuFactorDev fac;
-};
-
-__global__ __launch_bounds__(RP_THREADS) void ba_refine_pose_inertial(BaDims d, BaOpt opt, const double* __restrict__ pts,
-                                                                     const float2* __restrict__ uv, int n,
-                                                                     const RpInertial* __restrict__ ext,
-                                                                     double* __restrict__ cam_io /*[9]: pose, velocity*/,
-                                                                     BaState* __restrict__ st_out, volatile int* host_done)
-{
-    __shared__ double x[9], xn[9], prep[BA_PREP], prepn[BA_PREP], scratch[(RP_THREADS / 64 + 1) * 32];
-    __shared__ double s_extr[9], s_extJ[9][IMU_NP];
-    __shared__ BaState st;
-    __shared__ double sc[9];
-    const int tid = threadIdx.x;
-    const int nu = ext->kind == 2 ? 9 : 6;
-    if (tid == 0) {
-        for (int k = 0; k < 9; k++) x[k] = cam_io[k];
-        cam_prepare(x, prep);
-        st.radius = opt.r0; st.decrease_factor = 2.0; st.x_cost = 0.0; st.initial_cost = 0.0;
-        st.iter = 0; st.successful = 0; st.invalid_steps = 0; st.done = 0; st.termination = 0; st.cur = 0;
-        st.have_scale = 0; st.solver_failed = 0; st.fresh = 1; st.usable = 0; st.consec_accepts = 0; st.nact = 1;
-        st.n_rounds = 0; st.n_fresh = 0; st.n_sets = 0; st.hand_lost = 0;
-    }
-    __syncthreads();
-    double acc[28];
-    while (true) {
-        for (int k = 0; k < 28; k++) acc[k] = 0.0;
-        ObsLin o;
-        for (int i = tid; i < n; i += RP_THREADS) {
-            const double X[3] = {pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]};
-            obs_eval<true>(prep, X, uv[i], d, o);
-            int q = 0;
-#pragma unroll
-            for (int a = 0; a < 6; a++) {
-#pragma unroll
-                for (int e = a; e < 6; e++) acc[q++] += o.w * (o.jc[a] * o.jc[e] + o.jc[6 + a] * o.jc[6 + e]);
-            }
-#pragma unroll
-            for (int a = 0; a < 6; a++) acc[21 + a] += o.w * (o.jc[a] * o.r0 + o.jc[6 + a] * o.r1);
-            acc[27] += 0.5 * o.rho;
-        }
-        // the extra residual block at x: the first 32 lanes evaluate it with one partial per lane (imu_dual.h) and
-        // leave residual + Jacobian in LDS for the solving thread
-        if (tid < 32) {
-            if (ext->kind == 1) {
-                double r[3], jl[3];
-                imu_rotation_prior_lanes(ext->predicted, ext->sigma, x, r, jl);
-                for (int a = 0; a < 3; a++) { if (tid < 3) s_extJ[a][tid] = jl[a]; if (tid == 0) s_extr[a] = r[a]; }
-            } else {
-                double r[9], jl[9];
-                imu_preintegration_lanes(ext->fac, ext->gravity, ext->prev_pose, ext->prev_vel, ext->prev_bias, x, x + 6, r, jl);
-                for (int a = 0; a < 9; a++) { if (tid < IMU_NP) s_extJ[a][tid] = jl[a]; if (tid == 0) s_extr[a] = r[a]; }
-            }
-        }
-        block_sum(acc, 28, scratch);
-        if (tid == 0) {
-            double H[9][9], gv[9], lam[9], dlt[9];
-            for (int a = 0; a < 9; a++) { gv[a] = 0.0; for (int e = 0; e < 9; e++) H[a][e] = 0.0; }
-            int q = 0;
-            for (int a = 0; a < 6; a++)
-                for (int e = a; e < 6; e++) { H[a][e] = acc[q]; H[e][a] = acc[q]; q++; }
-            for (int a = 0; a < 6; a++) gv[a] = acc[21 + a];
-            double cost = acc[27];
-            if (ext->kind == 1) {
-                for (int a = 0; a < 3; a++) {
-                    cost += 0.5 * s_extr[a] * s_extr[a];
-                    for (int k = 0; k < 3; k++) { gv[k] += s_extJ[a][k] * s_extr[a]; for (int l = 0; l < 3; l++) H[k][l] += s_extJ[a][k] * s_extJ[a][l]; }
-                }
-            } else {
-                for (int a = 0; a < 9; a++) {
-                    cost += 0.5 * s_extr[a] * s_extr[a];
-                    for (int k = 0; k < 9; k++) {            // local parameters 15..23 = pose_j (6), velocity_j (3)
-                        const double jk = s_extJ[a][15 + k];
-                        gv[k] += jk * s_extr[a];
-                        for (int l = 0; l < 9; l++) H[k][l] += jk * s_extJ[a][15 + l];
-                    }
-                }
-            }
-            if (st.fresh) {
-                st.x_cost = cost;
-                if (st.iter == 0) st.initial_cost = st.x_cost;
-                if (!st.have_scale)
-                    for (int a = 0; a < nu; a++) sc[a] = opt.jacobi ? 1.0 / (1.0 + sqrt(H[a][a])) : 1.0;
-                double gm = 0.0;
-                for (int a = 0; a < nu; a++) gm = fmax(gm, fabs(gv[a]));
-                if (!isfinite(st.x_cost)) { st.done = 1; st.termination = RS_BA_FAILURE; }
-                else if (gm <= opt.gtol) { st.done = 1; st.termination = RS_BA_CONVERGENCE_GRADIENT; }
-            }
-            if (!st.done && st.iter >= opt.max_iter) { st.done = 1; st.termination = RS_BA_NO_CONVERGENCE; }
-            if (!st.done) {
-                bool fail = false;
-                for (int a = 0; a < nu; a++) {
-                    const double s2 = sc[a] * sc[a];
-                    lam[a] = clampd(s2 * H[a][a], opt.dmin, opt.dmax) / (st.radius * s2);
-                    H[a][a] += lam[a];
-                }
-                for (int j = 0; j < nu && !fail; j++) {     // Cholesky nu x nu
-                    double dj = H[j][j];
-                    for (int k = 0; k < j; k++) dj -= H[j][k] * H[j][k];
-                    if (!(dj > 0.0) || !isfinite(dj)) { fail = true; break; }
-                    dj = sqrt(dj);
-                    H[j][j] = dj;
-                    for (int i = j + 1; i < nu; i++) {
-                        double t = H[i][j];
-                        for (int k = 0; k < j; k++) t -= H[i][k] * H[j][k];
-                        H[i][j] = t / dj;
-                    }
-                }
-                if (!fail) {
-                    for (int i = 0; i < nu; i++) {
-                        double t = gv[i];
-                        for (int k = 0; k < i; k++) t -= H[i][k] * dlt[k];
-                        dlt[i] = t / H[i][i];
-                    }
-                    for (int i = nu - 1; i >= 0; i--) {
-                        double t = dlt[i];
-                        for (int k = i + 1; k < nu; k++) t -= H[k][i] * dlt[k];
-                        dlt[i] = t / H[i][i];
-                    }
-                    double mcc = 0.0, ssq = 0.0, xsq = 0.0;
-                    for (int a = 0; a < 9; a++) xn[a] = x[a];
-                    for (int a = 0; a < nu; a++) {
-                        dlt[a] = -dlt[a];
-                        if (!isfinite(dlt[a])) fail = true;
-                        mcc += 0.5 * (dlt[a] * dlt[a] * lam[a] - dlt[a] * gv[a]);
-                        xn[a] = x[a] + dlt[a];
-                        ssq += (x[a] - xn[a]) * (x[a] - xn[a]);
-                        xsq += x[a] * x[a];
-                    }
-                    st.cam_scal[0] = mcc; st.cam_scal[1] = ssq; st.cam_scal[2] = xsq;
-                    cam_prepare(xn, prepn);
-                    // the extra block at the candidate
-                    double ce = 0.0;
-                    if (!fail) {
-                        if (ext->kind == 1) {
-                            double r[3];
-                            imu_rotation_prior(ext->predicted, ext->sigma, xn, r, nullptr);
-                            for (int a = 0; a < 3; a++) ce += 0.5 * r[a] * r[a];
-                        } else {
-                            double r[9];
-                            imu_preintegration(ext->fac, ext->gravity, ext->prev_pose, ext->prev_vel, ext->prev_bias, xn, xn + 6, r, nullptr);
-                            for (int a = 0; a < 9; a++) ce += 0.5 * r[a] * r[a];
-                        }
-                    }
-                    st.cam_scal[3] = ce;
-                }
-                st.solver_failed = fail ? 1 : 0;
-            }
-        }
-        __syncthreads();
-        if (st.done) break;
-        double cc[1] = {0.0};
-        if (!st.solver_failed) {
-            for (int i = tid; i < n; i += RP_THREADS) {
-                const double X[3] = {pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]};
-                obs_eval<false>(prepn, X, uv[i], d, o);
-                cc[0] += 0.5 * o.rho;
-            }
-        }
-        block_sum(cc, 1, scratch);
-        if (tid == 0) {
-            st.iter++;
-            const double cand = cc[0] + st.cam_scal[3], mcc = st.cam_scal[0];
-            st.fresh = 0;
-            if (st.solver_failed || !(mcc > 0.0)) {
-                if (++st.invalid_steps >= opt.max_invalid) { st.done = 1; st.termination = RS_BA_FAILURE; }
-                else { st.radius /= st.decrease_factor; st.decrease_factor *= 2.0; }
-            } else {
-                st.invalid_steps = 0;
-                const double step_norm = sqrt(st.cam_scal[1]), x_norm = sqrt(st.cam_scal[2]);
-                if (step_norm <= opt.ptol * (x_norm + opt.ptol)) { st.done = 1; st.termination = RS_BA_CONVERGENCE_PARAMETER; }
-                else if (fabs(st.x_cost - cand) <= opt.ftol * st.x_cost) { st.done = 1; st.termination = RS_BA_CONVERGENCE_FUNCTION; }
-                else {
-                    const double rel = (st.x_cost - cand) / mcc;
-                    if (rel > opt.min_rel && isfinite(cand)) {
-                        for (int a = 0; a < 9; a++) x[a] = xn[a];
-                        for (int a = 0; a < BA_PREP; a++) prep[a] = prepn[a];
-                        st.successful++;
-                        const double t = 2.0 * rel - 1.0;
-                        st.radius = fmin(opt.rmax, st.radius / fmax(1.0 / 3.0, 1.0 - t * t * t));
-                        st.decrease_factor = 2.0;
-                        st.fresh = 1;
-                        st.x_cost = cand;
-                    } else {
-                        st.radius /= st.decrease_factor;
-                        st.decrease_factor *= 2.0;
-                        if (st.radius < opt.rmin) { st.done = 1; st.termination = RS_BA_CONVERGENCE_RADIUS; }
-                    }
-                }
-            }
-            st.solver_failed = 0;
-            st.have_scale = 1;
-        }
-        __syncthreads();
-        if (st.done) break;
-    }
-    if (tid == 0) {
-        st.usable = (st.termination != RS_BA_FAILURE && isfinite(st.x_cost) && st.x_cost <= st.initial_cost) ? 1 : 0;
-        if (st.usable)
-            for (int k = 0; k < 9; k++) cam_io[k] = x[k];
-        *st_out = st;
-        __threadfence_system();           // cam_io / st_out are pinned host memory
-        *host_done = 1;                   // the host spins on this instead of synchronising the stream
-        __threadfence_system();
-    }
-}
-
-extern "C" int rs_refine_pose_inertial(rs_context* ctx, double h_camera[6], const double* d_points, const float* d_uv, int n,
-                                       const float h_intrinsics[4], int kind, const double h_predicted[9], double sigma_radians,
-                                       const double h_prev_pose[6], const double h_prev_velocity[3], const double h_prev_bias[6],
-                                       const rs_imu_factor* h_delta, const double h_gravity[3], double h_velocity[3],
-                                       const rs_ba_options* options, rs_ba_summary* h_summary)
-{
-    if (!ctx || !h_summary) return RS_ERR_INVALID;
-    memset(h_summary, 0, sizeof *h_summary);     // a refused call leaves a zeroed summary too
-    if (!h_camera) return rs_fail(ctx, RS_ERR_INVALID, "null pointer");
-    if (kind < 0 || kind > 2) return rs_fail(ctx, RS_ERR_INVALID, "kind must be 0, 1 or 2");
-    // RotationPrior::enabled / InertialDelta::enabled (src/Optimization.h:50-53,60-63): a disabled constraint is no constraint
-    if (kind == 1 && (!h_predicted || !(sigma_radians > 0.0))) kind = 0;
-    if (kind == 2 && (!h_delta || !(h_delta->duration > 0.0))) kind = 0;
-    if (kind == 0) return rs_refine_pose(ctx, h_camera, d_points, d_uv, n, h_intrinsics, options, h_summary);
-    if (n < 0) return rs_fail(ctx, RS_ERR_INVALID, "negative n");
-    if (n == 0) return RS_OK;   // "nothing to constrain", src/Optimization.cpp:227-229 (checked before the inertial block is added)
-    if (!d_points || !d_uv || !h_intrinsics) return rs_fail(ctx, RS_ERR_INVALID, "null pointer");
-    if (kind == 2 && (!h_prev_pose || !h_prev_velocity || !h_prev_bias || !h_gravity || !h_velocity))
-        return rs_fail(ctx, RS_ERR_INVALID, "null pointer (inertial delta)");
-    rs_ba_options def;
-    if (!options) { rs_ba_default_options(&def); options = &def; }
-    RS_HIP(ctx, hipSetDevice(ctx->device));
-    BaDims d;
-    d.C = 1; d.Cf = 1; d.P = n; d.M = n; d.n = 6;
-    d.fx = h_intrinsics[0]; d.fy = h_intrinsics[1]; d.cx = h_intrinsics[2]; d.cy = h_intrinsics[3];
-    d.huber_a = options->huber_delta;
-    BaOpt opt;
-    opt.max_iter = options->max_num_iterations; opt.max_invalid = options->max_num_consecutive_invalid_steps;
-    opt.jacobi = options->jacobi_scaling; opt.r0 = options->initial_trust_region_radius;
-    opt.rmax = options->max_trust_region_radius; opt.rmin = options->min_trust_region_radius;
-    opt.min_rel = options->min_relative_decrease; opt.dmin = options->min_lm_diagonal;
-    opt.dmax = options->max_lm_diagonal; opt.ftol = options->function_tolerance;
-    opt.gtol = options->gradient_tolerance; opt.ptol = options->parameter_tolerance;
-    const size_t ext_off = 512, ws_bytes = ext_off + ((sizeof(RpInertial) + 255) & ~(size_t)255);
-    void* wsv = nullptr;
-    int rc = rs_workspace(ctx, ws_bytes, &wsv);
-    if (rc) return rc;
-    RpInertial* d_ext = (RpInertial*)((char*)wsv + ext_off);
-    void* pin = nullptr;
-    rc = rs_pinned(ctx, 1024 + sizeof(RpInertial), &pin);
-    if (rc) return rc;
-    ctx->ba_trace_n = 0;
-    ctx->ba_cams = nullptr;
-    ctx->ba_cams_n = 0;
-    double* h_cam = (double*)pin;
-    BaState* h_st = (BaState*)((char*)pin + 256);
-    RpInertial* h_ext = (RpInertial*)((char*)pin + 1024);
-    memset(h_ext, 0, sizeof *h_ext);
-    h_ext->kind = kind;
-    if (kind == 1) {
-        memcpy(h_ext->predicted, h_predicted, sizeof h_ext->predicted);
-        h_ext->sigma = sigma_radians;
-    } else {
-        memcpy(h_ext->prev_pose, h_prev_pose, sizeof h_ext->prev_pose);
-        memcpy(h_ext->prev_vel, h_prev_velocity, sizeof h_ext->prev_vel);
-        memcpy(h_ext->prev_bias, h_prev_bias, sizeof h_ext->prev_bias);
-        memcpy(h_ext->gravity, h_gravity, sizeof h_ext->gravity);
-        h_ext->fac.f = *h_delta;
-        imu_whitener(h_delta->covariance, h_ext->fac.W);
-    }
-    memcpy(h_cam, h_camera, 6 * sizeof(double));
-    for (int k = 0; k < 3; k++) h_cam[6 + k] = (kind == 2) ? h_velocity[k] : 0.0;
-    hipStream_t s = ctx->stream;
-    RS_HIP(ctx, hipMemcpyAsync(d_ext, h_ext, sizeof(RpInertial), hipMemcpyHostToDevice, s));   // read in the inner loops: device memory
-    {
-        rs_prof_scope ps(ctx, "K11_refine_pose_inertial");
-        volatile int* h_done = (volatile int*)((char*)pin + 448);
-        *h_done = 0;
-        hipLaunchKernelGGL(ba_refine_pose_inertial, dim3(1), dim3(RP_THREADS), 0, s, d, opt, d_points, (const float2*)d_uv, n,
-                           (const RpInertial*)d_ext, h_cam, h_st, h_done);                    // camera / state: the pinned block itself
-        RS_HIP(ctx, hipGetLastError());
-        long spins = 0;
-        while (*h_done != 1)
-            if ((++spins & 0x3FFFF) == 0 && hipStreamQuery(s) != hipErrorNotReady) break;
-        if (*h_done != 1) RS_HIP(ctx, hipStreamSynchronize(s));
-    }
-    RS_HIP(ctx, hipGetLastError());
-    if (h_st->usable) {
-        memcpy(h_camera, h_cam, 6 * sizeof(double));
-        if (kind == 2) memcpy(h_velocity, h_cam + 6, 3 * sizeof(double));    // unpack_inertial, :263-265
-    }
-    h_summary->termination = h_st->termination;
-    h_summary->iterations = h_st->iter;
-    h_summary->successful_steps = h_st->successful;
-    h_summary->usable = h_st->usable;
-    h_summary->initial_cost = h_st->initial_cost;
-    h_summary->final_cost = h_st->x_cost;
-    h_summary->final_radius = h_st->radius;
     return RS_OK;
 }

@@ -1,5 +1,5 @@
 // ba_common.h — structures and device math shared by the bundle-adjustment
-// translation units (ba.hip, ba_solve.hip, ba_schur.hip).
+// translation units (ba.hip, ba_solve.hip, ba_schur.hip, refine_pose.hip).
 #pragma once
 #include <math.h>
 
@@ -603,8 +603,35 @@ void ba_launch_setup_fused(rs_context* ctx, const BaDims& d, const BaBufs& b, co
 size_t ba_schur_lds_bytes(int C, int Cf, int it_l = 64, int ns = BA_MAXSETS);   // ns: speculative sets of the solve (sizes the G tables)
 int ba_prepare_schur(int C, int Cf);
 void ba_launch_schur(hipStream_t s, const BaDims& d, const BaBufs& b, const BaOpt& opt, const BaGroup& g, int it);
-// ---- blocked reduced solve for n > BA_MAX_LDS_N (ba_solve_big.hip)
 struct rs_context;
+// ---- host pieces shared by the entry points (ba.hip, refine_pose.hip)
+static inline BaOpt ba_opt_from(const rs_ba_options* o)
+{
+    BaOpt opt;
+    opt.max_iter = o->max_num_iterations; opt.max_invalid = o->max_num_consecutive_invalid_steps;
+    opt.jacobi = o->jacobi_scaling; opt.r0 = o->initial_trust_region_radius;
+    opt.rmax = o->max_trust_region_radius; opt.rmin = o->min_trust_region_radius;
+    opt.min_rel = o->min_relative_decrease; opt.dmin = o->min_lm_diagonal;
+    opt.dmax = o->max_lm_diagonal; opt.ftol = o->function_tolerance;
+    opt.gtol = o->gradient_tolerance; opt.ptol = o->parameter_tolerance;
+    return opt;
+}
+static inline void ba_summary_from(const BaState& st, rs_ba_summary* out)
+{
+    out->termination = st.termination; out->iterations = st.iter; out->successful_steps = st.successful; out->usable = st.usable;
+    out->initial_cost = st.initial_cost; out->final_cost = st.x_cost; out->final_radius = st.radius;
+}
+// waits for the value a kernel's last act stores to a flag in pinned host memory (instead of synchronising the stream);
+// falls back to the stream if it drains without the flag (a failed launch)
+static inline hipError_t ba_wait_flag(hipStream_t s, const volatile int* flag, int value)
+{
+    long spins = 0;
+    while (*flag != value)
+        if ((++spins & 0x3FFFF) == 0 && hipStreamQuery(s) != hipErrorNotReady) break;
+    return *flag != value ? hipStreamSynchronize(s) : hipSuccess;
+}
+void imu_whitener(const double cov[81], double W[81]);   // src/ImuFactor.cpp:10-17 (ba.hip)
+// ---- blocked reduced solve for n > BA_MAX_LDS_N (ba_solve_big.hip)
 size_t ba_big_bytes(int n);
 int ba_launch_reduced_solve_big(rs_context* ctx, const BaDims& d, const BaBufs& b, const BaOpt& opt, char* ws, int band);   // band: 0 general blocked, 1 banded (one workgroup), 2 banded, two-sided
 int ba_band_max_span();

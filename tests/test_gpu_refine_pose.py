@@ -1,4 +1,4 @@
-"""refine_pose on the GPU (K11: ba_refine_pose / ba_refine_pose_inertial, csrc/ba.hip) against the oracle over the cases of
+"""refine_pose on the GPU (K11: ba_refine_pose / ba_refine_pose_inertial, csrc/refine_pose.hip) against the oracle over the cases of
 tests/refine_cases.py — which tests/test_refine_pose_cpu.py pins the oracle on against dense_lm — plus the ABI's
 disabled-constraint, argument and context-state contracts."""
 import ctypes as C
