@@ -107,7 +107,9 @@ int rs_context_fork(rs_context* ctx, rs_context* const* others, int n);
  * where the windows allow it, 1 always the lanes.
  * "gftt_round_launches": rs_detect_features — how many launches of the parallel minimum-distance round (0 .. 12,
  * default 12) run before the single-workgroup finisher decides what they left undecided; 0 leaves every decision to
- * the finisher.  The detected corners do not depend on it, only the launches and rs_detector_stats' round counts do. */
+ * the finisher.  The detected corners do not depend on it, only the launches and rs_detector_stats' round counts do.
+ * "bow_score_mode": rs_bow_database_score — 0 (default) the query's values are found through the rs_bow's dense
+ * word table, 1 by binary search in its sorted words; the scores are identical. */
 int rs_context_set_int(rs_context* ctx, const char* name, int value);
 const char* rs_last_error(const rs_context* ctx);
 
@@ -960,6 +962,90 @@ int rs_pnp_estimator_stats(rs_context* ctx, const rs_pnp_estimator* est, int32_t
  * nmodels[h]).  Any pointer may be NULL. */
 int rs_pnp_hypotheses(rs_context* ctx, const rs_pnp_estimator* est, int32_t* h_samples, int32_t* h_nmodels, double* h_models,
                       int32_t* h_scores);
+
+/* ------------------------------------------------- key-frame recognition: vocabulary tree, BoW, L1 scores */
+
+/* The "Loop retrieval" stage of LoopDetector::query (src/LoopDetector.cpp:346-373 score_candidates, :231-265
+ * rank_candidates, timed at :492): a key frame's ORB rows descend the DBoW2 vocabulary tree to a bag-of-words vector
+ * (thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1066-1122, :1218-1259; BowVector.cpp:34-84), which is scored against
+ * every earlier key frame's vector (L1Scoring::score, ScoringObject.cpp:23-68).  The specification is tests/bow_ref.py.
+ * Word ids, occurrence counts and word lists equal it exactly; values, norms and scores are f64 sums in a fixed order
+ * (count x weight for TF_IDF / TF), within 2e-12 relative / 1e-11 absolute of it, and the same bytes on every run.
+ * FeatureVector (levelsup), scoring types other than L1 and vocabulary training are not implemented.
+ *
+ * rs_vocabulary: a tree of n_nodes nodes.  Node 0 is the root; node i > 0 has h_parent[i] < i (h_parent[0] is ignored),
+ * a 32-byte descriptor and an f64 weight.  A node's children are the nodes that name it as parent, in ascending node id
+ * (loadFromTextFile's push_back order, :1338-1424); a node without children is a leaf; leaves are words 0 .. W-1 in
+ * ascending node id.  weighting: 0 = TF_IDF, 1 = TF, 2 = IDF, 3 = BINARY; scoring: 0 = L1_NORM.  The tree need not be
+ * complete: a leaf may sit above depth L and a node may have 1 .. k children.  Refused with RS_ERR_INVALID (the
+ * reference would index out of range): a node with more than k children, a parent that is not below its node, an
+ * unknown weighting and, in a text file, a leaf flag that contradicts the node's children or a malformed line; with
+ * RS_ERR_UNSUPPORTED: a scoring type other than L1 and sizes outside the envelope k 1 .. 20, L 1 .. 10, n_nodes
+ * 2 .. 4194304.  The arrays are copied; creation synchronises. */
+typedef struct rs_vocabulary rs_vocabulary;
+int rs_vocabulary_create(rs_context* ctx, int k, int L, int weighting, int scoring, int n_nodes, const int32_t* h_parent /*[n]*/,
+                         const uint8_t* h_descriptors /*[n][32]*/, const double* h_weight /*[n]*/, rs_vocabulary** out_voc);
+/* saveToTextFile's layout: line 1 "k L scoring weighting", then one line per node after the root, "parent is_leaf b0 ..
+ * b31 weight" (node id = line number - 1).  Trailing blank lines are ignored: the extra node the reference's
+ * while(!f.eof()) loop makes from the empty last line is not reproduced. */
+int rs_vocabulary_load_text(rs_context* ctx, const char* path, rs_vocabulary** out_voc);
+/* h_info[6] = k, L, weighting, scoring, nodes, words. */
+int rs_vocabulary_info(const rs_vocabulary* voc, int32_t* h_info);
+/* Diagnostic: the arrays as given (or as read), in node order; h_parent[0] = -1.  Any pointer may be NULL. */
+int rs_vocabulary_arrays(const rs_vocabulary* voc, int32_t* h_parent, uint8_t* h_descriptors, double* h_weight);
+int rs_vocabulary_destroy(rs_vocabulary* voc);
+
+/* rs_bow holds the scratch of the transform and ONE resulting vector (allocated once; nothing is allocated per call),
+ * for a vocabulary that outlives it.  Envelope: max_points 1 .. 8192; beyond: RS_ERR_UNSUPPORTED. */
+typedef struct rs_bow rs_bow;
+int rs_bow_create(rs_context* ctx, rs_vocabulary* voc, int max_points, rs_bow** out_bow);
+int rs_bow_destroy(rs_bow* bow);
+/* TemplatedVocabulary::transform of rows d_desc [][32] (device, 16-byte aligned), one stream-ordered chain with no host
+ * synchronisation.  n = clamp(d_count[0], 0, min(max_n, max_points)) is read on the device: rs_describe_features'
+ * d_desc and d_n serve as d_desc and d_count.  Every feature steps from the root to the child of smallest Hamming
+ * distance (the first child among equals) until a leaf.  d_word [max_n] i32 (NULL = not written): the word of feature
+ * i < n (a stopped word, weight <= 0, is still reported), -1 from n on.  The vector stays in the object, on the device:
+ * the sorted unique words whose weight is > 0, their occurrence counts, their values (TF_IDF / TF: weight once per
+ * occurrence, IDF / BINARY: the weight once; divided by their sum if it is > 0), the word count and that sum. */
+int rs_bow_transform(rs_context* ctx, rs_bow* bow, const uint8_t* d_desc, const int32_t* d_count, int max_n, int32_t* d_word);
+/* Diagnostic (synchronises the stream): the object's vector.  h_words, h_counts [max_points] i32, h_values [max_points]
+ * f64 (the first *h_n_words entries are written), *h_norm the sum the values were divided by.  Any pointer may be NULL. */
+int rs_bow_download(rs_context* ctx, const rs_bow* bow, int32_t* h_words, int32_t* h_counts, double* h_values,
+                    int32_t* h_n_words, double* h_norm);
+
+/* rs_bow_database: the vectors of the key frames so far, a packed CSR on the device (allocated once).  Envelope:
+ * max_entries 1 .. 1048576, max_total_words 1 .. 2^30. */
+typedef struct rs_bow_database rs_bow_database;
+int rs_bow_database_create(rs_context* ctx, rs_vocabulary* voc, int max_entries, int max_total_words, rs_bow_database** out_db);
+int rs_bow_database_destroy(rs_bow_database* db);
+/* Appends the object's current vector as entry *h_entry (0, 1, ...) with device-to-device copies.  One 4-byte
+ * read-back of the vector's word count synchronises the stream (as rs_frame_assign_device's does): the capacities are
+ * checked on the host, and an entry or words that would not fit return RS_ERR_NOMEM with the database unchanged;
+ * nothing is ever written past a capacity.  Where the reference computes bow_of lazily per candidate (:366-368), the
+ * caller adds every key frame once. */
+int rs_bow_database_add(rs_context* ctx, rs_bow_database* db, const rs_bow* bow, int32_t* h_entry);
+/* L1Scoring::score of the object's vector against entries first .. first + count - 1: d_score [count] f64 (device), no
+ * host synchronisation.  Over the words present in both vectors s = sum(|v - w| - |v| - |w|), the score is -s / 2: 0 in
+ * magnitude when no word is shared, when the entry is empty or when the object's vector is. */
+int rs_bow_database_score(rs_context* ctx, const rs_bow_database* db, const rs_bow* bow, int first, int count, double* d_score);
+int rs_bow_database_counts(const rs_bow_database* db, int32_t* h_entries, int32_t* h_total_words);
+
+/* LoopDetector's score_candidates gates and rank_candidates (src/LoopDetector.cpp:346-373, :231-265, percentile
+ * :64-73).  Host only.  The query is key frame n_entries; h_score [n_entries] f64 are its scores against entries
+ * 0 .. n_entries-1 (rs_bow_database_score), h_frame_index [n_entries] their frame indices.  Entry i is considered
+ * unless n_entries - i < min_keyframe_gap or double(query_frame_index - h_frame_index[i]) * seconds_per_frame <
+ * min_loop_seconds; its score is cast to float there.  threshold = max(min_score, median * peak_over_median) with
+ * the median at index min(size - 1, size_t(0.5f * float(size - 1))) of the sorted considered scores; kept are the
+ * considered entries at or above it that are not below either neighbour in the considered list (a missing neighbour
+ * counts as 0), by descending score, equal scores in their considered order (the reference's std::sort leaves that
+ * unspecified), the first `top` of them.  The reference's constants: min_keyframe_gap 50, min_loop_seconds 10.0,
+ * min_score 0.02f, peak_over_median 1.25f, top 3.  Outputs: h_out_entry, h_out_score [top], *h_out_count; when nothing
+ * is kept and something was considered, *h_rejected_entry / *h_rejected_score are the first considered entry of
+ * greatest score (the one the reference prints), else -1 / 0. */
+int rs_rank_loop_candidates(const double* h_score, const int64_t* h_frame_index, int n_entries, int64_t query_frame_index,
+                            double seconds_per_frame, int min_keyframe_gap, double min_loop_seconds, float min_score,
+                            float peak_over_median, int top, int32_t* h_out_entry, float* h_out_score, int32_t* h_out_count,
+                            int32_t* h_rejected_entry, float* h_rejected_score);
 
 /* ------------------------------------------------------------- multi-GPU */
 

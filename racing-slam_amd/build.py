@@ -28,6 +28,7 @@ SOURCES = [
     ("orb.hip", ["-ffp-contract=off"]),
     ("pose.hip", ["-ffp-contract=off"]),
     ("pnp.hip", ["-ffp-contract=off"]),
+    ("bow.hip", ["-ffp-contract=off"]),
     ("ba.hip", ["-munsafe-fp-atomics"]),
     ("refine_pose.hip", ["-munsafe-fp-atomics"]),
     ("ba_solve.hip", ["-munsafe-fp-atomics"]),

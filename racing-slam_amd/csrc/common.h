@@ -77,6 +77,7 @@ struct rs_context {
     int k2_mode = 0;                    // rs_reproj_match: 0 = eight lanes per map point where the KD-tree fits in LDS, 1 = always one lane per point
     int ba_imu_mode = 0;                // inertial solves: 0 = z blocks eliminated around the LDS K7 where possible, 1 = always the N x N blocked solve
     int ba_batch_mode = 0;              // rs_bundle_adjust_batch: 0 = one grid for all windows where possible, 1 = lanes only
+    int bow_score_mode = 0;             // rs_bow_database_score: 0 = the query's dense word table, 1 = binary search in its sorted words
     int gftt_round_launches = 12;       // rs_detect_features: gftt_round launches before the finisher, 0 .. 12 (= GFTT_ROUNDS, gftt.hip)
     // child contexts of rs_bundle_adjust_batch (own stream / workspace each), created on first use
     std::vector<rs_context*> batch_lanes;

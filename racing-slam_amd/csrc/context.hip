@@ -173,6 +173,11 @@ extern "C" int rs_context_set_int(rs_context* ctx, const char* name, int value)
         ctx->ba_batch_mode = value;
         return RS_OK;
     }
+    if (strcmp(name, "bow_score_mode") == 0) {
+        if (value < 0 || value > 1) return rs_fail(ctx, RS_ERR_INVALID, "bow_score_mode must be 0 (dense word table) or 1 (binary search)");
+        ctx->bow_score_mode = value;
+        return RS_OK;
+    }
     if (strcmp(name, "gftt_round_launches") == 0) {
         if (value < 0 || value > GFTT_ROUNDS_KNOB) return rs_fail(ctx, RS_ERR_INVALID, "gftt_round_launches must be 0 .. 12 (default 12)");
         ctx->gftt_round_launches = value;

@@ -233,3 +233,56 @@ extern "C" int rs_parallax_requirements(const float* h_poses, int n_poses, int k
     }
     return RS_OK;
 }
+
+// LoopDetector's score_candidates gates and rank_candidates (src/LoopDetector.cpp:346-373, :231-265; percentile :64-73),
+// as restated by tests/bow_ref.py
+extern "C" int rs_rank_loop_candidates(const double* h_score, const int64_t* h_frame_index, int n_entries, int64_t query_frame_index,
+                                       double seconds_per_frame, int min_keyframe_gap, double min_loop_seconds, float min_score,
+                                       float peak_over_median, int top, int32_t* h_out_entry, float* h_out_score,
+                                       int32_t* h_out_count, int32_t* h_rejected_entry, float* h_rejected_score)
+{
+    if (n_entries < 0 || top < 0 || !h_out_count || (n_entries > 0 && (!h_score || !h_frame_index)) ||
+        (top > 0 && (!h_out_entry || !h_out_score)))
+        return RS_ERR_INVALID;
+    std::vector<int32_t> entry;
+    std::vector<float> score;
+    for (int i = 0; i < n_entries; i++) {
+        if (n_entries - i < min_keyframe_gap) continue;
+        const double dt = static_cast<double>(query_frame_index - h_frame_index[i]) * seconds_per_frame;
+        if (dt < min_loop_seconds) continue;
+        entry.push_back(i);
+        score.push_back(static_cast<float>(h_score[i]));
+    }
+    const size_t n = score.size();
+    float median = 0.0f;
+    if (n) {
+        std::vector<float> sorted(score);
+        std::sort(sorted.begin(), sorted.end());
+        median = sorted[std::min(n - 1, static_cast<size_t>(0.5f * static_cast<float>(n - 1)))];
+    }
+    const float thresh = std::max(min_score, median * peak_over_median);
+    std::vector<size_t> ranked;
+    for (size_t i = 0; i < n; i++) {
+        if (score[i] < thresh) continue;
+        const float left = i == 0 ? 0.0f : score[i - 1], right = i + 1 == n ? 0.0f : score[i + 1];
+        if (score[i] < left || score[i] < right) continue;
+        ranked.push_back(i);
+    }
+    std::stable_sort(ranked.begin(), ranked.end(), [&](size_t a, size_t b) { return score[a] > score[b]; });
+    if (ranked.size() > (size_t)top) ranked.resize((size_t)top);
+    for (size_t r = 0; r < ranked.size(); r++) {
+        h_out_entry[r] = entry[ranked[r]];
+        h_out_score[r] = score[ranked[r]];
+    }
+    *h_out_count = (int32_t)ranked.size();
+    int32_t rej = -1;
+    float rej_score = 0.0f;
+    if (ranked.empty() && n) {
+        const size_t b = (size_t)(std::max_element(score.begin(), score.end()) - score.begin());
+        rej = entry[b];
+        rej_score = score[b];
+    }
+    if (h_rejected_entry) *h_rejected_entry = rej;
+    if (h_rejected_score) *h_rejected_score = rej_score;
+    return RS_OK;
+}

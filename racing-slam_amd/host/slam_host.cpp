@@ -1028,4 +1028,63 @@ PnpEstimate estimate_pose_pnp(const std::vector<Vec3f>& object_points, const std
 
 }  // namespace pose
 
+// ------------------------------------------------------------------------ loop retrieval
+LoopRetrieval::LoopRetrieval(const std::string& vocabulary_path, size_t max_key_frames, size_t max_total_words, float seconds_per_frame)
+    : m_seconds_per_frame(seconds_per_frame)
+{
+    rs_context* ctx = Session::get().ctx();
+    if (!rs_ok(rs_vocabulary_load_text(ctx, vocabulary_path.c_str(), &m_voc), "rs_vocabulary_load_text")) return;
+    if (!rs_ok(rs_bow_create(ctx, m_voc, 8192, &m_bow), "rs_bow_create")) return;
+    if (hipMalloc(&m_d_score, sizeof(double) * std::max<size_t>(max_key_frames, 1)) != hipSuccess) {
+        std::printf("LoopRetrieval: no memory for %zu scores\n", max_key_frames);
+        m_d_score = nullptr;
+        return;
+    }
+    rs_ok(rs_bow_database_create(ctx, m_voc, (int)max_key_frames, (int)max_total_words, &m_db), "rs_bow_database_create");
+    m_frame_index.reserve(max_key_frames);
+}
+
+LoopRetrieval::~LoopRetrieval()
+{
+    rs_bow_database_destroy(m_db);
+    rs_bow_destroy(m_bow);
+    rs_vocabulary_destroy(m_voc);
+    if (m_d_score) (void)hipFree(m_d_score);
+}
+
+bool LoopRetrieval::add_key_frame(const uint8_t* d_desc, const int32_t* d_count, int max_n, size_t frame_index)
+{
+    if (!valid()) return false;
+    rs_context* ctx = Session::get().ctx();
+    int32_t entry = -1;
+    if (!rs_ok(rs_bow_transform(ctx, m_bow, d_desc, d_count, max_n, nullptr), "rs_bow_transform") ||
+        !rs_ok(rs_bow_database_add(ctx, m_db, m_bow, &entry), "rs_bow_database_add"))
+        return false;
+    m_frame_index.push_back((int64_t)frame_index);
+    return true;
+}
+
+std::vector<LoopCandidate> LoopRetrieval::query()
+{
+    std::vector<LoopCandidate> out;
+    if (!valid() || m_frame_index.size() < 2) return out;
+    rs_context* ctx = Session::get().ctx();
+    const int q = (int)m_frame_index.size() - 1;             // the query: the key frame added last, still in m_bow
+    if (!rs_ok(rs_bow_database_score(ctx, m_db, m_bow, 0, q, m_d_score), "rs_bow_database_score") ||
+        !rs_ok(rs_context_synchronize(ctx), "rs_context_synchronize"))
+        return out;
+    m_score.resize((size_t)q);
+    hip_ok(hipMemcpy(m_score.data(), m_d_score, sizeof(double) * (size_t)q, hipMemcpyDeviceToHost), "scores");
+    int32_t entry[3], count = 0, rejected = -1;
+    float score[3], rejected_score = 0.0f;
+    if (!rs_ok(rs_rank_loop_candidates(m_score.data(), m_frame_index.data(), q, m_frame_index[q], (double)m_seconds_per_frame, 50, 10.0,
+                                       0.02f, 1.25f, 3, entry, score, &count, &rejected, &rejected_score),
+               "rs_rank_loop_candidates"))
+        return out;
+    if (count == 0 && rejected >= 0) std::printf("Loop rejected: best kf %d bow %g\n", rejected, (double)rejected_score);   // :262
+    for (int32_t r = 0; r < count; r++)
+        out.push_back({(size_t)entry[r], score[r], (size_t)(m_frame_index[q] - m_frame_index[entry[r]])});
+    return out;
+}
+
 }  // namespace slam

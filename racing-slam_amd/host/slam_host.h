@@ -16,6 +16,7 @@
 #include <memory>
 #include <unordered_set>
 #include <utility>
+#include <string>
 #include <vector>
 
 #include "../../include/rsgpu.h"
@@ -321,5 +322,41 @@ PnpEstimate estimate_pose_pnp(const std::vector<Vec3f>& object_points, const std
                               double threshold_px);
 
 }  // namespace pose
+
+// LoopDetector::query's "Loop retrieval" stage (src/LoopDetector.cpp:346-373 Impl::score_candidates, :231-265
+// rank_candidates) on the device, as specified by tests/bow_ref.py: the DBoW2 vocabulary, one rs_bow and the database of
+// the key frames' vectors.  Where the reference computes bow_of lazily per candidate (:351-353, :366-368), every key
+// frame is transformed and added once, when it arrives; a query is one rs_bow_database_score call, one read-back of the
+// scores and rs_rank_loop_candidates with the reference's constants (:28-32).  update_streak stays with the caller.
+struct LoopCandidate {
+    size_t entry = 0;                            // index of the key frame in arrival order (Candidate::index)
+    float score = 0.0f;
+    size_t frame_gap = 0;                        // query frame index - candidate frame index
+};
+class LoopRetrieval {
+  public:
+    // vocabulary_path: DBoW2's text format (loadFromTextFile); capacities of the database
+    LoopRetrieval(const std::string& vocabulary_path, size_t max_key_frames, size_t max_total_words, float seconds_per_frame);
+    ~LoopRetrieval();
+    LoopRetrieval(const LoopRetrieval&) = delete;
+    LoopRetrieval& operator=(const LoopRetrieval&) = delete;
+    bool valid() const { return m_db != nullptr; }
+    const rs_vocabulary* vocabulary() const { return m_voc; }
+    size_t size() const { return m_frame_index.size(); }
+    // the key frame's ORB rows d_desc [max_n][32] and their count d_count [1], both on the device (rs_describe_features'
+    // d_desc and d_n): transformed and appended; false on failure (logged), e.g. a full database
+    bool add_key_frame(const uint8_t* d_desc, const int32_t* d_count, int max_n, size_t frame_index);
+    // the ranked candidates (at most 3) of the key frame added last against all earlier ones
+    std::vector<LoopCandidate> query();
+
+  private:
+    rs_vocabulary* m_voc = nullptr;
+    rs_bow* m_bow = nullptr;
+    rs_bow_database* m_db = nullptr;
+    double* m_d_score = nullptr;                 // [max_key_frames]
+    std::vector<int64_t> m_frame_index;
+    std::vector<double> m_score;
+    float m_seconds_per_frame = 0.0f;
+};
 
 }  // namespace slam

@@ -29,6 +29,10 @@ EXPORTS = [
     "rs_pose_estimator_create", "rs_pose_estimator_destroy", "rs_estimate_pose", "rs_estimate_pose_known_rotation",
     "rs_pose_estimator_stats", "rs_pose_hypotheses",
     "rs_pnp_estimator_create", "rs_pnp_estimator_destroy", "rs_estimate_pose_pnp", "rs_pnp_estimator_stats", "rs_pnp_hypotheses",
+    "rs_vocabulary_create", "rs_vocabulary_load_text", "rs_vocabulary_info", "rs_vocabulary_arrays", "rs_vocabulary_destroy",
+    "rs_bow_create", "rs_bow_destroy", "rs_bow_transform", "rs_bow_download",
+    "rs_bow_database_create", "rs_bow_database_destroy", "rs_bow_database_add", "rs_bow_database_score", "rs_bow_database_counts",
+    "rs_rank_loop_candidates",
     "rs_comm_get_unique_id", "rs_comm_init_rank", "rs_comm_destroy", "rs_comm_init_local", "rs_comm_count", "rs_prof_begin", "rs_prof_end", "rs_prof_counters", "rs_prof_empty_launch",
 ]
 
@@ -266,6 +270,27 @@ def build_local_window(n_kf, new_frame, window, fix_oldest, frame_ptr, frame_pt,
         raise RsError(f"rs_build_local_window -> {rc}")
     n = int(cnt[0])
     return of[:n].copy(), oo[:n].copy()
+
+
+def rank_loop_candidates(scores, frame_index, query_frame_index, seconds_per_frame, min_keyframe_gap=50, min_loop_seconds=10.0,
+                         min_score=0.02, peak_over_median=1.25, top=3):
+    """rs_rank_loop_candidates (host): LoopDetector's gates and rank_candidates over the query's scores against every
+    earlier entry.  dict(entries [<= top] i32, scores f32, rejected: (entry, score) of the best considered entry when
+    nothing is kept and something was considered, else None).  The defaults are the reference's constants."""
+    sc = np.ascontiguousarray(scores, np.float64)
+    fi = np.ascontiguousarray(frame_index, np.int64)
+    assert len(sc) == len(fi)
+    oe, os_ = np.zeros(max(top, 1), np.int32), np.zeros(max(top, 1), np.float32)
+    cnt, re_ = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    rs_ = np.zeros(1, np.float32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)         # noqa: E731
+    rc = load().rs_rank_loop_candidates(vp(sc), vp(fi), len(sc), C.c_int64(int(query_frame_index)), C.c_double(seconds_per_frame),
+                                        int(min_keyframe_gap), C.c_double(min_loop_seconds), C.c_float(min_score),
+                                        C.c_float(peak_over_median), int(top), vp(oe), vp(os_), vp(cnt), vp(re_), vp(rs_))
+    if rc:
+        raise RsError(f"rs_rank_loop_candidates -> {rc}")
+    n = int(cnt[0])
+    return dict(entries=oe[:n].copy(), scores=os_[:n].copy(), rejected=None if re_[0] < 0 else (int(re_[0]), rs_[0]))
 
 
 # ---- GPU context -------------------------------------------------------------
@@ -819,6 +844,21 @@ class Context:
                     "rs_estimate_pose_pnp")
         return out
 
+    # -- key-frame recognition (LoopDetector's "Loop retrieval")
+    def vocabulary(self, k, L, weighting, scoring, parent, desc, weight):
+        """rs_vocabulary from host arrays in node order (parent [n] i32, desc [n][32] u8, weight [n] f64)."""
+        return Vocabulary(self, k, L, weighting, scoring, parent, desc, weight)
+
+    def vocabulary_from_text(self, path):
+        return Vocabulary(self, path=path)
+
+    def bow(self, voc, max_points=8192):
+        """rs_bow: the transform's scratch and one resulting vector."""
+        return Bow(self, voc, max_points)
+
+    def bow_database(self, voc, max_entries, max_total_words):
+        return BowDatabase(self, voc, max_entries, max_total_words)
+
     def synchronize(self):
         self._check(self.lib.rs_context_synchronize(self.h), "rs_context_synchronize")
 
@@ -973,6 +1013,110 @@ class PnpEstimator(_RansacEstimator):
 
 
 # ---- §8(f) rank 4: the resident map (rs_map / rs_frame) -----------------------------------------------------
+class Vocabulary:
+    """rs_vocabulary: the DBoW2 tree on the device (children contiguous, top levels first)."""
+
+    def __init__(self, ctx, k=0, L=0, weighting=0, scoring=0, parent=None, desc=None, weight=None, path=None):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        if path is not None:
+            ctx._check(ctx.lib.rs_vocabulary_load_text(ctx.h, os.fsencode(path), C.byref(self.h)), "rs_vocabulary_load_text")
+        else:
+            p = np.ascontiguousarray(parent, np.int32)
+            d = np.ascontiguousarray(desc, np.uint8)
+            w = np.ascontiguousarray(weight, np.float64)
+            assert d.size == 32 * len(p) and len(w) == len(p)
+            vp = lambda a: a.ctypes.data_as(C.c_void_p)         # noqa: E731
+            ctx._check(ctx.lib.rs_vocabulary_create(ctx.h, int(k), int(L), int(weighting), int(scoring), len(p), vp(p), vp(d), vp(w),
+                                                    C.byref(self.h)), "rs_vocabulary_create")
+        self.__dict__.update(self.info())
+
+    def info(self):
+        v = (C.c_int32 * 6)()
+        self.ctx._check(self.ctx.lib.rs_vocabulary_info(self.h, v), "rs_vocabulary_info")
+        return dict(zip(("k", "L", "weighting", "scoring", "n_nodes", "n_words"), list(v)))
+
+    def arrays(self):
+        """(parent [n] i32, desc [n][32] u8, weight [n] f64) as given or read, in node order."""
+        n = self.n_nodes
+        p, d, w = np.zeros(n, np.int32), np.zeros((n, 32), np.uint8), np.zeros(n, np.float64)
+        self.ctx._check(self.ctx.lib.rs_vocabulary_arrays(self.h, p.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p),
+                                                          w.ctypes.data_as(C.c_void_p)), "rs_vocabulary_arrays")
+        return p, d, w
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.rs_vocabulary_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+class Bow:
+    """rs_bow: one bag-of-words vector on the device and the scratch that makes it."""
+
+    def __init__(self, ctx, voc, max_points=8192):
+        self.ctx, self.voc, self.max_points = ctx, voc, int(max_points)
+        self.h = C.c_void_p()
+        ctx._check(ctx.lib.rs_bow_create(ctx.h, voc.h, self.max_points, C.byref(self.h)), "rs_bow_create")
+
+    def transform(self, d_desc, d_count, max_n, words=True):
+        """rs_bow_transform; d_count is a device [1] i32.  Returns d_word [max_n] i32 (device), or None with words=False."""
+        d_word = self.ctx.empty((max(int(max_n), 1),), self.ctx.torch.int32) if words else None
+        self.ctx._check(self.ctx.lib.rs_bow_transform(self.ctx.h, self.h, _dp(d_desc), _dp(d_count), int(max_n), _dp(d_word)),
+                        "rs_bow_transform")
+        return d_word
+
+    def download(self):
+        """Diagnostic (synchronises): dict(words [m] i32, counts [m] i32, values [m] f64, norm)."""
+        m = self.max_points
+        w, c, v = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.float64)
+        n, norm = np.zeros(1, np.int32), np.zeros(1, np.float64)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)             # noqa: E731
+        self.ctx._check(self.ctx.lib.rs_bow_download(self.ctx.h, self.h, vp(w), vp(c), vp(v), vp(n), vp(norm)), "rs_bow_download")
+        k = int(n[0])
+        return dict(words=w[:k].copy(), counts=c[:k].copy(), values=v[:k].copy(), norm=float(norm[0]))
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.rs_bow_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+class BowDatabase:
+    """rs_bow_database: the key frames' vectors as a packed CSR on the device."""
+
+    def __init__(self, ctx, voc, max_entries, max_total_words):
+        self.ctx, self.voc = ctx, voc
+        self.h = C.c_void_p()
+        ctx._check(ctx.lib.rs_bow_database_create(ctx.h, voc.h, int(max_entries), int(max_total_words), C.byref(self.h)),
+                   "rs_bow_database_create")
+
+    def add(self, bow):
+        """Appends bow's current vector; returns its entry index (one 4-byte read-back)."""
+        e = C.c_int32(-1)
+        self.ctx._check(self.ctx.lib.rs_bow_database_add(self.ctx.h, self.h, bow.h, C.byref(e)), "rs_bow_database_add")
+        return e.value
+
+    def score(self, bow, first=0, count=None, out=None):
+        """rs_bow_database_score: device f64 [count] scores of bow's vector against entries first .. first + count - 1."""
+        if count is None:
+            count = self.counts()[0] - first
+        if out is None:
+            out = self.ctx.empty((max(int(count), 1),), self.ctx.torch.float64)
+        self.ctx._check(self.ctx.lib.rs_bow_database_score(self.ctx.h, self.h, bow.h, int(first), int(count), _dp(out)),
+                        "rs_bow_database_score")
+        return out[:max(int(count), 0)]
+
+    def counts(self):
+        e, w = C.c_int32(0), C.c_int32(0)
+        self.ctx._check(self.ctx.lib.rs_bow_database_counts(self.h, C.byref(e), C.byref(w)), "rs_bow_database_counts")
+        return e.value, w.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.rs_bow_database_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class ResidentFrame:
     def __init__(self, ctx, keypoints, descriptors):
         self.ctx = ctx

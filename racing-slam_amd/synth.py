@@ -752,3 +752,92 @@ def make_pnp_scene(seed=0, n=2000, outlier_frac=0.3, noise_px=0.5, layout="volum
         out.update(pixels=out["pixels"][perm], inlier=inlier[perm], desc_points=dp, desc_pixels=np.ascontiguousarray(dq[perm]),
                    pixel_point=perm.astype(np.int32))
     return out
+
+
+def _sparse_flips(rng, n):
+    """[n][32] u8 masks with every bit set with probability 1/8."""
+    return random_descriptors(rng, n) & random_descriptors(rng, n) & random_descriptors(rng, n)
+
+
+def make_vocabulary(k, L, seed=0, ragged=False, stopped_fraction=0.0, duplicate_children=False):
+    """A DBoW2-style vocabulary tree for key-frame recognition (LoopDetector's "Loop retrieval"): k children per node, L
+    levels below the root.  A child's descriptor is its parent's with 1/8 of the bits flipped (the children of the root
+    are random rows); leaves carry idf-like weights in [0.5, 8), inner nodes 0.  Node ids are a random numbering with
+    parent < child, so a node's children are neither contiguous nor in creation order.
+      ragged               about 15 % of the inner candidates above depth L become early leaves and the others get
+                           1 .. k children (one-child nodes among them)
+      stopped_fraction     that fraction of the leaves gets weight 0 (stopped words); 1.0 stops every word
+      duplicate_children   in about 30 % of the families two siblings carry identical descriptors (ties)
+    Returns dict(k, L, n_nodes, parent [n] i32 (parent[0] = -1), desc [n][32] u8, weight [n] f64, leaf [n] bool)."""
+    rng = np.random.default_rng([0xB0, int(k), int(L), int(seed), int(ragged), int(duplicate_children)])
+    parent, desc, depth = [np.array([-1], np.int64)], [np.zeros((1, 32), np.uint8)], [np.zeros(1, np.int64)]
+    key = [np.array([-1.0])]
+    level_ids, level_desc, level_key, total = np.array([0], np.int64), desc[0], key[0], 1
+    for d in range(1, L + 1):
+        m = len(level_ids)
+        cnt = np.full(m, k, np.int64)
+        if ragged and d > 1:                                    # (the root keeps its k children)
+            cnt = rng.integers(1, k + 1, m)
+            cnt[rng.random(m) < 0.2] = 1
+            if d > 1:
+                cnt[rng.random(m) < 0.15] = 0                   # early leaves
+            if not cnt.any():
+                cnt[0] = 1
+        owner = np.repeat(np.arange(m), cnt)
+        nc = len(owner)
+        if nc == 0:
+            break
+        cd = random_descriptors(rng, nc) if d == 1 else level_desc[owner] ^ _sparse_flips(rng, nc)
+        if duplicate_children:
+            first = np.concatenate([[0], np.cumsum(cnt)[:-1]])
+            fam = np.flatnonzero((cnt >= 2) & (rng.random(m) < 0.3))
+            a = first[fam] + rng.integers(0, cnt[fam])
+            b = first[fam] + (a - first[fam] + 1 + rng.integers(0, cnt[fam] - 1)) % cnt[fam]
+            cd[b] = cd[a]
+        parent.append(level_ids[owner])
+        desc.append(cd)
+        depth.append(np.full(nc, d, np.int64))
+        ck = level_key[owner] + rng.random(nc) + 1e-9
+        key.append(ck)
+        level_ids, level_desc, level_key = total + np.arange(nc), cd, ck
+        total += nc
+    parent, desc, key = np.concatenate(parent), np.concatenate(desc), np.concatenate(key)
+    order = np.argsort(key, kind="stable")                      # new id -> creation id; the root stays 0
+    new_id = np.empty(total, np.int64)
+    new_id[order] = np.arange(total)
+    p = parent[order]
+    p[1:] = new_id[p[1:]]
+    desc = np.ascontiguousarray(desc[order])
+    leaf = np.bincount(p[1:], minlength=total) == 0
+    weight = np.zeros(total, np.float64)
+    nl = int(leaf.sum())
+    w = rng.uniform(0.5, 8.0, nl)
+    w[rng.random(nl) < stopped_fraction] = 0.0
+    weight[leaf] = w
+    return dict(k=int(k), L=int(L), n_nodes=total, parent=p.astype(np.int32), desc=desc, weight=weight, leaf=leaf)
+
+
+def make_bow_descriptors(voc, n, seed=0, noise=0.04, equidistant_fraction=0.1):
+    """n ORB rows for make_vocabulary's tree `voc`: noisy copies (bit flips with probability `noise`) of random leaves'
+    descriptors; a fraction equidistant_fraction of the rows is instead built exactly equidistant from two sibling
+    leaves (half of the bits in which the two differ are taken from each; identical siblings are equidistant from any
+    row), which exercises the descent's tie rule.  Returns [n][32] u8."""
+    rng = np.random.default_rng([0xB1, int(seed), int(n)])
+    leaves = np.flatnonzero(voc["leaf"])
+    rows = flip_bits(rng, voc["desc"][leaves[rng.integers(0, len(leaves), n)]], noise) if n else np.zeros((0, 32), np.uint8)
+    parent = voc["parent"]
+    for r in np.flatnonzero(rng.random(n) < equidistant_fraction):
+        a = leaves[rng.integers(0, len(leaves))]
+        sib = np.flatnonzero(parent == parent[a]) if voc["n_nodes"] <= 4096 else \
+            parent[a] + 1 + np.flatnonzero(parent[parent[a] + 1:parent[a] + 200001] == parent[a])
+        sib = sib[sib != a]
+        if not len(sib):
+            continue
+        b = sib[rng.integers(0, len(sib))]
+        bits_a, bits_b = np.unpackbits(voc["desc"][a]), np.unpackbits(voc["desc"][b])
+        diff = np.flatnonzero(bits_a != bits_b)
+        diff = diff[:len(diff) - len(diff) % 2]
+        take = rng.permutation(diff)[:len(diff) // 2]
+        bits_a[take] = bits_b[take]
+        rows[r] = np.packbits(bits_a)
+    return np.ascontiguousarray(rows)

@@ -1,0 +1,350 @@
+"""Key-frame recognition on the GPU (csrc/bow.hip: rs_vocabulary_*, rs_bow_*, rs_bow_database_*) against the CPU
+restatement tests/bow_ref.py on the same inputs.
+
+Word ids, occurrence counts and word lists are integers: exact equality.  Values and the norm: relative error <= 2e-12
+(every term is a positive weight; any summation order of at most 8192 of them is within (n-1) 2^-53 ~ 9.1e-13 of the exact
+sum, so count x weight and tree reductions are allowed).  Scores: absolute error <= 1e-11, the same bound carried
+through |v-w| - v - w with sum v = sum w = 1.
+"""
+import functools
+import importlib
+
+import numpy as np
+import pytest
+
+import bow_ref as B
+from conftest import to_np
+
+pytestmark = pytest.mark.gpu
+
+VALUE_RTOL = 2e-12
+SCORE_ATOL = 1e-11
+
+
+def _synth():
+    return importlib.import_module("racing-slam_amd").synth
+
+
+def _key(kw):
+    return tuple(sorted(kw.items()))
+
+
+@functools.lru_cache(maxsize=None)
+def _tree(key):
+    kw = dict(key)
+    return _synth().make_vocabulary(**kw)
+
+
+@functools.lru_cache(maxsize=None)
+def _ref_voc(key, weighting):
+    v = _tree(key)
+    return B.Vocabulary(v["k"], v["L"], weighting, B.L1_NORM, v["parent"], v["desc"], v["weight"])
+
+
+@functools.lru_cache(maxsize=None)
+def _rows(key, n, seed=0):
+    return _synth().make_bow_descriptors(_tree(key), n, seed=seed)
+
+
+@functools.lru_cache(maxsize=None)
+def _ref(key, weighting, n, seed=0):
+    return B.transform(_ref_voc(key, weighting), _rows(key, n, seed))
+
+
+_GPU_VOC = {}
+
+
+def _gpu_voc(ctx, key, weighting):
+    """One device vocabulary per (tree, weighting) for the whole module."""
+    v = _GPU_VOC.get((key, weighting))
+    if v is None:
+        t = _tree(key)
+        v = _GPU_VOC[(key, weighting)] = ctx.vocabulary(t["k"], t["L"], weighting, 0, t["parent"], t["desc"], t["weight"])
+    return v
+
+
+def _i32(v):
+    return np.array([v], np.int32)
+
+
+def _run(ctx, bow, rows, count=None, max_n=None, words=True):
+    n = len(rows)
+    max_n = n if max_n is None else max_n
+    d_rows = ctx.dev(rows if n else np.zeros((1, 32), np.uint8))
+    d_word = bow.transform(d_rows, ctx.dev(_i32(n if count is None else count)), max_n, words=words)
+    return None if d_word is None else to_np(d_word)[:max_n].copy(), bow.download()
+
+
+def _check(word, dl, ref, n, max_n=None):
+    if word is not None:
+        assert np.array_equal(word[:n], ref["word_of_feature"][:n]), f"words differ at {np.flatnonzero(word[:n] != ref['word_of_feature'][:n])[:10]}"
+        assert np.all(word[n:] == -1)
+    assert np.array_equal(dl["words"], ref["words"])
+    assert np.array_equal(dl["counts"], ref["counts"])
+    if len(ref["values"]):
+        rel = np.abs(dl["values"] - ref["values"]) / ref["values"]
+        print(f"values: max relative error {rel.max():.3e}; norm {abs(dl['norm'] - ref['norm']) / ref['norm']:.3e}")
+        assert rel.max() <= VALUE_RTOL
+        assert abs(dl["norm"] - ref["norm"]) <= VALUE_RTOL * ref["norm"]
+    else:
+        assert dl["norm"] == 0.0
+
+
+TREES = [dict(k=2, L=1), dict(k=3, L=4), dict(k=10, L=3), dict(k=16, L=2), dict(k=17, L=2), dict(k=20, L=2),
+         dict(k=6, L=4, ragged=True), dict(k=5, L=3, duplicate_children=True), dict(k=19, L=2, ragged=True, duplicate_children=True)]
+
+
+@pytest.mark.parametrize("tree", TREES, ids=lambda t: "-".join(f"{k}{v}" for k, v in t.items()))
+def test_trees(ctx, tree):
+    key = _key(tree)
+    voc = _gpu_voc(ctx, key, B.TF_IDF)
+    R = _ref_voc(key, B.TF_IDF)
+    assert (voc.k, voc.L, voc.n_nodes, voc.n_words) == (R.k, R.L, R.n_nodes, R.n_words)
+    bow = ctx.bow(voc, 512)
+    try:
+        word, dl = _run(ctx, bow, _rows(key, 300))
+        _check(word, dl, _ref(key, B.TF_IDF, 300), 300)
+    finally:
+        bow.close()
+
+
+def test_deep_tree_beyond_the_lds_levels(ctx):
+    key = _key(dict(k=10, L=6))
+    voc = _gpu_voc(ctx, key, B.TF_IDF)
+    assert voc.n_nodes == 1111111 and voc.n_words == 1000000
+    bow = ctx.bow(voc, 256)
+    try:
+        word, dl = _run(ctx, bow, _rows(key, 200))
+        _check(word, dl, _ref(key, B.TF_IDF, 200), 200)
+    finally:
+        bow.close()
+
+
+K103 = _key(dict(k=10, L=3))
+
+
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 2000, 8192])
+def test_feature_counts(ctx, n):
+    bow = ctx.bow(_gpu_voc(ctx, K103, B.TF_IDF), 8192)
+    try:
+        word, dl = _run(ctx, bow, _rows(K103, n), max_n=max(n, 3))
+        _check(word, dl, _ref(K103, B.TF_IDF, n), n)
+    finally:
+        bow.close()
+
+
+def test_identical_features_clamped_count_and_no_word_output(ctx):
+    voc, R = _gpu_voc(ctx, K103, B.TF_IDF), _ref_voc(K103, B.TF_IDF)
+    bow = ctx.bow(voc, 8192)
+    small = ctx.bow(voc, 100)
+    try:
+        rows = np.repeat(_rows(K103, 1), 8192, 0)
+        word, dl = _run(ctx, bow, rows)
+        ref = B.transform(R, rows)
+        _check(word, dl, ref, 8192)
+        assert dl["counts"].tolist() == [8192] and dl["values"].tolist() == [1.0]
+        # d_count above max_n, and above the object's max_points: clamped on the device
+        rows = _rows(K103, 300)
+        word, dl = _run(ctx, bow, rows, count=100000, max_n=200)
+        _check(word, dl, B.transform(R, rows[:200]), 200)
+        word, dl = _run(ctx, small, rows, count=300, max_n=300)
+        _check(word, dl, B.transform(R, rows[:100]), 100)
+        word, dl = _run(ctx, bow, rows, count=-5)
+        _check(word, dl, B.transform(R, rows[:0]), 0)
+        # d_word = NULL
+        word, dl = _run(ctx, bow, rows, words=False)
+        assert word is None
+        _check(None, dl, _ref(K103, B.TF_IDF, 300), 300)
+    finally:
+        bow.close(); small.close()
+
+
+@pytest.mark.parametrize("weighting", [B.TF_IDF, B.TF, B.IDF, B.BINARY])
+@pytest.mark.parametrize("stopped", [0.0, 0.3, 1.0])
+def test_weightings_and_stopped_words(ctx, weighting, stopped):
+    key = _key(dict(k=4, L=3, stopped_fraction=stopped))
+    bow = ctx.bow(_gpu_voc(ctx, key, weighting), 1024)
+    try:
+        word, dl = _run(ctx, bow, _rows(key, 700))
+        ref = _ref(key, weighting, 700)
+        _check(word, dl, ref, 700)
+        assert (len(ref["words"]) == 0) == (stopped == 1.0) and (word >= 0).all()
+        if 0.0 < stopped < 1.0:
+            assert len(ref["words"]) < len(np.unique(ref["word_of_feature"]))   # some stopped words were hit
+    finally:
+        bow.close()
+
+
+def _fill(ctx, bow, db, key, weighting, n_entries, sizes=(120, 0, 60, 200)):
+    refs = []
+    for e in range(n_entries):
+        n = sizes[e % len(sizes)]
+        _run(ctx, bow, _rows(key, n, seed=100 + e), words=False)
+        assert db.add(bow) == e
+        refs.append(_ref(key, weighting, n, seed=100 + e))
+    return refs
+
+
+@pytest.mark.parametrize("n_entries", [0, 1, 65, 300])
+def test_database_scores(ctx, n_entries):
+    voc = _gpu_voc(ctx, K103, B.TF_IDF)
+    bow, db = ctx.bow(voc, 512), ctx.bow_database(voc, max(n_entries, 1), 200 * max(n_entries, 1))
+    try:
+        refs = _fill(ctx, bow, db, K103, B.TF_IDF, n_entries)
+        assert db.counts() == (n_entries, sum(len(r["words"]) for r in refs))
+        # a later transform does not disturb the entries; the query is entry 0's rows again, so it scores 1 against itself
+        _run(ctx, bow, _rows(K103, 120, seed=100), words=False)
+        q = _ref(K103, B.TF_IDF, 120, seed=100)
+        want = np.array([B.score(q, r) for r in refs])
+        got = to_np(db.score(bow))
+        assert got.shape == (n_entries,)
+        if n_entries:
+            print(f"scores: max absolute error {np.abs(got - want).max():.3e}")
+            assert np.abs(got - want).max() <= SCORE_ATOL
+            assert abs(got[0] - 1.0) <= SCORE_ATOL
+            assert np.all(got[1::4] == 0)                       # empty entries
+        for first, count in ((0, 0), (n_entries, 0), (n_entries // 2, n_entries - n_entries // 2), (3, 62), (64, 1), (1, 298)):
+            if first + count <= n_entries:
+                assert np.array_equal(to_np(db.score(bow, first, count)), got[first:first + count])
+        with pytest.raises(Exception, match="status 1"):
+            db.score(bow, 0, n_entries + 1)
+        # the other lookup of the query's values gives the same bytes
+        ctx.set_int("bow_score_mode", 1)
+        try:
+            assert to_np(db.score(bow)).tobytes() == got.tobytes()
+        finally:
+            ctx.set_int("bow_score_mode", 0)
+        # an empty query scores 0 everywhere
+        _run(ctx, bow, _rows(K103, 0), words=False)
+        assert np.all(to_np(db.score(bow)) == 0)
+    finally:
+        bow.close(); db.close()
+
+
+def test_disjoint_vectors_score_zero(ctx):
+    voc, R = _gpu_voc(ctx, K103, B.TF_IDF), _ref_voc(K103, B.TF_IDF)
+    rows = R.desc[R.node_of_word]                               # every leaf's own row
+    wid = B.descend(R, rows)
+    a, b = rows[:60], rows[np.flatnonzero(~np.isin(wid, wid[:60]))[:80]]
+    ra, rb = B.transform(R, a), B.transform(R, b)
+    assert len(rb["words"]) and not set(ra["words"]) & set(rb["words"]) and B.score(ra, rb) == 0
+    bow, db = ctx.bow(voc, 128), ctx.bow_database(voc, 2, 256)
+    try:
+        _run(ctx, bow, a, words=False)
+        db.add(bow)
+        _run(ctx, bow, b, words=False)
+        db.add(bow)
+        got = to_np(db.score(bow))
+        assert got[0] == 0 and abs(got[1] - 1.0) <= SCORE_ATOL
+    finally:
+        bow.close(); db.close()
+
+
+def test_database_capacities(ctx):
+    voc = _gpu_voc(ctx, K103, B.TF_IDF)
+    bow = ctx.bow(voc, 512)
+    n120 = len(_ref(K103, B.TF_IDF, 120, seed=100)["words"])
+    full, tight = ctx.bow_database(voc, 2, 4096), ctx.bow_database(voc, 8, n120 + 5)
+    try:
+        _run(ctx, bow, _rows(K103, 120, seed=100), words=False)
+        assert full.add(bow) == 0 and full.add(bow) == 1
+        before = to_np(full.score(bow)).copy()
+        with pytest.raises(Exception, match="status 3"):
+            full.add(bow)                                       # past max_entries
+        assert full.counts() == (2, 2 * n120) and np.array_equal(to_np(full.score(bow)), before)
+        assert tight.add(bow) == 0
+        with pytest.raises(Exception, match="status 3"):
+            tight.add(bow)                                      # past max_total_words
+        assert tight.counts() == (1, n120) and abs(to_np(tight.score(bow))[0] - 1.0) <= SCORE_ATOL
+        _run(ctx, bow, _rows(K103, 3), words=False)
+        assert tight.add(bow) == 1 and tight.counts()[0] == 2   # a small vector still fits
+    finally:
+        bow.close(); full.close(); tight.close()
+
+
+def test_two_runs_give_identical_bytes(ctx):
+    voc = _gpu_voc(ctx, K103, B.TF_IDF)
+    bow, db = ctx.bow(voc, 8192), ctx.bow_database(voc, 80, 80 * 200)
+    try:
+        _fill(ctx, bow, db, K103, B.TF_IDF, 80)
+        runs = []
+        for _ in range(2):
+            _run(ctx, bow, _rows(K103, 50), words=False)        # something else in between
+            word, dl = _run(ctx, bow, _rows(K103, 8192))
+            runs.append((word.tobytes(), dl["words"].tobytes(), dl["counts"].tobytes(), dl["values"].tobytes(),
+                         np.float64(dl["norm"]).tobytes(), to_np(db.score(bow)).tobytes(), to_np(db.score(bow)).tobytes()))
+        assert runs[0] == runs[1] and runs[0][5] == runs[0][6]
+    finally:
+        bow.close(); db.close()
+
+
+def test_describe_then_transform_on_the_device_count(ctx):
+    """rs_describe_features -> rs_bow_transform on one stream: d_desc and d_n plug in, no host step between."""
+    p = _synth().make_klt_pair(1)
+    W, H = p["width"], p["height"]
+    pts = p["pts"][:900]
+    im, d = ctx.image(W, H, frame=p["img2"]), ctx.describer(W, H, 2000)
+    voc, R = _gpu_voc(ctx, K103, B.TF_IDF), _ref_voc(K103, B.TF_IDF)
+    bow = ctx.bow(voc, 2000)
+    try:
+        o = ctx.describe_features(d, im, None, None, None, None, 0, ctx.dev(pts), ctx.dev(_i32(len(pts))))
+        d_word = bow.transform(o["desc"], o["n"], 2000)
+        n = int(to_np(o["n"])[0])
+        assert n == len(pts)
+        _check(to_np(d_word), bow.download(), B.transform(R, to_np(o["desc"])[:n]), n)
+    finally:
+        im.close(); d.close(); bow.close()
+
+
+def test_refusals(ctx, rs):
+    t = _tree(_key(dict(k=3, L=2)))
+    ok = dict(k=3, L=2, weighting=0, scoring=0, parent=t["parent"], desc=t["desc"], weight=t["weight"])
+    ctx.vocabulary(**ok).close()
+
+    def refused(status, **kw):
+        with pytest.raises(rs.RsError, match=f"status {status}"):
+            ctx.vocabulary(**dict(ok, **kw))
+
+    refused(1, k=2)                                             # a node with more than k children
+    p = t["parent"].copy()
+    p[3] = 3
+    refused(1, parent=p)                                        # a parent that is not below its node
+    p[3] = -1
+    refused(1, parent=p)
+    refused(1, weighting=4)
+    refused(4, scoring=1)                                       # only L1
+    for env in (dict(k=21), dict(k=0), dict(L=11), dict(L=0)):
+        refused(4, **env)
+    refused(4, parent=t["parent"][:1], desc=t["desc"][:1], weight=t["weight"][:1])      # n_nodes 1
+    voc = _gpu_voc(ctx, K103, B.TF_IDF)
+    for max_points, status in ((8193, 4), (0, 1)):
+        with pytest.raises(rs.RsError, match=f"status {status}"):
+            ctx.bow(voc, max_points)
+    with pytest.raises(rs.RsError, match="status 4"):
+        ctx.bow_database(voc, (1 << 20) + 1, 16)
+    with pytest.raises(rs.RsError, match="status 1"):
+        ctx.bow_database(voc, 0, 16)
+
+
+def test_text_file_vocabulary(ctx, rs, tmp_path):
+    key = _key(dict(k=4, L=3, ragged=True, stopped_fraction=0.2))
+    R = _ref_voc(key, B.IDF)
+    path = tmp_path / "voc.txt"
+    B.write_text(R, path)
+    voc = ctx.vocabulary_from_text(path)
+    bow = ctx.bow(voc, 512)
+    try:
+        assert voc.info() == dict(k=4, L=3, weighting=B.IDF, scoring=0, n_nodes=R.n_nodes, n_words=R.n_words)
+        p, d, w = voc.arrays()
+        assert np.array_equal(p, R.parent) and np.array_equal(d, R.desc) and np.array_equal(w, R.weight)
+        word, dl = _run(ctx, bow, _rows(key, 300))
+        _check(word, dl, _ref(key, B.IDF, 300), 300)
+    finally:
+        bow.close(); voc.close()
+    lines = path.read_text().split("\n")
+    f = lines[2].split()
+    f[1] = "0" if f[1] == "1" else "1"
+    lines[2] = " ".join(f)
+    path.write_text("\n".join(lines))
+    with pytest.raises(rs.RsError, match="status 1"):
+        ctx.vocabulary_from_text(path)                          # a leaf flag that contradicts the children
