@@ -50,7 +50,8 @@ typedef enum rs_status {
     RS_ERR_NOMEM = 3,       /* workspace allocation failed */
     RS_ERR_UNSUPPORTED = 4, /* valid request outside the implemented envelope */
     RS_ERR_RCCL = 5,        /* RCCL missing or a collective failed */
-    RS_ERR_NO_DEVICE = 6    /* no gfx950 device visible: there is NO CPU fallback */
+    RS_ERR_NO_DEVICE = 6,   /* no gfx950 device visible: there is NO CPU fallback */
+    RS_ERR_INTERNAL = 7     /* a result of the device contradicts the host mirror; see rs_last_error */
 } rs_status;
 
 typedef struct rs_context rs_context;
@@ -109,7 +110,9 @@ int rs_context_fork(rs_context* ctx, rs_context* const* others, int n);
  * default 12) run before the single-workgroup finisher decides what they left undecided; 0 leaves every decision to
  * the finisher.  The detected corners do not depend on it, only the launches and rs_detector_stats' round counts do.
  * "bow_score_mode": rs_bow_database_score — 0 (default) the query's values are found through the rs_bow's dense
- * word table, 1 by binary search in its sorted words; the scores are identical. */
+ * word table, 1 by binary search in its sorted words; the scores are identical.
+ * "loop_verify_streams": rs_map_verify_loop — 0 (default) each candidate's chain runs on a child context of its own
+ * between a fork and a join, 1 the chains follow one another on the context stream; the results are identical. */
 int rs_context_set_int(rs_context* ctx, const char* name, int value);
 const char* rs_last_error(const rs_context* ctx);
 
@@ -1046,6 +1049,83 @@ int rs_rank_loop_candidates(const double* h_score, const int64_t* h_frame_index,
                             double seconds_per_frame, int min_keyframe_gap, double min_loop_seconds, float min_score,
                             float peak_over_median, int top, int32_t* h_out_entry, float* h_out_score, int32_t* h_out_count,
                             int32_t* h_rejected_entry, float* h_rejected_score);
+
+/* ------------------------------------------------- loop verification against the resident map */
+
+/* The "Loop verify" stage of LoopDetector::query (src/LoopDetector.cpp:501-506): verify_pnp (:176-229) of the query key
+ * frame against each ranked candidate, both key frames of an rs_map.  The specification is tests/loop_ref.py, which
+ * composes tests/match_ref.py and tests/pnp_ref.py.  Per candidate, as one stream-ordered chain:
+ *   gather    the candidate's keypoints i with a map match (kp_point[i] >= 0), ascending i — Frame::map_matches() order
+ *             (src/Frame.cpp:14, :100): descriptor row, point position, keypoint index, point slot;
+ *   match     rs_match_descriptors of ALL the query key frame's rows against the gathered rows (MapMatcher::match_descriptors,
+ *             src/MapMatcher.cpp:129-163);
+ *   pose      rs_estimate_pose_pnp over the matches (object point = the matched row's point, pixel = the query keypoint),
+ *             skipped on the device below 12 correspondences (MIN_PNP_CORRESPONDENCES, :183-186);
+ *   verdict   status 1 = fewer than 12 correspondences, 2 = PnP status != 0 or no inliers (:215-218), 0 otherwise.  The
+ *             listed correspondences are the PnP inliers (ascending) for status 0 and all correspondences otherwise (what
+ *             the early returns hand to set_correspondences); correspondence j is (query keypoint, point slot, candidate
+ *             keypoint).  For status 0, in f32 without contraction and in the reference's operation order (:146-174):
+ *             spread = (max_x - min_x) / width over the listed query keypoints (0 with fewer than 2 or width <= 0), the
+ *             recovered centre -R^T t, drift / gap = its distance to the query's / the candidate's centre,
+ *             ok = inliers >= 20 && inliers / correspondences >= 0.35f && spread >= 0.25f.  For status 1 and 2: no inliers,
+ *             ok false, spread, drift, gap 0 and the identity pose. */
+typedef struct rs_loop_result {
+    int32_t status, ok, correspondences, inliers, listed;
+    float spread, drift, gap;
+    float pose[16];                 /* row-major world -> camera */
+} rs_loop_result;
+
+/* rs_loop_verifier owns every buffer of max_candidates chains (gathered rows, match lists, one rs_pnp_estimator per
+ * candidate and its outputs, one child context per candidate, a pinned result block): nothing is allocated per call.
+ * Envelope: max_points 1 .. 8192 (keypoints of any key frame involved), max_candidates 1 .. 8, max_hypotheses 1 .. 4096;
+ * outside it RS_ERR_UNSUPPORTED.  Creation synchronises the context stream. */
+typedef struct rs_loop_verifier rs_loop_verifier;
+int rs_loop_verifier_create(rs_context* ctx, int max_points, int max_candidates, int max_hypotheses, rs_loop_verifier** out_verifier);
+int rs_loop_verifier_destroy(rs_loop_verifier* verifier);
+/* Verifies h_candidate_kfs [n_candidates] (key frames of `map`; one may appear twice) against query_kf with ONE
+ * synchronisation, at the end, for all of them.  h_intrinsics = fx, fy, cx, cy; width = the image width in pixels;
+ * max_distance, threshold_px, confidence, max_hypotheses, seed as rs_match_descriptors / rs_estimate_pose_pnp take them
+ * (the reference: 64, PNP_REPROJ_ERROR, 0.99, 200); every candidate uses the same seed.  Outputs (host):
+ * h_result [n_candidates]; h_listed_query_kp / h_listed_point / h_listed_candidate_kp [n_candidates][max_points] i32 (row
+ * stride = the verifier's max_points; the first h_result[c].listed entries of row c are written; any of the three may be
+ * NULL).  n_candidates == 0 is valid and writes nothing.  RS_ERR_INVALID: a candidate equal to query_kf, a key frame that
+ * does not exist or has more than max_points keypoints, n_candidates outside 0 .. max_candidates; RS_ERR_UNSUPPORTED:
+ * max_hypotheses above the verifier's.  The context stays usable after every error.
+ * "loop_verify_streams" (rs_context_set_int): 0 (default, the faster by measurement: 0.79 against 2.03 ms for three
+ * candidates) one child context per candidate, forked from the context stream after the gather and joined before the
+ * verdict; 1 every chain on the context stream, one after the other.  Both forms return the same bytes. */
+int rs_map_verify_loop(rs_context* ctx, rs_loop_verifier* verifier, rs_map* map, int query_kf, const int32_t* h_candidate_kfs,
+                       int n_candidates, const float* h_intrinsics, int width, int max_distance, double threshold_px,
+                       double confidence, int max_hypotheses, uint64_t seed, rs_loop_result* h_result,
+                       int32_t* h_listed_query_kp, int32_t* h_listed_point, int32_t* h_listed_candidate_kp);
+/* Diagnostic of chain `candidate` of the last call (synchronises): *h_nt gathered rows; h_rows [nt][32] u8, h_slots,
+ * h_keypoints [nt] i32 and h_positions [nt][3] f32 as gathered; the raw match lists h_match_query / h_match_train (the
+ * first *h_match_count entries, at most the query's keypoints) and the PnP inlier index list h_inlier_index (the first
+ * *h_inlier_count).  Arrays are sized by the caller for max_points entries; any pointer may be NULL. */
+int rs_loop_verifier_download(rs_context* ctx, const rs_loop_verifier* verifier, int candidate, int32_t* h_nt, uint8_t* h_rows,
+                              int32_t* h_slots, int32_t* h_keypoints, float* h_positions, int32_t* h_match_query,
+                              int32_t* h_match_train, int32_t* h_match_count, int32_t* h_inlier_index, int32_t* h_inlier_count);
+
+/* LoopDetector's best_candidate (src/LoopDetector.cpp:267-285) and Impl::update_streak (:375-442).  Host only.  The
+ * caller keeps the constraints (from, to, relative pose, inlier pairs); the state is what update_streak reads of its
+ * streak: its length and the last hit's query and candidate index. */
+typedef struct rs_loop_streak {
+    int32_t length;
+    int64_t last_query, last_candidate;
+} rs_loop_streak;
+/* The verified candidate of most inliers (the first among equals); without a verified one, of most inliers; 0 for n == 1;
+ * RS_ERR_INVALID for n < 1. */
+int rs_loop_best_candidate(const rs_loop_result* h_results, int n, int32_t* h_best);
+/* One query: `from` = the query's index among the key frames, h_candidate_index [n] the ranked candidates' indices,
+ * h_results [n] their verdicts, h_constraint_from / h_constraint_to [n_constraints] the constraints so far.  n == 0 (nothing
+ * ranked) clears the streak, as LoopDetector::query does (:495-499).  *h_chosen = the candidate that entered the streak
+ * (-1: the streak was cleared and nothing entered); *h_new_constraint = 1 when the streak reached MIN_CONSISTENT = 3 and no
+ * constraint lies within MIN_LOOP_SEPARATION = 15 of (from, h_candidate_index[chosen]) on both ends: the caller then
+ * appends the constraint from -> h_candidate_index[chosen] with relative = pose * inverse(candidate pose) in f64 and the
+ * chosen candidate's listed (keypoint, point) pairs.  CONSISTENCY_WINDOW = 15. */
+int rs_loop_update_streak(rs_loop_streak* state, int64_t from, const int64_t* h_candidate_index, const rs_loop_result* h_results,
+                          int n, const int64_t* h_constraint_from, const int64_t* h_constraint_to, int n_constraints,
+                          int32_t* h_chosen, int32_t* h_new_constraint);
 
 /* ------------------------------------------------------------- multi-GPU */
 

@@ -29,6 +29,7 @@ SOURCES = [
     ("pose.hip", ["-ffp-contract=off"]),
     ("pnp.hip", ["-ffp-contract=off"]),
     ("bow.hip", ["-ffp-contract=off"]),
+    ("loop.hip", ["-ffp-contract=off"]),
     ("ba.hip", ["-munsafe-fp-atomics"]),
     ("refine_pose.hip", ["-munsafe-fp-atomics"]),
     ("ba_solve.hip", ["-munsafe-fp-atomics"]),

@@ -78,6 +78,7 @@ struct rs_context {
     int ba_imu_mode = 0;                // inertial solves: 0 = z blocks eliminated around the LDS K7 where possible, 1 = always the N x N blocked solve
     int ba_batch_mode = 0;              // rs_bundle_adjust_batch: 0 = one grid for all windows where possible, 1 = lanes only
     int bow_score_mode = 0;             // rs_bow_database_score: 0 = the query's dense word table, 1 = binary search in its sorted words
+    int loop_verify_streams = 0;        // rs_map_verify_loop: 0 = one forked child context per candidate, 1 = every candidate's chain on the context stream
     int gftt_round_launches = 12;       // rs_detect_features: gftt_round launches before the finisher, 0 .. 12 (= GFTT_ROUNDS, gftt.hip)
     // child contexts of rs_bundle_adjust_batch (own stream / workspace each), created on first use
     std::vector<rs_context*> batch_lanes;
@@ -111,6 +112,21 @@ struct rs_frame {
 
 int rs_fail(rs_context* ctx, int code, const char* fmt, ...);
 
+// What loop.hip reads of an rs_map (map.hip: rs_map_loop_sync brings the device image up to date first).
+struct rs_map_loop_view {
+    rs_context* ctx = nullptr;              // the map's context
+    int n_kf = 0, n_points = 0;
+    const uint8_t* d_pool = nullptr;        // [pool rows][32]
+    const float* d_kp_pool = nullptr;       // [pool rows][2]
+    const int32_t* d_kp_point = nullptr;    // [pool rows] point slot of the keypoint or -1
+    const float* d_pos = nullptr;           // [points][3]
+    const float* d_centres = nullptr;       // [key frames][3]
+};
+int rs_map_loop_sync(rs_map* m, rs_map_loop_view* out);
+rs_context* rs_map_context(const rs_map* m);
+// key frame kf of the mirror: keypoints, first pool row, keypoints with a map match; false = no such key frame
+bool rs_map_loop_keyframe(const rs_map* m, int kf, int* n, int* pool_row, int* n_matched);
+
 #define RS_HIP(ctx, call)                                                                  \
     do {                                                                                   \
         hipError_t e__ = (call);                                                           \
@@ -119,6 +135,7 @@ int rs_fail(rs_context* ctx, int code, const char* fmt, ...);
                            hipGetErrorString(e__), __FILE__, __LINE__);                    \
     } while (0)
 
+int rs_k1_reserve(rs_context* ctx, size_t entries);   // hamming.hip: K1's top-2 table for `entries` keys (grow-only)
 // workspace: returns a device pointer with at least `bytes` bytes, 256-B aligned.
 int rs_workspace(rs_context* ctx, size_t bytes, void** out);
 int rs_workspace_quiet(rs_context* ctx, size_t bytes, void** out);   // does not mark the bytes as possibly written (ba.hip keeps its own account)

@@ -178,6 +178,11 @@ extern "C" int rs_context_set_int(rs_context* ctx, const char* name, int value)
         ctx->bow_score_mode = value;
         return RS_OK;
     }
+    if (strcmp(name, "loop_verify_streams") == 0) {
+        if (value < 0 || value > 1) return rs_fail(ctx, RS_ERR_INVALID, "loop_verify_streams must be 0 (one child context per candidate) or 1 (the context stream)");
+        ctx->loop_verify_streams = value;
+        return RS_OK;
+    }
     if (strcmp(name, "gftt_round_launches") == 0) {
         if (value < 0 || value > GFTT_ROUNDS_KNOB) return rs_fail(ctx, RS_ERR_INVALID, "gftt_round_launches must be 0 .. 12 (default 12)");
         ctx->gftt_round_launches = value;

@@ -161,6 +161,21 @@ __global__ __launch_bounds__(1024) void k1_merge_filter(
     if (do_filter && threadIdx.x == 0) match_count[b] = running;
 }
 
+// K1's per-context top-2 table for `entries` (batch x nq) keys: grow-only, all-ones once, and every call leaves it
+// all-ones again.  Growing synchronises the stream.  (loop.hip reserves it at creation so that no call allocates.)
+int rs_k1_reserve(rs_context* ctx, size_t entries)
+{
+    if (entries <= ctx->k1_top_cap) return RS_OK;
+    RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->k1_top) RS_HIP(ctx, hipFree(ctx->k1_top));
+    ctx->k1_top = nullptr; ctx->k1_top_cap = 0;
+    const size_t cap = (entries + 4095) & ~(size_t)4095;
+    if (hipMalloc(&ctx->k1_top, sizeof(uint2) * cap) != hipSuccess) return rs_fail(ctx, RS_ERR_NOMEM, "top-2 table of %zu entries", cap);
+    RS_HIP(ctx, hipMemsetAsync(ctx->k1_top, 0xFF, sizeof(uint2) * cap, ctx->stream));
+    ctx->k1_top_cap = cap;
+    return RS_OK;
+}
+
 static int knn2_launch(rs_context* ctx, const uint8_t* d_query, int nq, const uint8_t* d_train, int nt,
                        int batch, int max_distance, int do_filter, int32_t* mq, int32_t* mt, int32_t* mc,
                        int32_t* i0, int32_t* d0, int32_t* i1, int32_t* d1)
@@ -186,16 +201,8 @@ static int knn2_launch(rs_context* ctx, const uint8_t* d_query, int nq, const ui
     if (nsplit < 1) nsplit = 1;
     const int rows_per_wave = (nt + nsplit * K1_WAVES - 1) / (nsplit * K1_WAVES);
     if ((size_t)nqb * nsplit * batch > 0x7fffffffu) return rs_fail(ctx, RS_ERR_UNSUPPORTED, "too many query blocks for one launch");
-    const size_t need = (size_t)batch * nq;
-    if (need > ctx->k1_top_cap) {        // grow-only; all-ones once, every call leaves it all-ones again
-        RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->k1_top) RS_HIP(ctx, hipFree(ctx->k1_top));
-        ctx->k1_top = nullptr; ctx->k1_top_cap = 0;
-        const size_t cap = (need + 4095) & ~(size_t)4095;
-        if (hipMalloc(&ctx->k1_top, sizeof(uint2) * cap) != hipSuccess) return rs_fail(ctx, RS_ERR_NOMEM, "top-2 table of %zu entries", cap);
-        RS_HIP(ctx, hipMemsetAsync(ctx->k1_top, 0xFF, sizeof(uint2) * cap, ctx->stream));
-        ctx->k1_top_cap = cap;
-    }
+    const int krc = rs_k1_reserve(ctx, (size_t)batch * nq);
+    if (krc) return krc;
     void* ws = ctx->k1_top;
     {
         rs_prof_scope ps(ctx, "K1_hamming_knn2");

@@ -286,3 +286,69 @@ extern "C" int rs_rank_loop_candidates(const double* h_score, const int64_t* h_f
     if (h_rejected_score) *h_rejected_score = rej_score;
     return RS_OK;
 }
+
+// LoopDetector's best_candidate (src/LoopDetector.cpp:267-285), as restated by tests/loop_ref.py
+static size_t loop_best(const rs_loop_result* v, size_t n)
+{
+    size_t best = 0;
+    bool found_verified = false;
+    for (size_t i = 0; i < n; i++)
+        if (v[i].ok && (!found_verified || v[i].inliers > v[best].inliers)) {
+            best = i;
+            found_verified = true;
+        }
+    if (!found_verified)
+        for (size_t i = 1; i < n; i++)
+            if (v[i].inliers > v[best].inliers) best = i;
+    return best;
+}
+
+extern "C" int rs_loop_best_candidate(const rs_loop_result* h_results, int n, int32_t* h_best)
+{
+    if (!h_results || n < 1 || !h_best) return RS_ERR_INVALID;
+    *h_best = (int32_t)loop_best(h_results, (size_t)n);
+    return RS_OK;
+}
+
+// LoopDetector::Impl::update_streak (src/LoopDetector.cpp:375-442; the constants :47-49).  Of its streak the function
+// reads the length and the last hit's indices only; the hit's pose and inlier matches are the chosen candidate's, which the
+// caller holds.
+extern "C" int rs_loop_update_streak(rs_loop_streak* state, int64_t from, const int64_t* h_candidate_index, const rs_loop_result* h_results,
+                                     int n, const int64_t* h_constraint_from, const int64_t* h_constraint_to, int n_constraints,
+                                     int32_t* h_chosen, int32_t* h_new_constraint)
+{
+    const int64_t MIN_LOOP_SEPARATION = 15, MIN_CONSISTENT = 3, CONSISTENCY_WINDOW = 15;
+    if (!state || n < 0 || n_constraints < 0 || !h_chosen || !h_new_constraint || (n > 0 && (!h_candidate_index || !h_results)) ||
+        (n_constraints > 0 && (!h_constraint_from || !h_constraint_to)))
+        return RS_ERR_INVALID;
+    *h_chosen = -1;
+    *h_new_constraint = 0;
+    if (n == 0) { state->length = 0; return RS_OK; }                            // :495-499
+    const size_t seed = loop_best(h_results, (size_t)n);
+    if (!h_results[seed].ok) { state->length = 0; return RS_OK; }               // :381-387
+    size_t chosen = seed;
+    const bool consecutive = state->length > 0 && from == state->last_query + 1;
+    if (consecutive) {
+        size_t continued = (size_t)n;
+        for (size_t i = 0; i < (size_t)n; i++) {
+            const int64_t d = h_candidate_index[i] - state->last_candidate, index_gap = d < 0 ? -d : d;
+            if (!h_results[i].ok || index_gap > CONSISTENCY_WINDOW) continue;
+            if (continued == (size_t)n || h_results[i].inliers > h_results[continued].inliers) continued = i;
+        }
+        if (continued < (size_t)n) chosen = continued;
+        else state->length = 0;
+    } else {
+        state->length = 0;
+    }
+    state->length++;
+    state->last_query = from;
+    state->last_candidate = h_candidate_index[chosen];
+    *h_chosen = (int32_t)chosen;
+    if (state->length < MIN_CONSISTENT) return RS_OK;
+    for (int c = 0; c < n_constraints; c++) {
+        const int64_t a = from - h_constraint_from[c], b = state->last_candidate - h_constraint_to[c];
+        if ((a < 0 ? -a : a) < MIN_LOOP_SEPARATION && (b < 0 ? -b : b) < MIN_LOOP_SEPARATION) return RS_OK;
+    }
+    *h_new_constraint = 1;
+    return RS_OK;
+}

@@ -52,11 +52,14 @@ struct rs_map {
     uint8_t* d_pool = nullptr; uint8_t* d_elig = nullptr; uint8_t* d_flag = nullptr;
     float* d_kp_pool = nullptr;                     // [pool rows][2] keypoints of the key frames, row for row with the descriptor pool
     size_t cap_kp_pool = 0;
+    int32_t* d_kp_point = nullptr;                  // [pool rows] point slot of each key-frame keypoint or -1, row for row with the pool:
+    size_t cap_kp_point = 0, kp_point_rows = 0;     // rewritten after a topology change by rs_map_loop_sync, its only reader's entry
+    bool dirty_kp_point = true;
     int32_t* d_win = nullptr; size_t cap_win = 0;   // scratch of rs_map_bundle_adjust: pid [P] | obs offset [P]
     size_t cap_points = 0, cap_obs = 0, cap_kf = 0, cap_pool_bytes = 0, pool_rows = 0, n_obs = 0;
     // scratch for match results
     int32_t* d_out = nullptr; size_t cap_out = 0;
-    std::vector<int32_t> h_obs_ptr, h_obs_kf, h_obs_desc;
+    std::vector<int32_t> h_obs_ptr, h_obs_kf, h_obs_desc, h_kp_point;
     std::vector<float> h_centres;
 };
 
@@ -96,7 +99,7 @@ extern "C" int rs_map_destroy(rs_map* m)
     (void)hipStreamSynchronize(m->ctx->stream);
     for (void* p : {(void*)m->d_pos, (void*)m->d_alive, (void*)m->d_obs_ptr, (void*)m->d_obs_kf, (void*)m->d_obs_desc,
                     (void*)m->d_centres, (void*)m->d_pool, (void*)m->d_elig, (void*)m->d_flag, (void*)m->d_out, (void*)m->d_kp_pool,
-                    (void*)m->d_win})
+                    (void*)m->d_win, (void*)m->d_kp_point})
         if (p) (void)hipFree(p);
     delete m;
     return RS_OK;
@@ -225,7 +228,7 @@ extern "C" int rs_map_remove_observation(rs_map* m, int point, int kf)
             auto& tab = m->kfs[(size_t)kf].kp_point;
             if (tab[(size_t)v[i].kp] == point) tab[(size_t)v[i].kp] = -1;
             v.erase(v.begin() + (long)i);
-            m->dirty_topology = true;
+            m->dirty_topology = m->dirty_kp_point = true;
             return RS_OK;
         }
     return RS_OK;       // MapPoint::remove_observation of an absent key frame is a no-op (src/Map.cpp:117-124)
@@ -247,7 +250,7 @@ extern "C" int rs_map_add_observation(rs_map* m, int point, int kf, int keypoint
     if (seen) rs_map_remove_observation(m, point, kf);                    // :107-109
     v.push_back({kf, keypoint});
     k.kp_point[(size_t)keypoint] = point;
-    m->dirty_topology = true;
+    m->dirty_topology = m->dirty_kp_point = true;
     return RS_OK;
 }
 
@@ -262,7 +265,7 @@ extern "C" int rs_map_remove_point(rs_map* m, int point)
     m->obs[(size_t)point].shrink_to_fit();
     m->alive[(size_t)point] = 0;
     m->n_alive--;
-    m->dirty_topology = true;
+    m->dirty_topology = m->dirty_kp_point = true;
     return RS_OK;
 }
 
@@ -349,6 +352,43 @@ static int map_sync_device(rs_map* m)
     if (m->dirty_topology || m->dirty_positions || m->dirty_centres) RS_HIP(ctx, hipStreamSynchronize(s));
     m->dirty_topology = m->dirty_positions = m->dirty_centres = false;
     return RS_OK;
+}
+
+// loop.hip's window into the map: the device image brought up to date, and a key frame of the mirror
+int rs_map_loop_sync(rs_map* m, rs_map_loop_view* out)
+{
+    int rc = map_sync_device(m);
+    if (rc) return rc;
+    // d_kp_point follows the topology, but only here: the other users of the device image never read it and pay nothing
+    if (m->dirty_kp_point || m->kp_point_rows != m->pool_rows) {         // (a new key frame adds rows of -1)
+        rs_context* ctx = m->ctx;
+        m->h_kp_point.clear();
+        for (const auto& k : m->kfs) m->h_kp_point.insert(m->h_kp_point.end(), k.kp_point.begin(), k.kp_point.end());
+        size_t ck = m->cap_kp_point;
+        rc = grow(ctx, &m->d_kp_point, &ck, m->pool_rows ? m->pool_rows : 1, 0);
+        if (rc) return rc;
+        m->cap_kp_point = ck;
+        if (m->pool_rows) {             // pageable source: complete before returning
+            RS_HIP(ctx, hipMemcpyAsync(m->d_kp_point, m->h_kp_point.data(), sizeof(int32_t) * m->pool_rows, hipMemcpyHostToDevice, ctx->stream));
+            RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        m->kp_point_rows = m->pool_rows;
+        m->dirty_kp_point = false;
+    }
+    *out = rs_map_loop_view{m->ctx, (int)m->kfs.size(), (int)m->alive.size(), m->d_pool, m->d_kp_pool, m->d_kp_point, m->d_pos, m->d_centres};
+    return RS_OK;
+}
+
+rs_context* rs_map_context(const rs_map* m) { return m->ctx; }
+
+bool rs_map_loop_keyframe(const rs_map* m, int kf, int* n, int* pool_row, int* n_matched)
+{
+    if (kf < 0 || kf >= (int)m->kfs.size()) return false;
+    const MapKeyFrame& k = m->kfs[(size_t)kf];
+    int c = 0;
+    for (const int32_t p : k.kp_point) c += p >= 0 ? 1 : 0;
+    *n = k.n; *pool_row = k.pool_row; *n_matched = c;
+    return true;
 }
 
 // per-call eligibility (src/MapMatcher.cpp:53, :169): alive, not already matched by the frame, and — for

@@ -1087,4 +1087,99 @@ std::vector<LoopCandidate> LoopRetrieval::query()
     return out;
 }
 
+// ------------------------------------------------------------------------ loop verification
+LoopVerifier::LoopVerifier(int max_points, int max_candidates) : m_max_points(max_points)
+{
+    if (!rs_ok(rs_loop_verifier_create(Session::get().ctx(), max_points, max_candidates, 200, &m_verifier), "rs_loop_verifier_create")) return;
+    m_result.resize((size_t)max_candidates);
+    for (auto& l : m_listed) l.resize((size_t)max_candidates * (size_t)max_points);
+}
+
+LoopVerifier::~LoopVerifier() { rs_loop_verifier_destroy(m_verifier); }
+
+std::vector<LoopVerification> LoopVerifier::verify(rs_map* map, int query_kf, const std::vector<int32_t>& candidates, const Camera& camera)
+{
+    std::vector<LoopVerification> out;
+    if (!valid() || candidates.empty() || candidates.size() > m_result.size()) return out;
+    const float K[4] = {camera.fx(), camera.fy(), camera.cx(), camera.cy()};
+    // MapMatcher's max_distance 64; PNP_REPROJ_ERROR 4 px, 0.99, 200 iterations (:38, :203-214)
+    if (!rs_ok(rs_map_verify_loop(Session::get().ctx(), m_verifier, map, query_kf, candidates.data(), (int)candidates.size(), K,
+                                  camera.get_width(), 64, 4.0, 0.99, 200, 0, m_result.data(), m_listed[0].data(), m_listed[1].data(),
+                                  m_listed[2].data()),
+               "rs_map_verify_loop"))
+        return out;
+    out.resize(candidates.size());
+    for (size_t c = 0; c < candidates.size(); c++) {
+        out[c].result = m_result[c];
+        const size_t o = c * (size_t)m_max_points, n = (size_t)m_result[c].listed;
+        out[c].query_kp.assign(m_listed[0].begin() + (long)o, m_listed[0].begin() + (long)(o + n));
+        out[c].point.assign(m_listed[1].begin() + (long)o, m_listed[1].begin() + (long)(o + n));
+        out[c].candidate_kp.assign(m_listed[2].begin() + (long)o, m_listed[2].begin() + (long)(o + n));
+    }
+    return out;
+}
+
+// inverse of an affine 4 x 4 (last row 0 0 0 1) in f64 by the cofactors of its 3 x 3 block
+static bool affine_inverse(const double* T, double* out)
+{
+    const double a = T[0], b = T[1], c = T[2], d = T[4], e = T[5], f = T[6], g = T[8], h = T[9], i = T[10];
+    const double A = e * i - f * h, B = -(d * i - f * g), C = d * h - e * g;
+    const double det = a * A + b * B + c * C;
+    if (det == 0.0) return false;
+    const double inv[9] = {A / det, -(b * i - c * h) / det, (b * f - c * e) / det,
+                           B / det, (a * i - c * g) / det,  -(a * f - c * d) / det,
+                           C / det, -(a * h - b * g) / det, (a * e - b * d) / det};
+    for (int r = 0; r < 3; r++) {
+        for (int k = 0; k < 3; k++) out[4 * r + k] = inv[3 * r + k];
+        out[4 * r + 3] = -(inv[3 * r] * T[3] + inv[3 * r + 1] * T[7] + inv[3 * r + 2] * T[11]);
+    }
+    out[12] = out[13] = out[14] = 0.0;
+    out[15] = 1.0;
+    return true;
+}
+
+int LoopStreak::update(size_t from, const std::vector<LoopCandidate>& ranked, const std::vector<LoopVerification>& verifications,
+                       const std::vector<Mat4f>& candidate_poses)
+{
+    if (ranked.size() != verifications.size() || ranked.size() != candidate_poses.size()) return -1;
+    std::vector<int64_t> index, cfrom, cto;
+    std::vector<rs_loop_result> results;
+    for (size_t i = 0; i < ranked.size(); i++) { index.push_back((int64_t)ranked[i].entry); results.push_back(verifications[i].result); }
+    for (const auto& c : m_constraints) { cfrom.push_back((int64_t)c.from); cto.push_back((int64_t)c.to); }
+    int32_t chosen = -1, is_new = 0;
+    if (rs_loop_update_streak(&m_state, (int64_t)from, index.data(), results.data(), (int)ranked.size(), cfrom.data(), cto.data(),
+                              (int)cfrom.size(), &chosen, &is_new) != RS_OK)
+        return -1;
+    if (!is_new) return chosen;
+    const LoopVerification& v = verifications[(size_t)chosen];
+    LoopConstraint c;
+    c.from = from;
+    c.to = ranked[(size_t)chosen].entry;
+    double P[16], Q[16], Qi[16];
+    for (int k = 0; k < 16; k++) { P[k] = (double)v.result.pose[k]; Q[k] = (double)candidate_poses[(size_t)chosen][(size_t)k]; }
+    if (!affine_inverse(Q, Qi)) {                  // a singular candidate pose: no constraint can be formed, the streak starts over
+        std::printf("Loop constraint kf %zu -> %zu dropped: the candidate's pose is singular\n", c.from, c.to);
+        m_state.length = 0;
+        return -1;
+    }
+    for (int r = 0; r < 4; r++)
+        for (int k = 0; k < 4; k++) {
+            double s = 0.0;
+            for (int j = 0; j < 4; j++) s += P[4 * r + j] * Qi[4 * j + k];
+            c.relative[(size_t)(4 * r + k)] = s;                                                   // :437
+        }
+    for (size_t k = 0; k < v.query_kp.size(); k++) c.inlier_matches.emplace_back(v.query_kp[k], v.point[k]);
+    std::printf("Loop constraint kf %zu -> %zu inliers %zu\n", c.from, c.to, c.inlier_matches.size());      // :439-440
+    m_constraints.push_back(std::move(c));
+    m_new_loop = true;
+    return chosen;
+}
+
+bool LoopStreak::consume_new_loop()
+{
+    const bool added = m_new_loop;
+    m_new_loop = false;
+    return added;
+}
+
 }  // namespace slam

@@ -327,7 +327,7 @@ PnpEstimate estimate_pose_pnp(const std::vector<Vec3f>& object_points, const std
 // rank_candidates) on the device, as specified by tests/bow_ref.py: the DBoW2 vocabulary, one rs_bow and the database of
 // the key frames' vectors.  Where the reference computes bow_of lazily per candidate (:351-353, :366-368), every key
 // frame is transformed and added once, when it arrives; a query is one rs_bow_database_score call, one read-back of the
-// scores and rs_rank_loop_candidates with the reference's constants (:28-32).  update_streak stays with the caller.
+// scores and rs_rank_loop_candidates with the reference's constants (:28-32).  LoopVerifier and LoopStreak below take it from there.
 struct LoopCandidate {
     size_t entry = 0;                            // index of the key frame in arrival order (Candidate::index)
     float score = 0.0f;
@@ -357,6 +357,53 @@ class LoopRetrieval {
     std::vector<int64_t> m_frame_index;
     std::vector<double> m_score;
     float m_seconds_per_frame = 0.0f;
+};
+
+// LoopDetector::query's "Loop verify" stage (src/LoopDetector.cpp:501-506, verify_pnp :176-229) against the resident map,
+// as specified by tests/loop_ref.py: ONE C-ABI call (rs_map_verify_loop) and one read-back per query for all candidates.
+struct LoopVerification {
+    rs_loop_result result{};                     // status, ok, correspondences, inliers, spread, drift, gap, pose
+    std::vector<int32_t> query_kp, point, candidate_kp;      // the listed correspondences (inlier_matches when status is 0)
+};
+class LoopVerifier {
+  public:
+    // up to max_points keypoints per key frame and max_candidates (<= 8) candidates per query; 200 hypotheses, seed 0
+    explicit LoopVerifier(int max_points = 8192, int max_candidates = 3);
+    ~LoopVerifier();
+    LoopVerifier(const LoopVerifier&) = delete;
+    LoopVerifier& operator=(const LoopVerifier&) = delete;
+    bool valid() const { return m_verifier != nullptr; }
+    // query_kf and candidates are key frames of `map`; empty on failure (logged) or when there is no candidate
+    std::vector<LoopVerification> verify(rs_map* map, int query_kf, const std::vector<int32_t>& candidates, const Camera& camera);
+
+  private:
+    rs_loop_verifier* m_verifier = nullptr;
+    int m_max_points = 0;
+    std::vector<rs_loop_result> m_result;
+    std::vector<int32_t> m_listed[3];
+};
+
+// What LoopDetector::Impl keeps between queries (:324-325, :336) and update_streak (:375-442), over rs_loop_update_streak.
+struct LoopConstraint {                          // optimization::PoseGraphConstraint
+    size_t from = 0, to = 0;
+    std::array<double, 16> relative{};           // row-major pose(query) * inverse(pose(candidate)), f64
+    std::vector<std::pair<int32_t, int32_t>> inlier_matches;     // (query keypoint, point slot)
+};
+class LoopStreak {
+  public:
+    // one query: `from` = the query's index among the key frames; ranked[i] verified as verifications[i]; candidate_poses[i]
+    // the candidate's pose in the map.  Nothing ranked clears the streak.  Returns the chosen candidate or -1.  A constraint
+    // whose candidate pose has no inverse is dropped and the streak cleared (-1).
+    int update(size_t from, const std::vector<LoopCandidate>& ranked, const std::vector<LoopVerification>& verifications,
+               const std::vector<Mat4f>& candidate_poses);
+    bool consume_new_loop();
+    const std::vector<LoopConstraint>& constraints() const { return m_constraints; }
+    size_t streak_length() const { return (size_t)m_state.length; }
+
+  private:
+    rs_loop_streak m_state{};
+    std::vector<LoopConstraint> m_constraints;
+    bool m_new_loop = false;
 };
 
 }  // namespace slam

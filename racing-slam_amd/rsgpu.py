@@ -33,6 +33,8 @@ EXPORTS = [
     "rs_bow_create", "rs_bow_destroy", "rs_bow_transform", "rs_bow_download",
     "rs_bow_database_create", "rs_bow_database_destroy", "rs_bow_database_add", "rs_bow_database_score", "rs_bow_database_counts",
     "rs_rank_loop_candidates",
+    "rs_loop_verifier_create", "rs_loop_verifier_destroy", "rs_map_verify_loop", "rs_loop_verifier_download",
+    "rs_loop_best_candidate", "rs_loop_update_streak",
     "rs_comm_get_unique_id", "rs_comm_init_rank", "rs_comm_destroy", "rs_comm_init_local", "rs_comm_count", "rs_prof_begin", "rs_prof_end", "rs_prof_counters", "rs_prof_empty_launch",
 ]
 
@@ -291,6 +293,73 @@ def rank_loop_candidates(scores, frame_index, query_frame_index, seconds_per_fra
         raise RsError(f"rs_rank_loop_candidates -> {rc}")
     n = int(cnt[0])
     return dict(entries=oe[:n].copy(), scores=os_[:n].copy(), rejected=None if re_[0] < 0 else (int(re_[0]), rs_[0]))
+
+
+class LoopResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("ok", C.c_int32), ("correspondences", C.c_int32), ("inliers", C.c_int32),
+                ("listed", C.c_int32), ("spread", C.c_float), ("drift", C.c_float), ("gap", C.c_float), ("pose", C.c_float * 16)]
+
+
+class LoopStreakState(C.Structure):
+    _fields_ = [("length", C.c_int32), ("last_query", C.c_int64), ("last_candidate", C.c_int64)]
+
+
+def _loop_results(verifications):
+    arr = (LoopResult * max(len(verifications), 1))()
+    for r, v in zip(arr, verifications):
+        r.ok, r.inliers = int(bool(v["ok"])), int(v["inliers"])
+    return arr
+
+
+def loop_best_candidate(verifications):
+    """rs_loop_best_candidate (host): LoopDetector's best_candidate over dicts with ok and inliers."""
+    best = C.c_int32(-1)
+    rc = load().rs_loop_best_candidate(_loop_results(verifications), len(verifications), C.byref(best))
+    if rc:
+        raise RsError(f"rs_loop_best_candidate -> {rc}")
+    return best.value
+
+
+def loop_update_streak(state, frm, candidate_index, verifications, constraints=()):
+    """rs_loop_update_streak (host): one query of LoopDetector's update_streak.  state: a LoopStreakState (updated in
+    place); candidate_index [n] the ranked candidates' key-frame indices; verifications [n] dicts with ok and inliers;
+    constraints: (from, to) pairs so far.  Returns (chosen or -1, new_constraint bool)."""
+    ci = np.ascontiguousarray(candidate_index, np.int64)
+    cf = np.ascontiguousarray([c[0] for c in constraints], np.int64)
+    ct = np.ascontiguousarray([c[1] for c in constraints], np.int64)
+    assert len(ci) == len(verifications)
+    chosen, new = C.c_int32(-1), C.c_int32(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)         # noqa: E731
+    rc = load().rs_loop_update_streak(C.byref(state), C.c_int64(int(frm)), vp(ci), _loop_results(verifications), len(ci), vp(cf),
+                                      vp(ct), len(cf), C.byref(chosen), C.byref(new))
+    if rc:
+        raise RsError(f"rs_loop_update_streak -> {rc}")
+    return chosen.value, bool(new.value)
+
+
+class LoopStreak:
+    """The streak and the constraints of LoopDetector::Impl over rs_loop_update_streak (the Python form of
+    slam::LoopStreak): update() per query, consume_new_loop() and constraints as the reference exposes them.  A constraint
+    is dict(from, to, relative [4][4] f64 = pose * inverse(candidate pose), pairs [k][2] (query keypoint, point slot))."""
+
+    def __init__(self):
+        self.state, self.constraints, self._new = LoopStreakState(0, 0, 0), [], False
+
+    def update(self, frm, candidate_index, verifications, candidate_poses):
+        chosen, new = loop_update_streak(self.state, frm, candidate_index, verifications,
+                                         [(c["from"], c["to"]) for c in self.constraints])
+        if new:
+            v = verifications[chosen]
+            inv = np.linalg.inv(np.asarray(candidate_poses[chosen], np.float64).reshape(4, 4))
+            self.constraints.append({"from": int(frm), "to": int(candidate_index[chosen]),
+                                     "relative": np.asarray(v["pose"], np.float64).reshape(4, 4) @ inv,
+                                     "pairs": np.stack([v["query_kp"], v["point"]], 1)})
+            self._new = True
+        return chosen
+
+    def consume_new_loop(self):
+        added, self._new = self._new, False
+        return added
 
 
 # ---- GPU context -------------------------------------------------------------
@@ -859,6 +928,11 @@ class Context:
     def bow_database(self, voc, max_entries, max_total_words):
         return BowDatabase(self, voc, max_entries, max_total_words)
 
+    # -- loop verification (LoopDetector's "Loop verify")
+    def loop_verifier(self, max_points=8192, max_candidates=3, max_hypotheses=200):
+        """rs_loop_verifier: every buffer of max_candidates verify_pnp chains (allocated once, reused)."""
+        return LoopVerifier(self, max_points, max_candidates, max_hypotheses)
+
     def synchronize(self):
         self._check(self.lib.rs_context_synchronize(self.h), "rs_context_synchronize")
 
@@ -1114,6 +1188,64 @@ class BowDatabase:
     def close(self):
         if self.h:
             self.ctx.lib.rs_bow_database_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+class LoopVerifier:
+    """rs_loop_verifier: verify_pnp of a query key frame against ranked candidates, all key frames of a ResidentMap."""
+
+    def __init__(self, ctx, max_points=8192, max_candidates=3, max_hypotheses=200):
+        self.ctx, self.max_points, self.max_candidates = ctx, int(max_points), int(max_candidates)
+        self.max_hypotheses = int(max_hypotheses)
+        self.h = C.c_void_p()
+        ctx._check(ctx.lib.rs_loop_verifier_create(ctx.h, self.max_points, self.max_candidates, self.max_hypotheses, C.byref(self.h)),
+                   "rs_loop_verifier_create")
+        n = max(self.max_candidates, 1)
+        self._res = (LoopResult * n)()
+        self._listed = [np.zeros((n, self.max_points), np.int32) for _ in range(3)]
+
+    def verify(self, map_, query_kf, candidates, K, width, max_distance=64, threshold_px=4.0, confidence=0.99, max_hypotheses=200,
+               seed=0):
+        """rs_map_verify_loop: one dict per candidate — status, ok, correspondences, inliers, listed, spread, drift, gap
+        (f32), pose [4][4] f32 and the listed correspondences query_kp / point / candidate_kp [listed] i32."""
+        cand = np.ascontiguousarray(candidates, np.int32)
+        n = len(cand)
+        if n > self.max_candidates:                      # (the library refuses it: ask it with buffers that hold the answer)
+            res, listed = (LoopResult * n)(), [np.zeros((n, self.max_points), np.int32) for _ in range(3)]
+        else:
+            res, listed = self._res, self._listed
+        Kc = (C.c_float * 4)(*[float(v) for v in K])
+        self.ctx._check(self.ctx.lib.rs_map_verify_loop(
+            self.ctx.h, self.h, map_.h, int(query_kf), cand.ctypes.data_as(C.c_void_p), n, Kc, int(width), int(max_distance),
+            C.c_double(threshold_px), C.c_double(confidence), int(max_hypotheses), C.c_uint64(int(seed) & (2 ** 64 - 1)), res,
+            *[a.ctypes.data_as(C.c_void_p) for a in listed]), "rs_map_verify_loop")
+        out = []
+        for c in range(n):
+            r, k = res[c], res[c].listed
+            out.append(dict(status=r.status, ok=bool(r.ok), correspondences=r.correspondences, inliers=r.inliers, listed=k,
+                            spread=np.float32(r.spread), drift=np.float32(r.drift), gap=np.float32(r.gap),
+                            pose=np.array(r.pose, np.float32).reshape(4, 4), query_kp=listed[0][c, :k].copy(),
+                            point=listed[1][c, :k].copy(), candidate_kp=listed[2][c, :k].copy()))
+        return out
+
+    def download(self, candidate):
+        """rs_loop_verifier_download (synchronises): chain `candidate` of the last call — dict(nt, rows [nt][32] u8, slots,
+        keypoints [nt] i32, positions [nt][3] f32, match_query, match_train [count] i32, inlier_index [inliers] i32)."""
+        m = self.max_points
+        rows, pos = np.zeros((m, 32), np.uint8), np.zeros((m, 3), np.float32)
+        slots, kps, mq, mt, ii = (np.zeros(m, np.int32) for _ in range(5))
+        nt, cnt, inl = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)         # noqa: E731
+        self.ctx._check(self.ctx.lib.rs_loop_verifier_download(self.ctx.h, self.h, int(candidate), C.byref(nt), vp(rows), vp(slots),
+                                                               vp(kps), vp(pos), vp(mq), vp(mt), C.byref(cnt), vp(ii), C.byref(inl)),
+                        "rs_loop_verifier_download")
+        return dict(nt=nt.value, rows=rows[:nt.value].copy(), slots=slots[:nt.value].copy(), keypoints=kps[:nt.value].copy(),
+                    positions=pos[:nt.value].copy(), match_query=mq[:cnt.value].copy(), match_train=mt[:cnt.value].copy(),
+                    inlier_index=ii[:inl.value].copy())
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.rs_loop_verifier_destroy(self.h)
             self.h = C.c_void_p()
 
 

@@ -841,3 +841,78 @@ def make_bow_descriptors(voc, n, seed=0, noise=0.04, equidistant_fraction=0.1):
         bits_a[take] = bits_b[take]
         rows[r] = np.packbits(bits_a)
     return np.ascontiguousarray(rows)
+
+
+def loop_scene(seed=0, nq=300, candidates=((400, 200, 80, 0.3, None),), width=1280, height=720, drift=(0.03, 0.3), flip=0.03):
+    """A query key frame and candidate key frames of one map, for LoopDetector's "Loop verify" stage (verify_pnp).
+    candidates: one (n, matched, shared, outlier_frac, strip) per candidate key frame — n keypoints, `matched` of them
+    (a random subset, point slots in random order) observe a map point, `shared` of those points are also seen by the
+    query: a query keypoint carries the candidate's row with a fraction `flip` of its bits flipped and lies at the point's
+    projection under the query's TRUE pose plus 0.5 px noise, except a fraction outlier_frac of the shared ones, which lie
+    anywhere in the image (wrong matches).  strip = (x0, x1) as fractions of the width confines the correctly placed ones
+    to that band.  All other rows are random, so they match nothing.  The candidates' shared query keypoints are disjoint
+    (their sum must not exceed nq).  The query's pose in the map is the true one turned by drift[0] rad and moved by
+    drift[1] m; a candidate's pose is the true one moved by a few decimetres.
+    Returns dict(K, width, height, points [P][3] f32, key_frames: list of dict(kp [n][2] f32, desc [n][32] u8, pose [4][4]
+    f32, kp_point [n] i32) with the query LAST, observations [(point, key frame, keypoint)] in the order to add them,
+    query = its index, true_pose [4][4] f64, shared: per candidate (query keypoints, candidate keypoints, placed bool))."""
+    rng = np.random.default_rng([0x100B, int(seed)])
+    K = np.array([700.0, 700.0, width / 2.0, height / 2.0], np.float32)
+    fx, fy, cx, cy = (float(k) for k in K)
+    R = rodrigues(np.array([0.1, -0.2, 0.05]) + rng.normal(0, 0.05, 3))
+    t = np.array([0.4, -0.2, 1.5]) + rng.normal(0, 0.2, 3)
+    true_pose = np.eye(4)
+    true_pose[:3, :3], true_pose[:3, 3] = R, t
+
+    def moved(rot, trans):
+        axis = rng.normal(0, 1, 3)
+        dR = rodrigues(rot * axis / np.linalg.norm(axis))
+        step = rng.normal(0, 1, 3)
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = dR @ R, dR @ t + trans * step / np.linalg.norm(step)
+        return T.astype(np.float32)
+
+    def world_points(u):
+        ray = np.stack([(u[:, 0] - cx) / fx, (u[:, 1] - cy) / fy, np.ones(len(u))], 1)
+        Xc = ray * rng.uniform(4.0, 40.0, len(u))[:, None]
+        return ((Xc - t) @ R).astype(np.float32)
+
+    def anywhere(n):
+        return np.stack([rng.uniform(0, width, n), rng.uniform(0, height, n)], 1)
+
+    assert sum(c[2] for c in candidates) <= nq
+    q_kp, q_desc = anywhere(nq), random_descriptors(rng, nq)
+    q_free = rng.permutation(nq)
+    points, key_frames, observations, shared_out = [], [], [], []
+    n_points = 0
+    for kf, (n, matched, shared, outlier_frac, strip) in enumerate(candidates):
+        assert shared <= matched <= n
+        kp, desc = anywhere(n), random_descriptors(rng, n)
+        kps = np.sort(rng.choice(n, matched, replace=False)) if matched else np.zeros(0, np.int64)
+        x0, x1 = strip if strip is not None else (0.02, 0.98)
+        u = np.stack([rng.uniform(x0 * width, x1 * width, matched), rng.uniform(0.02 * height, 0.98 * height, matched)], 1)
+        X = world_points(u)
+        slots = n_points + rng.permutation(matched)              # keypoint kps[i] observes point slots[i]
+        xyz = np.zeros((matched, 3), np.float32)
+        xyz[slots - n_points] = X
+        points.append(xyz)
+        kp_point = np.full(n, -1, np.int32)
+        kp_point[kps] = slots
+        for i in rng.permutation(matched):
+            observations.append((int(slots[i]), kf, int(kps[i])))
+        # the shared ones in the query
+        sh = rng.permutation(matched)[:shared]
+        qk, q_free = q_free[:shared], q_free[shared:]
+        Xf = X[sh].astype(np.float64) @ R.T + t
+        pix = np.stack([fx * Xf[:, 0] / Xf[:, 2] + cx, fy * Xf[:, 1] / Xf[:, 2] + cy], 1) + rng.normal(0, 0.5, (shared, 2))
+        placed = rng.random(shared) >= outlier_frac
+        pix[~placed] = anywhere(int((~placed).sum()))
+        q_kp[qk] = pix
+        q_desc[qk] = flip_bits(rng, desc[kps[sh]], flip)
+        shared_out.append((qk.astype(np.int32), kps[sh].astype(np.int32), placed))
+        key_frames.append(dict(kp=kp.astype(np.float32), desc=desc, pose=moved(0.02, 0.3), kp_point=kp_point))
+        n_points += matched
+    key_frames.append(dict(kp=q_kp.astype(np.float32), desc=q_desc, pose=moved(*drift), kp_point=np.full(nq, -1, np.int32)))
+    pts = np.concatenate(points) if points else np.zeros((0, 3), np.float32)
+    return dict(K=K, width=width, height=height, points=pts, key_frames=key_frames, observations=observations,
+                query=len(key_frames) - 1, true_pose=true_pose, shared=shared_out)
