@@ -330,6 +330,44 @@ int rs_map_match(rs_context* ctx, rs_map* map, rs_frame* frame, const float h_po
                  int required_observer_kf, const int32_t* h_only_points, int n_only, int replace, int max_distance,
                  int32_t* h_match_kp, int32_t* h_match_point, int* h_count);
 
+/* ---- the tail of Tracker::track on the resident map (src/Tracker.cpp:83-86): carry-over, pose refit, two matches.
+ * An rs_frame of either kind owns the frame's match table, Frame::m_map_matches: keypoint -> point slot or -1 (a frame
+ * from rs_frame_create_device: room for max_points; rs_frame_assign_device clears it for the new contents).  The calls
+ * below read and write it on the device; none walks map objects on the host and none moves a list.  Envelope: frames of
+ * at most 8192 keypoints and lists of at most 8192 entries (RS_ERR_UNSUPPORTED beyond), replace = 0 matching only
+ * (match_for_fuse stays on rs_map_match).  A table may hold the slot of a point that was removed since (the reference:
+ * a dangling pointer, undefined behaviour).  Here such a slot still counts as a match of its keypoint
+ * (Frame::is_matched, Frame::num_map_matches) but is never a carry-over candidate and never enters the refit.
+ * What still synchronises: the refit's completion flag, one count per match, rs_frame_assign_device's 4-byte n (and the
+ * map's lazy upload after an edit, as everywhere). */
+int rs_frame_matches_clear(rs_context* ctx, rs_frame* frame);
+/* Frame::add_map_match (src/Frame.cpp:80-102) for a list, applied in LIST ORDER: entry i sets table[d_kp[i]] =
+ * d_point[i] and clears any OTHER keypoint holding d_point[i]; repeated keypoints and repeated points resolve as the
+ * sequential rule does (the last writer of a keypoint wins, a point lives at its last keypoint).  The count is read on
+ * the device: n = clamp(d_count[0], 0, max_n), or max_n when d_count is NULL.  Entries with a keypoint outside the frame
+ * or a negative point are skipped.  Stream-ordered, no host synchronisation. */
+int rs_frame_matches_add(rs_context* ctx, rs_frame* frame, const int32_t* d_kp, const int32_t* d_point, const int32_t* d_count, int max_n);
+/* Diagnostic (synchronises): h_kp_point [n] (NULL = not wanted), *h_count = Frame::num_map_matches(). */
+int rs_frame_matches_download(rs_context* ctx, const rs_frame* frame, int32_t* h_kp_point, int* h_count);
+
+int rs_map_set_track_consistent(rs_map* map, int point);      /* MapPoint::set_track_consistent; host O(1), the device flag follows lazily */
+/* Tracker::track_from_last_frame (:197-230).  List entry i names keypoint j = d_inlier_index[i] of `next` (rs_estimate_pose's
+ * inlier list: positions into the tracked list, which are next's first keypoints; NULL: j = i) and keypoint
+ * d_prev_index[j] of `prev` (rs_track_features' d_kept_index).  n = clamp(d_count[0], 0, max_n) (NULL: max_n); both index
+ * lists hold at least max_n entries, and an entry whose j is outside [0, min(max_n, next's n)) or whose previous keypoint
+ * is outside prev is skipped.  An entry is a candidate when prev's table holds a point there that is alive and has >= 2
+ * observations or is track-consistent (:209).  Fewer than min_points candidates (MIN_TRACKED_MAP_POINTS = 15): nothing is
+ * written (:216-219).  Otherwise candidates are accepted in list order unless next already matches that keypoint or that
+ * point (:223).  d_stats [2] (device, NULL = not wanted): candidates, accepted.  Stream-ordered, no host synchronisation. */
+int rs_map_carry_matches(rs_context* ctx, rs_map* map, const rs_frame* prev, rs_frame* next, const int32_t* d_prev_index,
+                         const int32_t* d_inlier_index, const int32_t* d_count, int max_n, int min_points, int32_t* d_stats);
+/* (rs_map_refine_pose, Tracker::optimize_pose on the table: behind rs_refine_pose_inertial below) */
+/* match_with_last_key_frame / match_with_map (:232-248): rs_map_match with replace = 0 whose "already matched" keypoints
+ * and points are the frame's table, and whose accepted pairs go back into it (they are disjoint from it and unique on
+ * both sides: a scatter).  Only *h_count comes back.  The map's flag table is all-zero again afterwards. */
+int rs_map_match_frame(rs_context* ctx, rs_map* map, rs_frame* frame, const float h_pose[16], const float h_intrinsics[4],
+                       int width, int height, int required_observer_kf, int max_distance, int* h_count);
+
 /* (rs_map_bundle_adjust: see the optimisation section below) */
 
 /* ------------------------------------------------------ a5-a7: triangulation */
@@ -680,6 +718,20 @@ int rs_refine_pose_inertial(rs_context* ctx, double h_camera[6],
                             const double h_prev_pose[6], const double h_prev_velocity[3], const double h_prev_bias[6],
                             const rs_imu_factor* h_delta, const double h_gravity[3], double h_velocity[3],
                             const rs_ba_options* options, rs_ba_summary* h_summary);
+
+/* Tracker::optimize_pose -> optimization::refine_pose on the frame's table: a gather kernel walks it in ascending
+ * keypoint order (Frame::map_matches()), keeps the entries whose point is alive with >= 2 observations
+ * (MIN_OBSERVATIONS_TO_OPTIMIZE) and writes their positions (f32 widened to f64) and pixels; K11 runs on those arrays
+ * with the count read on the device — the result is bit for bit rs_refine_pose_inertial's on the same arrays.  The gates
+ * are evaluated on the device: fewer than min_matches table entries (:307, before the observation filter) or none kept
+ * -> no solve, h_camera untouched, zeroed summary (usable = 0); *h_n_used = the number of observations, or -1 for the
+ * first gate.  The constraint arguments are rs_refine_pose_inertial's.  Two launches, one wait on the completion flag.
+ * motion::is_rotation_plausible (:314) stays the caller's. */
+int rs_map_refine_pose(rs_context* ctx, rs_map* map, const rs_frame* frame, double h_camera[6], const float h_intrinsics[4],
+                       int min_matches, int kind, const double h_predicted[9], double sigma_radians,
+                       const double h_prev_pose[6], const double h_prev_velocity[3], const double h_prev_bias[6],
+                       const rs_imu_factor* h_delta, const double h_gravity[3], double h_velocity[3],
+                       const rs_ba_options* options, rs_ba_summary* h_summary, int* h_n_used);
 
 /* ------------------------------------------------------------------ a14: pose graph
  * optimization::pose_graph (src/Optimization.cpp:540-639), called once per detected loop (src/Slam.cpp:258-268).

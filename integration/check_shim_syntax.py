@@ -173,14 +173,56 @@ class ORB : public Feature2D { public: static Ptr<ORB> create(); };
 """
 
 
+# Tracker_track_tail.inc spliced into a skeleton of Tracker::track (kept head :72-82 reduced to the frame it builds, kept
+# tail :87), with the names the caller that owns the resident map supplies declared as locals.
+TRACK_TAIL_HARNESS = r"""
+#include <iostream>
+#include "Tracker.h"
+#include "Frame.h"
+#include "MapPoint.h"
+#include "MotionModel.h"
+#include "Slam.h"
+#include "features/FeatureExtractor.h"
+#include "rs_shim_common.h"
+namespace slam {
+namespace {
+constexpr size_t MIN_TRACKED_MAP_POINTS = 15;
+}
+std::shared_ptr<Frame> Tracker::track(const cv::Mat& image, size_t frame_index, const Trajectory& trajectory, KeyFrame& last_key_frame,
+                                      size_t num_key_frames)
+{
+    m_last_key_frame = &last_key_frame;
+    ExtractedFeatures features;
+    auto frame = std::make_shared<Frame>(frame_index, image, features);
+    rs_map* resident_map = nullptr;
+    std::vector<MapPoint*> resident_points;
+    rs_frame* resident_prev = nullptr;
+    rs_frame* resident_next = nullptr;
+    const int32_t* resident_kept_index = nullptr;
+    const int32_t* resident_inlier_index = nullptr;
+    const int32_t* resident_inlier_count = nullptr;
+    int resident_max_n = 0, resident_last_key_frame = 0;
+#include "Tracker_track_tail.inc"
+    return frame;
+}
+}  // namespace slam
+"""
+# Slam.h (for SlamConfig) pulls in VideoLoader.h, which holds a cv::VideoCapture by value
+TRACK_TAIL_STUB_FREE = """
+namespace cv {
+class VideoCapture {};
+}  // namespace cv
+"""
+
+
 def tracker_stubs(dst):
-    """tests/shim_stubs/ copied to dst with the declarations the Tracker block needs added to opencv2/core.hpp"""
+    """tests/shim_stubs/ copied to dst with the declarations the Tracker blocks need added to opencv2/core.hpp"""
     src = os.path.join(ROOT, "tests", "shim_stubs")
     shutil.copytree(src, dst)
     core = os.path.join(dst, "opencv2", "core.hpp")
     text = open(core).read()
     head, tail = text.split("    Mat clone() const;\n", 1)
-    text = head + "    Mat clone() const;\n" + TRACKER_STUB_EXTRA + REPLENISH_STUB_EXTRA + tail + TRACKER_STUB_FREE + REPLENISH_STUB_FREE
+    text = head + "    Mat clone() const;\n" + TRACKER_STUB_EXTRA + REPLENISH_STUB_EXTRA + tail + TRACKER_STUB_FREE + REPLENISH_STUB_FREE + TRACK_TAIL_STUB_FREE
     open(core, "w").write(text)
     return dst
 
@@ -219,6 +261,14 @@ def main(argv):
         if r.returncode:
             print(r.stderr[-4000:])
             failed.append("Replenish .inc harness")
+        tail = os.path.join(d, "track_tail_harness.cpp")
+        with open(tail, "w") as fh:
+            fh.write(TRACK_TAIL_HARNESS)
+        r = subprocess.run([cxx] + fl + [tail], capture_output=True, text=True)
+        print("%-22s %s" % ("Track tail .inc harness", "ok" if r.returncode == 0 else "FAILED"))
+        if r.returncode:
+            print(r.stderr[-4000:])
+            failed.append("Track tail .inc harness")
     sys.exit(1 if failed else 0)
 
 

@@ -40,6 +40,7 @@ SOURCES = [
     ("ba_round.hip", ["-munsafe-fp-atomics"]),
     ("map.hip", []),
     ("frame.hip", ["-ffp-contract=off"]),
+    ("frame_matches.hip", ["-ffp-contract=off"]),
     ("host.cpp", ["-ffp-contract=off"]),
     ("pose_graph.cpp", ["-ffp-contract=off"]),
 ]

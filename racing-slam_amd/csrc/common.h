@@ -108,6 +108,8 @@ struct rs_frame {
     uint32_t* d_rank = nullptr;         // [cap] rank_x | rank_y << 16 of the last assign
     int32_t* d_n = nullptr;             // [1] n of the last assign
     int32_t* h_n = nullptr;             // pinned word the one read-back per assign lands in
+    // Frame::m_map_matches (frame_matches.hip): point slot matched by keypoint i or -1; [cap], or [n] after rs_frame_create
+    int32_t* d_kp_point = nullptr;
 };
 
 int rs_fail(rs_context* ctx, int code, const char* fmt, ...);
@@ -126,6 +128,28 @@ int rs_map_loop_sync(rs_map* m, rs_map_loop_view* out);
 rs_context* rs_map_context(const rs_map* m);
 // key frame kf of the mirror: keypoints, first pool row, keypoints with a map match; false = no such key frame
 bool rs_map_loop_keyframe(const rs_map* m, int kf, int* n, int* pool_row, int* n_matched);
+
+// What frame_matches.hip reads and writes of an rs_map (map.hip: rs_map_track_sync brings the device image up to date first).
+struct rs_map_track_view {
+    int n_kf = 0;                           // key frames
+    rs_map_view mv;                         // the whole map as rs_reproj_match takes it (d_eligible: rs_map_launch_eligible's output)
+    const uint8_t* d_alive = nullptr;       // [points]
+    const uint8_t* d_consistent = nullptr;  // [points] MapPoint::track_consistent
+    uint8_t* d_flag = nullptr;              // [points] bit 0 = the frame already matches the point; all zero between calls
+    uint32_t* d_mark = nullptr;             // [points] scratch of the carry-over; all zero between calls
+    double* d_gather_pts = nullptr;         // [8192][3] the refit's points ...
+    float* d_gather_uv = nullptr;           // [8192][2] ... pixels ...
+    int32_t* d_gather_n = nullptr;          // [1] ... and count (-1: too few matches)
+    int32_t* d_out = nullptr;               // rs_reproj_match's outputs for a frame of n_out_kp keypoints (rs_map_match's layout)
+};
+int rs_map_track_sync(rs_map* m, int n_keypoints, rs_map_track_view* out);
+void rs_map_launch_eligible(rs_map* m, int required_kf);      // K2p over the synced image into mv.d_eligible, on the context stream
+// refine_pose.hip: K11 on device arrays whose count *d_n is read on the device (<= 0: no solve).  *h_n_used = that count.
+int rs_refine_pose_device_n(rs_context* ctx, double h_camera[6], const double* d_points, const float* d_uv, const int32_t* d_n, int max_n,
+                            const float h_intrinsics[4], int kind, const double h_predicted[9], double sigma_radians,
+                            const double h_prev_pose[6], const double h_prev_velocity[3], const double h_prev_bias[6],
+                            const rs_imu_factor* h_delta, const double h_gravity[3], double h_velocity[3],
+                            const rs_ba_options* options, rs_ba_summary* h_summary, int* h_n_used);
 
 #define RS_HIP(ctx, call)                                                                  \
     do {                                                                                   \

@@ -8,7 +8,8 @@
 // what follows in numpy; tests/test_frame_ref_cpu.py holds it against rs_kdtree_build).
 //
 //   k_frame_gather   n_a / n_b by rs_describe_features' clamp, read on the device; keypoints a_0 .. b_0 .. and the first
-//                    n descriptor rows into the frame; n to a device word; the rank table zeroed.
+//                    n descriptor rows into the frame; n to a device word; the rank table zeroed and the match table
+//                    (frame_matches.hip) cleared to -1.
 //   k_frame_rank     rank_x[i] = #{j : (key_x[j], j) < (key_x[i], i)}, likewise y, key = ordered_key(coordinate): a grid of
 //                    (256 i) x (256 j) tiles, each adding its count with one INTEGER atomic (rank_x | rank_y << 16; exact,
 //                    so repeated calls write the same bytes).  The ranks are two permutations of 0 .. n-1.
@@ -43,14 +44,15 @@ __device__ __forceinline__ void frame_counts(const int32_t* count_a, const int32
 __global__ __launch_bounds__(256) void k_frame_gather(int cap, const uint32_t* __restrict__ pt_a, const int32_t* __restrict__ count_a,
                                                       const uint32_t* __restrict__ pt_b, const int32_t* __restrict__ count_b,
                                                       const uint8_t* __restrict__ desc, int desc_aligned, uint32_t* __restrict__ kp,
-                                                      uint8_t* __restrict__ out_desc, uint32_t* __restrict__ rank, int32_t* __restrict__ d_n)
+                                                      uint8_t* __restrict__ out_desc, uint32_t* __restrict__ rank, int32_t* __restrict__ d_n,
+                                                      int32_t* __restrict__ kp_point)
 {
     int na, nb;
     frame_counts(pt_a ? count_a : nullptr, pt_b ? count_b : nullptr, cap, &na, &nb);
     const int n = na + nb;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t == 0) d_n[0] = n;
-    if (t < cap) rank[t] = 0;
+    if (t < cap) { rank[t] = 0; kp_point[t] = -1; }      // (the match table: no match yet)
     if (t < n) {
         const uint32_t* src = t < na ? pt_a + 2 * (size_t)t : pt_b + 2 * (size_t)(t - na);
         kp[2 * (size_t)t] = src[0];
@@ -190,7 +192,8 @@ extern "C" int rs_frame_create_device(rs_context* ctx, int max_points, rs_frame*
     if (hipMalloc((void**)&f->d_kp, sizeof(float) * 2 * m) != hipSuccess || hipMalloc((void**)&f->d_desc, 32 * m) != hipSuccess ||
         hipMalloc((void**)&f->d_kd, sizeof(int32_t) * 3 * m) != hipSuccess || hipMalloc((void**)&f->d_matched, m) != hipSuccess ||
         hipMalloc(&f->d_packed, 20 * m) != hipSuccess || hipMalloc((void**)&f->d_rank, sizeof(uint32_t) * m) != hipSuccess ||
-        hipMalloc((void**)&f->d_n, sizeof(int32_t)) != hipSuccess || hipHostMalloc((void**)&f->h_n, sizeof(int32_t)) != hipSuccess) {
+        hipMalloc((void**)&f->d_n, sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&f->d_kp_point, sizeof(int32_t) * m) != hipSuccess || hipHostMalloc((void**)&f->h_n, sizeof(int32_t)) != hipSuccess ||
+        hipMemsetAsync(f->d_kp_point, 0xFF, sizeof(int32_t) * m, ctx->stream) != hipSuccess) {       // no map match yet
         rs_frame_destroy(f);
         return rs_fail(ctx, RS_ERR_NOMEM, "frame buffers");
     }
@@ -214,7 +217,7 @@ extern "C" int rs_frame_assign_device(rs_context* ctx, rs_frame* f, const float*
         rs_prof_scope ps(ctx, "KF_frame_gather");
         hipLaunchKernelGGL(k_frame_gather, dim3((2 * cap + 255) / 256), dim3(256), 0, s, cap, (const uint32_t*)d_pt_a, d_count_a,
                            (const uint32_t*)d_pt_b, d_count_b, d_desc, ((uintptr_t)d_desc & 15) == 0 ? 1 : 0, (uint32_t*)f->d_kp, f->d_desc,
-                           f->d_rank, f->d_n);
+                           f->d_rank, f->d_n, f->d_kp_point);
     }
     RS_HIP(ctx, hipMemcpyAsync(f->h_n, f->d_n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     {

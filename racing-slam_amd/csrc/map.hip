@@ -61,6 +61,11 @@ struct rs_map {
     int32_t* d_out = nullptr; size_t cap_out = 0;
     std::vector<int32_t> h_obs_ptr, h_obs_kf, h_obs_desc, h_kp_point;
     std::vector<float> h_centres;
+    // the tracker's per-frame stages (frame_matches.hip)
+    std::vector<uint8_t> consistent;                // [P] MapPoint::track_consistent
+    bool dirty_consistent = true;
+    uint8_t* d_consistent = nullptr; uint32_t* d_mark = nullptr;    // [cap_points] both; d_mark all zero between calls
+    double* d_gather = nullptr;                     // pts [8192][3] f64 | uv [8192][2] f32 | n: the refit's gathered problem
 };
 
 // (struct rs_frame: common.h — frame.hip fills one from device arrays)
@@ -99,7 +104,7 @@ extern "C" int rs_map_destroy(rs_map* m)
     (void)hipStreamSynchronize(m->ctx->stream);
     for (void* p : {(void*)m->d_pos, (void*)m->d_alive, (void*)m->d_obs_ptr, (void*)m->d_obs_kf, (void*)m->d_obs_desc,
                     (void*)m->d_centres, (void*)m->d_pool, (void*)m->d_elig, (void*)m->d_flag, (void*)m->d_out, (void*)m->d_kp_pool,
-                    (void*)m->d_win, (void*)m->d_kp_point})
+                    (void*)m->d_win, (void*)m->d_kp_point, (void*)m->d_consistent, (void*)m->d_mark, (void*)m->d_gather})
         if (p) (void)hipFree(p);
     delete m;
     return RS_OK;
@@ -120,8 +125,10 @@ extern "C" int rs_frame_create(rs_context* ctx, const float* h_kp, const uint8_t
     if (n > 0) rs_kdtree_build(h_kp, n, kd.data(), kd.data() + m, kd.data() + 2 * m, &root);     // src/Frame.cpp:8-15
     f->kd_root = root;
     if (hipMalloc((void**)&f->d_kp, sizeof(float) * 2 * m) != hipSuccess || hipMalloc((void**)&f->d_desc, 32 * m) != hipSuccess ||
-        hipMalloc((void**)&f->d_kd, sizeof(int32_t) * 3 * m) != hipSuccess || hipMalloc((void**)&f->d_matched, m) != hipSuccess) {
-        delete f;
+        hipMalloc((void**)&f->d_kd, sizeof(int32_t) * 3 * m) != hipSuccess || hipMalloc((void**)&f->d_matched, m) != hipSuccess ||
+        hipMalloc((void**)&f->d_kp_point, sizeof(int32_t) * m) != hipSuccess ||
+        hipMemsetAsync(f->d_kp_point, 0xFF, sizeof(int32_t) * m, ctx->stream) != hipSuccess) {      // no map match yet
+        rs_frame_destroy(f);
         return rs_fail(ctx, RS_ERR_NOMEM, "frame buffers");
     }
     if (n > 0) {
@@ -149,7 +156,8 @@ extern "C" int rs_frame_destroy(rs_frame* f)
     if (!f) return RS_OK;
     (void)hipSetDevice(f->ctx->device);
     (void)hipStreamSynchronize(f->ctx->stream);
-    for (void* p : {(void*)f->d_kp, (void*)f->d_desc, (void*)f->d_kd, (void*)f->d_matched, f->d_packed, (void*)f->d_rank, (void*)f->d_n})
+    for (void* p : {(void*)f->d_kp, (void*)f->d_desc, (void*)f->d_kd, (void*)f->d_matched, f->d_packed, (void*)f->d_rank, (void*)f->d_n,
+                    (void*)f->d_kp_point})
         if (p) (void)hipFree(p);
     if (f->h_n) (void)hipHostFree(f->h_n);
     delete f;
@@ -202,9 +210,10 @@ extern "C" int rs_map_add_point(rs_map* m, const float xyz[3], int* out_point)
     if (!m || !xyz || !out_point) return RS_ERR_INVALID;
     m->pos.insert(m->pos.end(), xyz, xyz + 3);
     m->alive.push_back(1);
+    m->consistent.push_back(0);
     m->obs.emplace_back();
     m->n_alive++;
-    m->dirty_topology = m->dirty_positions = true;
+    m->dirty_topology = m->dirty_positions = m->dirty_consistent = true;      // (the device flag of the new slot is not yet written)
     *out_point = (int)m->alive.size() - 1;
     return RS_OK;
 }
@@ -307,18 +316,22 @@ static int map_sync_device(rs_map* m)
         if (P > m->cap_points) {
             // every per-point array is re-uploaded / recomputed / zeroed below: nothing to preserve
             RS_HIP(ctx, hipStreamSynchronize(s));
-            for (void* q : {(void*)m->d_alive, (void*)m->d_obs_ptr, (void*)m->d_pos, (void*)m->d_elig, (void*)m->d_flag})
+            for (void* q : {(void*)m->d_alive, (void*)m->d_obs_ptr, (void*)m->d_pos, (void*)m->d_elig, (void*)m->d_flag, (void*)m->d_consistent,
+                            (void*)m->d_mark})
                 if (q) RS_HIP(ctx, hipFree(q));
             m->d_alive = nullptr; m->d_obs_ptr = nullptr; m->d_pos = nullptr; m->d_elig = nullptr; m->d_flag = nullptr;
+            m->d_consistent = nullptr; m->d_mark = nullptr;
             size_t cap = m->cap_points ? m->cap_points : 4096;
             while (cap < P) cap *= 2;
             if (hipMalloc((void**)&m->d_alive, cap) != hipSuccess || hipMalloc((void**)&m->d_obs_ptr, sizeof(int32_t) * (cap + 1)) != hipSuccess ||
                 hipMalloc((void**)&m->d_pos, sizeof(float) * 3 * cap) != hipSuccess || hipMalloc((void**)&m->d_elig, cap) != hipSuccess ||
-                hipMalloc((void**)&m->d_flag, cap) != hipSuccess)
+                hipMalloc((void**)&m->d_flag, cap) != hipSuccess || hipMalloc((void**)&m->d_consistent, cap) != hipSuccess ||
+                hipMalloc((void**)&m->d_mark, sizeof(uint32_t) * cap) != hipSuccess)
                 return rs_fail(ctx, RS_ERR_NOMEM, "map buffers for %zu points", cap);
             RS_HIP(ctx, hipMemsetAsync(m->d_flag, 0, cap, s));
+            RS_HIP(ctx, hipMemsetAsync(m->d_mark, 0, sizeof(uint32_t) * cap, s));
             m->cap_points = cap;
-            m->dirty_positions = true;
+            m->dirty_positions = m->dirty_consistent = true;
         }
         if (m->n_obs > m->cap_obs) {
             RS_HIP(ctx, hipStreamSynchronize(s));
@@ -381,6 +394,47 @@ int rs_map_loop_sync(rs_map* m, rs_map_loop_view* out)
 
 rs_context* rs_map_context(const rs_map* m) { return m->ctx; }
 
+// MapPoint::set_track_consistent: the flag only ever goes up
+extern "C" int rs_map_set_track_consistent(rs_map* m, int point)
+{
+    if (!m || point < 0 || point >= (int)m->alive.size() || !m->alive[(size_t)point]) return RS_ERR_INVALID;
+    if (!m->consistent[(size_t)point]) { m->consistent[(size_t)point] = 1; m->dirty_consistent = true; }
+    return RS_OK;
+}
+
+#define MAP_GATHER_MAX 8192             // keypoints of a frame (frame.hip's FRAME_MAX_POINTS)
+
+// frame_matches.hip's window into the map: the device image brought up to date, the flags of part 2 with it, and the
+// scratch of its three stages (rs_reproj_match's outputs sized for a frame of n_keypoints)
+int rs_map_track_sync(rs_map* m, int n_keypoints, rs_map_track_view* out)
+{
+    rs_context* ctx = m->ctx;
+    const size_t P = m->alive.size();
+    int rc = P ? map_sync_device(m) : RS_OK;        // (an empty map has no image yet, and nothing reads one)
+    if (rc) return rc;
+    if (m->dirty_consistent && P && m->d_consistent) {      // pageable source: complete before returning
+        RS_HIP(ctx, hipMemcpyAsync(m->d_consistent, m->consistent.data(), P, hipMemcpyHostToDevice, ctx->stream));
+        RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        m->dirty_consistent = false;
+    }
+    if (!m->d_gather && hipMalloc((void**)&m->d_gather, (size_t)MAP_GATHER_MAX * 32 + 256) != hipSuccess)
+        return rs_fail(ctx, RS_ERR_NOMEM, "refit scratch");
+    const size_t N = (size_t)(n_keypoints > 0 ? n_keypoints : 0);
+    size_t co = m->cap_out;
+    rc = grow(ctx, &m->d_out, &co, 2 * P + 4 * N + 1, 0);
+    if (rc) return rc;
+    m->cap_out = co;
+    *out = rs_map_track_view{};
+    out->n_kf = (int)m->kfs.size();
+    out->mv = rs_map_view{(int)P, m->d_pos, m->d_elig, m->d_obs_ptr, m->d_obs_kf, m->d_obs_desc, m->d_centres, m->d_pool};
+    out->d_alive = m->d_alive; out->d_consistent = m->d_consistent; out->d_flag = m->d_flag; out->d_mark = m->d_mark;
+    out->d_gather_pts = m->d_gather;
+    out->d_gather_uv = (float*)(m->d_gather + 3 * (size_t)MAP_GATHER_MAX);
+    out->d_gather_n = (int32_t*)(out->d_gather_uv + 2 * (size_t)MAP_GATHER_MAX);
+    out->d_out = m->d_out;
+    return RS_OK;
+}
+
 bool rs_map_loop_keyframe(const rs_map* m, int kf, int* n, int* pool_row, int* n_matched)
 {
     if (kf < 0 || kf >= (int)m->kfs.size()) return false;
@@ -417,6 +471,14 @@ __global__ __launch_bounds__(256) void k_map_eligible(int P, const uint8_t* __re
         e = seen;
     }
     elig[p] = e ? 1 : 0;
+}
+
+void rs_map_launch_eligible(rs_map* m, int required_kf)
+{
+    rs_prof_scope ps(m->ctx, "K2p_map_eligible");
+    const int P = (int)m->alive.size();
+    hipLaunchKernelGGL(k_map_eligible, dim3((P + 255) / 256), dim3(256), 0, m->ctx->stream, P, m->d_alive, m->d_flag, m->d_obs_ptr, m->d_obs_kf,
+                       required_kf, 0, m->d_elig);
 }
 
 // MapMatcher::match_map / match_key_frame / match_for_fuse against the resident map.

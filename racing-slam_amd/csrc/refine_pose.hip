@@ -269,11 +269,13 @@ __device__ __forceinline__ void rp_finish(BaState& st, int nx, const double* x, 
     __threadfence_system();
 }
 
-// INERTIAL: the state is pose + velocity (cam_io[9]) and *ext holds the extra block; else the pose alone and ext is null
+// INERTIAL: the state is pose + velocity (cam_io[9]) and *ext holds the extra block; else the pose alone and ext is null.
+// d_n non-null: the count is d_n[0], read here and reported in *n_used; <= 0 ends the launch before the solve (the
+// completion flag is raised, cam_io and st_out stay as they are).
 template <bool INERTIAL>
 __device__ __forceinline__ void rp_body(const BaDims& d, const BaOpt& opt, const double* __restrict__ pts, const float2* __restrict__ uv,
-                                        int n, const RpInertial* __restrict__ ext, double* __restrict__ cam_io,
-                                        BaState* __restrict__ st_out, volatile int* host_done)
+                                        int n, const int* __restrict__ d_n, const RpInertial* __restrict__ ext, double* __restrict__ cam_io,
+                                        BaState* __restrict__ st_out, volatile int* host_done, int* __restrict__ n_used)
 {
     constexpr int NX = INERTIAL ? 9 : 6;
     __shared__ double x[NX], xn[NX], prep[BA_PREP], prepn[BA_PREP], scratch[(RP_THREADS / 64 + 1) * 32];
@@ -283,6 +285,14 @@ __device__ __forceinline__ void rp_body(const BaDims& d, const BaOpt& opt, const
     const int tid = threadIdx.x;
     int nu = 6;
     if constexpr (INERTIAL) nu = ext->kind == 2 ? 9 : 6;
+    if (d_n) {
+        n = d_n[0];
+        if (tid == 0) *n_used = n;
+        if (n <= 0) {
+            if (tid == 0) { __threadfence_system(); *host_done = 1; __threadfence_system(); }
+            return;
+        }
+    }
     if (tid == 0) rp_init(opt, cam_io, NX, x, prep, st);
     __syncthreads();
     double acc[28];
@@ -326,7 +336,7 @@ __global__ __launch_bounds__(RP_THREADS) void ba_refine_pose(BaDims d, BaOpt opt
                                                             const float2* __restrict__ uv, int n,
                                                             double* __restrict__ cam_io, BaState* __restrict__ st_out, volatile int* host_done)
 {
-    rp_body<false>(d, opt, pts, uv, n, nullptr, cam_io, st_out, host_done);
+    rp_body<false>(d, opt, pts, uv, n, nullptr, nullptr, cam_io, st_out, host_done, nullptr);
 }
 
 __global__ __launch_bounds__(RP_THREADS) void ba_refine_pose_inertial(BaDims d, BaOpt opt, const double* __restrict__ pts,
@@ -335,7 +345,25 @@ __global__ __launch_bounds__(RP_THREADS) void ba_refine_pose_inertial(BaDims d, 
                                                                      double* __restrict__ cam_io /*[9]: pose, velocity*/,
                                                                      BaState* __restrict__ st_out, volatile int* host_done)
 {
-    rp_body<true>(d, opt, pts, uv, n, ext, cam_io, st_out, host_done);
+    rp_body<true>(d, opt, pts, uv, n, nullptr, ext, cam_io, st_out, host_done, nullptr);
+}
+
+// the two kernels above on a count that lives on the device (rs_map_refine_pose: the gather kernel has just written it)
+__global__ __launch_bounds__(RP_THREADS) void ba_refine_pose_dn(BaDims d, BaOpt opt, const double* __restrict__ pts,
+                                                               const float2* __restrict__ uv, const int* __restrict__ d_n,
+                                                               double* __restrict__ cam_io, BaState* __restrict__ st_out,
+                                                               volatile int* host_done, int* __restrict__ n_used)
+{
+    rp_body<false>(d, opt, pts, uv, 0, d_n, nullptr, cam_io, st_out, host_done, n_used);
+}
+
+__global__ __launch_bounds__(RP_THREADS) void ba_refine_pose_inertial_dn(BaDims d, BaOpt opt, const double* __restrict__ pts,
+                                                                        const float2* __restrict__ uv, const int* __restrict__ d_n,
+                                                                        const RpInertial* __restrict__ ext, double* __restrict__ cam_io,
+                                                                        BaState* __restrict__ st_out, volatile int* host_done,
+                                                                        int* __restrict__ n_used)
+{
+    rp_body<true>(d, opt, pts, uv, 0, d_n, ext, cam_io, st_out, host_done, n_used);
 }
 
 // ---------------------------------------------------------------------- host
@@ -349,14 +377,17 @@ struct RpInertialArgs {
     double* velocity;         // [3] in/out (inertial delta)
 };
 
+// d_n null: n observations, as the caller counted them.  d_n non-null: at most n, the count is d_n[0] on the device; it
+// comes back in *h_n_used, and <= 0 means no solve ran (zeroed summary, h_camera untouched).
 static int refine_pose_solve(rs_context* ctx, double h_camera[6], const double* d_points, const float* d_uv, int n,
-                             const float h_intrinsics[4], const RpInertialArgs* in, const rs_ba_options* options, rs_ba_summary* h_summary)
+                             const float h_intrinsics[4], const RpInertialArgs* in, const rs_ba_options* options, rs_ba_summary* h_summary,
+                             const int32_t* d_n = nullptr, int* h_n_used = nullptr)
 {
     if (!ctx || !h_summary) return RS_ERR_INVALID;
     memset(h_summary, 0, sizeof *h_summary);     // a refused call leaves a zeroed summary too
     if (!h_camera) return rs_fail(ctx, RS_ERR_INVALID, "null pointer");
     if (n < 0) return rs_fail(ctx, RS_ERR_INVALID, "negative n");
-    if (n == 0) return RS_OK;   // "nothing to constrain", src/Optimization.cpp:227-229 (checked before the inertial block is added)
+    if (n == 0 && !d_n) return RS_OK;   // "nothing to constrain", src/Optimization.cpp:227-229 (checked before the inertial block is added)
     if (!d_points || !d_uv || !h_intrinsics) return rs_fail(ctx, RS_ERR_INVALID, "null pointer");
     if (in && in->kind == 2 && (!in->prev_pose || !in->prev_velocity || !in->prev_bias || !in->gravity || !in->velocity))
         return rs_fail(ctx, RS_ERR_INVALID, "null pointer (inertial delta)");
@@ -364,11 +395,11 @@ static int refine_pose_solve(rs_context* ctx, double h_camera[6], const double* 
     if (!options) { rs_ba_default_options(&def); options = &def; }
     RS_HIP(ctx, hipSetDevice(ctx->device));
     BaDims d;
-    d.C = 1; d.Cf = 1; d.P = n; d.M = n; d.n = 6;
+    d.C = 1; d.Cf = 1; d.P = n; d.M = n; d.n = 6;       // with d_n, P and M are only the upper bound: rp_body takes its own n, not these
     d.fx = h_intrinsics[0]; d.fy = h_intrinsics[1]; d.cx = h_intrinsics[2]; d.cy = h_intrinsics[3];
     d.huber_a = options->huber_delta;
     const BaOpt opt = ba_opt_from(options);
-    // pinned block: camera (+ velocity) at 0, BaState at 256, completion flag at 448, the inertial block at 1024
+    // pinned block: camera (+ velocity) at 0, BaState at 256, completion flag at 448, the device-side count at 456, the inertial block at 1024
     RpInertial* d_ext = nullptr;
     int rc;
     if (in) {
@@ -387,6 +418,8 @@ static int refine_pose_solve(rs_context* ctx, double h_camera[6], const double* 
     double* h_cam = (double*)pin;
     BaState* h_st = (BaState*)((char*)pin + 256);
     volatile int* h_done = (volatile int*)((char*)pin + 448);
+    int* h_nu = (int*)((char*)pin + 456);
+    *h_nu = 0;
     memcpy(h_cam, h_camera, 6 * sizeof(double));
     hipStream_t s = ctx->stream;
     if (in) {
@@ -412,7 +445,13 @@ static int refine_pose_solve(rs_context* ctx, double h_camera[6], const double* 
         // a 40 us kernel (three hipMemcpyAsync cost more than the solve)
         rs_prof_scope ps(ctx, in ? "K11_refine_pose_inertial" : "K11_refine_pose");
         *h_done = 0;
-        if (in)
+        if (d_n && in)
+            hipLaunchKernelGGL(ba_refine_pose_inertial_dn, dim3(1), dim3(RP_THREADS), 0, s, d, opt, d_points, (const float2*)d_uv, (const int*)d_n,
+                               (const RpInertial*)d_ext, h_cam, h_st, h_done, h_nu);
+        else if (d_n)
+            hipLaunchKernelGGL(ba_refine_pose_dn, dim3(1), dim3(RP_THREADS), 0, s, d, opt, d_points, (const float2*)d_uv, (const int*)d_n, h_cam,
+                               h_st, h_done, h_nu);
+        else if (in)
             hipLaunchKernelGGL(ba_refine_pose_inertial, dim3(1), dim3(RP_THREADS), 0, s, d, opt, d_points, (const float2*)d_uv, n,
                                (const RpInertial*)d_ext, h_cam, h_st, h_done);
         else
@@ -421,6 +460,10 @@ static int refine_pose_solve(rs_context* ctx, double h_camera[6], const double* 
         RS_HIP(ctx, ba_wait_flag(s, h_done, 1));
     }
     RS_HIP(ctx, hipGetLastError());
+    if (d_n) {
+        if (h_n_used) *h_n_used = *h_nu;
+        if (*h_nu <= 0) return RS_OK;
+    }
     if (h_st->usable) {
         memcpy(h_camera, h_cam, 6 * sizeof(double));
         if (in && in->kind == 2) memcpy(in->velocity, h_cam + 6, 3 * sizeof(double));    // unpack_inertial, :263-265
@@ -450,4 +493,20 @@ extern "C" int rs_refine_pose_inertial(rs_context* ctx, double h_camera[6], cons
     if (kind == 2 && (!h_delta || !(h_delta->duration > 0.0))) kind = 0;
     const RpInertialArgs in = {kind, h_predicted, sigma_radians, h_prev_pose, h_prev_velocity, h_prev_bias, h_delta, h_gravity, h_velocity};
     return refine_pose_solve(ctx, h_camera, d_points, d_uv, n, h_intrinsics, kind ? &in : nullptr, options, h_summary);
+}
+
+int rs_refine_pose_device_n(rs_context* ctx, double h_camera[6], const double* d_points, const float* d_uv, const int32_t* d_n, int max_n,
+                            const float h_intrinsics[4], int kind, const double h_predicted[9], double sigma_radians,
+                            const double h_prev_pose[6], const double h_prev_velocity[3], const double h_prev_bias[6],
+                            const rs_imu_factor* h_delta, const double h_gravity[3], double h_velocity[3],
+                            const rs_ba_options* options, rs_ba_summary* h_summary, int* h_n_used)
+{
+    if (!ctx || !h_summary) return RS_ERR_INVALID;
+    memset(h_summary, 0, sizeof *h_summary);
+    if (!h_camera || !d_n) return rs_fail(ctx, RS_ERR_INVALID, "null pointer");
+    if (kind < 0 || kind > 2) return rs_fail(ctx, RS_ERR_INVALID, "kind must be 0, 1 or 2");
+    if (kind == 1 && (!h_predicted || !(sigma_radians > 0.0))) kind = 0;      // (as rs_refine_pose_inertial)
+    if (kind == 2 && (!h_delta || !(h_delta->duration > 0.0))) kind = 0;
+    const RpInertialArgs in = {kind, h_predicted, sigma_radians, h_prev_pose, h_prev_velocity, h_prev_bias, h_delta, h_gravity, h_velocity};
+    return refine_pose_solve(ctx, h_camera, d_points, d_uv, max_n, h_intrinsics, kind ? &in : nullptr, options, h_summary, d_n, h_n_used);
 }

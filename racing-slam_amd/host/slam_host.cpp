@@ -1182,4 +1182,44 @@ bool LoopStreak::consume_new_loop()
     return added;
 }
 
+// ---------------------------------------------------------------------------------------------- the tail of Tracker::track
+bool track_tail(rs_context* ctx, rs_map* map, const rs_frame* prev, rs_frame* next, const int32_t* d_prev_index,
+                const int32_t* d_inlier_index, const int32_t* d_inlier_count, int max_n, const Camera& camera, bool optimize,
+                TrackTailConstraint* constraint, int last_key_frame, Mat4f& pose, TrackTail* out)
+{
+    TrackTail t;
+    const auto fail = [&](int rc, const char* what) {
+        std::printf("%s failed (status %d): %s\n", what, rc, ctx ? rs_last_error(ctx) : "no context");
+        if (out) *out = t;
+        return false;
+    };
+    int rc = rs_map_carry_matches(ctx, map, prev, next, d_prev_index, d_inlier_index, d_inlier_count, max_n, MIN_TRACKED_MAP_POINTS, nullptr);   // :83
+    if (rc != RS_OK) return fail(rc, "rs_map_carry_matches");
+    const float K[4] = {camera.fx(), camera.fy(), camera.cx(), camera.cy()};
+    if (optimize) {                                                                              // :84, :302-320
+        double cam[6];
+        rs_pack_pose(pose.data(), cam);
+        TrackTailConstraint none;
+        TrackTailConstraint& c = constraint ? *constraint : none;
+        rc = rs_map_refine_pose(ctx, map, next, cam, K, MIN_TRACKED_MAP_POINTS, c.kind, c.predicted, c.sigma_radians, c.prev_pose,
+                                c.prev_velocity, c.prev_bias, &c.delta, c.gravity, c.velocity, nullptr, &t.summary, &t.n_used);
+        if (rc != RS_OK) return fail(rc, "rs_map_refine_pose");
+        if (t.n_used > 0) {
+            std::printf("refine_pose: iterations %d, cost %.6e -> %.6e, termination %d\n", t.summary.iterations, t.summary.initial_cost,
+                        t.summary.final_cost, t.summary.termination);
+            if (!t.summary.usable) std::printf("Optimization rejected, unusable or non-improving solution\n");
+        }
+        t.refined = t.n_used > 0 && t.summary.usable != 0;
+        if (t.refined) rs_unpack_pose(cam, pose.data());
+    }
+    rc = rs_map_match_frame(ctx, map, next, pose.data(), K, camera.get_width(), camera.get_height(), last_key_frame, 64, &t.key_frame_matches);   // :85
+    if (rc != RS_OK) return fail(rc, "rs_map_match_frame");
+    std::printf("Map matches with last frame: %d\n", t.key_frame_matches);
+    rc = rs_map_match_frame(ctx, map, next, pose.data(), K, camera.get_width(), camera.get_height(), -1, 64, &t.map_matches);                     // :86
+    if (rc != RS_OK) return fail(rc, "rs_map_match_frame");
+    std::printf("Number of map matches: %d\n", t.map_matches);
+    if (out) *out = t;
+    return true;
+}
+
 }  // namespace slam

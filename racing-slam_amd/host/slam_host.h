@@ -323,6 +323,30 @@ PnpEstimate estimate_pose_pnp(const std::vector<Vec3f>& object_points, const std
 
 }  // namespace pose
 
+// The tail of Tracker::track (src/Tracker.cpp:83-86) on the frames' device tables: track_from_last_frame, optimize_pose's
+// refit, match_with_last_key_frame and match_with_map as four C-ABI calls (rs_map_carry_matches, rs_map_refine_pose,
+// rs_map_match_frame twice) with no host list in between.  prev / next: the rs_frames of the previous and this video
+// frame (refresh_descriptors' out_frame); d_prev_index: rs_track_features' d_kept_index; d_inlier_index / d_inlier_count:
+// rs_estimate_pose's (null index: every tracked keypoint), each with room for max_n entries.
+constexpr int MIN_TRACKED_MAP_POINTS = 15;      // src/Tracker.cpp's
+struct TrackTailConstraint {                     // optimization::InertialConstraint, flattened as rs_refine_pose_inertial takes it
+    int kind = 0;                                // 0 none, 1 RotationPrior, 2 InertialDelta
+    double predicted[9] = {}, sigma_radians = 0.0;
+    double prev_pose[6] = {}, prev_velocity[3] = {}, prev_bias[6] = {}, gravity[3] = {}, velocity[3] = {};   // velocity: in / out
+    rs_imu_factor delta = {};
+};
+struct TrackTail {
+    int n_used = 0;                              // observations of the refit; -1: fewer than 15 matches, 0: none with 2 observations
+    bool refined = false;                        // the solve was usable: `pose` is the refined one (is_rotation_plausible is the caller's)
+    rs_ba_summary summary = {};
+    int key_frame_matches = 0, map_matches = 0;
+};
+// `pose` in: the frame's initial pose (Tracker::initial_pose_estimate); out: the refined pose when refined.  `optimize`:
+// TrackerConfig::optimize_pose.  last_key_frame: its handle in the map.  False when a call failed (logged).
+bool track_tail(rs_context* ctx, rs_map* map, const rs_frame* prev, rs_frame* next, const int32_t* d_prev_index,
+                const int32_t* d_inlier_index, const int32_t* d_inlier_count, int max_n, const Camera& camera, bool optimize,
+                TrackTailConstraint* constraint, int last_key_frame, Mat4f& pose, TrackTail* out);
+
 // LoopDetector::query's "Loop retrieval" stage (src/LoopDetector.cpp:346-373 Impl::score_candidates, :231-265
 // rank_candidates) on the device, as specified by tests/bow_ref.py: the DBoW2 vocabulary, one rs_bow and the database of
 // the key frames' vectors.  Where the reference computes bow_of lazily per candidate (:351-353, :366-368), every key

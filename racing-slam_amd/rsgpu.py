@@ -19,6 +19,8 @@ EXPORTS = [
     "rs_context_synchronize", "rs_context_set_int", "rs_stage_begin", "rs_stage_alloc", "rs_stage_upload", "rs_stage_download", "rs_stage_sync", "rs_last_error", "rs_hamming_knn2", "rs_match_descriptors",
     "rs_kdtree_build", "rs_kdtree_pack", "rs_reproj_match", "rs_reproj_match_sharded", "rs_map_create", "rs_map_destroy", "rs_frame_create", "rs_frame_destroy",
     "rs_frame_create_device", "rs_frame_assign_device", "rs_frame_download",
+    "rs_frame_matches_clear", "rs_frame_matches_add", "rs_frame_matches_download",
+    "rs_map_set_track_consistent", "rs_map_carry_matches", "rs_map_refine_pose", "rs_map_match_frame",
     "rs_map_add_keyframe", "rs_map_set_keyframe_pose", "rs_map_add_point", "rs_map_set_position", "rs_map_remove_point",
     "rs_map_add_observation", "rs_map_remove_observation", "rs_map_counts", "rs_map_get_positions", "rs_map_match", "rs_map_pose_graph", "rs_pose_graph", "rs_pose_relative", "rs_transform_points", "rs_map_bundle_adjust", "rs_map_window", "rs_triangulate", "rs_triangulate_host", "rs_triangulate_matches", "rs_triangulate_matches_batch", "rs_triangulate_tracks", "rs_parallax_requirements", "rs_point_errors", "rs_ba_default_options",
     "rs_bundle_adjust", "rs_bundle_adjust_batch", "rs_ba_get_trace", "rs_ba_get_stats", "rs_ba_get_cameras", "rs_reanchor_points", "rs_reanchor_points_host_poses", "rs_refine_pose", "rs_bundle_adjust_inertial", "rs_refine_pose_inertial", "rs_pack_pose", "rs_unpack_pose", "rs_pack_poses", "rs_unpack_poses", "rs_build_local_window",
@@ -1249,7 +1251,26 @@ class LoopVerifier:
             self.h = C.c_void_p()
 
 
-class ResidentFrame:
+class _FrameMatches:
+    """The frame's match table (Frame::m_map_matches on the device), for both kinds of frame."""
+
+    def matches_clear(self):
+        self.ctx._check(self.ctx.lib.rs_frame_matches_clear(self.ctx.h, self.h), "rs_frame_matches_clear")
+
+    def matches_add(self, d_kp, d_point, d_count=None, max_n=None):
+        """Frame::add_map_match for a device list, in list order; the count is read on the device."""
+        n = int(d_kp.shape[0]) if max_n is None else int(max_n)
+        self.ctx._check(self.ctx.lib.rs_frame_matches_add(self.ctx.h, self.h, _dp(d_kp), _dp(d_point), _dp(d_count), n), "rs_frame_matches_add")
+
+    def matches(self):
+        """rs_frame_matches_download (synchronises): (table [n] i32, Frame::num_map_matches)."""
+        tab, cnt = np.full(max(self.n, 1), -1, np.int32), C.c_int(0)
+        self.ctx._check(self.ctx.lib.rs_frame_matches_download(self.ctx.h, self.h, tab.ctypes.data_as(C.c_void_p), C.byref(cnt)),
+                        "rs_frame_matches_download")
+        return tab[:self.n], cnt.value
+
+
+class ResidentFrame(_FrameMatches):
     def __init__(self, ctx, keypoints, descriptors):
         self.ctx = ctx
         kp = np.ascontiguousarray(keypoints, np.float32)
@@ -1283,7 +1304,7 @@ def frame_download(ctx, frame):
                 packed=packed[:20 * k])
 
 
-class DeviceFrame:
+class DeviceFrame(_FrameMatches):
     """rs_frame filled from device arrays (rs_frame_create_device / rs_frame_assign_device): allocated once for
     max_points keypoints, reassigned every video frame; usable wherever ResidentMap takes a frame."""
 
@@ -1380,6 +1401,51 @@ class ResidentMap:
             None if only is None else only.ctypes.data_as(C.c_void_p), -1 if only is None else len(only), int(replace), int(max_distance),
             mk.ctypes.data_as(C.c_void_p), mp.ctypes.data_as(C.c_void_p), C.byref(cnt)), "rs_map_match")
         return mk[:cnt.value].copy(), mp[:cnt.value].copy()
+
+    # -- the tail of Tracker::track on the frame's device table
+    def set_track_consistent(self, point):
+        self.ctx._check(self.lib.rs_map_set_track_consistent(self.h, int(point)), "rs_map_set_track_consistent")
+
+    def carry_matches(self, prev, nxt, d_prev_index, d_inlier_index=None, d_count=None, max_n=None, min_points=15, d_stats=None):
+        """Tracker::track_from_last_frame on the two frames' tables; stream-ordered, nothing comes back."""
+        n = int(d_prev_index.shape[0]) if max_n is None else int(max_n)
+        self.ctx._check(self.lib.rs_map_carry_matches(self.ctx.h, self.h, prev.h, nxt.h, _dp(d_prev_index), _dp(d_inlier_index),
+                                                      _dp(d_count), n, int(min_points), _dp(d_stats)), "rs_map_carry_matches")
+
+    def refine_pose(self, frame, cam, K, min_matches=15, prior=None, delta=None, options=None):
+        """Tracker::optimize_pose's refit from the frame's table; prior / delta as Context.refine_pose_inertial.
+        Returns cam, velocity, summary, n_used."""
+        cam = np.array(cam, np.float64, order="C")
+        Kc = (C.c_float * 4)(*[float(v) for v in K])
+        s, used = BaSummary(), C.c_int(0)
+        vel = np.zeros(3)
+        kind, pred, sigma, keep, args = 0, None, 0.0, [], [None, None, None, None, None]
+        if prior is not None:
+            kind, sigma = 1, float(prior[1])
+            keep.append(np.ascontiguousarray(prior[0], np.float64))
+            pred = keep[-1].ctypes.data_as(C.c_void_p)
+        if delta is not None:
+            kind = 2
+            farr, _ = imu_factor_array(delta["imu"])
+            keep += [np.ascontiguousarray(delta[k], np.float64) for k in ("prev_pose", "prev_velocity", "prev_bias")]
+            keep.append(np.ascontiguousarray(delta["imu"]["gravity"], np.float64))
+            vel = np.array(delta["velocity"], np.float64)
+            args = [keep[-4].ctypes.data_as(C.c_void_p), keep[-3].ctypes.data_as(C.c_void_p), keep[-2].ctypes.data_as(C.c_void_p),
+                    farr, keep[-1].ctypes.data_as(C.c_void_p)]
+        self.ctx._check(self.lib.rs_map_refine_pose(
+            self.ctx.h, self.h, frame.h, cam.ctypes.data_as(C.c_void_p), Kc, int(min_matches), kind, pred, C.c_double(sigma),
+            args[0], args[1], args[2], args[3], args[4], vel.ctypes.data_as(C.c_void_p),
+            None if options is None else C.byref(options), C.byref(s), C.byref(used)), "rs_map_refine_pose")
+        return cam, vel, s.as_dict(), used.value
+
+    def match_frame(self, frame, pose, K, width, height, required_observer=-1, max_distance=64):
+        """match_key_frame / match_map on the frame's table; returns the number of new matches."""
+        cnt = C.c_int(0)
+        p = np.ascontiguousarray(pose, np.float32).reshape(16)
+        Kc = (C.c_float * 4)(*[float(v) for v in K])
+        self.ctx._check(self.lib.rs_map_match_frame(self.ctx.h, self.h, frame.h, p.ctypes.data_as(C.c_void_p), Kc, int(width), int(height),
+                                                    int(required_observer), int(max_distance), C.byref(cnt)), "rs_map_match_frame")
+        return cnt.value
 
     def pose_graph(self, loops, four_dof=False, gravity=(0.0, 0.0, 0.0), options=None):
         n = self.counts()["key_frames"]
