@@ -368,6 +368,100 @@ int rs_map_carry_matches(rs_context* ctx, rs_map* map, const rs_frame* prev, rs_
 int rs_map_match_frame(rs_context* ctx, rs_map* map, rs_frame* frame, const float h_pose[16], const float h_intrinsics[4],
                        int width, int height, int required_observer_kf, int max_distance, int* h_count);
 
+/* ---- feature tracks on the device: TrackStore (src/TrackStore.cpp) and Mapper::needs_key_frame (src/Mapper.cpp:91-140).
+ * rs_track_store holds every live track — a 64-bit id, its keypoint in the current frame and up to max_sightings sightings
+ * {frame index, pixel, key-frame handle or -1, keypoint} — in a pool of max_points rows (1 .. 8192, the envelope of
+ * rs_frame_create_device; max_sightings 1 .. 128, the reference uses 100; outside either: RS_ERR_UNSUPPORTED).  Every
+ * call is ordered on the context stream and allocates nothing after creation.  Between rs_map_match_frame and the next
+ * rs_track_features a per-frame caller makes carry, query, extend: one read-back of 24 bytes (the query's).
+ * A frame of another context is RS_ERR_INVALID, a frame with more keypoints than max_points RS_ERR_UNSUPPORTED. */
+typedef struct rs_track_store rs_track_store;
+int rs_track_store_create(rs_context* ctx, int max_points, int max_sightings, rs_track_store** out_store);
+int rs_track_store_destroy(rs_track_store* store);
+int rs_track_store_clear(rs_context* ctx, rs_track_store* store);           /* a fresh TrackStore: no tracks, the id counter at 0 */
+/* TrackStore::carry_forward (:12-35) in rs_map_carry_matches' list form: entry i names current keypoint
+ * j = d_inlier_index[i] (NULL: j = i) and previous keypoint d_prev_index[j]; n = clamp(d_count[0], 0, max_n) read on the
+ * device (NULL: max_n; max_n <= 8192).  An entry whose j is outside [0, min(max_n, max_points)) or whose previous keypoint
+ * is outside the store or holds no track is skipped.  The track of a named previous keypoint moves to keypoint j with its
+ * id and sightings; every other track is dropped and its row freed (n = 0 drops everything).  Repeats: the FIRST entry
+ * naming a previous keypoint decides for its track, and of those entries the first naming a current keypoint gets it — a
+ * track whose deciding entry loses its keypoint is dropped.  No host synchronisation. */
+int rs_track_store_carry(rs_context* ctx, rs_track_store* store, const int32_t* d_prev_index, const int32_t* d_inlier_index,
+                         const int32_t* d_count, int max_n);
+/* TrackStore::extend (:37-54): every keypoint of `frame` without a track gets a new one, ids ascending with the keypoint
+ * index from the store's counter; then every track of a keypoint of the frame that holds fewer than max_sightings
+ * sightings appends {frame_index, the keypoint's pixel bit for bit, key_frame_handle (negative: -1), keypoint}.
+ * No host synchronisation. */
+int rs_track_store_extend(rs_context* ctx, rs_track_store* store, const rs_frame* frame, int frame_index, int key_frame_handle);
+/* Mapper::covisible_points and unmapped_tracks (:91-120) from the frame's match table, ONE read-back of six integers:
+ *   [0] covisible: table entries whose point is alive and observed by key frame last_key_frame (a removed point is not
+ *       covisible; map NULL or last_key_frame < 0: 0)      [1] Frame::num_map_matches
+ *   [2] waiting: tracks with >= min_sightings sightings, whose keypoint the table does not match, whose travel
+ *       sqrtf(fl(fl(dx dx) + fl(dy dy))) between the last and the first sighting is not below min_travel (:107-117)
+ *   [3] live tracks   [4] the smallest first-sighting frame index among them (-1 without tracks)
+ *   [5] the id counter's low 32 bits (diagnostic). */
+int rs_track_store_query(rs_context* ctx, rs_track_store* store, rs_map* map, const rs_frame* frame, int last_key_frame,
+                         int min_sightings, float min_travel, int32_t h_out[6]);
+/* Host function (no context, no device): Mapper::needs_key_frame's decision (:122-140) on rs_track_store_query's integers:
+ * frame_gap >= max_key_frame_gap (a negative gap is the reference's unsigned wrap: true), or waiting >=
+ * new_tracks_threshold, or covisible < min_covisible_points, or (float)covisible < min_covisible_fraction *
+ * (float)last_key_frame_matches in f32.  The reference's constants (:21-26): 20, 200, 50, 0.7f; the other two of that
+ * block, MIN_SIGHTINGS_FOR_TRACK = 3 and MIN_TRACK_TRAVEL_PIXELS = 20, are the query's parameters.  *h_out = 0 / 1. */
+int rs_needs_key_frame(const int32_t h_query[6], int frame_gap, int last_key_frame_matches, int max_key_frame_gap,
+                       int new_tracks_threshold, int min_covisible_points, float min_covisible_fraction, int* h_out);
+/* What Mapper::triangulate_tracks needs back (:306-330), filled by ONE read-back (a second copy and synchronisation
+ * follow only when the accepted tracks hold more than two key-frame sightings per packed track on average).  In: the capacities.  The accepted tracks
+ * come in rs_triangulate_tracks' order (creation order, the top-up last); entry a: h_keypoint[a] its keypoint in the frame,
+ * h_xyz[a] its position, h_sightings[a] its sighting count (the >= 3 rule of :326), and its KEY-FRAME sightings only as
+ * pairs (handle, keypoint) h_kf_pairs[2 h_kf_ptr[a] .. 2 h_kf_ptr[a + 1]) in sighting order.  capacity_tracks >= the live
+ * tracks of the last query (h_kf_ptr: one more entry); when n_pairs exceeds capacity_pairs only the first capacity_pairs
+ * pairs were copied. */
+typedef struct rs_track_results {
+    int capacity_tracks, capacity_pairs;
+    int32_t counts[3];          /* rs_triangulate_tracks' d_counts: accepted, of which top-up, inconsistent */
+    int32_t out_of_range;       /* tracks with a sighting outside the pose range: packed as skipped */
+    int32_t n_tracks;           /* tracks packed */
+    int32_t n_pairs;
+    int32_t* h_keypoint;        /* [capacity_tracks] */
+    float* h_xyz;               /* [capacity_tracks][3] */
+    int32_t* h_sightings;       /* [capacity_tracks] */
+    int32_t* h_kf_ptr;          /* [capacity_tracks + 1] */
+    int32_t* h_kf_pairs;        /* [capacity_pairs][2] */
+    /* the rest of tracks::Selection, each NULL = not wanted: per accepted track its index among the packed tracks (id
+     * order) and its parallax / required cosine; h_inconsistent [counts[2]] the packed indices the erase call will drop */
+    int32_t* h_track;           /* [capacity_tracks] */
+    float* h_parallax_cos;      /* [capacity_tracks] */
+    float* h_required_cos;      /* [capacity_tracks] */
+    int32_t* h_inconsistent;    /* [capacity_tracks] */
+} rs_track_results;
+/* Mapper::triangulate_tracks' loop (:246-305) from the store: the live tracks are packed on the device in ascending id
+ * order (the order of the reference's std::map) into rs_triangulate_tracks' inputs — d_track_uv from the frame's keypoints,
+ * d_skip from its match table (a track whose keypoint is outside the frame is skipped too), d_sight_ptr by a scan of the
+ * counts, d_sight_pose = frame index - pose_base, d_sight_uv — and rs_triangulate_tracks runs on them unchanged (its
+ * parameters as there; d_poses [n_poses][16] holds Trajectory::pose_at(pose_base + i)).  A track with a sighting outside
+ * [pose_base, pose_base + n_poses) is packed as skipped and counted in out_of_range.  The number of tracks is the live count
+ * the last rs_track_store_query read (no synchronisation of its own for it): a store changed since by carry or extend is
+ * refused with RS_ERR_INVALID.  `map` is not read (NULL is fine).  Window membership, is_matched checks, create_point and
+ * associate (:306-330) stay with the caller. */
+int rs_track_store_triangulate(rs_context* ctx, rs_track_store* store, rs_map* map, const rs_frame* frame, const float* d_poses,
+                               int n_poses, int pose_base, int kf_pose, const float h_intrinsics[4], float any_parallax_cosine,
+                               float max_reprojection_error, float min_parallax_cosine, float rotation_parallax_factor,
+                               int min_new_points, const float* d_required_by_pose, rs_track_results* results);
+/* The tracks.erase loop (:333-335) for the inconsistent tracks of the last rs_track_store_triangulate, on the device;
+ * nothing comes back.  Their keypoints get new tracks at the next extend.  Without a triangulate call since the store last
+ * changed it does nothing. */
+int rs_track_store_erase_inconsistent(rs_context* ctx, rs_track_store* store);
+/* Diagnostics (synchronise).  The live tracks in ascending id order: *h_n of them, *h_next_id the id counter, h_id [n],
+ * h_keypoint [n], h_count [n], h_sightings [n][max_sightings][5] 32-bit words {frame, x bits, y bits, key frame, keypoint}
+ * (the first h_count[t] of row t are written); arrays hold max_points rows, any may be NULL.
+ * rs_track_store_download_packed: the inputs the last rs_track_store_triangulate packed — h_track_uv [T][2], h_skip [T],
+ * h_sight_ptr [T + 1], and h_sight_pose [S] / h_sight_uv [S][2] when S <= capacity_sightings. */
+int rs_track_store_download(rs_context* ctx, const rs_track_store* store, int* h_n, uint64_t* h_next_id, uint64_t* h_id,
+                            int32_t* h_keypoint, int32_t* h_count, int32_t* h_sightings);
+int rs_track_store_download_packed(rs_context* ctx, const rs_track_store* store, int* h_n_tracks, int* h_n_sightings,
+                                   float* h_track_uv, uint8_t* h_skip, int32_t* h_sight_ptr, int32_t* h_sight_pose,
+                                   float* h_sight_uv, int capacity_sightings);
+
 /* (rs_map_bundle_adjust: see the optimisation section below) */
 
 /* ------------------------------------------------------ a5-a7: triangulation */

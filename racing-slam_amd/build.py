@@ -41,6 +41,7 @@ SOURCES = [
     ("map.hip", []),
     ("frame.hip", ["-ffp-contract=off"]),
     ("frame_matches.hip", ["-ffp-contract=off"]),
+    ("track_store.hip", ["-ffp-contract=off"]),
     ("host.cpp", ["-ffp-contract=off"]),
     ("pose_graph.cpp", ["-ffp-contract=off"]),
 ]

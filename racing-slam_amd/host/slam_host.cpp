@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -1220,6 +1221,165 @@ bool track_tail(rs_context* ctx, rs_map* map, const rs_frame* prev, rs_frame* ne
     std::printf("Number of map matches: %d\n", t.map_matches);
     if (out) *out = t;
     return true;
+}
+
+// ---------------------------------------------------------------------------------------------- TrackStore, host and device
+void HostTrackStore::carry_forward(const int32_t* prev_index, const int32_t* inlier_index, int n, int max_n, size_t max_points)
+{
+    std::map<uint64_t, StoredTrack> carried;
+    std::unordered_map<size_t, uint64_t> by_keypoint;
+    std::unordered_set<size_t> named;
+    const size_t lim = std::min((size_t)std::max(max_n, 0), max_points);
+    n = std::min(std::max(n, 0), std::max(max_n, 0));
+    by_keypoint.reserve((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const int64_t j = inlier_index ? inlier_index[i] : i;
+        if (j < 0 || (size_t)j >= lim) continue;
+        const int64_t q = prev_index[j];
+        if (q < 0) continue;
+        const auto existing = m_by_keypoint.find((size_t)q);
+        if (existing == m_by_keypoint.end()) continue;
+        if (!named.insert((size_t)q).second) continue;           // a later entry naming the same previous keypoint
+        if (by_keypoint.count((size_t)j)) continue;              // its current keypoint is taken: the track is dropped
+        auto track = m_tracks.find(existing->second);
+        track->second.keypoint_index = (size_t)j;
+        by_keypoint[(size_t)j] = existing->second;
+        carried.emplace(existing->second, std::move(track->second));
+    }
+    m_tracks = std::move(carried);
+    m_by_keypoint = std::move(by_keypoint);
+}
+
+void HostTrackStore::extend(const float* keypoints, size_t n, int frame_index, int key_frame, size_t max_sightings)
+{
+    for (size_t i = 0; i < n; i++) {
+        auto existing = m_by_keypoint.find(i);
+        if (existing == m_by_keypoint.end()) {
+            const uint64_t id = m_next_id++;
+            existing = m_by_keypoint.emplace(i, id).first;
+            StoredTrack t;
+            t.keypoint_index = i;
+            m_tracks.emplace(id, std::move(t));
+        }
+        auto& sightings = m_tracks.at(existing->second).sightings;
+        if (sightings.size() < max_sightings) {
+            StoredSighting s;
+            s.frame_index = frame_index; s.pixel = Vec2f{keypoints[2 * i], keypoints[2 * i + 1]};
+            s.key_frame = key_frame < 0 ? -1 : key_frame; s.keypoint_index = (int32_t)i;
+            sightings.push_back(s);
+        }
+    }
+}
+
+void HostTrackStore::erase(uint64_t id)
+{
+    const auto track = m_tracks.find(id);
+    if (track == m_tracks.end()) return;
+    m_by_keypoint.erase(track->second.keypoint_index);
+    m_tracks.erase(track);
+}
+
+size_t HostTrackStore::unmapped_tracks(const int32_t* table, size_t n, size_t min_sightings, float min_travel) const
+{
+    size_t count = 0;
+    for (const auto& [id, track] : m_tracks) {
+        (void)id;
+        if (track.sightings.size() < min_sightings) continue;
+        if (track.keypoint_index < n && table[track.keypoint_index] >= 0) continue;
+        const float dx = track.sightings.back().pixel.x - track.sightings.front().pixel.x;
+        const float dy = track.sightings.back().pixel.y - track.sightings.front().pixel.y;
+        const float xx = dx * dx, yy = dy * dy;
+        const float travel = std::sqrt(xx + yy);
+        if (travel < min_travel) continue;
+        count++;
+    }
+    return count;
+}
+
+DeviceTracks::DeviceTracks(rs_context* ctx, int max_points, int max_sightings) : m_ctx(ctx), m_max_points(max_points)
+{
+    const int rc = rs_track_store_create(ctx, max_points, max_sightings, &m_store);
+    if (rc != RS_OK) {
+        std::printf("rs_track_store_create failed (status %d): %s\n", rc, ctx ? rs_last_error(ctx) : "no context");
+        m_store = nullptr;
+        return;
+    }
+    m_i32.resize(6 * (size_t)max_points + 1 + 8 * (size_t)max_points);      // keypoint, sightings, kf_ptr, track, inconsistent | pairs
+    m_f32.resize(5 * (size_t)max_points);                                    // xyz, parallax, required
+}
+
+DeviceTracks::~DeviceTracks() { rs_track_store_destroy(m_store); }
+
+static bool tracks_fail(rs_context* ctx, int rc, const char* what)
+{
+    std::printf("%s failed (status %d): %s\n", what, rc, ctx ? rs_last_error(ctx) : "no context");
+    return false;
+}
+
+bool DeviceTracks::carry_forward(const int32_t* d_prev_index, const int32_t* d_inlier_index, const int32_t* d_inlier_count, int max_n)
+{
+    const int rc = rs_track_store_carry(m_ctx, m_store, d_prev_index, d_inlier_index, d_inlier_count, max_n);
+    return rc == RS_OK || tracks_fail(m_ctx, rc, "rs_track_store_carry");
+}
+
+bool DeviceTracks::needs_key_frame(rs_map* map, const rs_frame* frame, int last_key_frame, int frame_gap, int last_key_frame_matches,
+                                   bool* need, int32_t* query)
+{
+    int32_t q[6];
+    int rc = rs_track_store_query(m_ctx, m_store, map, frame, last_key_frame, 3, 20.0f, q);
+    if (rc != RS_OK) return tracks_fail(m_ctx, rc, "rs_track_store_query");
+    int out = 0;
+    if ((rc = rs_needs_key_frame(q, frame_gap, last_key_frame_matches, 20, 200, 50, 0.7f, &out)) != RS_OK) return tracks_fail(m_ctx, rc, "rs_needs_key_frame");
+    if (need) *need = out != 0;
+    if (query) memcpy(query, q, sizeof q);
+    return true;
+}
+
+bool DeviceTracks::extend(const rs_frame* frame, int frame_index, int key_frame)
+{
+    const int rc = rs_track_store_extend(m_ctx, m_store, frame, frame_index, key_frame);
+    return rc == RS_OK || tracks_fail(m_ctx, rc, "rs_track_store_extend");
+}
+
+bool DeviceTracks::triangulate_tracks(const rs_frame* frame, const float* d_poses, int n_poses, int pose_base, int kf_pose, const Camera& camera,
+                                      const float* d_required, DeviceTrackSelection* out, size_t min_new_points)
+{
+    const size_t T = (size_t)m_max_points;
+    rs_track_results r{};
+    r.capacity_tracks = m_max_points; r.capacity_pairs = 4 * m_max_points;
+    r.h_keypoint = m_i32.data(); r.h_sightings = r.h_keypoint + T; r.h_kf_ptr = r.h_sightings + T; r.h_track = r.h_kf_ptr + T + 1;
+    r.h_inconsistent = r.h_track + T; r.h_kf_pairs = r.h_inconsistent + T;
+    r.h_xyz = m_f32.data(); r.h_parallax_cos = r.h_xyz + 3 * T; r.h_required_cos = r.h_parallax_cos + T;
+    const float K[4] = {camera.fx(), camera.fy(), camera.cx(), camera.cy()};
+    const int rc = rs_track_store_triangulate(m_ctx, m_store, nullptr, frame, d_poses, n_poses, pose_base, kf_pose, K, tracks::ANY_PARALLAX_COSINE,
+                                              tracks::TRACK_MAX_REPROJECTION_ERROR, tracks::TRACK_MIN_PARALLAX_COSINE,
+                                              tracks::ROTATION_PARALLAX_FACTOR, (int)min_new_points, d_required, &r);
+    if (rc != RS_OK) return tracks_fail(m_ctx, rc, "rs_track_store_triangulate");
+    if (r.n_pairs > r.capacity_pairs) { std::printf("triangulate_tracks: %d key-frame sightings, room for %d\n", r.n_pairs, r.capacity_pairs); return false; }
+    if (!out) return true;
+    *out = DeviceTrackSelection{};
+    out->out_of_range = (size_t)r.out_of_range; out->tracks = (size_t)r.n_tracks;
+    out->selection.topped_up = (size_t)r.counts[1];
+    for (int a = 0; a < r.counts[0]; a++) {
+        tracks::Candidate c;
+        c.track = (size_t)r.h_track[a];
+        c.position = Vec3f{r.h_xyz[3 * a], r.h_xyz[3 * a + 1], r.h_xyz[3 * a + 2]};
+        c.keypoint_index = (size_t)r.h_keypoint[a];
+        c.parallax_cosine = r.h_parallax_cos[a]; c.required_cosine = r.h_required_cos[a];
+        out->selection.accepted.push_back(c);
+        out->sightings.push_back((size_t)r.h_sightings[a]);
+        std::vector<KeyFrameSighting> ks;
+        for (int i = r.h_kf_ptr[a]; i < r.h_kf_ptr[a + 1]; i++) ks.push_back(KeyFrameSighting{r.h_kf_pairs[2 * i], r.h_kf_pairs[2 * i + 1]});
+        out->key_frame_sightings.push_back(std::move(ks));
+    }
+    for (int i = 0; i < r.counts[2]; i++) out->selection.inconsistent.push_back((size_t)r.h_inconsistent[i]);
+    return true;
+}
+
+bool DeviceTracks::erase_inconsistent()
+{
+    const int rc = rs_track_store_erase_inconsistent(m_ctx, m_store);
+    return rc == RS_OK || tracks_fail(m_ctx, rc, "rs_track_store_erase_inconsistent");
 }
 
 }  // namespace slam

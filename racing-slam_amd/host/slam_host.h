@@ -11,6 +11,8 @@
 // There is no CPU fallback: without a GPU the Session constructor throws.
 #pragma once
 #include <array>
+#include <map>
+#include <unordered_map>
 #include <cstddef>
 #include <cstdint>
 #include <memory>
@@ -346,6 +348,65 @@ struct TrackTail {
 bool track_tail(rs_context* ctx, rs_map* map, const rs_frame* prev, rs_frame* next, const int32_t* d_prev_index,
                 const int32_t* d_inlier_index, const int32_t* d_inlier_count, int max_n, const Camera& camera, bool optimize,
                 TrackTailConstraint* constraint, int last_key_frame, Mat4f& pose, TrackTail* out);
+
+// TrackStore (src/TrackStore.h:17-45) on plain types, in the list form the device lists have: the three operations on a
+// std::map<id, track> as tests/trackstore_ref.py specifies them.  It is what a host caller would run after downloading the
+// lists, the keypoints and the match table, and what DeviceTracks below is held against (tests/test_trackstore_host.py,
+// tools/trackstore_time.py).
+struct StoredSighting { int32_t frame_index = 0; Vec2f pixel; int32_t key_frame = -1; int32_t keypoint_index = 0; };
+struct StoredTrack { std::vector<StoredSighting> sightings; size_t keypoint_index = 0; };
+class HostTrackStore {
+  public:
+    // entry i: current keypoint j = inlier_index[i] (null: i), previous keypoint prev_index[j]; n entries, lists of max_n.
+    // The first entry naming a previous keypoint decides for its track; if its current keypoint is taken, the track is dropped.
+    void carry_forward(const int32_t* prev_index, const int32_t* inlier_index, int n, int max_n, size_t max_points = 8192);
+    void extend(const float* keypoints /*[n][2]*/, size_t n, int frame_index, int key_frame, size_t max_sightings);
+    void erase(uint64_t id);
+    const std::map<uint64_t, StoredTrack>& tracks() const { return m_tracks; }
+    uint64_t next_id() const { return m_next_id; }
+    // Mapper::unmapped_tracks (src/Mapper.cpp:103-120) against a match table [n] (point slot or -1)
+    size_t unmapped_tracks(const int32_t* table, size_t n, size_t min_sightings = 3, float min_travel = 20.0f) const;
+
+  private:
+    std::map<uint64_t, StoredTrack> m_tracks;
+    std::unordered_map<size_t, uint64_t> m_by_keypoint;
+    uint64_t m_next_id = 0;
+};
+
+// The same store on the device (rs_track_store): Slam::step's three call sites and Mapper::triangulate_tracks' loop on the
+// front end's device lists.  Per frame: carry_forward, needs_key_frame (the one 24-byte read-back), extend.
+struct KeyFrameSighting { int32_t key_frame = -1; int32_t keypoint_index = 0; };
+struct DeviceTrackSelection {
+    tracks::Selection selection;                 // Candidate::track / inconsistent: positions among the live tracks in id order
+    std::vector<size_t> sightings;               // per accepted track (the >= 3 rule of src/Mapper.cpp:326)
+    std::vector<std::vector<KeyFrameSighting>> key_frame_sightings;     // per accepted track, sighting order
+    size_t out_of_range = 0, tracks = 0;
+};
+class DeviceTracks {
+  public:
+    DeviceTracks(rs_context* ctx, int max_points = 8192, int max_sightings = 100);
+    ~DeviceTracks();
+    DeviceTracks(const DeviceTracks&) = delete;
+    DeviceTracks& operator=(const DeviceTracks&) = delete;
+    bool valid() const { return m_store != nullptr; }
+    rs_track_store* store() const { return m_store; }
+    bool carry_forward(const int32_t* d_prev_index, const int32_t* d_inlier_index, const int32_t* d_inlier_count, int max_n);
+    // Mapper::needs_key_frame (src/Mapper.cpp:122-140) with the reference's constants; query (null = not wanted) gets the six integers
+    bool needs_key_frame(rs_map* map, const rs_frame* frame, int last_key_frame, int frame_gap, int last_key_frame_matches, bool* need,
+                         int32_t* query = nullptr);
+    bool extend(const rs_frame* frame, int frame_index, int key_frame);
+    // d_poses [n_poses][16] = Trajectory::pose_at(pose_base + i), kf_pose the key frame's entry; d_required as rs_triangulate_tracks
+    bool triangulate_tracks(const rs_frame* frame, const float* d_poses, int n_poses, int pose_base, int kf_pose, const Camera& camera,
+                            const float* d_required, DeviceTrackSelection* out, size_t min_new_points = tracks::MIN_NEW_POINTS_PER_KEY_FRAME);
+    bool erase_inconsistent();
+
+  private:
+    rs_context* m_ctx = nullptr;
+    rs_track_store* m_store = nullptr;
+    int m_max_points = 0;
+    std::vector<int32_t> m_i32;                  // result arrays, made once
+    std::vector<float> m_f32;
+};
 
 // LoopDetector::query's "Loop retrieval" stage (src/LoopDetector.cpp:346-373 Impl::score_candidates, :231-265
 // rank_candidates) on the device, as specified by tests/bow_ref.py: the DBoW2 vocabulary, one rs_bow and the database of

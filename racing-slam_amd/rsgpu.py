@@ -21,6 +21,9 @@ EXPORTS = [
     "rs_frame_create_device", "rs_frame_assign_device", "rs_frame_download",
     "rs_frame_matches_clear", "rs_frame_matches_add", "rs_frame_matches_download",
     "rs_map_set_track_consistent", "rs_map_carry_matches", "rs_map_refine_pose", "rs_map_match_frame",
+    "rs_track_store_create", "rs_track_store_destroy", "rs_track_store_clear", "rs_track_store_carry", "rs_track_store_extend",
+    "rs_track_store_query", "rs_needs_key_frame", "rs_track_store_triangulate", "rs_track_store_erase_inconsistent",
+    "rs_track_store_download", "rs_track_store_download_packed",
     "rs_map_add_keyframe", "rs_map_set_keyframe_pose", "rs_map_add_point", "rs_map_set_position", "rs_map_remove_point",
     "rs_map_add_observation", "rs_map_remove_observation", "rs_map_counts", "rs_map_get_positions", "rs_map_match", "rs_map_pose_graph", "rs_pose_graph", "rs_pose_relative", "rs_transform_points", "rs_map_bundle_adjust", "rs_map_window", "rs_triangulate", "rs_triangulate_host", "rs_triangulate_matches", "rs_triangulate_matches_batch", "rs_triangulate_tracks", "rs_parallax_requirements", "rs_point_errors", "rs_ba_default_options",
     "rs_bundle_adjust", "rs_bundle_adjust_batch", "rs_ba_get_trace", "rs_ba_get_stats", "rs_ba_get_cameras", "rs_reanchor_points", "rs_reanchor_points_host_poses", "rs_refine_pose", "rs_bundle_adjust_inertial", "rs_refine_pose_inertial", "rs_pack_pose", "rs_unpack_pose", "rs_pack_poses", "rs_unpack_poses", "rs_build_local_window",
@@ -1329,6 +1332,118 @@ class DeviceFrame(_FrameMatches):
         if self.h:
             self.ctx.lib.rs_frame_destroy(self.h)
             self.h = C.c_void_p()
+
+
+class TrackResults(C.Structure):
+    _fields_ = [("capacity_tracks", C.c_int), ("capacity_pairs", C.c_int), ("counts", C.c_int32 * 3), ("out_of_range", C.c_int32),
+                ("n_tracks", C.c_int32), ("n_pairs", C.c_int32), ("h_keypoint", C.c_void_p), ("h_xyz", C.c_void_p),
+                ("h_sightings", C.c_void_p), ("h_kf_ptr", C.c_void_p), ("h_kf_pairs", C.c_void_p), ("h_track", C.c_void_p),
+                ("h_parallax_cos", C.c_void_p), ("h_required_cos", C.c_void_p), ("h_inconsistent", C.c_void_p)]
+
+
+QUERY_FIELDS = ("covisible", "num_map_matches", "waiting", "live", "first_frame", "next_id_low")
+
+
+def needs_key_frame(query, frame_gap, last_key_frame_matches, max_key_frame_gap=20, new_tracks_threshold=200,
+                    min_covisible_points=50, min_covisible_fraction=0.7):
+    """Mapper::needs_key_frame's decision on TrackStore.query's six integers (host only: no context, no device)."""
+    q = (C.c_int32 * 6)(*[int(query[k]) for k in QUERY_FIELDS] if isinstance(query, dict) else [int(v) for v in query])
+    out = C.c_int(-1)
+    rc = load().rs_needs_key_frame(q, int(frame_gap), int(last_key_frame_matches), int(max_key_frame_gap), int(new_tracks_threshold),
+                                   int(min_covisible_points), C.c_float(min_covisible_fraction), C.byref(out))
+    if rc:
+        raise RsError(f"rs_needs_key_frame -> status {rc}")
+    return bool(out.value)
+
+
+class TrackStore:
+    """rs_track_store: TrackStore and the key-frame decision's counts on the device; every method is one C-ABI call."""
+
+    def __init__(self, ctx, max_points=8192, max_sightings=100):
+        self.ctx, self.lib, self.max_points, self.max_sightings = ctx, ctx.lib, int(max_points), int(max_sightings)
+        self.h, self._out = C.c_void_p(), None
+        ctx._check(self.lib.rs_track_store_create(ctx.h, self.max_points, self.max_sightings, C.byref(self.h)), "rs_track_store_create")
+
+    def close(self):
+        if self.h:
+            self.lib.rs_track_store_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def clear(self):
+        self.ctx._check(self.lib.rs_track_store_clear(self.ctx.h, self.h), "rs_track_store_clear")
+
+    def carry(self, d_prev_index, d_inlier_index=None, d_count=None, max_n=None):
+        """TrackStore::carry_forward on rs_track_features' kept-index list and rs_estimate_pose's inlier list; nothing comes back."""
+        n = int(d_prev_index.shape[0]) if max_n is None else int(max_n)
+        self.ctx._check(self.lib.rs_track_store_carry(self.ctx.h, self.h, _dp(d_prev_index), _dp(d_inlier_index), _dp(d_count), n),
+                        "rs_track_store_carry")
+
+    def extend(self, frame, frame_index, key_frame=-1):
+        self.ctx._check(self.lib.rs_track_store_extend(self.ctx.h, self.h, frame.h, int(frame_index), int(key_frame)), "rs_track_store_extend")
+
+    def query(self, frame, map_=None, last_key_frame=-1, min_sightings=3, min_travel=20.0):
+        """The path's one read-back per frame: dict of QUERY_FIELDS."""
+        out = (C.c_int32 * 6)()
+        self.ctx._check(self.lib.rs_track_store_query(self.ctx.h, self.h, None if map_ is None else map_.h, frame.h, int(last_key_frame),
+                                                      int(min_sightings), C.c_float(min_travel), out), "rs_track_store_query")
+        return dict(zip(QUERY_FIELDS, [int(v) for v in out]))
+
+    def triangulate(self, frame, d_poses, pose_base, kf_pose, K, map_=None, any_parallax_cosine=1.0, max_reproj=4.0,
+                    min_parallax_cosine=0.999848, rotation_parallax_factor=0.20, min_new_points=100, d_required=None,
+                    capacity_pairs=None):
+        """Mapper::triangulate_tracks' loop from the store.  Returns dict(counts [3], out_of_range, n_tracks, n_pairs and, per
+        accepted track, keypoint, xyz, sightings, kf_ptr, kf_pairs [n_pairs][2])."""
+        T = self.max_points
+        cp = 4 * T if capacity_pairs is None else int(capacity_pairs)
+        if self._out is None or self._out[0] != cp:            # the host arrays are made once, not per key frame
+            self._out = (cp, np.zeros(T, np.int32), np.zeros((T, 3), np.float32), np.zeros(T, np.int32), np.zeros(T + 1, np.int32),
+                         np.zeros((max(cp, 1), 2), np.int32), np.zeros(T, np.int32), np.zeros(T, np.float32), np.zeros(T, np.float32),
+                         np.zeros(T, np.int32))
+        _, kp, xyz, ns, ptr, pairs, trk, pc, rc, inc = self._out
+        r = TrackResults(capacity_tracks=T, capacity_pairs=cp, h_keypoint=kp.ctypes.data, h_xyz=xyz.ctypes.data, h_sightings=ns.ctypes.data,
+                         h_kf_ptr=ptr.ctypes.data, h_kf_pairs=pairs.ctypes.data, h_track=trk.ctypes.data, h_parallax_cos=pc.ctypes.data,
+                         h_required_cos=rc.ctypes.data, h_inconsistent=inc.ctypes.data)
+        Kc = (C.c_float * 4)(*[float(v) for v in K])
+        self.ctx._check(self.lib.rs_track_store_triangulate(
+            self.ctx.h, self.h, None if map_ is None else map_.h, frame.h, _dp(d_poses), int(d_poses.shape[0]), int(pose_base), int(kf_pose), Kc,
+            C.c_float(any_parallax_cosine), C.c_float(max_reproj), C.c_float(min_parallax_cosine), C.c_float(rotation_parallax_factor),
+            int(min_new_points), None if d_required is None else _dp(d_required), C.byref(r)), "rs_track_store_triangulate")
+        na = max(min(int(r.counts[0]), int(r.n_tracks)), 0)
+        return dict(counts=np.array(list(r.counts), np.int32), out_of_range=int(r.out_of_range), n_tracks=int(r.n_tracks), n_pairs=int(r.n_pairs),
+                    keypoint=kp[:na].copy(), xyz=xyz[:na].copy(), sightings=ns[:na].copy(), kf_ptr=ptr[:na + 1].copy(),
+                    kf_pairs=pairs[:min(int(r.n_pairs), cp)].copy(), track=trk[:na].copy(), parallax_cos=pc[:na].copy(),
+                    required_cos=rc[:na].copy(), inconsistent=inc[:max(min(int(r.counts[2]), int(r.n_tracks)), 0)].copy())
+
+    def erase_inconsistent(self):
+        self.ctx._check(self.lib.rs_track_store_erase_inconsistent(self.ctx.h, self.h), "rs_track_store_erase_inconsistent")
+
+    def download(self):
+        """Diagnostic (synchronises): the live tracks in id order — dict(n, next_id, id [n] u64, keypoint [n], count [n],
+        sightings [n][max_sightings] records (frame, x, y, kf, kp); entries past count[t] are zero)."""
+        T, S = self.max_points, self.max_sightings
+        n, nxt = C.c_int(0), C.c_uint64(0)
+        ids, kp, cnt = np.zeros(T, np.uint64), np.zeros(T, np.int32), np.zeros(T, np.int32)
+        sg = np.zeros((T, S), SIGHTING_DTYPE)
+        self.ctx._check(self.lib.rs_track_store_download(self.ctx.h, self.h, C.byref(n), C.byref(nxt), ids.ctypes.data_as(C.c_void_p),
+                                                         kp.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p),
+                                                         sg.ctypes.data_as(C.c_void_p)), "rs_track_store_download")
+        k = n.value
+        return dict(n=k, next_id=int(nxt.value), id=ids[:k].copy(), keypoint=kp[:k].copy(), count=cnt[:k].copy(), sightings=sg[:k].copy())
+
+    def packed(self):
+        """Diagnostic (synchronises): rs_triangulate_tracks' inputs as the last triangulate call packed them."""
+        nt, ns = C.c_int(0), C.c_int(0)
+        T, S = self.max_points, self.max_points * self.max_sightings
+        uv, skip, ptr = np.zeros((T, 2), np.float32), np.zeros(T, np.uint8), np.zeros(T + 1, np.int32)
+        pose, suv = np.zeros(S, np.int32), np.zeros((S, 2), np.float32)
+        self.ctx._check(self.lib.rs_track_store_download_packed(
+            self.ctx.h, self.h, C.byref(nt), C.byref(ns), uv.ctypes.data_as(C.c_void_p), skip.ctypes.data_as(C.c_void_p),
+            ptr.ctypes.data_as(C.c_void_p), pose.ctypes.data_as(C.c_void_p), suv.ctypes.data_as(C.c_void_p), S), "rs_track_store_download_packed")
+        t, s = nt.value, ns.value
+        return dict(track_uv=uv[:t].copy(), skip=skip[:t].copy(), sight_ptr=ptr[:t + 1].copy(), sight_pose=pose[:s].copy(), sight_uv=suv[:s].copy())
+
+
+SIGHTING_DTYPE = np.dtype([("frame", np.int32), ("x", np.float32), ("y", np.float32), ("kf", np.int32), ("kp", np.int32)])
 
 
 class ResidentMap:

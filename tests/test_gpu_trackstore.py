@@ -1,0 +1,305 @@
+"""rs_track_store (racing-slam_amd/csrc/track_store.hip) against tests/trackstore_ref.py: after every frame the store is
+downloaded and its ids, keypoint indices, counts and sightings equal the specification's (integers byte for byte, pixels
+bit for bit); the query's six integers; the packed inputs and the results of the triangulate call against
+rs_triangulate_tracks on arrays built on the host; erase and row reuse; the refusals."""
+import numpy as np
+import pytest
+
+import trackstore_ref as R
+from conftest import to_np
+from test_gpu_track import SimpleMap, i32, set_table
+
+pytestmark = pytest.mark.gpu
+
+
+def make_frame(ctx, rs, pixels):
+    pixels = np.ascontiguousarray(pixels, np.float32)
+    return rs.ResidentFrame(ctx, pixels, np.zeros((len(pixels), 32), np.uint8))
+
+
+class Pair:
+    """the device store and the specification, stepped together"""
+
+    def __init__(self, ctx, rs, cap, max_sightings):
+        self.ctx, self.rs = ctx, rs
+        self.dev, self.ref = rs.TrackStore(ctx, cap, max_sightings), R.Store(cap, max_sightings)
+        assert rs.SIGHTING_DTYPE == R.SIGHTING
+
+    def carry(self, prev, inlier=None, count=None, max_n=None):
+        self.dev.carry(i32(self.ctx, prev), None if inlier is None else i32(self.ctx, inlier), None if count is None else i32(self.ctx, [count]),
+                       max_n)
+        self.ref.carry(prev, inlier, count, len(prev) if max_n is None else max_n)
+
+    def extend(self, pixels, frame_index, key_frame=-1):
+        f = make_frame(self.ctx, self.rs, pixels)
+        self.dev.extend(f, frame_index, key_frame)
+        f.close()
+        self.ref.extend(pixels, frame_index, key_frame)
+
+    def check(self):
+        d, r = self.dev.download(), self.ref
+        assert d["n"] == len(r.id) and d["next_id"] == r.next_id
+        assert d["id"].tobytes() == r.id.tobytes() and d["keypoint"].tobytes() == r.keypoint.tobytes() and d["count"].tobytes() == r.count.tobytes()
+        sel = np.arange(r.max_sightings)[None, :] < r.count[:, None]
+        assert d["sightings"][sel].tobytes() == r.sightings[sel].tobytes()
+        return d
+
+    def close(self):
+        self.dev.close()
+
+
+def monotone_lists(rng, n_prev, n_next, keep=0.8, inliers=0.7):
+    """rs_track_features' kept-index list (ascending previous keypoints) and an ascending inlier list into it"""
+    m = min(n_next, int(rng.binomial(n_prev, keep)))
+    prev = np.sort(rng.choice(n_prev, m, replace=False)).astype(np.int32)
+    return prev, np.flatnonzero(rng.random(m) < inliers).astype(np.int32)
+
+
+SEQUENCES = [
+    ([1, 2, 63, 64, 65, 257, 2000, 8192, 2000, 257], 3, False),
+    ([65, 64, 63, 257, 2000, 257, 64, 2, 1, 65, 8192, 63], 1, False),
+    ([257, 2000, 257, 65, 64, 63, 2000, 2], 2, True),
+    ([2000, 8192, 8192, 2000, 257, 1, 2, 2000], 100, False),
+]
+
+
+@pytest.mark.parametrize("ns,max_sightings,repeats", SEQUENCES)
+def test_sequence_equals_the_specification(ctx, rs, ns, max_sightings, repeats):
+    rng = np.random.default_rng([len(ns), max_sightings])
+    p = Pair(ctx, rs, 8192, max_sightings)
+    n_prev, disorder, capped = 0, False, False
+    for frame, n in enumerate(ns):
+        if frame:
+            prev, inl = monotone_lists(rng, n_prev, n)
+            m = len(prev)
+            if repeats:                                    # repeated previous keypoints and repeated current keypoints
+                prev = rng.integers(0, max(1, n_prev // 2), m).astype(np.int32)
+                inl = rng.integers(0, max(1, m), m + 7).astype(np.int32)
+            form = frame % 6
+            if form == 1:
+                p.carry(prev, inl, len(inl), m)
+            elif form == 2:
+                p.carry(prev, None, None, m)               # d_inlier_index = NULL, d_count = NULL
+            elif form == 3:                                # a count above max_n; junk entries on both sides
+                prev[rng.random(m) < 0.1] = rng.choice([-1, n_prev, 8192, 2 ** 30, -2 ** 31])
+                full = np.concatenate([inl, rng.choice([-1, m, m + 3, 8192, 2 ** 30], max(m - len(inl), 0) + 1)])[:max(m, 1)].astype(np.int32)
+                rng.shuffle(full)
+                p.carry(prev, full if m else None, m + 50, m)
+            elif form == 4:
+                p.carry(prev, inl, -7, m)                  # a negative count: n = 0 drops everything
+                assert len(p.ref.id) == 0
+            elif form == 5:
+                p.carry(prev, inl[:0] if m == 0 else inl, 0, m)      # an empty inlier list
+            else:
+                p.carry(prev, inl, len(inl), m)
+            d = p.check()
+        pixels = rng.uniform(0, 700, (n, 2)).astype(np.float32)
+        p.extend(pixels, 10 + frame, frame // 3 if frame % 3 == 0 else -1)
+        d = p.check()
+        assert d["n"] >= n
+        disorder |= bool(np.any(np.diff(d["keypoint"]) < 0))
+        capped |= bool(np.any(d["count"] == max_sightings))
+        n_prev = n
+    assert disorder, "no sequence point at which id order differs from keypoint order"
+    assert capped or max_sightings == 100
+    p.close()
+
+
+def test_rejected_keypoints_in_the_middle_get_larger_ids(ctx, rs):
+    """tracked-but-rejected keypoints: KLT kept all of 0 .. 99, RANSAC rejected 40 .. 59"""
+    p = Pair(ctx, rs, 128, 4)
+    rng = np.random.default_rng(5)
+    p.extend(rng.uniform(0, 100, (100, 2)).astype(np.float32), 0)
+    inl = np.concatenate([np.arange(40), np.arange(60, 100)]).astype(np.int32)
+    p.carry(np.arange(100, dtype=np.int32), inl, len(inl), 100)
+    p.extend(rng.uniform(0, 100, (100, 2)).astype(np.float32), 1)
+    d = p.check()
+    assert d["keypoint"].tolist() == list(range(40)) + list(range(60, 100)) + list(range(40, 60))
+    assert d["id"].tolist() == list(range(40)) + list(range(60, 120))
+    p.close()
+
+
+def test_query_counts(ctx, rs):
+    rng = np.random.default_rng(11)
+    P, cap = 40, 64
+    n_obs = rng.integers(0, 4, P)
+    dead = [3, 17, 30]
+    sm = SimpleMap(ctx, rs, rng.uniform(-1, 1, (P, 3)).astype(np.float32), n_obs, dead=dead)
+    p = Pair(ctx, rs, cap, 8)
+    # tracks 0 .. 15 move by (12 - k ulps, 16): travel is exactly 20 for k = 0 and falls below it within a few ulps;
+    # tracks born in frame 1 hold min_sightings - 1 sightings at the query, those of frame 0 exactly min_sightings
+    base = rng.uniform(50, 60, (24, 2)).astype(np.float32)
+    base[:16] = 0.0
+    p.extend(base[:20], 0)
+    p.carry(np.arange(20, dtype=np.int32))
+    p.extend(base, 1)
+    p.carry(np.arange(24, dtype=np.int32))
+    moved = base.copy()
+    x = np.float32(12.0)
+    for k in range(16):
+        moved[k] = (x, 16.0)
+        x = np.nextafter(x, np.float32(0))
+    moved[16:20] += np.float32(30.0)
+    moved[20:] += np.float32(30.0)
+    p.extend(moved, 2)
+    p.check()
+    travel = p.ref.travel()[:16]
+    below = np.nextafter(np.float32(20.0), np.float32(0))
+    assert travel[0] == np.float32(20.0) and travel[2] == below and np.all(travel[2:] < np.float32(20.0))
+    assert sorted(set(p.ref.count.tolist())) == [2, 3]
+    table = np.full(24, -1, np.int32)
+    table[[1, 17, 21, 22, 23]] = [0, 3, 5, 17, 39]                     # matched keypoints; 3 and 17 are dead slots
+    table[[8, 9, 10, 11]] = [8, 9, 10, 11]
+    fr = make_frame(ctx, rs, moved)
+    set_table(ctx, fr, table)
+    for last_kf in (-1, 0, 1, 2):
+        cov = (sm.alive > 0) & (sm.n_obs > last_kf) if last_kf >= 0 else np.zeros(P, bool)
+        want = p.ref.query(table, cov, 3, 20.0)
+        got = p.dev.query(fr, sm.map, last_kf, 3, 20.0)
+        assert got == want, (last_kf, got, want)
+    # of tracks 0 .. 15 only track 0 (exactly 20.0, unmatched) waits: track 1 is matched, track 2 (one ulp below, unmatched)
+    # and the rest are below; 16, 18 and 19 moved far and are unmatched, 17 is matched, 20 .. 23 hold two sightings
+    assert table[0] < 0 and table[2] < 0 and want["waiting"] == 4 and want["num_map_matches"] == 9 and want["first_frame"] == 0
+    nudged = moved.copy()
+    nudged[2, 0] = np.float32(12.0)                      # the one-ulp-below track at exactly 20.0: one more waits
+    f2 = make_frame(ctx, rs, nudged)
+    set_table(ctx, f2, table)
+    p.dev.carry(i32(ctx, np.arange(24)), None, i32(ctx, [0]), 24)
+    p.ref.carry(np.arange(24, dtype=np.int32), None, 0, 24)
+    for k, pix in enumerate((base[:20], base, nudged)):
+        p.extend(pix, k)
+        if k < 2:
+            p.carry(np.arange(len(pix), dtype=np.int32))
+    p.check()
+    again = p.dev.query(f2, sm.map, 2, 3, 20.0)
+    assert again == p.ref.query(table, cov, 3, 20.0) and again["waiting"] == 5
+    f2.close()
+    assert p.dev.query(fr, None, 0, 3, 20.0) == p.ref.query(table, np.zeros(0, bool), 3, 20.0)       # no map: nothing covisible
+    assert p.dev.query(fr, sm.map, 0, 2, 0.0) == p.ref.query(table, (sm.alive > 0) & (sm.n_obs > 0), 2, 0.0)
+    fr.close(); p.close(); sm.close()
+
+
+def scene(rng, n, frames):
+    """static points in front of a camera moving along x: pixels per frame, poses, intrinsics"""
+    K = (500.0, 500.0, 320.0, 240.0)
+    X = np.stack([rng.uniform(-2, 2, n), rng.uniform(-1.5, 1.5, n), rng.uniform(4, 9, n)], axis=1)
+    poses = np.tile(np.eye(4, dtype=np.float32), (frames, 1, 1))
+    pix = np.zeros((frames, n, 2), np.float32)
+    for f in range(frames):
+        poses[f, 0, 3] = -0.15 * f
+        pix[f, :, 0] = K[0] * (X[:, 0] - 0.15 * f) / X[:, 2] + K[2]
+        pix[f, :, 1] = K[1] * X[:, 1] / X[:, 2] + K[3]
+    return pix, poses.reshape(frames, 16), K
+
+
+def test_triangulate_and_erase(ctx, rs):
+    rng = np.random.default_rng(21)
+    n, F = 300, 7
+    pix, poses, K = scene(rng, n, F + 1)
+    pix[3, 100:130] += np.float32(25.0)                    # a bad sighting in frame 3: those tracks are inconsistent
+    p = Pair(ctx, rs, 512, 16)
+    ident = np.arange(n, dtype=np.int32)
+    p.extend(pix[0], 0, 0)                                 # frame 0 is key frame 0
+    p.carry(ident, np.array([5], np.int32), 1, n)          # only keypoint 5's track survives into frame 1
+    p.extend(pix[1], 1)
+    for f in range(2, F):
+        inl = np.flatnonzero((rng.random(n) < 0.93) | (ident == 5) | ((ident >= 100) & (ident < 130))).astype(np.int32)
+        p.carry(ident, inl, len(inl), n)
+        p.extend(pix[f], f, 1 if f == 4 else -1)           # frame 4 is key frame 1
+    inl = np.flatnonzero(rng.random(n) < 0.95).astype(np.int32)
+    inl = np.union1d(inl, np.concatenate([[5], np.arange(100, 130)])).astype(np.int32)
+    p.carry(ident, inl, len(inl), n)
+    d = p.check()
+    assert np.any(np.diff(d["keypoint"]) < 0)
+    table = np.full(n, -1, np.int32)
+    table[130 + rng.choice(n - 130, 40, replace=False)] = np.arange(40)
+    table[5] = -1
+    fr = make_frame(ctx, rs, pix[F])
+    set_table(ctx, fr, table)
+    with pytest.raises(rs.RsError):                        # the live count is not known after a carry
+        p.dev.triangulate(fr, ctx.dev(poses[1:]), 1, F - 1, K)
+    q = p.dev.query(fr)
+    T = len(p.ref.id)
+    assert q["live"] == T and q["first_frame"] == 0
+    got = p.dev.triangulate(fr, ctx.dev(poses[1:]), 1, F - 1, K)
+    want = p.ref.pack(table, pix[F], 1, F)
+    pk = p.dev.packed()
+    for name in ("track_uv", "skip", "sight_ptr", "sight_pose", "sight_uv"):
+        assert pk[name].tobytes() == want[name].tobytes(), name
+    assert got["out_of_range"] == want["out_of_range"] == 1 and got["n_tracks"] == T
+    assert want["skip"][list(p.ref.keypoint).index(5)] == 1
+    host = ctx.triangulate_tracks(ctx.dev(want["track_uv"]), ctx.dev(want["sight_ptr"]), ctx.dev(want["sight_pose"]), ctx.dev(want["sight_uv"]),
+                                  ctx.dev(poses[1:]), F - 1, K, d_skip=ctx.dev(want["skip"]))
+    counts = to_np(host["counts"])
+    acc, inc = to_np(host["accepted"])[:counts[0]], to_np(host["inconsistent"])[:counts[2]]
+    assert got["counts"].tobytes() == counts.tobytes() and counts[0] >= 100 and counts[2] >= 20
+    assert got["keypoint"].tobytes() == p.ref.keypoint[acc].tobytes()
+    assert got["xyz"].tobytes() == to_np(host["xyz"])[acc].tobytes()
+    assert got["sightings"].tobytes() == p.ref.count[acc].tobytes()
+    assert got["track"].tobytes() == acc.tobytes() and got["inconsistent"].tobytes() == inc.tobytes()
+    assert got["parallax_cos"].tobytes() == to_np(host["parallax_cos"])[acc].tobytes()
+    assert got["required_cos"].tobytes() == to_np(host["required_cos"])[acc].tobytes()
+    few = p.dev.triangulate(fr, ctx.dev(poses[1:]), 1, F - 1, K, capacity_pairs=3)          # a short pair array: n_pairs says so
+    assert few["n_pairs"] == got["n_pairs"] and few["kf_pairs"].tobytes() == got["kf_pairs"][:3].tobytes()
+    pairs = [p.ref.key_frame_pairs(t) for t in acc]
+    assert got["kf_ptr"].tolist() == np.concatenate([[0], np.cumsum([len(x) for x in pairs])]).tolist()
+    assert got["n_pairs"] == got["kf_ptr"][-1] > 0 and got["kf_pairs"].tobytes() == np.concatenate(pairs).astype(np.int32).tobytes()
+    # erase: the inconsistent tracks go, their rows are reused, and their keypoints get fresh ids in keypoint order
+    gone = np.sort(p.ref.keypoint[inc])
+    p.dev.erase_inconsistent()
+    p.ref.erase(inc)
+    p.check()
+    p.dev.erase_inconsistent()                             # a second call has nothing to apply
+    first_new = p.ref.next_id
+    p.extend(pix[F], F, 2)
+    d = p.check()
+    fresh = d["keypoint"][d["id"] >= first_new]
+    assert np.all(np.diff(fresh) > 0) and set(gone.tolist()) <= set(fresh.tolist())
+    assert p.dev.query(fr)["live"] == n
+    fr.close(); p.close()
+
+
+def test_rows_are_reused_under_churn(ctx, rs):
+    rng = np.random.default_rng(31)
+    p = Pair(ctx, rs, 64, 3)
+    n_prev = 0
+    for frame in range(40):
+        n = int(rng.integers(40, 65))
+        if frame:
+            prev, inl = monotone_lists(rng, n_prev, n, keep=0.6, inliers=0.5)
+            p.carry(prev, inl, len(inl), len(prev))
+            p.check()
+        p.extend(rng.uniform(0, 100, (n, 2)).astype(np.float32), frame)
+        d = p.check()
+        assert d["n"] == n
+        n_prev = n
+    assert p.ref.next_id > 10 * 64
+    p.close()
+
+
+def test_refusals(ctx, rs):
+    for bad in (0, 129, -1):
+        with pytest.raises(rs.RsError, match="status 4"):
+            rs.TrackStore(ctx, 64, bad)
+    for bad in (0, 8193):
+        with pytest.raises(rs.RsError, match="status 4"):
+            rs.TrackStore(ctx, bad, 4)
+    st = rs.TrackStore(ctx, 16, 2)
+    big = make_frame(ctx, rs, np.zeros((17, 2), np.float32))
+    with pytest.raises(rs.RsError, match="status 4"):      # a frame above the store's capacity
+        st.extend(big, 0)
+    with pytest.raises(rs.RsError, match="status 4"):
+        st.query(big)
+    other = rs.Context(0)
+    foreign = make_frame(other, rs, np.zeros((4, 2), np.float32))
+    with pytest.raises(rs.RsError, match="status 1"):      # a frame of another context
+        st.extend(foreign, 0)
+    with pytest.raises(rs.RsError, match="status 1"):
+        st.query(foreign)
+    with pytest.raises(rs.RsError, match="status 4"):      # a list beyond the envelope
+        st.carry(i32(ctx, np.zeros(8193)))
+    assert st.download()["n"] == 0                         # nothing was applied and the store still works
+    ok = make_frame(ctx, rs, np.ones((16, 2), np.float32))
+    st.extend(ok, 0)
+    assert st.query(ok)["live"] == 16
+    foreign.close(); other.close(); big.close(); ok.close(); st.close()
