@@ -695,6 +695,55 @@ int rs_map_window(rs_context* ctx, rs_map* map, const int32_t* h_kfs, const uint
                   int32_t* h_points, double* h_xyz, int32_t* h_obs_ptr, int32_t* h_obs_cam, float* h_obs_uv,
                   int cap_points, int cap_obs, int* h_n_points, int* h_n_obs);
 
+/* ---- Mapper::insert (src/Mapper.cpp:152-174) on the resident map.  With rs_track_store_triangulate, rs_track_store_
+ * erase_inconsistent and rs_map_bundle_adjust the five calls below take a key frame from "the tracker's frame with its device
+ * match table" to "inserted, adjusted, re-anchored, culled" without a host pass over map objects:
+ *   rs_map_insert_keyframe -> rs_track_store_triangulate -> rs_map_add_track_points -> rs_track_store_erase_inconsistent
+ *   -> rs_map_bundle_adjust -> rs_map_reanchor -> rs_map_cull_points.
+ *
+ * rs_map_insert_keyframe: rs_map_add_keyframe followed by the adoption loop (:157-159).  The frame's device match table is
+ * read back once (one synchronisation); in ascending keypoint order every entry whose point is alive is associated with the
+ * new key frame by rs_map_add_observation's rule (Map::associate: a point named by two keypoints ends up at the later one).
+ * An entry that names a removed slot, or a slot the map never had, is skipped (a dangling pointer in the reference).
+ * *out_kf = the handle, *h_n_adopted = the associations made.  RS_ERR_INVALID: null argument, a map or frame of another
+ * context. */
+int rs_map_insert_keyframe(rs_context* ctx, rs_map* map, const rs_frame* frame, const float h_pose[16], int* out_kf,
+                           int* h_n_adopted);
+/* Mapper::triangulate_tracks' creation loop (:310-331) for the accepted tracks of rs_track_store_triangulate's results, in
+ * their order.  Host only (mirror edits, no kernel, no synchronisation).  Per accepted track a: rs_map_add_point at h_xyz[a],
+ * associate it with key frame kf at h_keypoint[a] (Map::create_point, :312), then its key-frame sighting pairs (handle,
+ * keypoint) in sighting order: a pair is skipped when its handle is negative, equals kf, or is not in h_window_kfs [n_window]
+ * (:316-318), or when the observer already matches that keypoint or that point (:319-321); otherwise it is associated
+ * (:322).  h_sightings[a] >= 3 sets track-consistent (:326-329).  h_new_points [counts[0]] (NULL: not wanted) gets the new
+ * slots.  RS_ERR_INVALID with the map unchanged: n_pairs > capacity_pairs (the pairs are incomplete), counts[0] outside
+ * 0 .. capacity_tracks, an unknown key frame in the window list, a keypoint outside its key frame, a null array. */
+int rs_map_add_track_points(rs_map* map, int kf, const rs_track_results* results, const int32_t* h_window_kfs, int n_window,
+                            int32_t* h_new_points);
+/* The tail of Mapper::bundle_adjust (:379-393) on the device image: h_kfs [n_kfs] the OPTIMISED key frames of the window,
+ * h_before [n_kfs][16] their poses before the adjustment; "after" is the map's current pose.  One lane per point slot: a slot
+ * that is alive, has exactly one observation and whose observer is listed moves to
+ *     X' = R_after^T ((R_before X + t_before) - t_after)            (f32, rs_reanchor_points' body and operation order)
+ * in the image, in place; the moved slots come back in ascending order with their new positions through one read-back, the
+ * mirror takes them, and the caller gets them in h_out_points / h_out_xyz (`capacity` entries, either may be NULL;
+ * *h_n_points = how many there were, as rs_map_bundle_adjust).  The image stays current: the next use of the map uploads
+ * nothing.  RS_ERR_INVALID: an unknown key frame or one listed twice, a null list, a map of another context. */
+int rs_map_reanchor(rs_context* ctx, rs_map* map, const int32_t* h_kfs, const float* h_before, int n_kfs,
+                    int32_t* h_out_points, float* h_out_xyz, int capacity, int* h_n_points);
+/* Mapper::cull_points (:396-431) on the device image.  Local points (:398-408): alive and observed by a key frame of h_kfs
+ * [n_kfs] (the window's key frames plus the new one; the map keeps a key frame's match table and the points' observation
+ * lists consistent, so "matched by the frame" is "observed by it").  Per local point, over ALL of its observations in
+ * insertion order: err += sqrtf(dx dx + dy dy) of Camera::project under the observer's pose against its keypoint, in f32
+ * (rs_point_errors' body); culled when cnt > 0 && err / (float)cnt > max_mean_error (:420; the reference's
+ * MAX_POINT_REPROJECTION_ERROR is 3).  h_removed [capacity] the culled slots ascending, h_removed_xyz [capacity][3] (NULL:
+ * not wanted) their positions (diagnostics.culled, :426-428); *h_n_removed their number, *h_n_local (NULL: not wanted) the
+ * local points.  apply = 0 reports and changes nothing; apply = 1 removes each listed point as rs_map_remove_point does, in
+ * ascending order (the device image is re-flattened at its next use).  One synchronisation and one read-back per call.
+ * RS_ERR_INVALID: *h_n_removed > capacity (the count is reported, nothing is removed), an unknown key frame or one listed
+ * twice, a null argument, a map of another context. */
+int rs_map_cull_points(rs_context* ctx, rs_map* map, const int32_t* h_kfs, int n_kfs, const float h_intrinsics[4],
+                       float max_mean_error, int apply, int32_t* h_removed, float* h_removed_xyz, int capacity,
+                       int* h_n_removed, int* h_n_local);
+
 /* Throughput mode: B INDEPENDENT windows (several sessions / maps served by one GPU) in one call.  A local-window
  * solve is a chain of small dependent launches that leaves most of the 256 CUs idle.
  *   grid mode (default)  every kernel of the solve runs ONCE for all windows (grid z = window, per-window arguments in a

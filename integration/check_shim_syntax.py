@@ -215,6 +215,53 @@ class VideoCapture {};
 """
 
 
+# Mapper_insert.inc's three blocks spliced into skeletons of Mapper::insert, Mapper::bundle_adjust and Mapper::cull_points
+# (kept lines reduced to the declarations the blocks rely on), with the names the caller that owns the resident map
+# supplies declared as locals.
+MAPPER_INSERT_HARNESS = r"""
+#include <iostream>
+#include <unordered_map>
+#include "Mapper.h"
+#include "Frame.h"
+#include "Map.h"
+#include "MapPoint.h"
+#include "Optimization.h"
+#include "Slam.h"
+#include "TrackStore.h"
+#include "Trajectory.h"
+#include "rs_shim_common.h"
+namespace slam {
+namespace {
+constexpr size_t BA_WINDOW = 20;
+constexpr float MAX_POINT_REPROJECTION_ERROR = 3.0F;
+rs_map* resident_map = nullptr;
+std::vector<MapPoint*> resident_points;
+std::unordered_map<const Frame*, int32_t> resident_key_frames;
+rs_frame* resident_frame = nullptr;
+}
+std::shared_ptr<KeyFrame> Mapper::insert(Frame&& frame, TrackStore& tracks, const Trajectory& trajectory, FrameDiagnostics& diagnostics)
+{
+    auto key_frame = std::make_shared<KeyFrame>(std::move(frame));
+    for (const auto& match : key_frame->map_matches()) m_map.associate(*key_frame, match.point, match.keypoint_index);
+#define RS_MAPPER_INSERT_PART 1
+#include "Mapper_insert.inc"
+    return key_frame;
+}
+void Mapper::bundle_adjust(KeyFrame& key_frame, bool fix_oldest)
+{
+    std::vector<std::pair<Frame*, Eigen::Matrix4f>> anchors;
+#define RS_MAPPER_INSERT_PART 2
+#include "Mapper_insert.inc"
+}
+void Mapper::cull_points(FrameDiagnostics& diagnostics, KeyFrame& key_frame)
+{
+#define RS_MAPPER_INSERT_PART 3
+#include "Mapper_insert.inc"
+}
+}  // namespace slam
+"""
+
+
 def tracker_stubs(dst):
     """tests/shim_stubs/ copied to dst with the declarations the Tracker blocks need added to opencv2/core.hpp"""
     src = os.path.join(ROOT, "tests", "shim_stubs")
@@ -269,6 +316,14 @@ def main(argv):
         if r.returncode:
             print(r.stderr[-4000:])
             failed.append("Track tail .inc harness")
+        insert = os.path.join(d, "mapper_insert_harness.cpp")
+        with open(insert, "w") as fh:
+            fh.write(MAPPER_INSERT_HARNESS)
+        r = subprocess.run([cxx] + fl + [insert], capture_output=True, text=True)
+        print("%-26s %s" % ("Mapper insert .inc harness", "ok" if r.returncode == 0 else "FAILED"))
+        if r.returncode:
+            print(r.stderr[-4000:])
+            failed.append("Mapper insert .inc harness")
     sys.exit(1 if failed else 0)
 
 

@@ -39,6 +39,7 @@ SOURCES = [
     ("ba_update.hip", ["-munsafe-fp-atomics"]),
     ("ba_round.hip", ["-munsafe-fp-atomics"]),
     ("map.hip", []),
+    ("map_keyframe.hip", ["-ffp-contract=off"]),
     ("frame.hip", ["-ffp-contract=off"]),
     ("frame_matches.hip", ["-ffp-contract=off"]),
     ("track_store.hip", ["-ffp-contract=off"]),

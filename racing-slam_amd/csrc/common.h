@@ -151,6 +151,15 @@ int rs_refine_pose_device_n(rs_context* ctx, double h_camera[6], const double* d
                             const rs_imu_factor* h_delta, const double h_gravity[3], double h_velocity[3],
                             const rs_ba_options* options, rs_ba_summary* h_summary, int* h_n_used);
 
+// map_keyframe.hip: the per-key-frame stages over the resident image (P > 0 slots; d_sel [P] selection bytes; d_out 2 + 4 P words:
+// selected count, local count, the selected slots ascending, their positions).  Two launches each on the context stream.
+void rs_kf_launch_reanchor(rs_context* ctx, int P, const uint8_t* d_alive, const int32_t* d_obs_ptr, const int32_t* d_obs_kf,
+                           const int32_t* d_win_of_kf, const float* d_before, const float* d_poses, float* d_pos, uint8_t* d_sel,
+                           int32_t* d_out);
+void rs_kf_launch_cull(rs_context* ctx, int P, const uint8_t* d_alive, const int32_t* d_obs_ptr, const int32_t* d_obs_kf,
+                       const int32_t* d_obs_desc, const int32_t* d_win_of_kf, const float* d_poses, const float* d_kp_pool,
+                       const float* d_pos, const float h_intrinsics[4], float max_mean_error, uint8_t* d_sel, int32_t* d_out);
+
 #define RS_HIP(ctx, call)                                                                  \
     do {                                                                                   \
         hipError_t e__ = (call);                                                           \

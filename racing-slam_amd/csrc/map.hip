@@ -26,44 +26,27 @@
 #include <algorithm>
 
 #include "common.h"
+#include "map_mirror.h"
 
-struct MapObs { int32_t kf, kp; };
-
-struct MapKeyFrame {
-    int n = 0;
-    int pool_row = 0;                  // first row of its descriptors in the device pool
-    float pose[16];
-    std::vector<float> kp;             // [n][2]
-    std::vector<int32_t> kp_point;     // [n] point slot matched by keypoint i or -1 (Frame::map_matches)
-};
-
-struct rs_map {
+// (MapObs, MapKeyFrame and the mirror's fields and edits: map_mirror.h)
+struct rs_map : MapMirror {
     rs_context* ctx = nullptr;
-    // host mirror
-    std::vector<float> pos;                         // [P][3]
-    std::vector<uint8_t> alive;                     // [P]
-    std::vector<std::vector<MapObs>> obs;           // [P]
-    std::vector<MapKeyFrame> kfs;
-    int n_alive = 0;
-    bool dirty_topology = true, dirty_positions = true, dirty_centres = true;
     // device image
     float* d_pos = nullptr; uint8_t* d_alive = nullptr; int32_t* d_obs_ptr = nullptr;
     int32_t* d_obs_kf = nullptr; int32_t* d_obs_desc = nullptr; float* d_centres = nullptr;
+    float* d_poses = nullptr;                       // [KF][16] the key frames' poses (hipMalloc: 16-byte aligned for load_pose), uploaded with the centres
     uint8_t* d_pool = nullptr; uint8_t* d_elig = nullptr; uint8_t* d_flag = nullptr;
     float* d_kp_pool = nullptr;                     // [pool rows][2] keypoints of the key frames, row for row with the descriptor pool
     size_t cap_kp_pool = 0;
     int32_t* d_kp_point = nullptr;                  // [pool rows] point slot of each key-frame keypoint or -1, row for row with the pool:
     size_t cap_kp_point = 0, kp_point_rows = 0;     // rewritten after a topology change by rs_map_loop_sync, its only reader's entry
-    bool dirty_kp_point = true;
-    int32_t* d_win = nullptr; size_t cap_win = 0;   // scratch of rs_map_bundle_adjust: pid [P] | obs offset [P]
-    size_t cap_points = 0, cap_obs = 0, cap_kf = 0, cap_pool_bytes = 0, pool_rows = 0, n_obs = 0;
+    int32_t* d_win = nullptr; size_t cap_win = 0;   // scratch of rs_map_bundle_adjust: pid [P] | obs offset [P]; flags [P] of the key-frame stages
+    size_t cap_points = 0, cap_obs = 0, cap_kf = 0, cap_poses = 0, cap_pool_bytes = 0, pool_rows = 0, n_obs = 0;
     // scratch for match results
     int32_t* d_out = nullptr; size_t cap_out = 0;
     std::vector<int32_t> h_obs_ptr, h_obs_kf, h_obs_desc, h_kp_point;
-    std::vector<float> h_centres;
+    std::vector<float> h_centres, h_poses;
     // the tracker's per-frame stages (frame_matches.hip)
-    std::vector<uint8_t> consistent;                // [P] MapPoint::track_consistent
-    bool dirty_consistent = true;
     uint8_t* d_consistent = nullptr; uint32_t* d_mark = nullptr;    // [cap_points] both; d_mark all zero between calls
     double* d_gather = nullptr;                     // pts [8192][3] f64 | uv [8192][2] f32 | n: the refit's gathered problem
 };
@@ -104,7 +87,7 @@ extern "C" int rs_map_destroy(rs_map* m)
     (void)hipStreamSynchronize(m->ctx->stream);
     for (void* p : {(void*)m->d_pos, (void*)m->d_alive, (void*)m->d_obs_ptr, (void*)m->d_obs_kf, (void*)m->d_obs_desc,
                     (void*)m->d_centres, (void*)m->d_pool, (void*)m->d_elig, (void*)m->d_flag, (void*)m->d_out, (void*)m->d_kp_pool,
-                    (void*)m->d_win, (void*)m->d_kp_point, (void*)m->d_consistent, (void*)m->d_mark, (void*)m->d_gather})
+                    (void*)m->d_win, (void*)m->d_kp_point, (void*)m->d_consistent, (void*)m->d_mark, (void*)m->d_gather, (void*)m->d_poses})
         if (p) (void)hipFree(p);
     delete m;
     return RS_OK;
@@ -208,17 +191,11 @@ extern "C" int rs_map_set_keyframe_pose(rs_map* m, int kf, const float h_pose[16
 extern "C" int rs_map_add_point(rs_map* m, const float xyz[3], int* out_point)
 {
     if (!m || !xyz || !out_point) return RS_ERR_INVALID;
-    m->pos.insert(m->pos.end(), xyz, xyz + 3);
-    m->alive.push_back(1);
-    m->consistent.push_back(0);
-    m->obs.emplace_back();
-    m->n_alive++;
-    m->dirty_topology = m->dirty_positions = m->dirty_consistent = true;      // (the device flag of the new slot is not yet written)
-    *out_point = (int)m->alive.size() - 1;
+    *out_point = mirror_add_point(m, xyz);
     return RS_OK;
 }
 
-static bool point_ok(const rs_map* m, int p) { return p >= 0 && p < (int)m->alive.size() && m->alive[(size_t)p]; }
+static bool point_ok(const rs_map* m, int p) { return mirror_point_ok(m, p); }
 
 extern "C" int rs_map_set_position(rs_map* m, int point, const float xyz[3])
 {
@@ -230,52 +207,21 @@ extern "C" int rs_map_set_position(rs_map* m, int point, const float xyz[3])
 
 extern "C" int rs_map_remove_observation(rs_map* m, int point, int kf)
 {
-    if (!m || !point_ok(m, point) || kf < 0 || kf >= (int)m->kfs.size()) return RS_ERR_INVALID;
-    auto& v = m->obs[(size_t)point];
-    for (size_t i = 0; i < v.size(); i++)
-        if (v[i].kf == kf) {
-            auto& tab = m->kfs[(size_t)kf].kp_point;
-            if (tab[(size_t)v[i].kp] == point) tab[(size_t)v[i].kp] = -1;
-            v.erase(v.begin() + (long)i);
-            m->dirty_topology = m->dirty_kp_point = true;
-            return RS_OK;
-        }
-    return RS_OK;       // MapPoint::remove_observation of an absent key frame is a no-op (src/Map.cpp:117-124)
+    if (!m) return RS_ERR_INVALID;
+    return mirror_remove_observation(m, point, kf);
 }
 
-// Map::associate (src/Map.cpp:95-113): the key frame's keypoint and the point end up matched to each other; whatever
-// either was matched to before (in that key frame) is disassociated first.
+// Map::associate (src/Map.cpp:95-113): map_mirror.h
 extern "C" int rs_map_add_observation(rs_map* m, int point, int kf, int keypoint)
 {
-    if (!m || !point_ok(m, point) || kf < 0 || kf >= (int)m->kfs.size()) return RS_ERR_INVALID;
-    MapKeyFrame& k = m->kfs[(size_t)kf];
-    if (keypoint < 0 || keypoint >= k.n) return RS_ERR_INVALID;
-    const int existing = k.kp_point[(size_t)keypoint];
-    auto& v = m->obs[(size_t)point];
-    bool seen = false;
-    for (const auto& o : v) seen = seen || o.kf == kf;
-    if (existing == point && seen) return RS_OK;                          // :97-100
-    if (existing >= 0 && existing != point) rs_map_remove_observation(m, existing, kf);     // :101-106
-    if (seen) rs_map_remove_observation(m, point, kf);                    // :107-109
-    v.push_back({kf, keypoint});
-    k.kp_point[(size_t)keypoint] = point;
-    m->dirty_topology = m->dirty_kp_point = true;
-    return RS_OK;
+    if (!m) return RS_ERR_INVALID;
+    return mirror_add_observation(m, point, kf, keypoint);
 }
 
 extern "C" int rs_map_remove_point(rs_map* m, int point)
 {
-    if (!m || !point_ok(m, point)) return RS_ERR_INVALID;
-    for (const auto& o : m->obs[(size_t)point]) {                         // Frame::remove_map_match for every observer
-        auto& tab = m->kfs[(size_t)o.kf].kp_point;
-        if (tab[(size_t)o.kp] == point) tab[(size_t)o.kp] = -1;
-    }
-    m->obs[(size_t)point].clear();
-    m->obs[(size_t)point].shrink_to_fit();
-    m->alive[(size_t)point] = 0;
-    m->n_alive--;
-    m->dirty_topology = m->dirty_kp_point = true;
-    return RS_OK;
+    if (!m) return RS_ERR_INVALID;
+    return mirror_remove_point(m, point);
 }
 
 extern "C" int rs_map_counts(const rs_map* m, int h_out[4])
@@ -361,6 +307,14 @@ static int map_sync_device(rs_map* m)
         if (rc) return rc;
         m->cap_kf = ck;
         if (KF) RS_HIP(ctx, hipMemcpyAsync(m->d_centres, m->h_centres.data(), sizeof(float) * 3 * KF, hipMemcpyHostToDevice, s));
+        // the poses themselves, for the key-frame stages (rs_map_reanchor, rs_map_cull_points)
+        m->h_poses.resize(16 * (KF ? KF : 1));
+        for (size_t k = 0; k < KF; k++) memcpy(&m->h_poses[16 * k], m->kfs[k].pose, sizeof(float) * 16);
+        size_t cp = m->cap_poses;
+        rc = grow(ctx, &m->d_poses, &cp, 16 * (KF ? KF : 1), 0);
+        if (rc) return rc;
+        m->cap_poses = cp;
+        if (KF) RS_HIP(ctx, hipMemcpyAsync(m->d_poses, m->h_poses.data(), sizeof(float) * 16 * KF, hipMemcpyHostToDevice, s));
     }
     if (m->dirty_topology || m->dirty_positions || m->dirty_centres) RS_HIP(ctx, hipStreamSynchronize(s));
     m->dirty_topology = m->dirty_positions = m->dirty_centres = false;
@@ -394,12 +348,10 @@ int rs_map_loop_sync(rs_map* m, rs_map_loop_view* out)
 
 rs_context* rs_map_context(const rs_map* m) { return m->ctx; }
 
-// MapPoint::set_track_consistent: the flag only ever goes up
 extern "C" int rs_map_set_track_consistent(rs_map* m, int point)
 {
-    if (!m || point < 0 || point >= (int)m->alive.size() || !m->alive[(size_t)point]) return RS_ERR_INVALID;
-    if (!m->consistent[(size_t)point]) { m->consistent[(size_t)point] = 1; m->dirty_consistent = true; }
-    return RS_OK;
+    if (!m) return RS_ERR_INVALID;
+    return mirror_set_track_consistent(m, point);
 }
 
 #define MAP_GATHER_MAX 8192             // keypoints of a frame (frame.hip's FRAME_MAX_POINTS)
@@ -696,7 +648,7 @@ static int window_of_kf(rs_context* ctx, const rs_map* m, const int32_t* h_kfs, 
     for (size_t c = 0; c < C; c++) {
         if (h_kfs[c] < 0 || h_kfs[c] >= (int)KF) return rs_fail(ctx, RS_ERR_INVALID, "unknown key frame");
         if ((*win)[(size_t)h_kfs[c]] >= 0) return rs_fail(ctx, RS_ERR_INVALID, "key frame %d listed twice", h_kfs[c]);
-        (*win)[(size_t)h_kfs[c]] = (int32_t)c | (h_free[c] ? 1 << 16 : 0);
+        (*win)[(size_t)h_kfs[c]] = (int32_t)c | (h_free && h_free[c] ? 1 << 16 : 0);       // (h_free null: no frame is free)
     }
     return RS_OK;
 }
@@ -826,6 +778,134 @@ extern "C" int rs_map_window(rs_context* ctx, rs_map* m, const int32_t* h_kfs, c
     if ((rc = rs_stage_sync(ctx))) return rc;
     *h_n_points = (int)w.Pf;
     *h_n_obs = (int)w.M;
+    return RS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ key-frame insertion
+// Mapper::insert (reference src/Mapper.cpp:152-174) on the resident map: the two mirror halves (adoption of the frame's
+// matches, creation of the triangulated points) and the two device stages that follow the adjustment (map_keyframe.hip).
+extern "C" int rs_map_insert_keyframe(rs_context* ctx, rs_map* m, const rs_frame* f, const float h_pose[16], int* out_kf, int* h_n_adopted)
+{
+    if (!ctx || !m || m->ctx != ctx || !f || f->ctx != ctx || !h_pose || !out_kf || !h_n_adopted) return RS_ERR_INVALID;
+    *h_n_adopted = 0;
+    RS_HIP(ctx, hipSetDevice(ctx->device));
+    // the frame's table first: a failed read-back leaves the map without the key frame
+    std::vector<int32_t> tab((size_t)(f->n > 0 ? f->n : 1));
+    int in_table = 0;
+    int rd = rs_frame_matches_download(ctx, f, tab.data(), &in_table);
+    if (rd) return rd;
+    const int rc = rs_map_add_keyframe(m, f, h_pose, out_kf);
+    if (rc) return rc;
+    *h_n_adopted = mirror_adopt_table(m, *out_kf, tab.data(), f->n);                     // :157-159
+    return RS_OK;
+}
+
+extern "C" int rs_map_add_track_points(rs_map* m, int kf, const rs_track_results* results, const int32_t* h_window_kfs, int n_window,
+                                       int32_t* h_new_points)
+{
+    if (!m) return RS_ERR_INVALID;
+    const int rc = mirror_add_track_points(m, kf, results, h_window_kfs, n_window, h_new_points);
+    if (rc && results && results->n_pairs > results->capacity_pairs)
+        return rs_fail(m->ctx, rc, "rs_map_add_track_points: %d key-frame sightings, room for %d: the pairs are incomplete", results->n_pairs,
+                       results->capacity_pairs);
+    if (rc) return rs_fail(m->ctx, rc, "rs_map_add_track_points: bad argument");
+    return RS_OK;
+}
+
+// The image brought up to date, the list's table of key frames staged, the selection bytes and the output block made:
+// what both device stages start with.  d_out: 2 + 4 P words (rs_kf_launch_*).
+static int map_keyframe_stage(rs_context* ctx, rs_map* m, const std::vector<int32_t>& win, int32_t** d_winkf, uint8_t** d_sel, int32_t** d_out)
+{
+    const size_t P = m->alive.size();
+    RS_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = map_sync_device(m);
+    if (rc) return rc;
+    // the per-slot selection bytes [P] live in rs_map_bundle_adjust's scratch (nothing else uses it between calls); it is
+    // grown to that call's size, 2 P + 2 words, so that the two users never reallocate it in turn
+    size_t cw = m->cap_win;
+    rc = grow(ctx, &m->d_win, &cw, 2 * P + 2, 0);
+    if (rc) return rc;
+    m->cap_win = cw;
+    if ((rc = rs_stage_begin(ctx))) return rc;
+    if ((rc = rs_stage_upload(ctx, win.data(), sizeof(int32_t) * win.size(), (void**)d_winkf))) return rc;
+    if ((rc = rs_stage_alloc(ctx, sizeof(int32_t) * (2 + 4 * P), (void**)d_out))) return rc;
+    *d_sel = (uint8_t*)m->d_win;                      // (not rs_map::d_flag, the matcher's table that is all zero between calls)
+    return RS_OK;
+}
+
+extern "C" int rs_map_reanchor(rs_context* ctx, rs_map* m, const int32_t* h_kfs, const float* h_before, int n_kfs,
+                               int32_t* h_out_points, float* h_out_xyz, int capacity, int* h_n_points)
+{
+    if (!ctx || !m || m->ctx != ctx || n_kfs < 0 || (n_kfs > 0 && (!h_kfs || !h_before)) || !h_n_points) return RS_ERR_INVALID;
+    *h_n_points = 0;
+    const size_t C = (size_t)n_kfs, P = m->alive.size();
+    std::vector<int32_t> win;
+    int rc = window_of_kf(ctx, m, h_kfs, nullptr, C, &win);
+    if (rc) return rc;
+    if (P == 0 || C == 0) return RS_OK;
+    int32_t *d_winkf = nullptr, *d_out = nullptr;
+    uint8_t* d_sel = nullptr;
+    float* d_before = nullptr;
+    if ((rc = map_keyframe_stage(ctx, m, win, &d_winkf, &d_sel, &d_out))) return rc;
+    if ((rc = rs_stage_upload(ctx, h_before, sizeof(float) * 16 * C, (void**)&d_before))) return rc;
+    // From the launch on the image's positions are ahead of the mirror's.  Until the mirror has taken them the positions count
+    // as dirty: if the read-back fails, the next use uploads the mirror's and the two agree again (the mirror wins).
+    m->dirty_positions = true;
+    rs_kf_launch_reanchor(ctx, (int)P, m->d_alive, m->d_obs_ptr, m->d_obs_kf, d_winkf, d_before, m->d_poses, m->d_pos, d_sel, d_out);
+    RS_HIP(ctx, hipGetLastError());
+    std::vector<int32_t> out(2 + 4 * P);
+    if ((rc = rs_stage_download(ctx, d_out, sizeof(int32_t) * out.size(), out.data()))) return rc;      // one read-back
+    if ((rc = rs_stage_sync(ctx))) return rc;
+    const size_t n = (size_t)out[0];
+    if (n > P) return rs_fail(ctx, RS_ERR_INTERNAL, "rs_map_reanchor: %zu moved points of %zu slots", n, P);
+    const int32_t* list = out.data() + 2;
+    const float* xyz = (const float*)(out.data() + 2 + P);
+    for (size_t q = 0; q < n; q++)
+        if (list[q] < 0 || (size_t)list[q] >= P) return rs_fail(ctx, RS_ERR_INTERNAL, "rs_map_reanchor: slot %d out of range", list[q]);
+    for (size_t q = 0; q < n; q++) memcpy(&m->pos[3 * (size_t)list[q]], xyz + 3 * q, sizeof(float) * 3);
+    m->dirty_positions = false;                      // the mirror has followed: the image is current, nothing to upload
+    const size_t cap = (size_t)(capacity > 0 ? capacity : 0), nout = n < cap ? n : cap;
+    if (h_out_points && nout) memcpy(h_out_points, list, sizeof(int32_t) * nout);
+    if (h_out_xyz && nout) memcpy(h_out_xyz, xyz, sizeof(float) * 3 * nout);
+    *h_n_points = (int)n;
+    return RS_OK;
+}
+
+extern "C" int rs_map_cull_points(rs_context* ctx, rs_map* m, const int32_t* h_kfs, int n_kfs, const float h_intrinsics[4],
+                                  float max_mean_error, int apply, int32_t* h_removed, float* h_removed_xyz, int capacity,
+                                  int* h_n_removed, int* h_n_local)
+{
+    if (!ctx || !m || m->ctx != ctx || n_kfs < 0 || (n_kfs > 0 && !h_kfs) || !h_intrinsics || !h_n_removed) return RS_ERR_INVALID;
+    *h_n_removed = 0;
+    if (h_n_local) *h_n_local = 0;
+    if (capacity > 0 && !h_removed) return rs_fail(ctx, RS_ERR_INVALID, "rs_map_cull_points: null output");
+    const size_t C = (size_t)n_kfs, P = m->alive.size();
+    std::vector<int32_t> win;
+    int rc = window_of_kf(ctx, m, h_kfs, nullptr, C, &win);
+    if (rc) return rc;
+    if (P == 0 || C == 0) return RS_OK;
+    int32_t *d_winkf = nullptr, *d_out = nullptr;
+    uint8_t* d_sel = nullptr;
+    if ((rc = map_keyframe_stage(ctx, m, win, &d_winkf, &d_sel, &d_out))) return rc;
+    rs_kf_launch_cull(ctx, (int)P, m->d_alive, m->d_obs_ptr, m->d_obs_kf, m->d_obs_desc, d_winkf, m->d_poses, m->d_kp_pool, m->d_pos,
+                      h_intrinsics, max_mean_error, d_sel, d_out);
+    RS_HIP(ctx, hipGetLastError());
+    std::vector<int32_t> out(2 + 4 * P);
+    if ((rc = rs_stage_download(ctx, d_out, sizeof(int32_t) * out.size(), out.data()))) return rc;      // one read-back
+    if ((rc = rs_stage_sync(ctx))) return rc;
+    const size_t n = (size_t)out[0];
+    if (n > P || (size_t)out[1] > P) return rs_fail(ctx, RS_ERR_INTERNAL, "rs_map_cull_points: %zu culled points of %zu slots", n, P);
+    *h_n_removed = (int)n;
+    if (h_n_local) *h_n_local = out[1];
+    if (n > (size_t)(capacity > 0 ? capacity : 0))
+        return rs_fail(ctx, RS_ERR_INVALID, "rs_map_cull_points: %zu points to remove, room for %d: nothing was removed", n, capacity);
+    const int32_t* list = out.data() + 2;
+    for (size_t q = 0; q < n; q++)
+        if (!point_ok(m, list[q])) return rs_fail(ctx, RS_ERR_INTERNAL, "rs_map_cull_points: slot %d is not an alive point", list[q]);
+    if (n) memcpy(h_removed, list, sizeof(int32_t) * n);
+    if (h_removed_xyz && n) memcpy(h_removed_xyz, out.data() + 2 + P, sizeof(float) * 3 * n);      // diagnostics.culled, :426-428
+    if (apply)
+        for (size_t q = 0; q < n; q++) mirror_remove_point(m, list[q]);                            // :429, ascending slot
     return RS_OK;
 }
 

@@ -10,7 +10,7 @@
 // quota — the best of the rest by parallax cosine ascending (ties: candidate order; the reference's
 // std::sort leaves them unspecified).  Built with -ffp-contract=off; acosf / cosf are the device libm's
 // (last-ulp differences to glibc only move `required`).
-#include "tri_core.h"
+#include "point_core.h"
 
 struct TrackParams {
     TriParams tri;               // loose gates of the per-track triangulation
@@ -197,22 +197,13 @@ __global__ __launch_bounds__(256) void k12_point_errors(const float* __restrict_
     if (p < n_points) {
         const float X[3] = {pos[3 * (size_t)p], pos[3 * (size_t)p + 1], pos[3 * (size_t)p + 2]};
         const int o0 = obs_ptr[p], o1 = obs_ptr[p + 1];
-        float err = 0.0f;
-        for (int o = o0; o < o1; o++) {
-            float T[16];
-            load_pose(poses, obs_pose[o], T);
-            const float2 pr = project_f32(k, T, X);
-            const float2 px = obs_uv[o];
-            const float dx = pr.x - px.x, dy = pr.y - px.y;
-            const float e = sqrtf(dx * dx + dy * dy);
-            err += e;                                                    // :413
-            esum += (double)e;
-        }
+        const float err = point_error_sum_f32(k, poses, obs_pose, obs_uv, nullptr, X, o0, o1, &esum);
         const int cnt = o1 - o0;
         ecnt = (double)cnt;
-        const float mean = cnt > 0 ? err / (float)cnt : 0.0f;
+        float mean;
+        const bool c = point_cull_rule_f32(err, cnt, max_mean_error, &mean);
         mean_err[p] = mean;
-        cull[p] = (cnt > 0 && mean > max_mean_error) ? 1 : 0;            // :416
+        cull[p] = c ? 1 : 0;                                             // :416
     }
     // Slam::reprojection_error: sum and count over all observations (f64 sum of the f32 errors)
     esum = wave_sum_f64(esum);
@@ -291,15 +282,7 @@ __global__ __launch_bounds__(256) void k13_reanchor(int n, const int32_t* __rest
     load_pose(before, frame_idx[i], B);
     load_pose(after, frame_idx[i], A);
     const float X[3] = {pos[3 * (size_t)p], pos[3 * (size_t)p + 1], pos[3 * (size_t)p + 2]};
-    float c[3], d[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        c[r] = ((B[4 * r] * X[0] + B[4 * r + 1] * X[1]) + B[4 * r + 2] * X[2]) + B[4 * r + 3];     // :389
-        d[r] = c[r] - A[4 * r + 3];
-    }
-#pragma unroll
-    for (int r = 0; r < 3; r++)                                                                       // :390
-        pos[3 * (size_t)p + r] = (A[r] * d[0] + A[4 + r] * d[1]) + A[8 + r] * d[2];
+    reanchor_f32(B, A, X, pos + 3 * (size_t)p);                     // :389-390 (point_core.h)
 }
 
 extern "C" int rs_reanchor_points(rs_context* ctx, int n, const int32_t* d_point_idx, const int32_t* d_frame_idx,
@@ -336,15 +319,7 @@ __global__ __launch_bounds__(256) void k13_reanchor_args(int n, const int32_t* _
     const float* B = poses.before[f];
     const float* A = poses.after[f];
     const float X[3] = {pos[3 * (size_t)p], pos[3 * (size_t)p + 1], pos[3 * (size_t)p + 2]};
-    float c[3], d[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        c[r] = ((B[4 * r] * X[0] + B[4 * r + 1] * X[1]) + B[4 * r + 2] * X[2]) + B[4 * r + 3];     // :389
-        d[r] = c[r] - A[4 * r + 3];
-    }
-#pragma unroll
-    for (int r = 0; r < 3; r++)                                                                       // :390
-        pos[3 * (size_t)p + r] = (A[r] * d[0] + A[4 + r] * d[1]) + A[8 + r] * d[2];
+    reanchor_f32(B, A, X, pos + 3 * (size_t)p);                     // :389-390 (point_core.h)
 }
 
 extern "C" int rs_reanchor_points_host_poses(rs_context* ctx, int n, const int32_t* d_point_idx, const int32_t* d_frame_idx,

@@ -1345,7 +1345,8 @@ bool DeviceTracks::triangulate_tracks(const rs_frame* frame, const float* d_pose
                                       const float* d_required, DeviceTrackSelection* out, size_t min_new_points)
 {
     const size_t T = (size_t)m_max_points;
-    rs_track_results r{};
+    rs_track_results& r = m_results;
+    r = rs_track_results{};
     r.capacity_tracks = m_max_points; r.capacity_pairs = 4 * m_max_points;
     r.h_keypoint = m_i32.data(); r.h_sightings = r.h_keypoint + T; r.h_kf_ptr = r.h_sightings + T; r.h_track = r.h_kf_ptr + T + 1;
     r.h_inconsistent = r.h_track + T; r.h_kf_pairs = r.h_inconsistent + T;
@@ -1380,6 +1381,81 @@ bool DeviceTracks::erase_inconsistent()
 {
     const int rc = rs_track_store_erase_inconsistent(m_ctx, m_store);
     return rc == RS_OK || tracks_fail(m_ctx, rc, "rs_track_store_erase_inconsistent");
+}
+
+// ---------------------------------------------------------------------------------------------- Mapper::insert
+bool insert_key_frame(rs_context* ctx, rs_map* map, DeviceTracks* tracks, const rs_frame* frame, const Mat4f& pose,
+                      const KeyFrameWindow& window, const KeyFrameTrajectory& trajectory, const Camera& camera, bool bundle_adjust,
+                      bool cull_points, KeyFrameInsert* out)
+{
+    KeyFrameInsert r;
+    const auto done = [&](bool ok) { if (out) *out = std::move(r); return ok; };
+    const auto fail = [&](int rc, const char* what) {
+        std::printf("%s failed (status %d): %s\n", what, rc, ctx ? rs_last_error(ctx) : "no context");
+        return done(false);
+    };
+    if (window.optimize.size() != window.key_frames.size() || window.poses.size() != window.key_frames.size()) return fail(RS_ERR_INVALID, "insert_key_frame: window");
+    int rc = rs_map_insert_keyframe(ctx, map, frame, pose.data(), &r.key_frame, &r.adopted);                  // :155-159
+    if (rc != RS_OK) return fail(rc, "rs_map_insert_keyframe");
+    if (tracks) {                                                                                             // :161-163
+        if (!tracks->triangulate_tracks(frame, trajectory.d_poses, trajectory.n_poses, trajectory.pose_base, trajectory.kf_pose, camera,
+                                        trajectory.d_required, &r.selection))
+            return done(false);
+        r.created.assign((size_t)std::max(tracks->results().counts[0], 0), -1);
+        rc = rs_map_add_track_points(map, r.key_frame, &tracks->results(), window.key_frames.data(), (int)window.key_frames.size(),
+                                     r.created.data());                                                       // :306-331
+        if (rc != RS_OK) return fail(rc, "rs_map_add_track_points");
+        if (!tracks->erase_inconsistent()) return done(false);                                                // :333-335
+        std::printf("Triangulated from tracks: %zu of %zu tracks, inconsistent %zu, topped up %zu\n", r.created.size(), r.selection.tracks,
+                    r.selection.selection.inconsistent.size(), r.selection.selection.topped_up);
+    }
+    r.window = window.key_frames;
+    r.window.push_back(r.key_frame);
+    std::vector<uint8_t> free_flags = window.optimize;
+    free_flags.push_back(1);
+    const int C = (int)r.window.size();
+    const float K[4] = {camera.fx(), camera.fy(), camera.cx(), camera.cy()};
+    int counts[4] = {0, 0, 0, 0};
+    if ((rc = rs_map_counts(map, counts)) != RS_OK) return fail(rc, "rs_map_counts");
+    const int cap = counts[0];
+    if (bundle_adjust) {                                                                                      // :165-167, :364-394
+        // the anchors: the optimised frames and their poses before the adjustment (:369-375)
+        std::vector<int32_t> anchors;
+        std::vector<float> before;
+        for (int c = 0; c < C; c++) {
+            if (!free_flags[(size_t)c]) continue;
+            const Mat4f& T = c + 1 < C ? window.poses[(size_t)c] : pose;
+            anchors.push_back(r.window[(size_t)c]);
+            before.insert(before.end(), T.begin(), T.end());
+        }
+        r.poses.assign(16 * (size_t)C, 0.0f);
+        r.adjusted.assign((size_t)cap, 0);
+        r.adjusted_xyz.assign(3 * (size_t)cap, 0.0f);
+        int n = 0;
+        rc = rs_map_bundle_adjust(ctx, map, r.window.data(), free_flags.data(), C, K, nullptr, &r.summary, r.poses.data(), r.adjusted.data(),
+                                  r.adjusted_xyz.data(), cap, &n);
+        if (rc != RS_OK) return fail(rc, "rs_map_bundle_adjust");
+        r.adjusted.resize((size_t)std::min(n, cap));
+        r.adjusted_xyz.resize(3 * r.adjusted.size());
+        r.reanchored.assign((size_t)cap, 0);
+        r.reanchored_xyz.assign(3 * (size_t)cap, 0.0f);
+        rc = rs_map_reanchor(ctx, map, anchors.data(), before.data(), (int)anchors.size(), r.reanchored.data(), r.reanchored_xyz.data(), cap, &n);
+        if (rc != RS_OK) return fail(rc, "rs_map_reanchor");
+        r.reanchored.resize((size_t)std::min(n, cap));
+        r.reanchored_xyz.resize(3 * r.reanchored.size());
+    }
+    if (cull_points) {                                                                                        // :168-170, :396-431
+        r.culled.assign((size_t)cap, 0);
+        r.culled_xyz.assign(3 * (size_t)cap, 0.0f);
+        int n = 0;
+        rc = rs_map_cull_points(ctx, map, r.window.data(), C, K, tracks::MAX_POINT_REPROJECTION_ERROR, 1, r.culled.data(), r.culled_xyz.data(),
+                                cap, &n, &r.local_points);
+        if (rc != RS_OK) return fail(rc, "rs_map_cull_points");
+        r.culled.resize((size_t)n);
+        r.culled_xyz.resize(3 * r.culled.size());
+        std::printf("Number of points to remove: %d\n", n);
+    }
+    return done(true);
 }
 
 }  // namespace slam

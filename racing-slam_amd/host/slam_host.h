@@ -399,14 +399,45 @@ class DeviceTracks {
     bool triangulate_tracks(const rs_frame* frame, const float* d_poses, int n_poses, int pose_base, int kf_pose, const Camera& camera,
                             const float* d_required, DeviceTrackSelection* out, size_t min_new_points = tracks::MIN_NEW_POINTS_PER_KEY_FRAME);
     bool erase_inconsistent();
+    // what the last triangulate_tracks read back, as rs_map_add_track_points takes it (its arrays live in this object)
+    const rs_track_results& results() const { return m_results; }
 
   private:
     rs_context* m_ctx = nullptr;
     rs_track_store* m_store = nullptr;
     int m_max_points = 0;
+    rs_track_results m_results{};
     std::vector<int32_t> m_i32;                  // result arrays, made once
     std::vector<float> m_f32;
 };
+
+// Mapper::insert (src/Mapper.cpp:152-174) on the resident map, next to track_tail: the tracker's frame with its device match
+// table and the track store go in, the key frame comes out inserted, adjusted, re-anchored and culled, with no host pass over
+// map objects.  The chain: rs_map_insert_keyframe -> rs_track_store_triangulate -> rs_map_add_track_points ->
+// rs_track_store_erase_inconsistent -> rs_map_bundle_adjust -> rs_map_reanchor -> rs_map_cull_points.
+struct KeyFrameWindow {
+    std::vector<int32_t> key_frames;             // the BA window BEFORE the new key frame (:227-231), in FrameConfig order
+    std::vector<uint8_t> optimize;               // FrameConfig::optimize per entry; the new key frame is always optimised
+    std::vector<Mat4f> poses;                    // Frame::pose() per entry, as the map holds them: the anchors' poses before (:369-375)
+};
+struct KeyFrameTrajectory {                      // rs_track_store_triangulate's pose arguments
+    const float* d_poses = nullptr; int n_poses = 0, pose_base = 0, kf_pose = 0; const float* d_required = nullptr;
+};
+struct KeyFrameInsert {
+    int key_frame = -1, adopted = 0;
+    DeviceTrackSelection selection;              // Mapper::triangulate_tracks' selection (diagnostics)
+    std::vector<int32_t> created;                // the point slots of the accepted tracks
+    rs_ba_summary summary{};
+    std::vector<int32_t> window;                 // the adjusted window: key_frames + the new one
+    std::vector<float> poses;                    // [window][16] after the adjustment
+    std::vector<int32_t> adjusted; std::vector<float> adjusted_xyz;        // rs_map_bundle_adjust's free points
+    std::vector<int32_t> reanchored; std::vector<float> reanchored_xyz;    // the single-observation points carried along
+    std::vector<int32_t> culled; std::vector<float> culled_xyz;            // diagnostics.culled (:426-428)
+    int local_points = 0;
+};
+bool insert_key_frame(rs_context* ctx, rs_map* map, DeviceTracks* tracks, const rs_frame* frame, const Mat4f& pose,
+                      const KeyFrameWindow& window, const KeyFrameTrajectory& trajectory, const Camera& camera, bool bundle_adjust,
+                      bool cull_points, KeyFrameInsert* out);
 
 // LoopDetector::query's "Loop retrieval" stage (src/LoopDetector.cpp:346-373 Impl::score_candidates, :231-265
 // rank_candidates) on the device, as specified by tests/bow_ref.py: the DBoW2 vocabulary, one rs_bow and the database of

@@ -24,6 +24,7 @@ EXPORTS = [
     "rs_track_store_create", "rs_track_store_destroy", "rs_track_store_clear", "rs_track_store_carry", "rs_track_store_extend",
     "rs_track_store_query", "rs_needs_key_frame", "rs_track_store_triangulate", "rs_track_store_erase_inconsistent",
     "rs_track_store_download", "rs_track_store_download_packed",
+    "rs_map_insert_keyframe", "rs_map_add_track_points", "rs_map_reanchor", "rs_map_cull_points",
     "rs_map_add_keyframe", "rs_map_set_keyframe_pose", "rs_map_add_point", "rs_map_set_position", "rs_map_remove_point",
     "rs_map_add_observation", "rs_map_remove_observation", "rs_map_counts", "rs_map_get_positions", "rs_map_match", "rs_map_pose_graph", "rs_pose_graph", "rs_pose_relative", "rs_transform_points", "rs_map_bundle_adjust", "rs_map_window", "rs_triangulate", "rs_triangulate_host", "rs_triangulate_matches", "rs_triangulate_matches_batch", "rs_triangulate_tracks", "rs_parallax_requirements", "rs_point_errors", "rs_ba_default_options",
     "rs_bundle_adjust", "rs_bundle_adjust_batch", "rs_ba_get_trace", "rs_ba_get_stats", "rs_ba_get_cameras", "rs_reanchor_points", "rs_reanchor_points_host_poses", "rs_refine_pose", "rs_bundle_adjust_inertial", "rs_refine_pose_inertial", "rs_pack_pose", "rs_unpack_pose", "rs_pack_poses", "rs_unpack_poses", "rs_build_local_window",
@@ -1590,6 +1591,64 @@ class ResidentMap:
             pts.ctypes.data_as(C.c_void_p), xyz.ctypes.data_as(C.c_void_p), cap, C.byref(n)), "rs_map_bundle_adjust")
         k = min(n.value, max(cap, 0))
         return dict(s.as_dict(), n_points=n.value), poses, pts[:k].copy(), xyz[:k].copy()
+
+    # -- Mapper::insert on the resident map
+    def insert_keyframe(self, frame, pose):
+        """rs_map_add_keyframe + the adoption of the frame's device match table.  Returns (key-frame handle, adopted)."""
+        kf, n = C.c_int(-1), C.c_int(0)
+        p = np.ascontiguousarray(pose, np.float32).reshape(16)
+        self.ctx._check(self.lib.rs_map_insert_keyframe(self.ctx.h, self.h, frame.h, p.ctypes.data_as(C.c_void_p), C.byref(kf), C.byref(n)),
+                        "rs_map_insert_keyframe")
+        return kf.value, n.value
+
+    def add_track_points(self, kf, results, window_kfs, capacity_pairs=None):
+        """Mapper::triangulate_tracks' creation loop for TrackStore.triangulate's dict (keypoint, xyz, sightings, kf_ptr,
+        kf_pairs, n_pairs).  capacity_pairs: the room the pairs had (default: n_pairs).  Returns the new point slots."""
+        na = len(results["keypoint"])
+        kp = np.ascontiguousarray(results["keypoint"], np.int32)
+        xyz = np.ascontiguousarray(results["xyz"], np.float32).reshape(-1, 3)
+        ns = np.ascontiguousarray(results["sightings"], np.int32)
+        ptr = np.ascontiguousarray(results["kf_ptr"], np.int32)
+        pairs = np.ascontiguousarray(results["kf_pairs"], np.int32).reshape(-1, 2)
+        n_pairs = int(results.get("n_pairs", len(pairs)))
+        cp = n_pairs if capacity_pairs is None else int(capacity_pairs)
+        r = TrackResults(capacity_tracks=max(na, 1), capacity_pairs=cp, h_keypoint=kp.ctypes.data, h_xyz=xyz.ctypes.data,
+                         h_sightings=ns.ctypes.data, h_kf_ptr=ptr.ctypes.data, h_kf_pairs=pairs.ctypes.data)
+        r.counts[0], r.n_tracks, r.n_pairs = na, na, n_pairs
+        win = np.ascontiguousarray(window_kfs, np.int32)
+        out = np.full(max(na, 1), -1, np.int32)
+        self.ctx._check(self.lib.rs_map_add_track_points(self.h, int(kf), C.byref(r), win.ctypes.data_as(C.c_void_p), len(win),
+                                                         out.ctypes.data_as(C.c_void_p)), "rs_map_add_track_points")
+        return out[:na].copy()
+
+    def reanchor(self, kfs, before, capacity=None):
+        """rs_map_reanchor.  Returns (n_points, moved slots, their new positions); the arrays hold min(n_points, capacity)."""
+        kfs = np.ascontiguousarray(kfs, np.int32)
+        before = np.ascontiguousarray(before, np.float32).reshape(-1, 16)
+        cap = self.counts()["slots"] if capacity is None else int(capacity)
+        pts, xyz = np.zeros(max(cap, 1), np.int32), np.zeros((max(cap, 1), 3), np.float32)
+        n = C.c_int(0)
+        self.ctx._check(self.lib.rs_map_reanchor(self.ctx.h, self.h, kfs.ctypes.data_as(C.c_void_p), before.ctypes.data_as(C.c_void_p),
+                                                 len(kfs), pts.ctypes.data_as(C.c_void_p), xyz.ctypes.data_as(C.c_void_p), cap, C.byref(n)),
+                        "rs_map_reanchor")
+        k = min(n.value, max(cap, 0))
+        return n.value, pts[:k].copy(), xyz[:k].copy()
+
+    def cull_points(self, kfs, K, max_mean_error=3.0, apply=True, capacity=None, check=True):
+        """rs_map_cull_points.  Returns dict(status, n_removed, n_local, removed, xyz).  check=False returns the status of a
+        refused call (capacity too small) instead of raising."""
+        kfs = np.ascontiguousarray(kfs, np.int32)
+        Kc = (C.c_float * 4)(*[float(v) for v in K])
+        cap = self.counts()["slots"] if capacity is None else int(capacity)
+        pts, xyz = np.zeros(max(cap, 1), np.int32), np.zeros((max(cap, 1), 3), np.float32)
+        n, nl = C.c_int(0), C.c_int(0)
+        rc = self.lib.rs_map_cull_points(self.ctx.h, self.h, kfs.ctypes.data_as(C.c_void_p), len(kfs), Kc, C.c_float(max_mean_error),
+                                         int(bool(apply)), pts.ctypes.data_as(C.c_void_p), xyz.ctypes.data_as(C.c_void_p), cap,
+                                         C.byref(n), C.byref(nl))
+        if check:
+            self.ctx._check(rc, "rs_map_cull_points")
+        k = min(n.value, max(cap, 0)) if rc == 0 else 0
+        return dict(status=rc, n_removed=n.value, n_local=nl.value, removed=pts[:k].copy(), xyz=xyz[:k].copy())
 
     def window(self, kfs, free):
         """rs_map_window: the problem bundle_adjust would solve, unsolved: dict(points, positions f64, obs_ptr, obs_cam,
