@@ -31,6 +31,7 @@
 // K10 applies the last decision and writes the result back.
 #include <stdlib.h>
 #include <atomic>
+#include <thread>
 
 #include "ba_common.h"
 #include "ba_backsub_body.h"
@@ -519,8 +520,6 @@ extern "C" void rs_ba_default_options(rs_ba_options* o)
     o->jacobi_scaling = 1;
 }
 
-void rs_ba_cache_free(rs_context* ctx) { (void)ctx; }
-
 extern "C" int rs_prof_counters(rs_context* ctx, uint64_t* h_out, int n)
 {
     if (!ctx || !h_out || n < 0 || n > 64) return RS_ERR_INVALID;
@@ -636,354 +635,395 @@ struct BaInFlight {
     ~BaInFlight() { g_ba_in_flight.fetch_sub(1); }
 };
 
-static int ba_solve_once(rs_context* ctx, int n_cameras, int n_points, int n_obs, double* d_cameras,
-                         const uint8_t* h_cam_free, double* d_points, const int32_t* d_obs_ptr,
-                         const int32_t* d_obs_cam, const float* d_obs_uv, const float h_intrinsics[4],
-                         const rs_ba_options* options, rs_ba_summary* h_summary, const BaInertialArgs* in,
-                         bool allow_fuse, bool* hand_lost)
+// The argument list of rs_bundle_adjust as one record.  (A missing intrinsics pointer travels as a missing free-camera
+// table: ba_solve_once refuses both in the same null-pointer test.)
+static rs_ba_problem ba_problem_from(int n_cameras, int n_points, int n_obs, double* d_cameras, const uint8_t* h_cam_free, double* d_points,
+                                     const int32_t* d_obs_ptr, const int32_t* d_obs_cam, const float* d_obs_uv, const float* K)
+{
+    return {n_cameras, n_points, n_obs, d_cameras, K ? h_cam_free : nullptr, d_points, d_obs_ptr, d_obs_cam, d_obs_uv, {K ? K[0] : 0, K ? K[1] : 0, K ? K[2] : 0, K ? K[3] : 0}};
+}
+
+// Inertial frames: the cameras an IMU factor touches get a velocity (3) + bias (6) block; inert[c] = index of that block or
+// -1, *Ci their number.  *chain: the factors join consecutive inertial cameras (what the reference builds: block-tridiagonal H_zz)
+static int ba_inertial_slots(rs_context* ctx, const rs_ba_problem& q, const BaInertialArgs& in, std::vector<int32_t>& inert, int* Ci, bool* chain)
+{
+    const int C = q.n_cameras;
+    for (int f = 0; f < in.n_factors; f++) {
+        const int i = in.factors[f].cam_i, j = in.factors[f].cam_j;
+        if (i < 0 || j < 0 || i >= C || j >= C || i == j || !q.h_cam_free[i] || !q.h_cam_free[j])
+            return rs_fail(ctx, RS_ERR_INVALID, "IMU factor %d must join two distinct optimised cameras", f);
+    }
+    std::vector<uint8_t> touched(C, 0);
+    for (int f = 0; f < in.n_factors; f++) { touched[in.factors[f].cam_i] = 1; touched[in.factors[f].cam_j] = 1; }
+    for (int c = 0; c < C; c++) if (touched[c]) inert[c] = (*Ci)++;
+    *chain = true;
+    for (int f = 0; f < in.n_factors && *chain; f++) *chain = inert[in.factors[f].cam_j] == inert[in.factors[f].cam_i] + 1;
+    return RS_OK;
+}
+
+// Launch fusion, decided once the grouping is carved.  `others`: solves of this process in flight besides this one.
+static void ba_choose_fusion(const rs_context* ctx, const BaDims& d, const BaBufs& b, const BaGroup& grp, BaPath& path, bool allow_fuse, bool inertial, int others)
+{
+    // K7 + K8 as one launch (ba_solve.hip): the plain local window only — vision-only, one rank, both LDS kernels
+    // and only while all of its workgroups are resident at once (one per CU: the launch carries K7's LDS): beyond that
+    // K8's workgroups would run in several shifts behind the hand-off, and the launch of its own (many per CU) is faster
+    // The whole round as ONE launch (ba_round.hip: K5's item workgroups become K8's after they have counted themselves for
+    // K7): the same conditions plus the MFMA K5 with its camera blocks in LDS, and again every workgroup resident at once.
+    // (a landmark shard may fuse K7 + K8 too: the launch sits between the two exchange steps of the round, C1 in front of
+    // it and C2 behind; whether a rank fuses is its own business — shard sizes differ — but a lost hand-off is agreed on by
+    // all ranks after the solve, so that every rank re-runs it or none does)
+    path.may_fuse = allow_fuse && path.solve_lds && path.k8_lds && !inertial;
+    // Measured (tools/round_stamps.py, DESIGN.md 4.2b): 86 us per round against 43 + 45 as two launches — the round is a strict
+    // chain (linearise -> solve -> back-substitute), so keeping the workgroups resident buys the boundary and little else.
+    // It is therefore opt-in ("ba_fuse_mode" 3); the default stays K5, then K7 + K8 in one launch.
+    path.fuse_round = path.may_fuse && !rs_comm_active(ctx) && path.use_mfma && ctx->ba_fuse_mode == 3 && path.ns <= BA_CALIBRATED_SETS &&
+                      ba_round_eligible(d) && ba_round_workgroups(d, b, grp) <= ctx->n_cu;
+    path.fuse78 = !path.fuse_round && path.may_fuse && d.P > 0 /* an empty landmark shard has no K8 workgroup to clear the accumulators */ &&
+                  (ctx->ba_fuse_mode >= 2 || (ctx->ba_fuse_mode == 0 && others == 0)) &&
+                  ba_solve_backsub_workgroups(d, b, ctx->n_cu) <= ctx->n_cu;
+}
+
+// Offsets into the pinned block of one window.  The single solve keeps its slot and free-camera tables (windows of more
+// than 64 cameras upload them from here) behind the summary and the inertial state at the end; a window of the grid batch
+// has neither, and whole 64-byte lines per part.  `key`: a word of the progress line's unused half (span / lost-key reads).
+struct BaPinned { size_t st, slot, fre, prog, key, trace, cams, vb, bytes; };
+static BaPinned ba_pinned_single(size_t C, int max_iter, bool inertial)
+{
+    BaPinned p;
+    p.st = 0; p.slot = sizeof(BaState); p.fre = p.slot + sizeof(int32_t) * C;
+    p.prog = align_up(p.fre + C, 64); p.key = p.prog + 32; p.trace = p.prog + 64;
+    p.cams = p.trace + sizeof(BaTrace) * (size_t)(max_iter + 1); p.vb = align_up(p.cams + sizeof(double) * 6 * C, 64);
+    p.bytes = p.vb + (inertial ? sizeof(double) * 9 * C : 0);
+    return p;
+}
+static BaPinned ba_pinned_batch(size_t C, int max_iter)
+{
+    BaPinned p;
+    p.st = p.slot = p.fre = 0; p.prog = align_up(sizeof(BaState), 64); p.key = p.prog + 32; p.trace = p.prog + 64;
+    p.cams = p.trace + align_up(sizeof(BaTrace) * (size_t)(max_iter + 1), 64); p.vb = p.bytes = p.cams + align_up(sizeof(double) * 6 * C, 64);
+    return p;
+}
+
+// A 64-bit key every rank holds, MIN-reduced over the ranks and read by the host (the stream is drained when it returns).
+static int ba_min_key_to_host(rs_context* ctx, unsigned long long* d_key, volatile unsigned long long* h_key)
+{
+    const int rc = rs_allreduce_min_u64(ctx, d_key, 1);
+    if (rc) return rc;
+    RS_HIP(ctx, hipMemcpyAsync((void*)h_key, d_key, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RS_OK;
+}
+
+// Blocked reduced solve: is S block-banded?  The grouping has just computed the largest camera span of a landmark; one
+// word travels to the host (the solve is milliseconds: the wait costs a few per cent of one round) and decides between
+// the one-launch banded factorisation and the general blocked one (*band as in BaPath).
+static int ba_choose_band(rs_context* ctx, const BaPath& path, bool inertial, const BaGroup& grp, const BaBufs& b, volatile unsigned long long* h_key, int* band)
+{
+    *band = 0;
+    if (!path.solve_big || !path.use_mfma || inertial || ctx->ba_band_mode == 1) return RS_OK;
+    hipStream_t s = ctx->stream;
+    const int banded = ctx->ba_band_mode == 2 ? 1 : 2;
+    if (rs_comm_active(ctx)) {
+        // landmark shards: the span of the WHOLE window is the largest of the ranks' spans (round 4; every rank then runs
+        // the same banded factorisation on the same all-reduced system, as it runs the same general one)
+        *h_key = 0ull;
+        hipLaunchKernelGGL(ba_span_key, dim3(1), dim3(1), 0, s, (const int32_t*)grp.maxspan, b.dbg + BA_KEY_SPAN);
+        const int rc = ba_min_key_to_host(ctx, b.dbg + BA_KEY_SPAN, h_key);
+        if (rc) return rc;
+        if (~*h_key <= (unsigned long long)ba_band_max_span()) *band = banded;      // (the key is ~span)
+        return RS_OK;
+    }
+    volatile int32_t* h_span = (volatile int32_t*)h_key;
+    *h_span = -1;
+    RS_HIP(ctx, hipMemcpyAsync((void*)h_span, grp.maxspan, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    long spins = 0;
+    while (*h_span < 0)
+        if ((++spins & 0x3FFFF) == 0 && hipStreamQuery(s) != hipErrorNotReady) break;
+    if (*h_span < 0) RS_HIP(ctx, hipStreamSynchronize(s));
+    if (*h_span >= 0 && *h_span <= ba_band_max_span()) *band = banded;
+    return RS_OK;
+}
+
+// Inertial blocks onto the device: the carve behind the common workspace, the whitened factors, the inertial slots and the
+// velocity | bias state of both parities.  fac_host, xv_host and inert are pageable sources of asynchronous copies: the
+// caller keeps them alive until it has synchronised (the copies complete before the call returns — it waits for finalize).
+static int ba_inertial_upload(rs_context* ctx, const BaInertialArgs& in, const BaDims& d, BaBufs& b, const BaPath& path, char* ws_big, char* ws_zacc,
+                              const std::vector<int32_t>& inert, int Ci, std::vector<ImuFactorDev>& fac_host, std::vector<double>& xv_host)
+{
+    hipStream_t s = ctx->stream;
+    const size_t C = (size_t)d.C;
+    const int N_in = d.n + 9 * Ci;
+    ImuFactorDev* d_fac = nullptr; int32_t* d_inert = nullptr;
+    ba_inertial_carve(ws_big, N_in, in.n_factors, d.C, &b.imu, &d_fac, &d_inert);
+    b.imu.n_fac = in.n_factors; b.imu.Ci = Ci; b.imu.N = N_in;
+    if (path.imu_lds) {
+        b.imu.zacc = (double*)ws_zacc;
+        b.imu.zacc_n = (int)ba_imu_lds_zacc_doubles(Ci, d.n);
+        RS_HIP(ctx, hipMemsetAsync(b.imu.zacc, 0, sizeof(double) * (size_t)b.imu.zacc_n, s));
+    }
+    for (int k = 0; k < 3; k++) b.imu.gravity[k] = in.gravity[k];
+    fac_host.resize((size_t)in.n_factors);
+    for (int f = 0; f < in.n_factors; f++) { fac_host[(size_t)f].f = in.factors[f]; imu_whitener(in.factors[f].covariance, fac_host[(size_t)f].W); }
+    xv_host.resize(9 * C);
+    for (size_t c = 0; c < C; c++) {
+        for (int k = 0; k < 3; k++) xv_host[9 * c + k] = in.h_velocity[3 * c + k];
+        for (int k = 0; k < 6; k++) xv_host[9 * c + 3 + k] = in.h_bias[6 * c + k];
+    }
+    RS_HIP(ctx, hipMemcpyAsync(d_fac, fac_host.data(), sizeof(ImuFactorDev) * fac_host.size(), hipMemcpyHostToDevice, s));
+    RS_HIP(ctx, hipMemcpyAsync(d_inert, inert.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice, s));
+    RS_HIP(ctx, hipMemcpyAsync(b.imu.Xv, xv_host.data(), sizeof(double) * 9 * C, hipMemcpyHostToDevice, s));
+    RS_HIP(ctx, hipMemcpyAsync(b.imu.Xv + 9 * C, xv_host.data(), sizeof(double) * 9 * C, hipMemcpyHostToDevice, s));
+    return RS_OK;
+}
+// unpack_inertial for the optimised frames, src/Optimization.cpp:363-368: velocity | bias of the accepted state (h_vb, finalize)
+static void ba_inertial_unpack(const BaInertialArgs& in, const rs_ba_problem& q, const double* h_vb)
+{
+    for (size_t c = 0; c < (size_t)q.n_cameras; c++) {
+        if (!q.h_cam_free[c]) continue;
+        for (int k = 0; k < 3; k++) in.h_velocity[3 * c + k] = h_vb[9 * c + k];
+        for (int k = 0; k < 6; k++) in.h_bias[6 * c + k] = h_vb[9 * c + 3 + k];
+    }
+}
+
+// LDS attributes of the kernels the path uses (sticky per process: rs_lds_attr)
+static int ba_prepare_kernels(rs_context* ctx, const BaDims& d, const BaPath& path)
+{
+    if (path.solve_lds && ba_prepare_reduced_solve_lds(d.n) != 0) return rs_fail(ctx, RS_ERR_HIP, "LDS attribute (K7)");
+    const size_t k5_lds = sizeof(double) * (size_t)d.Cf * 42;
+    if (!path.use_mfma && k5_lds > 48 * 1024)
+        RS_HIP(ctx, rs_lds_attr((const void*)ba_linearize_schur, k5_lds));
+    if (path.use_mfma && ba_prepare_schur(d.C, d.Cf) != 0) return rs_fail(ctx, RS_ERR_HIP, "LDS attribute (K5)");
+    return RS_OK;
+}
+
+// Set-up launches.  Local windows: K0 and the grouping's count in one launch, its scatter (incl. the item masks) in a
+// second — two instead of four (*fused).  The count adds into a histogram that must be zero when the launch starts: the
+// finalize kernel of the previous solve leaves it so, and the context remembers that (grp_zero_ptr) unless the workspace was
+// reallocated or another caller asked for workspace bytes reaching into it since (ws_dirty_hi); otherwise one memset.
+static int ba_enqueue_setup(rs_context* ctx, const rs_ba_problem& q, const BaDims& d, const BaBufs& b, const BaOpt& opt, const BaGroup& grp, bool use_mfma,
+                            const char* ws, unsigned long long free_mask, int from_mask, uint8_t* d_cam_free, int32_t* zero_ptr, int zero_n, bool* fused)
+{
+    hipStream_t s = ctx->stream;
+    *fused = use_mfma && ba_setup_fusable(d, grp);
+    if (*fused) {
+        const bool known_zero = ctx->grp_zero_ptr == zero_ptr && ctx->grp_zero_n == zero_n &&
+                                ctx->ws_dirty_hi <= (size_t)((char*)zero_ptr - ws);
+        ctx->grp_zero_ptr = nullptr;                                  // (until this solve's finalize kernel is enqueued)
+        if (!known_zero) RS_HIP(ctx, hipMemsetAsync(zero_ptr, 0, sizeof(int32_t) * (size_t)zero_n, s));
+        ba_launch_setup_fused(ctx, d, b, opt, grp, (const double*)q.d_cameras, (const double*)q.d_points, free_mask, from_mask, d_cam_free);
+    } else {
+        ctx->grp_zero_ptr = nullptr;
+        {
+            rs_prof_scope ps(ctx, "K0_ba_init");
+            hipLaunchKernelGGL(ba_init, dim3(64), dim3(256), 0, s, d, b, opt, (const double*)q.d_cameras, (const double*)q.d_points,
+                               free_mask, from_mask, d_cam_free, zero_ptr, zero_n);
+        }
+        if (use_mfma) {
+            const int rc = ba_launch_grouping(ctx, d, b, grp);
+            if (rc) return rc;
+        }
+    }
+    ctx->ws_dirty_hi = 0;
+    return RS_OK;
+}
+
+// Double-buffered state / step-scalar / set blocks: round `it` works on [it & 1] and reads [(it + 1) & 1].  last: the
+// finalize launch (round index = rounds enqueued) only reads the blocks of the round before it.
+struct BaRoundBases {
+    BaState* st; double* pts; BaSetOut* set; size_t pts_block;
+};
+static void ba_point_round(BaBufs& b, const BaRoundBases& r, int it, bool last = false)
+{
+    b.st = r.st + (it & 1); b.st_prev = r.st + ((it + 1) & 1);
+    b.pt_prev = r.pts + (size_t)((it + 1) & 1) * r.pts_block;
+    b.set_prev = r.set + (size_t)((it + 1) & 1) * BA_MAXSETS;
+    if (last) return;
+    b.pt_scal = r.pts + (size_t)(it & 1) * r.pts_block;
+    b.set_out = r.set + (size_t)(it & 1) * BA_MAXSETS;
+}
+
+// K7 of a round, with K8 inside when path.fuse78
+static int ba_enqueue_reduced_solve(rs_context* ctx, const BaDims& d, const BaBufs& b, const BaOpt& opt, const BaPath& path, bool inertial, char* ws_big)
+{
+    hipStream_t s = ctx->stream;
+    if (inertial && path.imu_lds) {
+        { rs_prof_scope ps(ctx, "K6i_imu_eliminate"); ba_launch_imu_eliminate(s, d, b, opt); }
+        { rs_prof_scope ps(ctx, "K7_ba_reduced_solve"); ba_launch_reduced_solve_lds(s, d, b, opt); }
+        { rs_prof_scope ps(ctx, "K7i_imu_expand"); ba_launch_imu_expand(s, d, b, opt); }
+    }
+    else if (inertial) { rs_prof_scope ps(ctx, "K7_ba_reduced_solve_inertial"); return ba_launch_reduced_solve_inertial(ctx, d, b, opt, ws_big); }
+    else if (path.solve_lds && path.fuse78) { rs_prof_scope ps(ctx, "K78_ba_solve_backsub"); ba_launch_solve_backsub(s, d, b, opt, ctx->n_cu); }
+    else if (path.solve_lds) { rs_prof_scope ps(ctx, "K7_ba_reduced_solve"); ba_launch_reduced_solve_lds(s, d, b, opt); }
+    else if (path.solve_big) { rs_prof_scope ps(ctx, "K7_ba_reduced_solve_blocked"); return ba_launch_reduced_solve_big(ctx, d, b, opt, ws_big, path.band); }
+    else { rs_prof_scope ps(ctx, "K7_ba_reduced_solve_global"); hipLaunchKernelGGL(ba_reduced_solve, dim3(1), dim3(256), 0, s, d, b, opt, 0); }
+    return RS_OK;
+}
+
+// One round of the single solve: K5 [C1] K7 K8 [C2], or fewer launches where the path fuses them
+static int ba_enqueue_round(rs_context* ctx, const BaDims& d, BaBufs& b, const BaOpt& opt, const BaGroup& grp, const BaPath& path,
+                            const BaRoundBases& bases, bool inertial, char* ws_big, int it)
+{
+    hipStream_t s = ctx->stream;
+    const int pblocks = d.P > 0 ? (d.P + BA_THREADS - 1) / BA_THREADS : 1;      // (an empty shard still runs the round's decision)
+    ba_point_round(b, bases, it);
+    if (path.fuse_round) {
+        rs_prof_scope ps(ctx, "K578_ba_round");
+        ba_launch_round(s, d, b, opt, grp, it);
+        return RS_OK;
+    }
+    if (path.use_mfma) {
+        rs_prof_scope ps(ctx, "K5_ba_schur_mfma");
+        // more items than compute units: the round's decision once, in front, instead of in every item's prologue
+        b.decided = grp.n_items > ctx->n_cu ? 1 : 0;
+        if (b.decided) ba_launch_decide(s, b, opt, it);
+        ba_launch_schur(s, d, b, opt, grp, it);
+        b.decided = 0;
+    } else {
+        rs_prof_scope ps(ctx, "K5_ba_linearize_schur");
+        hipLaunchKernelGGL(ba_linearize_schur, dim3(pblocks), dim3(BA_THREADS), sizeof(double) * (size_t)d.Cf * 42, s, d, b, opt, it);
+    }
+    if (rs_comm_active(ctx)) {
+        rs_prof_scope ps(ctx, "C1_allreduce_system");
+        // one SUM all-reduce: S | 8 x {rhs, U, gc} | cost / failure slots | every rank's gradient-max block
+        const int rc = rs_allreduce_f64(ctx, b.acc, b.acc_count, false);
+        if (rc) return rc;
+    }
+    const int rc = ba_enqueue_reduced_solve(ctx, d, b, opt, path, inertial, ws_big);
+    if (rc) return rc;
+    if (path.fuse78) { /* K8 ran inside the K7 launch */ }
+    else if (path.k8_lds) { rs_prof_scope ps(ctx, "K8_ba_backsub_cost"); ba_launch_backsub(s, d, b); }
+    else { rs_prof_scope ps(ctx, "K8_ba_backsub_cost_global"); hipLaunchKernelGGL(ba_backsub_cost, dim3(pblocks), dim3(BA_THREADS), 0, s, d, b); }
+    if (rs_comm_active(ctx)) {
+        rs_prof_scope ps(ctx, "C2_allreduce_cost");
+        return rs_allreduce_f64(ctx, b.pt_scal, bases.pts_block, false);
+    }
+    return RS_OK;
+}
+
+static int ba_solve_once(rs_context* ctx, const rs_ba_problem& q, const rs_ba_options* options, rs_ba_summary* h_summary,
+                         const BaInertialArgs* in, bool allow_fuse, bool* hand_lost)
 {
     *hand_lost = false;
     if (!ctx || !h_summary) return RS_ERR_INVALID;
     const BaInFlight in_flight;
     memset(h_summary, 0, sizeof *h_summary);
-    if (n_cameras < 0 || n_points < 0 || n_obs < 0) return rs_fail(ctx, RS_ERR_INVALID, "negative size");
+    if (q.n_cameras < 0 || q.n_points < 0 || q.n_obs < 0) return rs_fail(ctx, RS_ERR_INVALID, "negative size");
     // A landmark shard may be EMPTY (more ranks than landmarks, or a rank whose range holds none): the rank still takes
     // part in every exchange step with zero contributions and solves the reduced system like the others.  Cameras are
     // replicated, so n_cameras == 0 is the same on every rank and ends the call everywhere.
     const bool sharded = rs_comm_active(ctx) && ctx->n_ranks > 1;
-    if (n_cameras == 0 || ((n_points == 0 || n_obs == 0) && !sharded)) {   // nothing to optimise
+    if (q.n_cameras == 0 || ((q.n_points == 0 || q.n_obs == 0) && !sharded)) {   // nothing to optimise
         h_summary->usable = 0;
         h_summary->termination = RS_BA_FAILURE;
         return RS_OK;
     }
-    if (!d_cameras || !h_cam_free || !d_obs_ptr || !h_intrinsics || (n_points > 0 && !d_points) || (n_obs > 0 && (!d_obs_cam || !d_obs_uv)))
+    if (!q.d_cameras || !q.h_cam_free || !q.d_obs_ptr || (q.n_points > 0 && !q.d_points) || (q.n_obs > 0 && (!q.d_obs_cam || !q.d_obs_uv)))
         return rs_fail(ctx, RS_ERR_INVALID, "null pointer");
     rs_ba_options def;
     if (!options) { rs_ba_default_options(&def); options = &def; }
     RS_HIP(ctx, hipSetDevice(ctx->device));
 
+    // dimensions, inertial slots, kernel path
     BaDims d;
-    d.C = n_cameras; d.P = n_points; d.M = n_obs;
-    std::vector<int32_t> slot(n_cameras);
-    d.Cf = 0;
-    for (int c = 0; c < n_cameras; c++) slot[c] = h_cam_free[c] ? d.Cf++ : -1;
-    d.n = 6 * d.Cf;
-    d.fx = h_intrinsics[0]; d.fy = h_intrinsics[1]; d.cx = h_intrinsics[2]; d.cy = h_intrinsics[3];
-    d.huber_a = options->huber_delta;
+    std::vector<int32_t> slot(q.n_cameras), inert(q.n_cameras, -1);
+    unsigned long long free_mask = 0;
+    const bool supported = ba_dims_from(q, options, d, slot.data(), &free_mask);
     const BaOpt opt = ba_opt_from(options);
     if (opt.max_iter < 0 || opt.max_iter > 1000) return rs_fail(ctx, RS_ERR_INVALID, "max_num_iterations out of range");
-    // beyond 128 free cameras K5 is the generic kernel with its U / gc partial sums in LDS: 42 doubles per free camera of
-    // the 160 KB a workgroup may hold
-    if ((size_t)d.Cf * 42 * sizeof(double) > 159 * 1024) return rs_fail(ctx, RS_ERR_UNSUPPORTED, "more than 484 free cameras");
+    if (!supported) return rs_fail(ctx, RS_ERR_UNSUPPORTED, "more than 484 free cameras");
+    int Ci = 0, rc = RS_OK; bool imu_chain = false;
+    if (in && (rc = ba_inertial_slots(ctx, q, *in, inert, &Ci, &imu_chain)) != RS_OK) return rc;
+    // (inertial solves keep three sets: their per-radius elimination kernels were sized and tested for that)
+    BaPath path = ba_choose_path(ctx, d, opt.max_iter, in != nullptr, Ci, imu_chain, in ? BA_CALIBRATED_SETS : BA_DEFAULT_SETS,
+                                 in ? BA_CALIBRATED_SETS : BA_MAXSETS);
 
-    // which kernels: the MFMA Schur path + LDS reduced solve + LDS back-substitution form the fast path of a local
-    // window; only that path evaluates speculative radii (ns > 1)
-    const bool use_mfma = d.Cf >= 1 && d.Cf <= 128 && ba_schur_lds_bytes(d.C, d.Cf) <= 160 * 1024;
-    const bool k8_lds = ba_backsub_lds_bytes(d.C, d.n) <= 64 * 1024;
-    const bool solve_lds = d.n >= 6 && d.n <= BA_MAX_LDS_N;
-    const bool solve_big = d.n > BA_MAX_LDS_N;
-    // inertial frames: the cameras an IMU factor touches get a velocity (3) + bias (6) block
-    std::vector<int32_t> inert(n_cameras, -1);
-    int Ci = 0;
-    if (in) {
-        for (int f = 0; f < in->n_factors; f++) {
-            const int i = in->factors[f].cam_i, j = in->factors[f].cam_j;
-            if (i < 0 || j < 0 || i >= n_cameras || j >= n_cameras || i == j || !h_cam_free[i] || !h_cam_free[j])
-                return rs_fail(ctx, RS_ERR_INVALID, "IMU factor %d must join two distinct optimised cameras", f);
-        }
-        std::vector<uint8_t> touched(n_cameras, 0);
-        for (int f = 0; f < in->n_factors; f++) { touched[in->factors[f].cam_i] = 1; touched[in->factors[f].cam_j] = 1; }
-        for (int c = 0; c < n_cameras; c++) if (touched[c]) inert[c] = Ci++;
-    }
-    const int N_in = d.n + 9 * Ci;
-    // inertial solve on the local-window kernels (ba_imu.hip): the velocity / bias blocks are eliminated around the LDS
-    // K7.  Needs the factors to join consecutive inertial cameras (what the reference builds: block-tridiagonal H_zz).
-    bool imu_lds = in && use_mfma && k8_lds && solve_lds && Ci >= 2 && Ci <= ba_imu_lds_path_max_ci() && ctx->ba_imu_mode == 0;
-    if (imu_lds)
-        for (int f = 0; f < in->n_factors && imu_lds; f++) imu_lds = inert[in->factors[f].cam_j] == inert[in->factors[f].cam_i] + 1;
-    int ns = 1;
-    if (use_mfma && k8_lds && solve_lds && (!in || imu_lds)) {
-        // (inertial solves keep three: their per-radius elimination kernels were sized and tested for that)
-        ns = ctx->ba_sets > 0 ? ctx->ba_sets : (in ? BA_CALIBRATED_SETS : BA_DEFAULT_SETS);
-        if (ns > BA_MAXSETS) ns = BA_MAXSETS;
-        if (in && ns > BA_CALIBRATED_SETS) ns = BA_CALIBRATED_SETS;
-        if (ns > opt.max_iter) ns = opt.max_iter > 0 ? opt.max_iter : 1;
-    }
+    // workspace: the common layout, then the blocked / inertial solve's part and the accumulators of the inertial elimination
     const size_t C = (size_t)d.C;
     const size_t n_ranks = rs_comm_active(ctx) ? (size_t)ctx->n_ranks : 1;
-    // replicas of S for K5's scatter: the plain local window only (MFMA K5 + LDS K7, one rank, vision only)
-    int srep = 1;
-    if (use_mfma && solve_lds && !in && !rs_comm_active(ctx)) srep = ctx->ba_s_replicas > 0 ? ctx->ba_s_replicas : BA_DEFAULT_SREP;
-    const BaLayout L = ba_layout(d, ns, opt.max_iter, n_ranks, use_mfma ? ba_group_bytes(d.P, d.Cf, d.M) : 16, srep);
-    const size_t o_grp = L.grp, o_free = L.fre, pts_block = L.pts_block;
+    const BaLayout L = ba_layout(d, path.ns, opt.max_iter, n_ranks, path.use_mfma ? ba_group_bytes(d.P, d.Cf, d.M) : 16, path.srep);
     const size_t o_big = L.bytes;
-    const size_t big_bytes = align_up(in ? ba_inertial_bytes(N_in, in->n_factors, d.C) : (solve_big ? ba_big_bytes(d.n) : 16), 256);
+    const size_t big_bytes = align_up(in ? ba_inertial_bytes(d.n + 9 * Ci, in->n_factors, d.C) : (path.solve_big ? ba_big_bytes(d.n) : 16), 256);
     const size_t o_zacc = o_big + big_bytes;
-    const size_t ws_bytes = o_zacc + (imu_lds ? align_up(sizeof(double) * ba_imu_lds_total_doubles(Ci, d.n, ns), 256) : 0);
+    const size_t ws_bytes = o_zacc + (path.imu_lds ? align_up(sizeof(double) * ba_imu_lds_total_doubles(Ci, d.n, path.ns), 256) : 0);
     void* wsv = nullptr;
-    int rc = rs_workspace_quiet(ctx, ws_bytes, &wsv);      // (this solve keeps its own account of what it leaves behind, below)
+    rc = rs_workspace_quiet(ctx, ws_bytes, &wsv);      // (this solve keeps its own account of what it leaves behind: ba_enqueue_setup)
     if (rc) return rc;
     char* ws = (char*)wsv;
     BaBufs b;
     memset(&b.imu, 0, sizeof b.imu);
-    b.obs_ptr = d_obs_ptr; b.obs_cam = d_obs_cam; b.obs_uv = (const float2*)d_obs_uv;
-    ba_bind(b, ws, L, d, ns, (int)n_ranks, rs_comm_active(ctx) ? ctx->rank : 0, srep);
-    BaState* const st_base = b.st;
-    double* const pts_base = b.pt_scal;
-    BaSetOut* const set_base = b.set_out;
+    b.obs_ptr = q.d_obs_ptr; b.obs_cam = q.d_obs_cam; b.obs_uv = (const float2*)q.d_obs_uv;
+    ba_bind(b, ws, L, d, path.ns, (int)n_ranks, rs_comm_active(ctx) ? ctx->rank : 0, path.srep);
+    const BaRoundBases bases = {b.st, b.pt_scal, b.set_out, L.pts_block};
 #if RS_STAMPS
     RS_HIP(ctx, hipMemsetAsync(b.dbg, 0, sizeof(unsigned long long) * BA_DBG_WORDS, ctx->stream));
 #endif
     ctx->ba_cache = b.dbg;
 
-    void* pin = nullptr;
-    const size_t pin_prog = align_up(sizeof(BaState) + sizeof(int32_t) * C + C, 64);
-    const size_t pin_trace = pin_prog + 64;
-    const size_t pin_cams = pin_trace + sizeof(BaTrace) * (size_t)(opt.max_iter + 1);
-    const size_t pin_vb = align_up(pin_cams + sizeof(double) * 6 * C, 64);
-    rc = rs_pinned(ctx, pin_vb + (in ? sizeof(double) * 9 * C : 0), &pin);
+    // pinned block
+    const BaPinned pl = ba_pinned_single(C, opt.max_iter, in != nullptr);
+    void* pinv = nullptr;
+    rc = rs_pinned(ctx, pl.bytes, &pinv);
     if (rc) return rc;
-    double* h_vb = in ? (double*)((char*)pin + pin_vb) : nullptr;
-    ctx->ba_cams = nullptr;
-    ctx->ba_cams_n = 0;
-    BaProgress* h_prog = (BaProgress*)((char*)pin + pin_prog);
+    char* pin = (char*)pinv;
+    double* h_vb = in ? (double*)(pin + pl.vb) : nullptr;
+    ctx->ba_cams = nullptr; ctx->ba_cams_n = 0;
+    BaProgress* h_prog = (BaProgress*)(pin + pl.prog);
     h_prog->round = 0; h_prog->done = 0; h_prog->iter = 0;
-    b.prog = ns > 1 ? h_prog : nullptr;
-    BaState* h_st = (BaState*)pin;
-    int32_t* h_slot = (int32_t*)((char*)pin + sizeof(BaState));
-    uint8_t* h_free = (uint8_t*)(h_slot + C);
-    BaTrace* h_trace = (BaTrace*)((char*)pin + pin_trace);
+    b.prog = path.ns > 1 ? h_prog : nullptr;
+    BaState* h_st = (BaState*)(pin + pl.st);
+    BaTrace* h_trace = (BaTrace*)(pin + pl.trace);
+    volatile unsigned long long* h_key = (volatile unsigned long long*)(pin + pl.key);
     ctx->ba_trace_n = 0;
-    uint8_t* d_cam_free = (uint8_t*)(ws + o_free);
-    unsigned long long free_mask = 0;
+    uint8_t* d_cam_free = (uint8_t*)(ws + L.fre);
     const int from_mask = C <= 64 ? 1 : 0;
-    if (from_mask) {
-        for (size_t c = 0; c < C; c++) if (h_cam_free[c]) free_mask |= 1ull << c;
-    } else {
-        memcpy(h_slot, slot.data(), sizeof(int32_t) * C);
-        memcpy(h_free, h_cam_free, C);
-        RS_HIP(ctx, hipMemcpyAsync(b.slot, h_slot, sizeof(int32_t) * C, hipMemcpyHostToDevice, ctx->stream));
-        RS_HIP(ctx, hipMemcpyAsync(d_cam_free, h_free, C, hipMemcpyHostToDevice, ctx->stream));
+    if (!from_mask) {
+        memcpy(pin + pl.slot, slot.data(), sizeof(int32_t) * C);
+        memcpy(pin + pl.fre, q.h_cam_free, C);
+        RS_HIP(ctx, hipMemcpyAsync(b.slot, pin + pl.slot, sizeof(int32_t) * C, hipMemcpyHostToDevice, ctx->stream));
+        RS_HIP(ctx, hipMemcpyAsync(d_cam_free, pin + pl.fre, C, hipMemcpyHostToDevice, ctx->stream));
     }
 
-    if (solve_lds && ba_prepare_reduced_solve_lds(d.n) != 0) return rs_fail(ctx, RS_ERR_HIP, "LDS attribute (K7)");
-    const size_t k5_lds = sizeof(double) * (size_t)d.Cf * 42;
-    if (!use_mfma && k5_lds > 48 * 1024)
-        RS_HIP(ctx, rs_lds_attr((const void*)ba_linearize_schur, k5_lds));
-    if (use_mfma && ba_prepare_schur(d.C, d.Cf) != 0) return rs_fail(ctx, RS_ERR_HIP, "LDS attribute (K5)");
+    // kernel attributes, landmark grouping, inertial blocks, set-up launches
+    rc = ba_prepare_kernels(ctx, d, path);
+    if (rc) return rc;
     BaGroup grp;
     memset(&grp, 0, sizeof grp);
-    if (use_mfma) {
-        ba_group_carve(ws + o_grp, d.P, d.Cf, d.M, &grp);
+    int32_t* zero_ptr = nullptr; int zero_n = 0;
+    if (path.use_mfma) {
+        ba_group_carve(ws + L.grp, d.P, d.Cf, d.M, &grp);
         if (ctx->ba_item) ba_group_set_items(&grp, d.P, true, ctx->ba_item);
+        ba_group_zero_range(grp, &zero_ptr, &zero_n);
     }
-    b.obs_cs = use_mfma ? grp.obs_cs : nullptr;
-
-    const int pblocks = d.P > 0 ? (d.P + BA_THREADS - 1) / BA_THREADS : 1;      // (an empty shard still runs the round's decision)
-    int32_t* zero_ptr = nullptr;
-    int zero_n = 0;
-    if (use_mfma) ba_group_zero_range(grp, &zero_ptr, &zero_n);
+    b.obs_cs = path.use_mfma ? grp.obs_cs : nullptr;
     hipStream_t s = ctx->stream;
-    std::vector<ImuFactorDev> fac_host;
-    std::vector<double> xv_host;
-    if (in) {
-        ImuFactorDev* d_fac = nullptr;
-        int32_t* d_inert = nullptr;
-        ba_inertial_carve(ws + o_big, N_in, in->n_factors, d.C, &b.imu, &d_fac, &d_inert);
-        b.imu.n_fac = in->n_factors; b.imu.Ci = Ci; b.imu.N = N_in;
-        if (imu_lds) {
-            b.imu.zacc = (double*)(ws + o_zacc);
-            b.imu.zacc_n = (int)ba_imu_lds_zacc_doubles(Ci, d.n);
-            RS_HIP(ctx, hipMemsetAsync(b.imu.zacc, 0, sizeof(double) * (size_t)b.imu.zacc_n, s));
-        }
-        for (int k = 0; k < 3; k++) b.imu.gravity[k] = in->gravity[k];
-        fac_host.resize((size_t)in->n_factors);
-        for (int f = 0; f < in->n_factors; f++) { fac_host[(size_t)f].f = in->factors[f]; imu_whitener(in->factors[f].covariance, fac_host[(size_t)f].W); }
-        xv_host.resize(9 * C);
-        for (size_t c = 0; c < C; c++) {
-            for (int k = 0; k < 3; k++) xv_host[9 * c + k] = in->h_velocity[3 * c + k];
-            for (int k = 0; k < 6; k++) xv_host[9 * c + 3 + k] = in->h_bias[6 * c + k];
-        }
-        // (pageable sources: the copies complete before the call returns — it synchronises below)
-        RS_HIP(ctx, hipMemcpyAsync(d_fac, fac_host.data(), sizeof(ImuFactorDev) * fac_host.size(), hipMemcpyHostToDevice, s));
-        RS_HIP(ctx, hipMemcpyAsync(d_inert, inert.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice, s));
-        RS_HIP(ctx, hipMemcpyAsync(b.imu.Xv, xv_host.data(), sizeof(double) * 9 * C, hipMemcpyHostToDevice, s));
-        RS_HIP(ctx, hipMemcpyAsync(b.imu.Xv + 9 * C, xv_host.data(), sizeof(double) * 9 * C, hipMemcpyHostToDevice, s));
-    }
-    // Set-up launches.  Local windows: K0 and the grouping's count in one launch, its scatter (incl. the item masks) in a
-    // second — two instead of four.  The count adds into a histogram that must be zero when the launch starts: the finalize
-    // kernel of the previous solve leaves it so, and the context remembers that (grp_zero_ptr) unless the workspace was
-    // reallocated or another caller asked for workspace bytes reaching into it since (ws_dirty_hi); otherwise one memset.
-    const bool fused_setup = use_mfma && ba_setup_fusable(d, grp);
-    if (fused_setup) {
-        const bool known_zero = ctx->grp_zero_ptr == zero_ptr && ctx->grp_zero_n == zero_n &&
-                                ctx->ws_dirty_hi <= (size_t)((char*)zero_ptr - ws);
-        ctx->grp_zero_ptr = nullptr;                                  // (until this solve's finalize kernel is enqueued)
-        if (!known_zero) RS_HIP(ctx, hipMemsetAsync(zero_ptr, 0, sizeof(int32_t) * (size_t)zero_n, s));
-        ba_launch_setup_fused(ctx, d, b, opt, grp, (const double*)d_cameras, (const double*)d_points, free_mask, from_mask, d_cam_free);
-    } else {
-        ctx->grp_zero_ptr = nullptr;
-        {
-            rs_prof_scope ps(ctx, "K0_ba_init");
-            hipLaunchKernelGGL(ba_init, dim3(64), dim3(256), 0, s, d, b, opt, (const double*)d_cameras, (const double*)d_points,
-                               free_mask, from_mask, d_cam_free, zero_ptr, zero_n);
-        }
-        if (use_mfma) {
-            rc = ba_launch_grouping(ctx, d, b, grp);
-            if (rc) return rc;
-        }
-    }
-    ctx->ws_dirty_hi = 0;
-    // Blocked reduced solve: is S block-banded?  The grouping has just computed the largest camera span of a landmark; one
-    // word travels to the host (the solve is milliseconds: the wait costs a few per cent of one round) and decides between
-    // the one-launch banded factorisation and the general blocked one.  Sharded solves keep the general form: every rank
-    // must run the same arithmetic on the all-reduced system.
-    int band = 0;                     // 1: one workgroup, 2: two-sided (ba_solve_big.hip)
-    if (solve_big && use_mfma && !in && ctx->ba_band_mode != 1) {
-        if (rs_comm_active(ctx)) {
-            // landmark shards: the span of the WHOLE window is the largest of the ranks' spans (round 4; every rank then runs
-            // the same banded factorisation on the same all-reduced system, as it runs the same general one)
-            volatile unsigned long long* h_key = (volatile unsigned long long*)((char*)pin + pin_prog + 32);
-            *h_key = 0ull;
-            hipLaunchKernelGGL(ba_span_key, dim3(1), dim3(1), 0, s, (const int32_t*)grp.maxspan, b.dbg + BA_KEY_SPAN);
-            rc = rs_allreduce_min_u64(ctx, b.dbg + BA_KEY_SPAN, 1);
-            if (rc) return rc;
-            RS_HIP(ctx, hipMemcpyAsync((void*)h_key, b.dbg + BA_KEY_SPAN, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-            RS_HIP(ctx, hipStreamSynchronize(s));
-            const unsigned long long span = ~*h_key;
-            if (span <= (unsigned long long)ba_band_max_span()) band = ctx->ba_band_mode == 2 ? 1 : 2;
-        } else {
-            volatile int32_t* h_span = (volatile int32_t*)((char*)pin + pin_prog + 32);
-            *h_span = -1;
-            RS_HIP(ctx, hipMemcpyAsync((void*)h_span, grp.maxspan, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            long spins = 0;
-            while (*h_span < 0) {
-                if ((++spins & 0x3FFFF) == 0 && hipStreamQuery(s) != hipErrorNotReady) break;
-            }
-            if (*h_span < 0) RS_HIP(ctx, hipStreamSynchronize(s));
-            if (*h_span >= 0 && *h_span <= ba_band_max_span()) band = ctx->ba_band_mode == 2 ? 1 : 2;
-        }
-    }
-    // One ROUND = K5 + K7 + K8 and evaluates the next `ns` LM iterations of the sequential loop (all of them only if
-    // the first ns - 1 are rejected).  At least ceil(max_iter / ns) rounds are needed and at most max_iter; beyond the
-    // minimum the host follows the state machine through the progress word the first kernel of every round publishes
-    // in pinned memory: when round r starts with `iter` iterations done, at most max_iter - iter rounds (r included)
-    // can still do work.  The host stays one round ahead of the GPU, so the stream never drains.
-    // K7 + K8 as one launch (ba_solve.hip): the plain local window only — vision-only, one rank, both LDS kernels
-    // and only while all of its workgroups are resident at once (one per CU: the launch carries K7's LDS): beyond that
-    // K8's workgroups would run in several shifts behind the hand-off, and the launch of its own (many per CU) is faster
+    std::vector<ImuFactorDev> fac_host; std::vector<double> xv_host;      // (sources of ba_inertial_upload's copies: alive until the solve has been waited for)
+    if (in && (rc = ba_inertial_upload(ctx, *in, d, b, path, ws + o_big, ws + o_zacc, inert, Ci, fac_host, xv_host)) != RS_OK) return rc;
+    bool fused_setup = false;
+    rc = ba_enqueue_setup(ctx, q, d, b, opt, grp, path.use_mfma, ws, free_mask, from_mask, d_cam_free, zero_ptr, zero_n, &fused_setup);
+    if (rc) return rc;
+
+    // what only exists now: the band form (sharded solves agree on it) and the launch fusion
+    rc = ba_choose_band(ctx, path, in != nullptr, grp, b, h_key, &path.band);
+    if (rc) return rc;
     b.hand_timeout = 100ull * (unsigned long long)ctx->ba_handoff_timeout_us;
-    // The whole round as ONE launch (ba_round.hip: K5's item workgroups become K8's after they have counted themselves for
-    // K7): the same conditions plus the MFMA K5 with its camera blocks in LDS, and again every workgroup resident at once.
-    // (a landmark shard may fuse K7 + K8 too: the launch sits between the two exchange steps of the round, C1 in front of
-    // it and C2 behind; whether a rank fuses is its own business — shard sizes differ — but a lost hand-off is agreed on by
-    // all ranks below, so that every rank re-runs the solve or none does)
-    const bool plain_window = allow_fuse && solve_lds && k8_lds && !in;
-    // Measured (tools/round_stamps.py, DESIGN.md 4.2b): 86 us per round against 43 + 45 as two launches — the round is a strict
-    // chain (linearise -> solve -> back-substitute), so keeping the workgroups resident buys the boundary and little else.
-    // It is therefore opt-in ("ba_fuse_mode" 3); the default stays K5, then K7 + K8 in one launch.
-    const bool fuse_round = plain_window && !rs_comm_active(ctx) && use_mfma && ctx->ba_fuse_mode == 3 && ns <= BA_CALIBRATED_SETS &&
-                            ba_round_eligible(d) && ba_round_workgroups(d, b, grp) <= ctx->n_cu;
-    const bool fuse78 = !fuse_round && plain_window && d.P > 0 /* an empty landmark shard has no K8 workgroup to clear the accumulators */ &&
-                        (ctx->ba_fuse_mode >= 2 || (ctx->ba_fuse_mode == 0 && in_flight.others == 0)) &&
-                        ba_solve_backsub_workgroups(d, b, ctx->n_cu) <= ctx->n_cu;
-    if (fuse_round && ba_prepare_round(d) != 0) return rs_fail(ctx, RS_ERR_HIP, "LDS attribute (round)");
-    auto enqueue_round = [&](int it) -> int {
-        // double-buffered state / step-scalar blocks: round `it` works on [it & 1] and reads [(it + 1) & 1]
-        b.st = st_base + (it & 1); b.st_prev = st_base + ((it + 1) & 1);
-        b.pt_scal = pts_base + (size_t)(it & 1) * pts_block;
-        b.pt_prev = pts_base + (size_t)((it + 1) & 1) * pts_block;
-        b.set_out = set_base + (size_t)(it & 1) * BA_MAXSETS; b.set_prev = set_base + (size_t)((it + 1) & 1) * BA_MAXSETS;
-        if (fuse_round) {
-            rs_prof_scope ps(ctx, "K578_ba_round");
-            ba_launch_round(s, d, b, opt, grp, it);
-            return RS_OK;
-        }
-        if (use_mfma) {
-            rs_prof_scope ps(ctx, "K5_ba_schur_mfma");
-            // more items than compute units: the round's decision once, in front, instead of in every item's prologue
-            b.decided = grp.n_items > ctx->n_cu ? 1 : 0;
-            if (b.decided) ba_launch_decide(s, b, opt, it);
-            ba_launch_schur(s, d, b, opt, grp, it);
-            b.decided = 0;
-        } else {
-            rs_prof_scope ps(ctx, "K5_ba_linearize_schur");
-            hipLaunchKernelGGL(ba_linearize_schur, dim3(pblocks), dim3(BA_THREADS), k5_lds, s, d, b, opt, it);
-        }
-        if (rs_comm_active(ctx)) {
-            rs_prof_scope ps(ctx, "C1_allreduce_system");
-            // one SUM all-reduce: S | 8 x {rhs, U, gc} | cost / failure slots | every rank's gradient-max block
-            int rc2 = rs_allreduce_f64(ctx, b.acc, b.acc_count, false);
-            if (rc2) return rc2;
-        }
-        if (in && imu_lds) {
-            { rs_prof_scope ps(ctx, "K6i_imu_eliminate"); ba_launch_imu_eliminate(s, d, b, opt); }
-            { rs_prof_scope ps(ctx, "K7_ba_reduced_solve"); ba_launch_reduced_solve_lds(s, d, b, opt); }
-            { rs_prof_scope ps(ctx, "K7i_imu_expand"); ba_launch_imu_expand(s, d, b, opt); }
-        } else if (in) {
-            rs_prof_scope ps(ctx, "K7_ba_reduced_solve_inertial");
-            int rc2 = ba_launch_reduced_solve_inertial(ctx, d, b, opt, ws + o_big);
-            if (rc2) return rc2;
-        } else if (solve_lds && fuse78) {
-            rs_prof_scope ps(ctx, "K78_ba_solve_backsub");
-            ba_launch_solve_backsub(s, d, b, opt, ctx->n_cu);
-        } else if (solve_lds) {
-            rs_prof_scope ps(ctx, "K7_ba_reduced_solve");
-            ba_launch_reduced_solve_lds(s, d, b, opt);
-        } else if (solve_big) {
-            rs_prof_scope ps(ctx, "K7_ba_reduced_solve_blocked");
-            int rc2 = ba_launch_reduced_solve_big(ctx, d, b, opt, ws + o_big, band);
-            if (rc2) return rc2;
-        } else {
-            rs_prof_scope ps(ctx, "K7_ba_reduced_solve_global");
-            hipLaunchKernelGGL(ba_reduced_solve, dim3(1), dim3(256), 0, s, d, b, opt, 0);
-        }
-        if (fuse78) {
-            // K8 ran inside the K7 launch
-        } else if (k8_lds) {
-            rs_prof_scope ps(ctx, "K8_ba_backsub_cost");
-            ba_launch_backsub(s, d, b);
-        } else {
-            rs_prof_scope ps(ctx, "K8_ba_backsub_cost_global");
-            hipLaunchKernelGGL(ba_backsub_cost, dim3(pblocks), dim3(BA_THREADS), 0, s, d, b);
-        }
-        if (rs_comm_active(ctx)) {
-            rs_prof_scope ps(ctx, "C2_allreduce_cost");
-            int rc2 = rs_allreduce_f64(ctx, b.pt_scal, pts_block, false);
-            if (rc2) return rc2;
-        }
-        return RS_OK;
-    };
+    ba_choose_fusion(ctx, d, b, grp, path, allow_fuse, in != nullptr, in_flight.others);
+    if (path.fuse_round && ba_prepare_round(d) != 0) return rs_fail(ctx, RS_ERR_HIP, "LDS attribute (round)");
+
+    // rounds
     int rounds = 0;
-    const int min_rounds = (opt.max_iter + ns - 1) / ns;
-    for (; rounds < min_rounds; rounds++) {
-        rc = enqueue_round(rounds);
-        if (rc) return rc;
-    }
-    while (ns > 1 && rounds < opt.max_iter) {
-        // wait until the GPU has started the last enqueued round (it then has a whole round of work in front of it)
-        long spins = 0;
-        while (h_prog->round < rounds) {
-            if ((++spins & 0xFFFFF) == 0 && hipStreamQuery(s) != hipErrorNotReady) break;   // stream drained or failed
-        }
-        if (h_prog->round < rounds) break;                 // nothing left in flight: finalize reports the state
-        const int it_seen = h_prog->iter, done_seen = h_prog->done;
-        if (done_seen || opt.max_iter - it_seen <= 1) break;          // the round in flight is the last that can matter
-        rc = enqueue_round(rounds);
-        if (rc) return rc;
-        rounds++;
-    }
+    const BaProgress* const progs[1] = {h_prog};
+    rc = ba_follow_rounds(s, opt.max_iter, path.ns, progs, 1,
+                          [&](int it) { return ba_enqueue_round(ctx, d, b, opt, grp, path, bases, in != nullptr, ws + o_big, it); }, rounds);
+    if (rc) return rc;
     {
         rs_prof_scope ps(ctx, "K10_ba_finalize");
         // the last decisions: round index `rounds` reads the blocks of round rounds - 1
         const int itf = rounds;
-        b.st = st_base + (itf & 1); b.st_prev = st_base + ((itf + 1) & 1);
-        b.pt_prev = pts_base + (size_t)((itf + 1) & 1) * pts_block;
-        b.set_prev = set_base + (size_t)((itf + 1) & 1) * BA_MAXSETS;
+        ba_point_round(b, bases, itf, true);
         b.prog = nullptr;
         h_prog->pad = 0;
-        hipLaunchKernelGGL(ba_finalize, dim3(BA_FINALIZE_WGS), dim3(256), 0, s, d, b, opt, itf, d_cameras, (const uint8_t*)d_cam_free, d_points, h_st, h_trace,
-                           (double*)((char*)pin + pin_cams), h_vb, &h_prog->pad, fused_setup ? zero_ptr : nullptr, fused_setup ? zero_n : 0);
+        hipLaunchKernelGGL(ba_finalize, dim3(BA_FINALIZE_WGS), dim3(256), 0, s, d, b, opt, itf, q.d_cameras, (const uint8_t*)d_cam_free, q.d_points, h_st, h_trace,
+                           (double*)(pin + pl.cams), h_vb, &h_prog->pad, fused_setup ? zero_ptr : nullptr, fused_setup ? zero_n : 0);
         RS_HIP(ctx, hipGetLastError());
         if (fused_setup) { ctx->grp_zero_ptr = zero_ptr; ctx->grp_zero_n = zero_n; }      // stream-ordered in front of the next solve
         // wait for the completion flag the last workgroup of ba_finalize raises in pinned memory (summary, trace, camera
@@ -991,48 +1031,35 @@ static int ba_solve_once(rs_context* ctx, int n_cameras, int n_points, int n_obs
         RS_HIP(ctx, ba_wait_flag(s, &h_prog->pad, itf + 1));
     }
     RS_HIP(ctx, hipGetLastError());
+
+    // results
     ba_summary_from(*h_st, h_summary);
     ctx->ba_trace = h_trace;            // stays valid until the next call that uses the pinned block
     ctx->ba_trace_n = h_st->iter;
-    ctx->ba_stats[0] = h_st->n_rounds; ctx->ba_stats[1] = h_st->n_fresh; ctx->ba_stats[2] = h_st->n_sets;
-    ctx->ba_stats[3] = rounds;
+    ctx->ba_stats[0] = h_st->n_rounds; ctx->ba_stats[1] = h_st->n_fresh; ctx->ba_stats[2] = h_st->n_sets; ctx->ba_stats[3] = rounds;
     *hand_lost = h_st->hand_lost != 0;
-    if (rs_comm_active(ctx) && allow_fuse && solve_lds && k8_lds && !in) {
-        // every rank gets here (the conditions above are the same on all of them: cameras are replicated), fused or not
-        volatile unsigned long long* h_key = (volatile unsigned long long*)((char*)pin + pin_prog + 32);
+    if (rs_comm_active(ctx) && path.may_fuse) {
+        // every rank gets here (the conditions are the same on all of them: cameras are replicated), fused or not
         hipLaunchKernelGGL(ba_lost_key, dim3(1), dim3(1), 0, s, (const BaState*)b.st, b.dbg + BA_KEY_LOST);
-        rc = rs_allreduce_min_u64(ctx, b.dbg + BA_KEY_LOST, 1);
+        rc = ba_min_key_to_host(ctx, b.dbg + BA_KEY_LOST, h_key);
         if (rc) return rc;
-        RS_HIP(ctx, hipMemcpyAsync((void*)h_key, b.dbg + BA_KEY_LOST, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        RS_HIP(ctx, hipStreamSynchronize(s));
         *hand_lost = *h_key == 0ull;
     }
-    ctx->ba_cams = (const double*)((char*)pin + pin_cams);
-    ctx->ba_cams_n = n_cameras;
-    if (in && h_st->usable)                                  // unpack_inertial for the optimised frames, src/Optimization.cpp:363-368
-        for (size_t c = 0; c < C; c++) {
-            if (!h_cam_free[c]) continue;
-            for (int k = 0; k < 3; k++) in->h_velocity[3 * c + k] = h_vb[9 * c + k];
-            for (int k = 0; k < 6; k++) in->h_bias[6 * c + k] = h_vb[9 * c + 3 + k];
-        }
+    ctx->ba_cams = (const double*)(pin + pl.cams); ctx->ba_cams_n = q.n_cameras;
+    if (in && h_st->usable) ba_inertial_unpack(*in, q, h_vb);
     return RS_OK;
 }
 
 // A lost hand-off inside the fused K7 + K8 launch (ba_backsub_body.h) says something about scheduling, not about the
 // data: the inputs are untouched (nothing is written back from an unusable solve), so the solve runs once more as
 // separate launches, which need no hand-off.  Counted in rs_ba_get_stats [4].
-static int ba_solve_impl(rs_context* ctx, int n_cameras, int n_points, int n_obs, double* d_cameras,
-                         const uint8_t* h_cam_free, double* d_points, const int32_t* d_obs_ptr,
-                         const int32_t* d_obs_cam, const float* d_obs_uv, const float h_intrinsics[4],
-                         const rs_ba_options* options, rs_ba_summary* h_summary, const BaInertialArgs* in)
+static int ba_solve_impl(rs_context* ctx, const rs_ba_problem& q, const rs_ba_options* options, rs_ba_summary* h_summary, const BaInertialArgs* in)
 {
     bool lost = false;
-    int rc = ba_solve_once(ctx, n_cameras, n_points, n_obs, d_cameras, h_cam_free, d_points, d_obs_ptr, d_obs_cam, d_obs_uv,
-                           h_intrinsics, options, h_summary, in, true, &lost);
+    int rc = ba_solve_once(ctx, q, options, h_summary, in, true, &lost);
     if (rc == RS_OK && lost) {
         ctx->ba_stats[4]++;
-        rc = ba_solve_once(ctx, n_cameras, n_points, n_obs, d_cameras, h_cam_free, d_points, d_obs_ptr, d_obs_cam, d_obs_uv,
-                           h_intrinsics, options, h_summary, in, false, &lost);
+        rc = ba_solve_once(ctx, q, options, h_summary, in, false, &lost);
     }
     return rc;
 }
@@ -1042,8 +1069,8 @@ extern "C" int rs_bundle_adjust(rs_context* ctx, int n_cameras, int n_points, in
                                 const int32_t* d_obs_cam, const float* d_obs_uv, const float h_intrinsics[4],
                                 const rs_ba_options* options, rs_ba_summary* h_summary)
 {
-    return ba_solve_impl(ctx, n_cameras, n_points, n_obs, d_cameras, h_cam_free, d_points, d_obs_ptr, d_obs_cam, d_obs_uv,
-                         h_intrinsics, options, h_summary, nullptr);
+    return ba_solve_impl(ctx, ba_problem_from(n_cameras, n_points, n_obs, d_cameras, h_cam_free, d_points, d_obs_ptr, d_obs_cam, d_obs_uv, h_intrinsics),
+                         options, h_summary, nullptr);
 }
 
 extern "C" int rs_bundle_adjust_inertial(rs_context* ctx, int n_cameras, int n_points, int n_obs, double* d_cameras,
@@ -1052,14 +1079,13 @@ extern "C" int rs_bundle_adjust_inertial(rs_context* ctx, int n_cameras, int n_p
                                          double* h_velocity, double* h_bias, const rs_imu_factor* h_factors, int n_factors,
                                          const double h_gravity[3], const rs_ba_options* options, rs_ba_summary* h_summary)
 {
+    const rs_ba_problem q = ba_problem_from(n_cameras, n_points, n_obs, d_cameras, h_cam_free, d_points, d_obs_ptr, d_obs_cam, d_obs_uv, h_intrinsics);
     if (n_factors < 0) return ctx ? rs_fail(ctx, RS_ERR_INVALID, "negative n_factors") : RS_ERR_INVALID;
     if (n_factors == 0)                                      // InertialInput::usable() false / no pair with >= 2 samples
-        return ba_solve_impl(ctx, n_cameras, n_points, n_obs, d_cameras, h_cam_free, d_points, d_obs_ptr, d_obs_cam, d_obs_uv,
-                             h_intrinsics, options, h_summary, nullptr);
+        return ba_solve_impl(ctx, q, options, h_summary, nullptr);
     if (!h_velocity || !h_bias || !h_factors || !h_gravity) return ctx ? rs_fail(ctx, RS_ERR_INVALID, "null pointer") : RS_ERR_INVALID;
     const BaInertialArgs in{h_velocity, h_bias, h_factors, n_factors, h_gravity};
-    return ba_solve_impl(ctx, n_cameras, n_points, n_obs, d_cameras, h_cam_free, d_points, d_obs_ptr, d_obs_cam, d_obs_uv,
-                         h_intrinsics, options, h_summary, &in);
+    return ba_solve_impl(ctx, q, options, h_summary, &in);
 }
 
 // ---------------------------------------------------------------- batch of independent windows
@@ -1067,7 +1093,6 @@ extern "C" int rs_bundle_adjust_inertial(rs_context* ctx, int n_cameras, int n_p
 // that fills a fraction of the chip, so they overlap on the device when they sit on different streams.  Lanes = child
 // contexts (stream + workspace + pinned block each); one host thread per lane walks its share of the windows with the
 // ordinary solve (incl. the round-following logic), which keeps every lane's stream fed.
-#include <thread>
 
 // Grid mode: the B windows run as ONE launch sequence, blockIdx.z = window (BaWin, ba_common.h).  Every kernel of the
 // local-window fast path has a batched entry point that takes its per-window arguments from a device array; a round's
@@ -1081,13 +1106,10 @@ static int ba_solve_batch_grid(rs_context* ctx, int B, const rs_ba_problem* Q, c
     if (!options) { rs_ba_default_options(&def); options = &def; }
     const BaOpt opt = ba_opt_from(options);
     if (opt.max_iter < 1 || opt.max_iter > 1000) return 1;
-    int ns = ctx->ba_sets > 0 ? ctx->ba_sets : BA_CALIBRATED_SETS;      // (throughput mode: extra radii are CU time other windows want)
-    if (ns > BA_CALIBRATED_SETS) ns = BA_CALIBRATED_SETS;
-    if (ns > opt.max_iter) ns = opt.max_iter;
     std::vector<BaWin> wins((size_t)B);
     std::vector<size_t> ws_off((size_t)B), pin_off((size_t)B);
     size_t ws_total = align_up(sizeof(BaWin) * (size_t)B, 256), pin_total = 0;
-    int max_P = 0, max_items = 0, max_n = 0, max_C = 0;
+    int max_P = 0, max_items = 0, max_n = 0, max_C = 0, ns = 1;
     size_t k5_lds = 0, k8_lds = 0;
     std::vector<BaLayout> lay((size_t)B);
     for (int i = 0; i < B; i++) {
@@ -1097,23 +1119,17 @@ static int ba_solve_batch_grid(rs_context* ctx, int B, const rs_ba_problem* Q, c
         BaWin& w = wins[(size_t)i];
         memset(&w, 0, sizeof w);
         BaDims& d = w.d;
-        d.C = q.n_cameras; d.P = q.n_points; d.M = q.n_obs;
-        d.Cf = 0;
-        unsigned long long mask = 0;
-        for (int c = 0; c < d.C; c++) if (q.h_cam_free[c]) { mask |= 1ull << c; d.Cf++; }
-        d.n = 6 * d.Cf;
-        d.fx = q.intrinsics[0]; d.fy = q.intrinsics[1]; d.cx = q.intrinsics[2]; d.cy = q.intrinsics[3];
-        d.huber_a = options->huber_delta;
-        const bool use_mfma = d.Cf >= 1 && ba_schur_lds_bytes(d.C, d.Cf) <= 160 * 1024;
-        if (!use_mfma || ba_backsub_lds_bytes(d.C, d.n) > 64 * 1024 || d.n < 6 || d.n > BA_MAX_LDS_N) return 1;
-        w.free_mask = mask;
-        const size_t C = (size_t)d.C;
+        if (!ba_dims_from(q, options, d, nullptr, &w.free_mask)) return 1;
+        // the plain local-window path only, with at most three sets (throughput mode: extra radii are CU time other windows
+        // want) and one copy of S whatever "ba_s_replicas" says
+        const BaPath path = ba_choose_path(ctx, d, opt.max_iter, false, 0, false, BA_CALIBRATED_SETS, BA_CALIBRATED_SETS);
+        if (!path.local_window()) return 1;
+        ns = path.ns;                                   // (the same for every window: context and options decide it)
         lay[(size_t)i] = ba_layout(d, ns, opt.max_iter, 1, ba_group_bytes(d.P, d.Cf, d.M));   // the single solve's layout, one copy per window
-        const BaLayout& L = lay[(size_t)i];
         ws_off[(size_t)i] = ws_total;
-        ws_total += L.bytes;
+        ws_total += lay[(size_t)i].bytes;
         pin_off[(size_t)i] = pin_total;
-        pin_total += align_up(sizeof(BaState), 64) + 64 + align_up(sizeof(BaTrace) * (size_t)(opt.max_iter + 1), 64) + align_up(sizeof(double) * 6 * C, 64);
+        pin_total += ba_pinned_batch((size_t)d.C, opt.max_iter).bytes;
         max_P = std::max(max_P, d.P); max_n = std::max(max_n, d.n); max_C = std::max(max_C, d.C);
         k8_lds = std::max(k8_lds, ba_backsub_lds_bytes(d.C, d.n));
     }
@@ -1126,6 +1142,7 @@ static int ba_solve_batch_grid(rs_context* ctx, int B, const rs_ba_problem* Q, c
     rc = rs_pinned(ctx, pin_wins + sizeof(BaWin) * (size_t)B, &pinv);
     if (rc) { *rc_out = rc; return 0; }
     char* pin = (char*)pinv;
+    std::vector<const BaProgress*> progs((size_t)B);
     for (int i = 0; i < B; i++) {
         const rs_ba_problem& q = Q[i];
         BaWin& w = wins[(size_t)i];
@@ -1142,12 +1159,13 @@ static int ba_solve_batch_grid(rs_context* ctx, int B, const rs_ba_problem* Q, c
         k5_lds = std::max(k5_lds, ba_schur_lds_bytes(d.C, d.Cf, w.g.it_l, ns));
         w.st_base = b.st; w.pts_base = b.pt_scal; w.set_base = b.set_out; w.pts_block = L.pts_block;
         char* hp = pin + pin_off[(size_t)i];
-        w.h_st = (BaState*)hp;
-        w.prog = (BaProgress*)(hp + align_up(sizeof(BaState), 64));
-        w.h_trace = (BaTrace*)(hp + align_up(sizeof(BaState), 64) + 64);
-        w.h_cams = (double*)((char*)w.h_trace + align_up(sizeof(BaTrace) * (size_t)(opt.max_iter + 1), 64));
+        const BaPinned pl = ba_pinned_batch((size_t)d.C, opt.max_iter);
+        w.h_st = (BaState*)(hp + pl.st);
+        w.prog = (BaProgress*)(hp + pl.prog);
+        w.h_trace = (BaTrace*)(hp + pl.trace);
+        w.h_cams = (double*)(hp + pl.cams);
         w.prog->round = 0; w.prog->done = 0; w.prog->iter = 0;
-        b.prog = w.prog;
+        progs[(size_t)i] = b.prog = w.prog;
         w.cams_in = q.d_cameras; w.pts_in = q.d_points; w.cams_out = q.d_cameras; w.pts_out = q.d_points;
         w.cam_free = (uint8_t*)(base + L.fre);
         ba_group_zero_range(w.g, &w.zero_ptr, &w.zero_n);
@@ -1170,28 +1188,10 @@ static int ba_solve_batch_grid(rs_context* ctx, int B, const rs_ba_problem* Q, c
         { rs_prof_scope ps(ctx, "K5_ba_schur_mfma"); ba_launch_decide_batch(s, d_wins, B, opt, it); ba_launch_schur_batch(s, d_wins, B, opt, it, max_items, wins[0].g.it_l, k5_lds); }
         { rs_prof_scope ps(ctx, "K7_ba_reduced_solve"); ba_launch_reduced_solve_lds_batch(s, d_wins, B, opt, it, ns, max_n); }
         { rs_prof_scope ps(ctx, "K8_ba_backsub_cost"); ba_launch_backsub_batch(s, d_wins, B, it, ns, max_P, k8_lds); }
+        return (int)RS_OK;
     };
     int rounds = 0;
-    const int min_rounds = (opt.max_iter + ns - 1) / ns;
-    for (; rounds < min_rounds; rounds++) enqueue_round(rounds);
-    while (ns > 1 && rounds < opt.max_iter) {
-        // as in the single solve, for the slowest window: wait until every window has started the last enqueued round
-        long spins = 0;
-        bool drained = false;
-        for (int i = 0; i < B && !drained; i++)
-            while (wins[(size_t)i].prog->round < rounds) {
-                if ((++spins & 0xFFFFF) == 0 && hipStreamQuery(s) != hipErrorNotReady) { drained = true; break; }
-            }
-        if (drained) break;
-        bool more = false;
-        for (int i = 0; i < B; i++) {
-            const BaProgress* pr = wins[(size_t)i].prog;
-            if (!pr->done && opt.max_iter - pr->iter > 1) more = true;
-        }
-        if (!more) break;
-        enqueue_round(rounds);
-        rounds++;
-    }
+    (void)ba_follow_rounds(s, opt.max_iter, ns, progs.data(), B, enqueue_round, rounds);      // (the slowest window decides)
     {
         rs_prof_scope ps(ctx, "K10_ba_finalize");
         hipLaunchKernelGGL(ba_finalize_batch, dim3(16, 1, B), dim3(256), 0, s, d_wins, opt, rounds);
@@ -1235,9 +1235,7 @@ extern "C" int rs_bundle_adjust_batch(rs_context* ctx, int n_problems, const rs_
         rs_context* c = ctx->batch_lanes[(size_t)lane];
         c->ba_sets = ctx->ba_sets;
         for (int i = lane; i < n_problems; i += lanes) {
-            const rs_ba_problem& q = h_problems[i];
-            const int rc = rs_bundle_adjust(c, q.n_cameras, q.n_points, q.n_obs, q.d_cameras, q.h_cam_free, q.d_points, q.d_obs_ptr,
-                                            q.d_obs_cam, q.d_obs_uv, q.intrinsics, options, &h_summaries[i]);
+            const int rc = ba_solve_impl(c, h_problems[i], options, &h_summaries[i], nullptr);
             if (rc && !status[(size_t)lane]) status[(size_t)lane] = rc;
         }
     };

@@ -659,3 +659,93 @@ void ba_launch_round(hipStream_t s, const BaDims& d, const BaBufs& b, const BaOp
 // ---- back-substitution + candidate cost (ba_update.hip)
 size_t ba_backsub_lds_bytes(int C, int n);
 void ba_launch_backsub(hipStream_t s, const BaDims& d, const BaBufs& b);
+
+// ---- host pieces shared by the single solve and the grid batch (ba.hip)
+// BaDims of a problem; slot[c] = index of camera c among the free ones or -1 (null: not wanted); the free cameras as a bit
+// mask (windows of at most 64 cameras: the mask is then the free-camera table).  False: more than 484 free cameras.
+static inline bool ba_dims_from(const rs_ba_problem& q, const rs_ba_options* options, BaDims& d, int32_t* slot, unsigned long long* free_mask)
+{
+    d.C = q.n_cameras; d.P = q.n_points; d.M = q.n_obs; d.Cf = 0;
+    *free_mask = 0;
+    for (int c = 0; c < d.C; c++) {
+        if (slot) slot[c] = q.h_cam_free[c] ? d.Cf : -1;
+        if (q.h_cam_free[c] && d.C <= 64) *free_mask |= 1ull << c;
+        if (q.h_cam_free[c]) d.Cf++;
+    }
+    d.n = 6 * d.Cf;
+    d.fx = q.intrinsics[0]; d.fy = q.intrinsics[1]; d.cx = q.intrinsics[2]; d.cy = q.intrinsics[3];
+    d.huber_a = options->huber_delta;
+    // beyond 128 free cameras K5 is the generic kernel with its U / gc partial sums in LDS: 42 doubles per free camera of
+    // the 160 KB a workgroup may hold
+    return (size_t)d.Cf * 42 * sizeof(double) <= 159 * 1024;
+}
+
+// The kernel choice of one solve, as a value.  ba_choose_path fills the first block before anything is allocated,
+// ba_choose_band and ba_choose_fusion the rest once the grouping is carved and the set-up launches are enqueued.
+struct BaPath {
+    bool use_mfma, k8_lds;         // K5 is the MFMA Schur kernel (else ba_linearize_schur); K8 holds the cameras in LDS (else ba_backsub_cost)
+    bool solve_lds, solve_big;     // K7 with S in LDS (ba_solve.hip) / blocked (ba_solve_big.hip); neither: ba_reduced_solve
+    bool imu_lds;                  // inertial blocks eliminated around the LDS K7 (ba_imu.hip), else the N x N blocked solve
+    int ns, srep, band;            // speculative radii per round; replicas of S; blocked solve: 0 general, 1 banded in one workgroup, 2 two-sided
+    bool may_fuse;                 // the plain local window on its first attempt: K7 + K8 may share a launch (and lose a hand-off)
+    bool fuse_round, fuse78;       // K5 + K7 + K8 as one launch (ba_round.hip); K7 + K8 as one launch (ba_solve.hip)
+    // the MFMA Schur path + LDS reduced solve + LDS back-substitution form the fast path of a local window
+    bool local_window() const { return use_mfma && k8_lds && solve_lds; }
+};
+
+// sets_default / sets_max: the speculative radii per round when "ba_speculative_sets" is 0, and their cap
+static inline BaPath ba_choose_path(const rs_context* ctx, const BaDims& d, int max_iter, bool inertial, int Ci, bool imu_chain, int sets_default, int sets_max)
+{
+    BaPath p = {};
+    p.use_mfma = d.Cf >= 1 && d.Cf <= 128 && ba_schur_lds_bytes(d.C, d.Cf) <= 160 * 1024;
+    p.k8_lds = ba_backsub_lds_bytes(d.C, d.n) <= 64 * 1024;
+    p.solve_lds = d.n >= 6 && d.n <= BA_MAX_LDS_N;
+    p.solve_big = d.n > BA_MAX_LDS_N;
+    // inertial solve on the local-window kernels (ba_imu.hip): the velocity / bias blocks are eliminated around the LDS
+    // K7.  Needs the factors to join consecutive inertial cameras (ba_inertial_slots).
+    p.imu_lds = inertial && p.local_window() && Ci >= 2 && Ci <= ba_imu_lds_path_max_ci() && ctx->ba_imu_mode == 0 && imu_chain;
+    // only the local-window path evaluates speculative radii (ns > 1)
+    p.ns = 1;
+    if (p.local_window() && (!inertial || p.imu_lds)) {
+        p.ns = ctx->ba_sets > 0 ? ctx->ba_sets : sets_default;
+        if (p.ns > sets_max) p.ns = sets_max;
+        if (p.ns > max_iter) p.ns = max_iter > 0 ? max_iter : 1;
+    }
+    // replicas of S for K5's scatter: the plain local window only (MFMA K5 + LDS K7, one rank, vision only)
+    p.srep = 1;
+    if (p.use_mfma && p.solve_lds && !inertial && !rs_comm_active(ctx)) p.srep = ctx->ba_s_replicas > 0 ? ctx->ba_s_replicas : BA_DEFAULT_SREP;
+    return p;
+}
+
+// One ROUND = K5 + K7 + K8 and evaluates the next `ns` LM iterations of the sequential loop (all of them only if
+// the first ns - 1 are rejected).  At least ceil(max_iter / ns) rounds are needed and at most max_iter; beyond the
+// minimum the host follows the state machine through the progress word the first kernel of every round publishes
+// in pinned memory (one per window): when round r starts with `iter` iterations done, at most max_iter - iter rounds (r
+// included) can still do work.  The host stays one round ahead of the GPU, so the stream never drains.  With several
+// windows (grid batch) it follows the slowest.  `rounds`: how many were enqueued (enqueue(r) returns a status).
+template <class Enqueue>
+static inline int ba_follow_rounds(hipStream_t s, int max_iter, int ns, const BaProgress* const* prog, int n_windows, Enqueue enqueue, int& rounds)
+{
+    const int min_rounds = (max_iter + ns - 1) / ns;
+    for (rounds = 0; rounds < min_rounds; rounds++)
+        if (const int rc = enqueue(rounds)) return rc;
+    while (ns > 1 && rounds < max_iter) {
+        // wait until the GPU has started the last enqueued round of every window (it then has a whole round of work in front of it)
+        long spins = 0;
+        bool in_flight = true, more = false;
+        for (int i = 0; i < n_windows && in_flight; i++) {
+            while (prog[i]->round < rounds)
+                if ((++spins & 0xFFFFF) == 0 && hipStreamQuery(s) != hipErrorNotReady) break;   // stream drained or failed
+            in_flight = prog[i]->round >= rounds;
+        }
+        if (!in_flight) break;                             // nothing left in flight: finalize reports the state
+        for (int i = 0; i < n_windows; i++) {
+            const int it_seen = prog[i]->iter, done_seen = prog[i]->done;
+            if (!done_seen && max_iter - it_seen > 1) more = true;
+        }
+        if (!more) break;                                  // the round in flight is the last that can matter
+        if (const int rc = enqueue(rounds)) return rc;
+        rounds++;
+    }
+    return RS_OK;
+}

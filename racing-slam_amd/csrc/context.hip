@@ -46,7 +46,6 @@ extern "C" int rs_context_create(int device_id, rs_context** out)
     return RS_OK;
 }
 
-void rs_ba_cache_free(rs_context* ctx);
 static void arena_free(rs_arena& a, bool pinned);
 
 extern "C" int rs_context_destroy(rs_context* ctx)
@@ -54,7 +53,6 @@ extern "C" int rs_context_destroy(rs_context* ctx)
     if (!ctx) return RS_OK;
     (void)hipSetDevice(ctx->device);
     rs_comm_destroy(ctx);
-    rs_ba_cache_free(ctx);
     for (rs_context* lane : ctx->batch_lanes) rs_context_destroy(lane);
     for (hipStream_t st : ctx->batch_streams) (void)hipStreamDestroy(st);
     ctx->batch_lanes.clear();
