@@ -1125,7 +1125,9 @@ int rs_pose_hypotheses(rs_context* ctx, const rs_pose_estimator* est, int32_t* h
  * verify_pnp (src/LoopDetector.cpp:176-229) and Initialization's third-view check (src/Initialization.cpp:188-228, 2.0 px).
  * OpenCV's RNG and RANSAC internals cannot be restated bit for bit; the specification is tests/pnp_ref.py: hashed
  * samples of 4, Grunert's P3P on the first three (the quartic's real roots by bisection between the roots of its
- * derivatives; R, t from the orthonormal frames of the two triangles), every model scored by its integer count of
+ * derivatives; the distance ratios polished by two Newton steps in the cosine laws, and taken from the third cosine
+ * law where the quartic's quotient is 0 / 0; R, t from the orthonormal frames of the two triangles; at most 4 models
+ * per sample, the first 4 in ascending root order), every model scored by its integer count of
  * points with positive depth and squared reprojection error < threshold_px^2, the adaptive stop after each round of
  * 256 hypotheses (sample size 4), and one EPnP refit (normalised coordinates; beta cases N = 1, 2, 3 with 5
  * Gauss-Newton steps each) over the best model's inliers when there are >= 6, kept iff its count over all points is
@@ -1143,7 +1145,8 @@ int rs_pnp_estimator_destroy(rs_pnp_estimator* est);
  * the caller's arrays.  n = clamp(d_count[0], 0, max_n), read on the device.  h_intrinsics = fx, fy, cx, cy.
  * Hypotheses h = 0 .. max_hypotheses-1 (<= the estimator's; the reference passes 200) in rounds of 256; seed selects
  * the samples.  Outputs (device): d_pose [16] f32 row-major world -> camera (X_cam = R X + t), d_inlier [max_n] u8
- * (entries from n on are 0), d_inlier_index [max_n] (ascending), d_inlier_count [1], d_status [1]: 0 = ok, 1 = fewer
+ * (entries from n on are 0), d_inlier_index [max_n] (the first d_inlier_count entries, ascending; the entries from
+ * d_inlier_count on are not written and keep what the caller had there), d_inlier_count [1], d_status [1]: 0 = ok, 1 = fewer
  * than 4 finite correspondences, 2 = no model with >= 4 inliers (both: identity pose, no inliers; the reference gets
  * solved == false).  A correspondence with a non-finite coordinate is never sampled, never an inlier, never refitted. */
 int rs_estimate_pose_pnp(rs_context* ctx, rs_pnp_estimator* est, const float* d_object, const int32_t* d_object_index,

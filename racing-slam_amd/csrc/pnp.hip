@@ -11,7 +11,9 @@
 //                 correspondences, reset the state and the table
 //   pnp_hyp       one lane per hypothesis (4 wave64 workgroups per round of 256): the sample (every lane, in registers),
 //                 Grunert's quartic, its real roots by the bisection of ordered 64-bit keys between the roots of the
-//                 derivatives (serial per lane), up to 4 models [R | t] from the orthonormal frames of the two triangles
+//                 derivatives (serial per lane), each (u, v) polished by two Newton steps in the cosine laws, up to 4
+//                 models [R | t] from the orthonormal frames of the two triangles (the first 4 in ascending root order,
+//                 should a near-double root yield a fifth)
 //   pnp_score     one workgroup per hypothesis: every point is loaded once and tested against all of its models;
 //                 integer counts, the key's atomicMax
 //   pnp_stop_k    the adaptive stop after each round of 256 (at once with fewer than 4 finite correspondences); later
@@ -24,6 +26,10 @@
 #include "tri_core.h"
 
 #define PNP_P3P_EPS 1e-6            // relative residual of each cosine law that a model may have
+#define PNP_D_EPS 1e-3              // |D(v)| <= this times (|D0| + |D1 v|): u = N / D is 0 / 0, u from the third cosine law
+#define PNP_POLISH_STEPS 2          // Newton steps on (u, v) in the cosine laws after the quartic
+#define PNP_POLISH_MAX 1e-3         // a polishing step longer than this times (1 + |u|) or (1 + |v|) is not taken
+#define PNP_DUP_EPS 1e-6            // a polished (u, v) this close, times (1 + |.|), to an earlier model's is dropped
 #define PNP_COLLINEAR_EPS 1e-6      // |(P2 - P1) x (P3 - P1)| must exceed this times |P2 - P1| |P3 - P1|
 #define PNP_SOLVE_EPS 1e-13
 #define PNP_GN_STEPS 5
@@ -216,32 +222,77 @@ __global__ __launch_bounds__(64) void pnp_hyp(int round, int max_hyp, unsigned l
     double Fw[9];
     const bool wok = tri_frame(P[0], P[1], P[2], Fw);
     int nm = 0;
+    double ku[4], kv[4];                                     // the (u, v) of the models so far
     for (int q = 0; q < nroot && wok; q++) {
         const double v = z[q];
         if (!(v > 0.0)) continue;
-        const double Dv = D[1] * v + D[0];
-        if (Dv == 0.0) continue;
-        const double u = ((N[2] * v + N[1]) * v + N[0]) / Dv;
+        const double D0 = D[0], D1 = D[1] * v;
+        const double Dv = D1 + D0;
         const double den = (v * v - (2.0 * cb) * v) + 1.0;
-        if (!(u > 0.0 && den > 0.0)) continue;
-        const double s1 = sqrt(b2 / den), s2 = u * s1, s3 = v * s1;
-        const double r1 = ((s2 * s2 + s3 * s3) - ((2.0 * s2) * s3) * ca) - a2;
-        const double r2 = ((s1 * s1 + s3 * s3) - ((2.0 * s1) * s3) * cb) - b2;
-        const double r3 = ((s1 * s1 + s2 * s2) - ((2.0 * s1) * s2) * cg) - c2;
-        if (!(fabs(r1) <= PNP_P3P_EPS * a2 && fabs(r2) <= PNP_P3P_EPS * b2 && fabs(r3) <= PNP_P3P_EPS * c2)) continue;
-        double C[3][3], Fc[9], m[12];
-        for (int i = 0; i < 3; i++) { C[0][i] = s1 * jv[0][i]; C[1][i] = s2 * jv[1][i]; C[2][i] = s3 * jv[2][i]; }
-        if (!tri_frame(C[0], C[1], C[2], Fc)) continue;
-        bool fin = true;
-        for (int i = 0; i < 3; i++) {
-            for (int c = 0; c < 3; c++) m[4 * i + c] = (Fc[i] * Fw[c] + Fc[3 + i] * Fw[3 + c]) + Fc[6 + i] * Fw[6 + c];
-            m[4 * i + 3] = C[0][i] - dot3(m + 4 * i, P[0]);
+        if (!(den > 0.0)) continue;
+        // u = N(v) / D(v); where D(v) nearly vanishes N(v) does too (a triangle seen from near a plane of symmetry: a
+        // near-double root) and the quotient keeps no digits: u then comes from the third cosine law with s1^2 = b2 / den,
+        // u^2 - 2 cg u + (1 - r den) = 0, and both of its roots go through the gates below (tests/pnp_ref.p3p_ratios)
+        double us[2];
+        int nu = 0;
+        if (fabs(Dv) <= PNP_D_EPS * (fabs(D0) + fabs(D1))) {
+            const double c0 = 1.0 - r * den;
+            const double disc = cg * cg - c0;
+            if (!(disc >= 0.0)) continue;
+            const double qq = cg + copysign(sqrt(disc), cg);
+            if (qq == 0.0) continue;
+            const double ua = qq, ub = c0 / qq;
+            us[0] = fmin(ua, ub); us[1] = fmax(ua, ub);
+            nu = 2;
+        } else {
+            us[0] = ((N[2] * v + N[1]) * v + N[0]) / Dv;
+            nu = 1;
         }
-        for (int i = 0; i < 12; i++) fin = fin && isfinite(m[i]);
-        if (!fin) continue;
-        double* out = s.t.models + 48 * (size_t)h + 12 * nm;
-        for (int i = 0; i < 12; i++) out[i] = m[i];
-        nm++;
+        for (int k = 0; k < nu && nm < 4; k++) {             // a fifth model of one triple is dropped: ascending root order
+            // two guarded Newton steps on (u, v) in the cosine laws divided by s1^2 (tests/pnp_ref.p3p_polish): the quartic's
+            // coefficients lose digits where its roots lie close together, the pair of quadrics does not
+            double u = us[k], vv = v;
+            const double qa = a2 / b2;
+            for (int it = 0; it < PNP_POLISH_STEPS; it++) {
+                const double dn = (vv * vv - (2.0 * cb) * vv) + 1.0;
+                const double dd = 2.0 * vv - 2.0 * cb;
+                const double f1 = ((u * u + vv * vv) - ((2.0 * u) * vv) * ca) - qa * dn;
+                const double f2 = ((1.0 + u * u) - (2.0 * u) * cg) - r * dn;
+                const double j11 = 2.0 * u - (2.0 * vv) * ca, j12 = (2.0 * vv - (2.0 * u) * ca) - qa * dd;
+                const double j21 = 2.0 * u - 2.0 * cg, j22 = -(r * dd);
+                const double det = j11 * j22 - j12 * j21;
+                if (det == 0.0) break;
+                const double du = (f1 * j22 - j12 * f2) / det, dv = (j11 * f2 - f1 * j21) / det;
+                if (!(fabs(du) <= PNP_POLISH_MAX * (1.0 + fabs(u)) && fabs(dv) <= PNP_POLISH_MAX * (1.0 + fabs(vv)))) break;
+                u = u - du; vv = vv - dv;
+            }
+            // the wrong one of the cosine law's two roots may be drawn onto a neighbouring solution: once is enough
+            bool dup = false;
+            for (int j = 0; j < nm; j++)
+                dup = dup || (fabs(u - ku[j]) <= PNP_DUP_EPS * (1.0 + fabs(u)) && fabs(vv - kv[j]) <= PNP_DUP_EPS * (1.0 + fabs(vv)));
+            if (dup) continue;
+            const double dp = (vv * vv - (2.0 * cb) * vv) + 1.0;
+            if (!(u > 0.0 && vv > 0.0 && dp > 0.0)) continue;
+            const double s1 = sqrt(b2 / dp), s2 = u * s1, s3 = vv * s1;
+            const double r1 = ((s2 * s2 + s3 * s3) - ((2.0 * s2) * s3) * ca) - a2;
+            const double r2 = ((s1 * s1 + s3 * s3) - ((2.0 * s1) * s3) * cb) - b2;
+            const double r3 = ((s1 * s1 + s2 * s2) - ((2.0 * s1) * s2) * cg) - c2;
+            if (!(fabs(r1) <= PNP_P3P_EPS * a2 && fabs(r2) <= PNP_P3P_EPS * b2 && fabs(r3) <= PNP_P3P_EPS * c2)) continue;
+            double C[3][3], Fc[9], m[12];
+            for (int i = 0; i < 3; i++) { C[0][i] = s1 * jv[0][i]; C[1][i] = s2 * jv[1][i]; C[2][i] = s3 * jv[2][i]; }
+            if (!tri_frame(C[0], C[1], C[2], Fc)) continue;
+            bool fin = true;
+            for (int i = 0; i < 3; i++) {
+                for (int c = 0; c < 3; c++) m[4 * i + c] = (Fc[i] * Fw[c] + Fc[3 + i] * Fw[3 + c]) + Fc[6 + i] * Fw[6 + c];
+                m[4 * i + 3] = C[0][i] - dot3(m + 4 * i, P[0]);
+            }
+            for (int i = 0; i < 12; i++) fin = fin && isfinite(m[i]);
+            if (!fin) continue;
+            double* out = s.t.models + 48 * (size_t)h + 12 * nm;
+            for (int i = 0; i < 12; i++) out[i] = m[i];
+            ku[nm] = u; kv[nm] = vv;
+            nm++;
+        }
     }
     s.t.nmod[h] = nm;
 }

@@ -708,7 +708,7 @@ PNP_LAYOUTS = ("volume", "far", "near_planar", "narrow")
 
 
 def make_pnp_scene(seed=0, n=2000, outlier_frac=0.3, noise_px=0.5, layout="volume", width=1280, height=720,
-                   descriptors=False):
+                   descriptors=False, K=None, rotvec=None, t=None, world_offset=None, plane=None):
     """Object points and their pixels for the absolute-pose stage (the cv::solvePnPRansac calls of LoopDetector's
     verify_pnp and Initialization's third-view check) under a known world -> camera pose.  layout: "volume" (depths of
     4 .. 40 m over the whole image), "far" (60 .. 200 m), "near_planar" (a tilted plane 12 m away, 2 cm thick) or
@@ -718,12 +718,19 @@ def make_pnp_scene(seed=0, n=2000, outlier_frac=0.3, noise_px=0.5, layout="volum
     Returns dict(points [n][3] f32, pixels [n][2] f32, K (f32 fx, fy, cx, cy), pose [4][4] f64 world -> camera,
     inlier [n] bool).  With descriptors=True the pixels are permuted and the dict also holds desc_points [n][32] u8
     (random_descriptors), desc_pixels [n][32] u8 (flip_bits of the point's row; random rows for outliers) and
-    pixel_point [n] (the object point of each pixel); inlier then follows the pixels' order."""
+    pixel_point [n] (the object point of each pixel); inlier then follows the pixels' order.
+    The knobs leave the default output as it is: K = (fx, fy, cx, cy) replaces the centred 700 px camera; rotvec and t
+    replace the drawn world -> camera pose; world_offset [3] moves the world's origin away from the scene (the points
+    become Xw + offset, t becomes t - R offset, and the pixels are the projections of the f32-rounded points, so the
+    returned pose stays their exact truth); plane = "z3" puts every point exactly on Z = 3 and "tilted" on
+    Z = X / 2 + Y / 4 + 1 with X, Y multiples of 1 / 64 (exact in f32) instead of the layout's depths."""
     rng = np.random.default_rng([0x9A9, PNP_LAYOUTS.index(layout), int(seed)])
-    K = np.array([700.0, 700.0, width / 2.0, height / 2.0], np.float32)
+    K = np.array([700.0, 700.0, width / 2.0, height / 2.0] if K is None else K, np.float32)
     fx, fy, cx, cy = (float(k) for k in K)
     R = rodrigues(np.array([0.2, -0.4, 0.1]) + rng.normal(0, 0.05, 3))
-    t = np.array([0.5, -0.3, 2.0]) + rng.normal(0, 0.2, 3)
+    t_drawn = np.array([0.5, -0.3, 2.0]) + rng.normal(0, 0.2, 3)
+    R = R if rotvec is None else rodrigues(np.asarray(rotvec, np.float64))
+    t = t_drawn if t is None else np.asarray(t, np.float64)
     span = 0.15 if layout == "narrow" else 1.0
     u = np.stack([cx + span * rng.uniform(-0.5, 0.5, n) * width, cy + span * rng.uniform(-0.5, 0.5, n) * height], 1)
     ray = np.stack([(u[:, 0] - cx) / fx, (u[:, 1] - cy) / fy, np.ones(n)], 1)
@@ -733,7 +740,18 @@ def make_pnp_scene(seed=0, n=2000, outlier_frac=0.3, noise_px=0.5, layout="volum
         lo, hi = {"volume": (4.0, 40.0), "far": (60.0, 200.0), "narrow": (10.0, 30.0)}[layout]
         depth = rng.uniform(lo, hi, n)
     Xc = ray * depth[:, None]
-    Xw = ((Xc - t) @ R).astype(np.float32)            # R^T (Xc - t)
+    Xw = (Xc - t) @ R                                 # R^T (Xc - t)
+    if plane == "z3":
+        Xw = np.stack([rng.uniform(-2.0, 2.0, n), rng.uniform(-2.0, 2.0, n), np.full(n, 3.0)], 1)
+    elif plane == "tilted":
+        g = rng.integers(-128, 129, (n, 2)) / 64.0
+        Xw = np.stack([g[:, 0], g[:, 1], g[:, 0] / 2.0 + g[:, 1] / 4.0 + 1.0], 1)
+    elif plane is not None:
+        raise ValueError(plane)
+    if world_offset is not None:
+        off = np.asarray(world_offset, np.float64)
+        Xw, t = Xw + off, t - R @ off
+    Xw = Xw.astype(np.float32)
     Xf = Xw.astype(np.float64) @ R.T + t
     pix = np.stack([fx * Xf[:, 0] / Xf[:, 2] + cx, fy * Xf[:, 1] / Xf[:, 2] + cy], 1)
     pix = pix + rng.normal(0, noise_px, pix.shape)

@@ -13,9 +13,14 @@ so, as with the essential matrix (essential_ref.py), this file is the project's 
   solver      Grunert's P3P on the first three of the four: with s2 = u s1, s3 = v s1 the law of cosines gives
               u = N(v) / D(v) (N quadratic, D linear) and the quartic N^2 - 2 cos(gamma) N D + (1 - (c^2 / b^2) W) D^2,
               W = 1 - 2 cos(beta) v + v^2, built by polynomial products.  Its real roots come from
-              essential_ref.real_roots (zero-padded to degree 10).  A root gives a model iff v > 0, u > 0, the three
+              essential_ref.real_roots (zero-padded to degree 10).  Where D(v) nearly vanishes (a near-double root:
+              a triangle seen from near a plane of symmetry) u comes from the third cosine law instead, both of its
+              roots; every (u, v) then takes two Newton steps in the cosine laws themselves (p3p_ratios, p3p_polish)
+              and is dropped if it lands on a pair that the triple already has.
+              A pair gives a model iff v > 0, u > 0, the three
               cosine laws hold to P3P_EPS, and the model is finite; R, t from the orthonormal frames of the two
-              triangles (no SVD).  Up to 4 models; a collinear or coincident triple yields none.  The fourth index
+              triangles (no SVD).  Up to 4 models, the first 4 in ascending root order should a near-double root
+              yield a fifth; a collinear or coincident triple yields none.  The fourth index
               only keeps OpenCV's sample size.
   score       the integer count of points with positive depth and squared reprojection error (pixels) < threshold^2.
               Every model of every hypothesis is scored; ties go to the lower 4 h + m.
@@ -38,6 +43,10 @@ import essential_ref as E
 from essential_ref import MAX_DRAWS, ROUND, THREADS, draw, jacobi_eigen, real_roots, splitmix64, svd3  # noqa: F401
 
 P3P_EPS = 1e-6              # relative residual of each cosine law that a model may have
+D_EPS = 1e-3                # |D(v)| <= D_EPS (|D0| + |D1 v|): u = N / D is 0 / 0, take u from the third cosine law
+POLISH_STEPS = 2            # Newton steps on (u, v) in the cosine laws after the quartic
+POLISH_MAX = 1e-3           # a polishing step longer than POLISH_MAX (1 + |u|) or (1 + |v|) is not taken
+DUP_EPS = 1e-6              # a polished (u, v) within DUP_EPS (1 + |.|) of an earlier model's of the same triple is dropped
 COLLINEAR_EPS = 1e-6        # |(P2 - P1) x (P3 - P1)| must exceed COLLINEAR_EPS |P2 - P1| |P3 - P1|
 SOLVE_EPS = 1e-13           # a pivot of the small normal equations must exceed SOLVE_EPS * max |entry|
 GN_STEPS = 5
@@ -116,16 +125,60 @@ def _frame(p0, p1, p2):
     return e1, _cross(e3, e1), e3
 
 
-def p3p_model(s, v):
-    """The model [R | t] (12 floats, row-major 3 x 4) of root v, or None."""
+def p3p_ratios(s, v):
+    """(den, the candidates for u = s2 / s1 in ascending order) of root v.  u = N(v) / D(v), except where D(v) nearly
+    vanishes: |D(v)| <= D_EPS (|D0| + |D1 v|).  There N(v) vanishes with it (a triangle seen from near a plane of
+    symmetry: a near-double root) and the quotient keeps no digits, so u comes from the third cosine law with
+    s1^2 = b2 / den instead, u^2 - 2 cos(gamma) u + (1 - (c2 / b2) den) = 0; both roots go through the gates."""
     if not v > 0.0:
-        return None
-    Dv = s["D"][1] * v + s["D"][0]
-    if Dv == 0.0:
-        return None
-    u = ((s["N"][2] * v + s["N"][1]) * v + s["N"][0]) / Dv
+        return 0.0, []
+    D0, D1 = s["D"][0], s["D"][1] * v
+    Dv = D1 + D0
     den = (v * v - (2.0 * s["cb"]) * v) + 1.0
-    if not (u > 0.0 and den > 0.0):
+    if not den > 0.0:
+        return den, []
+    if abs(Dv) <= D_EPS * (abs(D0) + abs(D1)):
+        c0 = 1.0 - (s["c2"] / s["b2"]) * den
+        disc = s["cg"] * s["cg"] - c0
+        if not disc >= 0.0:
+            return den, []
+        q = s["cg"] + math.copysign(math.sqrt(disc), s["cg"])
+        if q == 0.0:
+            return den, []
+        ua, ub = q, c0 / q
+        return den, [min(ua, ub), max(ua, ub)]
+    return den, [((s["N"][2] * v + s["N"][1]) * v + s["N"][0]) / Dv]
+
+
+def p3p_polish(s, u, v):
+    """POLISH_STEPS guarded Newton steps on (u, v) in the two cosine laws divided by s1^2 = b2 / den,
+    f1 = u^2 + v^2 - 2 u v cos(alpha) - (a2 / b2) den, f2 = 1 + u^2 - 2 u cos(gamma) - (c2 / b2) den.  The quartic's
+    coefficients lose digits where its four roots lie close together (a small triangle far away, two bearings nearly
+    equal), and u = N / D loses more; the pair of quadrics is as well conditioned as the pose itself.  A step is taken
+    only if it is finite and no longer than POLISH_MAX (1 + |.|), so a double root (a singular Jacobian) stays put."""
+    qa, qc = s["a2"] / s["b2"], s["c2"] / s["b2"]
+    ca, cb, cg = s["ca"], s["cb"], s["cg"]
+    for _ in range(POLISH_STEPS):
+        den = (v * v - (2.0 * cb) * v) + 1.0
+        dd = 2.0 * v - 2.0 * cb
+        f1 = ((u * u + v * v) - ((2.0 * u) * v) * ca) - qa * den
+        f2 = ((1.0 + u * u) - (2.0 * u) * cg) - qc * den
+        j11, j12 = 2.0 * u - (2.0 * v) * ca, (2.0 * v - (2.0 * u) * ca) - qa * dd
+        j21, j22 = 2.0 * u - 2.0 * cg, -(qc * dd)
+        det = j11 * j22 - j12 * j21
+        if det == 0.0:
+            break
+        du, dv = (f1 * j22 - j12 * f2) / det, (j11 * f2 - f1 * j21) / det
+        if not (abs(du) <= POLISH_MAX * (1.0 + abs(u)) and abs(dv) <= POLISH_MAX * (1.0 + abs(v))):
+            break
+        u, v = u - du, v - dv
+    return u, v
+
+
+def p3p_model(s, v, u):
+    """The model [R | t] (12 floats, row-major 3 x 4) of the polished pair (u, v), or None."""
+    den = (v * v - (2.0 * s["cb"]) * v) + 1.0
+    if not (u > 0.0 and v > 0.0 and den > 0.0):
         return None
     s1 = math.sqrt(s["b2"] / den)
     s2, s3 = u * s1, v * s1
@@ -161,14 +214,25 @@ def p3p(P, x, y):
     if S == 0:
         return models, count
     z, nroot = real_roots(polys)
+    kept = [[] for _ in range(S)]
     for s, st in enumerate(setups):
         if st is None:
             continue
         for k in range(int(nroot[s])):
-            m = p3p_model(st, float(z[s, k]))
-            if m is not None:
-                models[s, count[s]] = m
-                count[s] += 1
+            v = float(z[s, k])
+            _, us = p3p_ratios(st, v)
+            for u in us:
+                if count[s] >= 4:
+                    break
+                up, vp = p3p_polish(st, u, v)
+                # the wrong one of the cosine law's two roots may be drawn onto a neighbouring solution: once is enough
+                if any(abs(up - ua) <= DUP_EPS * (1.0 + abs(up)) and abs(vp - va) <= DUP_EPS * (1.0 + abs(vp)) for ua, va in kept[s]):
+                    continue
+                m = p3p_model(st, vp, up)
+                if m is not None:
+                    models[s, count[s]] = m
+                    kept[s].append((up, vp))
+                    count[s] += 1
     return models, count
 
 

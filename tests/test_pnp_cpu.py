@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import pnp_ref as P  # noqa: E402
+from pnp_hp import lsq_optimum  # noqa: E402
 
 LAYOUTS = ("volume", "far", "near_planar", "narrow")
 
@@ -116,29 +117,12 @@ def _rms(m, X, Y, Z, x, y, K):
     return math.sqrt(float(e2.mean()))
 
 
-def _optimum(d, prep):
-    """scipy's least squares on the reprojection residual (pixels) over the same points, started at the truth."""
-    from scipy.optimize import least_squares
-    synth = _synth()
-    X, Y, Z, x, y, _ = prep
-    fx, fy = float(d["K"][0]), float(d["K"][1])
-    W = np.stack([X, Y, Z], 1)
-
-    def f(p):
-        Xc = W @ synth.rodrigues(p[:3]).T + p[3:]
-        return np.concatenate([fx * (Xc[:, 0] / Xc[:, 2] - x), fy * (Xc[:, 1] / Xc[:, 2] - y)])
-
-    p0 = np.concatenate([synth.log_so3(d["pose"][:3, :3]), d["pose"][:3, 3]])
-    r = least_squares(f, p0, xtol=1e-15, ftol=1e-15, gtol=1e-15)
-    return math.sqrt(float((r.fun ** 2).sum() / len(x)))
-
-
 def _epnp_ratio(layout, seed, n=1000):
     d = _synth().make_pnp_scene(seed, n, 0.0, 0.5, layout)
     prep = P.prepare(d["points"], d["pixels"], d["K"])
     m, case = P.epnp(*prep[:5], prep[5], float(d["K"][0]), float(d["K"][1]))
     assert m is not None
-    return _rms(m, *prep[:5], d["K"]) / _optimum(d, prep), case
+    return _rms(m, *prep[:5], d["K"]) / lsq_optimum(d["points"], d["pixels"], d["K"], d["pose"]), case
 
 
 # RMS reprojection error of EPnP (no polish) over the optimum's, 1000 inliers, 0.5 px noise; printed by
