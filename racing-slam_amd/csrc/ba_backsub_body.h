@@ -5,6 +5,9 @@
 
 #define K8_THREADS 256
 #define K8_PRE 3                 // observation rounds (4 lanes each) of a landmark held in registers
+#define K8_HELD 2                // ... of which this many hold their linearisation too, formed in front of the hand-off (13 doubles
+                                 // each; with all three the fused kernel needs more than its 256 VGPRs and spills)
+static_assert(K8_HELD >= K8_PRE - 1 && K8_HELD <= K8_PRE, "the loop behind the hand-off takes at most one round from cs_pre");
 #define K8_MAX_THREADS 512        // the fused kernel runs this body with K7's 512 threads (128 landmarks per workgroup)
 
 // Hand-off words of the fused kernel (ba_solve.hip, ba_solve_backsub), one pair per speculative set, each
@@ -166,6 +169,28 @@ static __device__ __forceinline__ void ba_backsub_cost4_body(const BaDims& d, co
     }
     const double* prep = cprep;
     __shared__ double redw[K8_MAX_THREADS / 64][4];
+    // The linearisation of the held observation rounds at the current cameras and the current point depends on nothing K7
+    // produces: it is formed here, in front of the hand-off (the fused kernel's consumers would only poll meanwhile), and
+    // every radius this workgroup evaluates reuses it.  Held per round: the loss weight, d r / d point (2 x 3) and the
+    // d r / d angle-axis half of the camera Jacobian; its d r / d centre half is -jp (obs_eval).
+    double hw[K8_HELD], hjp[K8_HELD][6], hja[K8_HELD][6];
+    __syncthreads();                                            // cprep is staged
+    {
+        ObsLin o;
+#pragma unroll
+        for (int r = 0; r < K8_HELD; r++) {
+            hw[r] = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; k++) hjp[r][k] = hja[r][k] = 0.0;
+            if ((cs_pre[r] >> 16) - 1 < 0) continue;            // no observation in this round, or one of a fixed camera
+            obs_eval<true>(prep + (size_t)(cs_pre[r] & 0xFFFF) * BA_PREP_LDS, X, uv_pre[r], d, o);
+            hw[r] = o.w;
+#pragma unroll
+            for (int k = 0; k < 6; k++) hjp[r][k] = o.jp[k];
+#pragma unroll
+            for (int k = 0; k < 3; k++) { hja[r][k] = o.jc[k]; hja[r][3 + k] = o.jc[6 + k]; }
+        }
+    }
 
 #pragma unroll 1
     for (;; pass++) {
@@ -215,10 +240,25 @@ static __device__ __forceinline__ void ba_backsub_cost4_body(const BaDims& d, co
         double cost = 0.0, mcc = 0.0, ssq = 0.0, xsq = 0.0;
         double t[3] = {0, 0, 0};
         ObsLin o;
-        for (int j = sub, r = 0; j < nobs; j += 4, r++) {
+        // the held rounds: only the products with delta_c are left
+#pragma unroll
+        for (int r = 0; r < K8_HELD; r++) {
+            const int s = (cs_pre[r] >> 16) - 1;
+            if (s < 0) continue;
+            double m0 = 0.0, m1 = 0.0;
+#pragma unroll
+            for (int a = 0; a < 3; a++) { const double dc = dcl[6 * s + a]; m0 += hja[r][a] * dc; m1 += hja[r][3 + a] * dc; }
+#pragma unroll
+            for (int a = 0; a < 3; a++) { const double dc = dcl[6 * s + 3 + a]; m0 += -hjp[r][a] * dc; m1 += -hjp[r][3 + a] * dc; }
+#pragma unroll
+            for (int k = 0; k < 3; k++) t[k] += hw[r] * (hjp[r][k] * m0 + hjp[r][3 + k] * m1);   // W_i^T delta_c
+        }
+        // the other observations are linearised here: those of the remaining prefetched rounds from registers, later ones
+        // loaded on demand
+        for (int j = sub + 4 * K8_HELD, r = K8_HELD; j < nobs; j += 4, r++) {
             int cs;
             float2 uvv;
-            if (r < K8_PRE) { cs = r == 0 ? cs_pre[0] : r == 1 ? cs_pre[1] : cs_pre[2]; uvv = r == 0 ? uv_pre[0] : r == 1 ? uv_pre[1] : uv_pre[2]; }
+            if (r < K8_PRE) { cs = cs_pre[K8_PRE - 1]; uvv = uv_pre[K8_PRE - 1]; }
             else {
                 const int oi = o0 + j;
                 if (b.obs_cs) cs = b.obs_cs[oi];

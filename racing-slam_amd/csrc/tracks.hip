@@ -19,14 +19,30 @@ struct TrackParams {
     int kf_pose;
 };
 
+// K.T of every pose is the same for all tracks: with at most K6_TABLE_POSES poses the workgroup forms projection_rows of each
+// once, in LDS (n_table = n_poses; the same f32 operations as project_f32, so nothing changes in the results), and the
+// sightings loop takes its rows from there instead of gathering a 64-byte pose and redoing the product per sighting.
+// n_table = 0 (more poses than the table holds): the loop gathers the poses as before.
+#define K6_TABLE_POSES 512
+#define K6_BATCH 4               // sightings whose index and pixel loads leave together
+
 __global__ __launch_bounds__(64) void k6_tracks(const float2* __restrict__ track_uv, const uint8_t* __restrict__ skip,
                                                const int32_t* __restrict__ sight_ptr,
                                                const int32_t* __restrict__ sight_pose,
                                                const float2* __restrict__ sight_uv, const float* __restrict__ poses,
-                                               int n_tracks, TrackParams prm, uint8_t* __restrict__ status,
+                                               int n_tracks, int n_table, TrackParams prm, uint8_t* __restrict__ status,
                                                float* __restrict__ xyz, float* __restrict__ parallax_cos,
                                                float* __restrict__ required_cos, const float* __restrict__ required_by_pose)
 {
+    extern __shared__ float kp_rows[];                                     // [n_table][12]
+    for (int i = threadIdx.x; i < n_table; i += blockDim.x) {
+        float T[16], KP[12];
+        load_pose(poses, i, T);
+        projection_rows(prm.tri, T, KP);
+#pragma unroll
+        for (int k = 0; k < 12; k++) kp_rows[12 * i + k] = KP[k];
+    }
+    __syncthreads();
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_tracks) return;
     const int s0 = sight_ptr[t], s1 = sight_ptr[t + 1];
@@ -39,6 +55,26 @@ __global__ __launch_bounds__(64) void k6_tracks(const float2* __restrict__ track
         const bool ok = dlt_one(sight_uv[s0], track_uv[t], Tf, Tk, prm.tri, X);   // :254-263
         if (ok) {
             bool consistent = true;
+            if (n_table > 0) {
+                // a batch at a time: the status does not depend on WHICH sighting fails first, and a slot past the end
+                // repeats the last sighting (same verdict)
+                for (int s = s0; s < s1 && consistent; s += K6_BATCH) {    // :265-271
+                    int ip[K6_BATCH];
+                    float2 px[K6_BATCH];
+#pragma unroll
+                    for (int u = 0; u < K6_BATCH; u++) { const int su = min(s + u, s1 - 1); ip[u] = sight_pose[su]; px[u] = sight_uv[su]; }
+#pragma unroll
+                    for (int u = 0; u < K6_BATCH; u++) {
+                        float KP[12];
+                        const int iu = min(max(ip[u], 0), n_table - 1);    // (an index outside the pose array reads no LDS of others)
+#pragma unroll
+                        for (int k = 0; k < 12; k++) KP[k] = kp_rows[12 * iu + k];
+                        const float2 pr = project_rows_f32(KP, X);
+                        const float dx = pr.x - px[u].x, dy = pr.y - px[u].y;
+                        if (sqrtf(dx * dx + dy * dy) > prm.tri.max_reprojection_error) consistent = false;
+                    }
+                }
+            } else
             for (int s = s0; s < s1; s++) {                                // :265-271
                 float Ts[16];
                 load_pose(poses, sight_pose[s], Ts);
@@ -166,8 +202,9 @@ extern "C" int rs_triangulate_tracks(rs_context* ctx, int n_tracks, const float*
     prm.kf_pose = kf_pose;
     {
         rs_prof_scope ps(ctx, "K6_tracks");
-        hipLaunchKernelGGL(k6_tracks, dim3((n_tracks + 63) / 64), dim3(64), 0, ctx->stream, (const float2*)d_track_uv,
-                           d_skip, d_sight_ptr, d_sight_pose, (const float2*)d_sight_uv, d_poses, n_tracks, prm,
+        const int n_table = n_poses <= K6_TABLE_POSES ? n_poses : 0;
+        hipLaunchKernelGGL(k6_tracks, dim3((n_tracks + 63) / 64), dim3(64), sizeof(float) * 12 * (size_t)n_table, ctx->stream,
+                           (const float2*)d_track_uv, d_skip, d_sight_ptr, d_sight_pose, (const float2*)d_sight_uv, d_poses, n_tracks, n_table, prm,
                            d_status, d_xyz, d_parallax_cos, d_required_cos, d_required_by_pose);
     }
     {

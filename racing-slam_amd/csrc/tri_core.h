@@ -101,17 +101,23 @@ __device__ __forceinline__ void load_pose(const float* __restrict__ poses, int i
     }
 }
 
-// Camera::project, src/Camera.cpp:25-32: K * pose.block<3,4> first, then * homogeneous
-__device__ __forceinline__ float2 project_f32(const TriParams& k, const float* T, const float* X)
+// the second half of Camera::project: KP = projection_rows(k, pose) applied to the homogeneous point
+__device__ __forceinline__ float2 project_rows_f32(const float* KP, const float* X)
 {
-    float KP[12];
-    projection_rows(k, T, KP);
     float uvw[3];
 #pragma unroll
     for (int i = 0; i < 3; i++)
         uvw[i] = (KP[4 * i] * X[0] + KP[4 * i + 1] * X[1]) + (KP[4 * i + 2] * X[2] + KP[4 * i + 3] * 1.0f);
     if (uvw[2] < 0.0f) return make_float2(-1.0f, -1.0f);
     return make_float2(uvw[0] / uvw[2], uvw[1] / uvw[2]);
+}
+
+// Camera::project, src/Camera.cpp:25-32: K * pose.block<3,4> first, then * homogeneous
+__device__ __forceinline__ float2 project_f32(const TriParams& k, const float* T, const float* X)
+{
+    float KP[12];
+    projection_rows(k, T, KP);
+    return project_rows_f32(KP, X);
 }
 
 // -R^T t, src/MotionModel.cpp:8-11, src/Frame.cpp:39-42
