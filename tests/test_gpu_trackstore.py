@@ -1,13 +1,16 @@
 """rs_track_store (racing-slam_amd/csrc/track_store.hip) against tests/trackstore_ref.py: after every frame the store is
 downloaded and its ids, keypoint indices, counts and sightings equal the specification's (integers byte for byte, pixels
 bit for bit); the query's six integers; the packed inputs and the results of the triangulate call against
-rs_triangulate_tracks on arrays built on the host; erase and row reuse; the refusals."""
+rs_triangulate_tracks on arrays built on the host; erase and row reuse; the refusals.  These are the small shapes (one row
+and one track per thread, or eight rows at cap 8192); tests/test_gpu_trackstore_envelope.py runs the cases of
+tests/trackstore_cases.py, where the per-thread chunks, the sort width, the copy's trip count and the read-back split change."""
 import numpy as np
 import pytest
 
 import trackstore_ref as R
 from conftest import to_np
 from test_gpu_track import SimpleMap, i32, set_table
+from trackstore_cases import monotone_lists, scene
 
 pytestmark = pytest.mark.gpu
 
@@ -46,13 +49,6 @@ class Pair:
 
     def close(self):
         self.dev.close()
-
-
-def monotone_lists(rng, n_prev, n_next, keep=0.8, inliers=0.7):
-    """rs_track_features' kept-index list (ascending previous keypoints) and an ascending inlier list into it"""
-    m = min(n_next, int(rng.binomial(n_prev, keep)))
-    prev = np.sort(rng.choice(n_prev, m, replace=False)).astype(np.int32)
-    return prev, np.flatnonzero(rng.random(m) < inliers).astype(np.int32)
 
 
 SEQUENCES = [
@@ -177,19 +173,6 @@ def test_query_counts(ctx, rs):
     assert p.dev.query(fr, None, 0, 3, 20.0) == p.ref.query(table, np.zeros(0, bool), 3, 20.0)       # no map: nothing covisible
     assert p.dev.query(fr, sm.map, 0, 2, 0.0) == p.ref.query(table, (sm.alive > 0) & (sm.n_obs > 0), 2, 0.0)
     fr.close(); p.close(); sm.close()
-
-
-def scene(rng, n, frames):
-    """static points in front of a camera moving along x: pixels per frame, poses, intrinsics"""
-    K = (500.0, 500.0, 320.0, 240.0)
-    X = np.stack([rng.uniform(-2, 2, n), rng.uniform(-1.5, 1.5, n), rng.uniform(4, 9, n)], axis=1)
-    poses = np.tile(np.eye(4, dtype=np.float32), (frames, 1, 1))
-    pix = np.zeros((frames, n, 2), np.float32)
-    for f in range(frames):
-        poses[f, 0, 3] = -0.15 * f
-        pix[f, :, 0] = K[0] * (X[:, 0] - 0.15 * f) / X[:, 2] + K[2]
-        pix[f, :, 1] = K[1] * X[:, 1] / X[:, 2] + K[3]
-    return pix, poses.reshape(frames, 16), K
 
 
 def test_triangulate_and_erase(ctx, rs):
