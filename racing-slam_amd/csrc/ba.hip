@@ -1,8 +1,9 @@
 // ba.hip — local-window bundle adjustment (Levenberg-Marquardt with point-block
 // Schur elimination), all in f64, with the whole LM schedule resident on the
 // device (no host round trip until the summary is read): host orchestration,
-// K0 init, K10 finalize and the generic (any size) fallback kernels.  The fast
-// paths live in ba_schur.hip (K5), ba_solve.hip (K7) and ba_update.hip (K8);
+// K0 init, K10 finalize, the generic (any size) K5 and K8 and the K7 of a window
+// without a free camera.  The fast paths live in ba_schur.hip (K5), ba_solve.hip
+// (K7) and ba_update.hip (K8), the K7 of larger systems in ba_solve_big.hip;
 // the pose solve of one frame (K11) follows the same schedule in refine_pose.hip.
 //
 // Replaces optimization::bundle_adjust's ceres::Solve
@@ -36,6 +37,7 @@
 #include "ba_common.h"
 #include "ba_backsub_body.h"
 #include "ba_init_body.h"
+#include "ba_step_body.h"
 #include "imu_dual.h"
 
 // ---------------------------------------------------------------------- K0 (body: ba_init_body.h)
@@ -179,170 +181,31 @@ __global__ __launch_bounds__(BA_THREADS) void ba_linearize_schur(BaDims d, BaBuf
     }
 }
 
-// ---------------------------------------------------------------------- K7
-// Single workgroup.  S lives in LDS when n <= BA_MAX_LDS_N, otherwise in place
-// in the global accumulator.
-__global__ __launch_bounds__(256) void ba_reduced_solve(BaDims d, BaBufs b, BaOpt opt, int use_lds)
+// ---------------------------------------------------------------------- K7 (bodies: ba_step_body.h)
+// A window without a free camera (n == 0) has no reduced system: only the ends of the round are left.  The landmarks
+// still move, so the cost, the gradient test and K5's failure flag come from the slot lines; the candidate cameras are
+// the cameras.  One workgroup.
+__global__ __launch_bounds__(256) void ba_no_free_camera(BaDims d, BaBufs b, BaOpt opt)
 {
-    extern __shared__ __attribute__((aligned(16))) double sm[];
-    const int n = d.n, tid = threadIdx.x, nt = blockDim.x;
+    const int tid = threadIdx.x, nt = blockDim.x;
     __shared__ BaState st;
     __shared__ int s_fail;
-    __shared__ double red[8];
-    if (tid == 0) { st = *b.st; s_fail = 0; }
+    __shared__ double red[16], red3[16][3];
+    if (!ba_step_begin(d, b, &st, &s_fail)) return;
     __syncthreads();
-    if (st.done) return;
-    for (int i = tid; i < BA_NSLOT * BA_SLOT_STRIDE; i += nt) b.pt_scal[i] = 0.0;     // K8 of this iteration accumulates here
-    // fold the BA_UREP replicas of the camera-side accumulators into replica 0
-    for (size_t i = tid; i < b.cam_stride; i += nt) {
-        double v = 0.0;
-        for (int r = 0; r < BA_UREP; r++) v += b.rhs[(size_t)r * b.cam_stride + i];
-        b.rhs[i] = v;
-    }
-    __syncthreads();
-    double* S = use_lds ? sm : b.S;
-    double* y = use_lds ? sm + (size_t)n * n : b.dc;    // rhs / solution vector
-    double* lam = use_lds ? y + n : b.rhs;               // camera damping (rhs buffer is free once y is formed)
-
-    // (1) fresh linearisation: cost at x, Jacobi scaling of the camera blocks, gradient test
-    if (st.fresh) {
-        if (tid < 64) {
-            const double c = slot_sum(b.scal, 0);
-            if (tid == 0) {
-                st.x_cost = c;
-                if (st.iter == 0) st.initial_cost = st.x_cost;
-            }
-        }
-        if (!st.have_scale)
-            for (int i = tid; i < n; i += nt) {
-                const double h = b.U[(i / 6) * 36 + (i % 6) * 7];
-                b.sc[i] = opt.jacobi ? 1.0 / (1.0 + sqrt(h)) : 1.0;
-            }
-        double gm = 0.0;
-        for (int i = tid; i < n; i += nt) gm = fmax(gm, fabs(b.gc[i]));
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) gm = fmax(gm, __shfl_down(gm, off, 64));
-        if ((tid & 63) == 0) red[tid >> 6] = gm;
-        __syncthreads();
-        double gslots = 0.0;
-        if (tid < 64) gslots = slot_max_all(b);
-        if (tid == 0) {
-            double g = gslots;
-            for (int w = 0; w < (nt + 63) / 64; w++) g = fmax(g, red[w]);
-            if (!isfinite(st.x_cost)) { st.done = 1; st.termination = RS_BA_FAILURE; }
-            else if (g <= opt.gtol) { st.done = 1; st.termination = RS_BA_CONVERGENCE_GRADIENT; }
-        }
-        __syncthreads();
-        if (st.done) { if (tid == 0) *b.st = st; return; }
-    }
-    __syncthreads();
-
-    // (2) assemble S = U + Lambda_c + (-sum Y W^T), y = gc + (-sum Y g)
-    const double radius = st.radius;
-    for (int i = tid; i < n; i += nt) {
-        const double h = b.U[(i / 6) * 36 + (i % 6) * 7];
-        const double s2 = b.sc[i] * b.sc[i];
-        const double l = clampd(s2 * h, opt.dmin, opt.dmax) / (radius * s2);
-        const double yy = b.gc[i] + b.rhs[i];   // lam may alias rhs (global path): same thread, same index
-        lam[i] = l;
-        y[i] = yy;
-    }
-    __syncthreads();
-    // S is accumulated in its upper triangle.  Two phases because S may BE b.S (in place):
-    // first mirror upper -> lower, then add the block diagonal and the damping.
-    for (int idx = tid; idx < n * n; idx += nt) {
-        const int i = idx / n, j = idx % n;
-        if (i > j) S[idx] = b.S[(size_t)j * n + i];
-        else if (S != b.S) S[idx] = b.S[idx];
-    }
-    __syncthreads();
-    for (int idx = tid; idx < n * n; idx += nt) {
-        const int i = idx / n, j = idx % n;
-        if (i / 6 != j / 6) continue;
-        const int a = i % 6, e = j % 6;
-        double v = S[idx] + ((a <= e) ? b.U[(i / 6) * 36 + a * 6 + e] : b.U[(i / 6) * 36 + e * 6 + a]);
-        if (i == j) v += lam[i];
-        S[idx] = v;
-    }
-    __syncthreads();
-
-    // (3) dense Cholesky S = L L^T (left-looking, column j by thread-per-row)
-    for (int j = 0; j < n; j++) {
-        for (int i = j + tid; i < n; i += nt) {
-            double acc = S[(size_t)i * n + j];
-            for (int k = 0; k < j; k++) acc -= S[(size_t)i * n + k] * S[(size_t)j * n + k];
-            S[(size_t)i * n + j] = acc;   // unscaled column
-        }
-        __syncthreads();
-        const double dj = S[(size_t)j * n + j];
-        if (!(dj > 0.0) || !isfinite(dj)) { if (tid == 0) s_fail = 1; }
-        const double inv = 1.0 / sqrt(dj);
-        __syncthreads();
-        for (int i = j + tid; i < n; i += nt) S[(size_t)i * n + j] = (i == j) ? sqrt(dj) : S[(size_t)i * n + j] * inv;
-        __syncthreads();
-    }
-    if (tid < 64) { const double f = slot_sum(b.scal, 1); if (f > 0.0 && tid == 0) s_fail = 1; }
+    double cost = 0.0;
+    if (st.fresh && tid < 64) cost = slot_sum(b.scal, 0);
+    if (!ba_step_gradient_test(b, opt, &st, &s_fail, red, 0.0, cost)) return;
     __syncthreads();
     if (s_fail) {
         if (tid == 0) { st.solver_failed = 1; *b.st = st; }
         return;
     }
-    // (4) forward / backward substitution, column oriented
-    for (int j = 0; j < n; j++) {
-        if (tid == 0) y[j] = y[j] / S[(size_t)j * n + j];
-        __syncthreads();
-        const double yj = y[j];
-        for (int i = j + 1 + tid; i < n; i += nt) y[i] -= S[(size_t)i * n + j] * yj;
-        __syncthreads();
-    }
-    for (int j = n - 1; j >= 0; j--) {
-        if (tid == 0) y[j] = y[j] / S[(size_t)j * n + j];
-        __syncthreads();
-        const double yj = y[j];
-        for (int i = tid; i < j; i += nt) y[i] -= S[(size_t)j * n + i] * yj;
-        __syncthreads();
-    }
-    // (5) delta_c = -y, candidate cameras, camera part of the scalars
-    double mcc = 0.0, ssq = 0.0, xsq = 0.0;
+    double acc[3] = {0.0, 0.0, 0.0};
     bool bad = false;
-    const double* Xc = b.Xc + (size_t)st.cur * d.C * 6;
-    double* Xn = b.Xc + (size_t)(st.cur ^ 1) * d.C * 6;
-    for (int c = tid; c < d.C; c += nt) {
-        const int s = b.slot[c];
-        bool active = false;
-        if (s >= 0)
-            for (int k = 0; k < 6; k++) active = active || b.U[s * 36 + k * 7] > 0.0;
-        for (int k = 0; k < 6; k++) {
-            const double x = Xc[6 * c + k];
-            double dlt = 0.0;
-            if (s >= 0) {
-                dlt = -y[6 * s + k];
-                if (!isfinite(dlt)) bad = true;
-                mcc += 0.5 * (dlt * dlt * lam[6 * s + k] - dlt * b.gc[6 * s + k]);
-                const double xn = x + dlt;
-                if (active) { ssq += (x - xn) * (x - xn); xsq += x * x; }
-                Xn[6 * c + k] = xn;
-            } else {
-                Xn[6 * c + k] = x;
-            }
-        }
-        cam_prepare(Xn + 6 * c, b.prep + ((size_t)(st.cur ^ 1) * d.C + c) * BA_PREP);
-    }
-    __syncthreads();   // all reads of y done before dc (may alias y) is rewritten
-    for (int i = tid; i < n; i += nt) { const double v = -y[i]; b.dc[i] = v; }   // dc may alias y: same index
-    mcc = wave_sum(mcc); ssq = wave_sum(ssq); xsq = wave_sum(xsq);
-    if (__any(bad) && (tid & 63) == 0) s_fail = 1;
-    __syncthreads();
-    __shared__ double red3[4][3];
-    if ((tid & 63) == 0) { red3[tid >> 6][0] = mcc; red3[tid >> 6][1] = ssq; red3[tid >> 6][2] = xsq; }
-    __syncthreads();
-    if (tid == 0) {
-        double a0 = 0, a1 = 0, a2 = 0;
-        for (int w = 0; w < (nt + 63) / 64; w++) { a0 += red3[w][0]; a1 += red3[w][1]; a2 += red3[w][2]; }
-        st.cam_scal[0] = a0; st.cam_scal[1] = a1; st.cam_scal[2] = a2;
-        st.solver_failed = s_fail;
-        *b.st = st;
-    }
+    for (int c = tid; c < d.C; c += nt) bad |= ba_step_camera(d, b, st, c, b.dc, b.rhs, b.gc, false, acc);
+    ba_step_reduce(&st, &s_fail, red3, acc, bad);
+    if (tid == 0) *b.st = st;
 }
 
 // ---------------------------------------------------------------------- K8
@@ -855,7 +718,7 @@ static int ba_enqueue_reduced_solve(rs_context* ctx, const BaDims& d, const BaBu
     else if (path.solve_lds && path.fuse78) { rs_prof_scope ps(ctx, "K78_ba_solve_backsub"); ba_launch_solve_backsub(s, d, b, opt, ctx->n_cu); }
     else if (path.solve_lds) { rs_prof_scope ps(ctx, "K7_ba_reduced_solve"); ba_launch_reduced_solve_lds(s, d, b, opt); }
     else if (path.solve_big) { rs_prof_scope ps(ctx, "K7_ba_reduced_solve_blocked"); return ba_launch_reduced_solve_big(ctx, d, b, opt, ws_big, path.band); }
-    else { rs_prof_scope ps(ctx, "K7_ba_reduced_solve_global"); hipLaunchKernelGGL(ba_reduced_solve, dim3(1), dim3(256), 0, s, d, b, opt, 0); }
+    else { rs_prof_scope ps(ctx, "K7_ba_reduced_solve_global"); hipLaunchKernelGGL(ba_no_free_camera, dim3(1), dim3(256), 0, s, d, b, opt); }   // n == 0
     return RS_OK;
 }
 

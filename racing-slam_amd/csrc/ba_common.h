@@ -266,6 +266,13 @@ __device__ __forceinline__ double lane63_f64(double v)
 {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
+// broadcast one lane's double to the wave (lane is wave-uniform)
+__device__ __forceinline__ double readlane_f64(double v, int lane)
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+    return __hiloint2double(hi, lo);
+}
 // total valid in LANE 63 ONLY
 __device__ __forceinline__ double wave_sum_lane63(double v)
 {
@@ -637,7 +644,7 @@ int ba_launch_reduced_solve_big(rs_context* ctx, const BaDims& d, const BaBufs& 
 int ba_band_max_span();
 // ---- inertial reduced solve (ba_solve_big.hip): N = 6 Cf + 9 Ci unknowns
 size_t ba_inertial_bytes(int N, int n_fac, int C);
-void ba_inertial_carve(char* ws, int N, int n_fac, int C, BaImu* imu, ImuFactorDev** d_fac, int32_t** d_inert);
+size_t ba_inertial_carve(char* ws, int N, int n_fac, int C, BaImu* imu, ImuFactorDev** d_fac, int32_t** d_inert);
 int ba_launch_reduced_solve_inertial(rs_context* ctx, const BaDims& d, const BaBufs& b, const BaOpt& opt, char* ws);
 // ---- inertial blocks eliminated around the LDS reduced solve (ba_imu.hip)
 void ba_launch_imu_eliminate(hipStream_t s, const BaDims& d, const BaBufs& b, const BaOpt& opt);
@@ -684,7 +691,7 @@ static inline bool ba_dims_from(const rs_ba_problem& q, const rs_ba_options* opt
 // ba_choose_band and ba_choose_fusion the rest once the grouping is carved and the set-up launches are enqueued.
 struct BaPath {
     bool use_mfma, k8_lds;         // K5 is the MFMA Schur kernel (else ba_linearize_schur); K8 holds the cameras in LDS (else ba_backsub_cost)
-    bool solve_lds, solve_big;     // K7 with S in LDS (ba_solve.hip) / blocked (ba_solve_big.hip); neither: ba_reduced_solve
+    bool solve_lds, solve_big;     // K7 with S in LDS (ba_solve.hip) / blocked (ba_solve_big.hip); neither: no free camera, n == 0 (ba_no_free_camera)
     bool imu_lds;                  // inertial blocks eliminated around the LDS K7 (ba_imu.hip), else the N x N blocked solve
     int ns, srep, band;            // speculative radii per round; replicas of S; blocked solve: 0 general, 1 banded in one workgroup, 2 two-sided
     bool may_fuse;                 // the plain local window on its first attempt: K7 + K8 may share a launch (and lose a hand-off)

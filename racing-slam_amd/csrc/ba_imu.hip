@@ -21,18 +21,6 @@
 #define IMU_MAXCI 21            // inertial cameras (<= optimised cameras of a window the LDS K7 takes)
 #define KI_THREADS 512
 
-__device__ __forceinline__ double imu_rl64(double v, int lane)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-__device__ __forceinline__ double imu_rcp(double p)
-{
-    double r = __builtin_amdgcn_rcp(p);
-    r = fma(fma(-p, r, 1.0), r, r);
-    r = fma(fma(-p, r, 1.0), r, r);
-    return r;
-}
-
 // Layout behind BaImu::zacc.  SHARED by the speculative sets, zeroed before every round (K8): H [9 Ci][n + 1] (row z:
 // H_zp | g_z), the diagonal blocks of H_zz [Ci][81], the sub-diagonal blocks (q + 1, q) [Ci][81], g_z [9 Ci].
 // Then PER SET (its radius damps z differently): W = L^-1 H [9 Ci][n + 1], the factor L [Ci][81] | [Ci][81], D^-1 [9 Ci]
@@ -199,12 +187,12 @@ __global__ __launch_bounds__(KI_THREADS) void ba_imu_eliminate(BaDims d, BaBufs 
             for (int cc = 0; cc < 9; cc++) {
                 int lane_o = lane;
                 asm volatile("" : "+v"(lane_o));            // per-step lane masks (hoisted, they spill SGPR pairs)
-                const double piv = imu_rl64(a[cc], cc);
+                const double piv = readlane_f64(a[cc], cc);
                 bad = bad || !(piv > 0.0) || !isfinite(piv);
-                const double rd = imu_rcp(piv);
+                const double rd = rcp_nr(piv);
                 const double lc = a[cc] * rd;
 #pragma unroll
-                for (int k = cc + 1; k < 18; k++) a[k] -= lc * imu_rl64(a[cc], k);
+                for (int k = cc + 1; k < 18; k++) a[k] -= lc * readlane_f64(a[cc], k);
                 a[cc] = lane_o > cc ? lc : a[cc];
                 if (lane == cc) dinv[q * 9 + cc] = rd;
                 __builtin_amdgcn_sched_barrier(0);
@@ -361,11 +349,11 @@ __global__ __launch_bounds__(KI_THREADS) void ba_imu_expand(BaDims d, BaBufs b, 
             double y = u[9 * q + k];
             if (q + 1 < Ci) {
 #pragma unroll
-                for (int r = 0; r < 9; r++) y -= V.Lo[q * 81 + r * 9 + k] * imu_rl64(ynext, r);       // L_{q+1,q}^T x_{q+1}
+                for (int r = 0; r < 9; r++) y -= V.Lo[q * 81 + r * 9 + k] * readlane_f64(ynext, r);       // L_{q+1,q}^T x_{q+1}
             }
 #pragma unroll
             for (int r = 8; r >= 1; r--) {                  // unit upper-triangular solve: x_r is final when step r runs
-                const double xr = imu_rl64(y, r);
+                const double xr = readlane_f64(y, r);
                 y -= (k < r) ? V.Ld[q * 81 + r * 9 + k] * xr : 0.0;
             }
             ynext = y;

@@ -18,6 +18,7 @@
 // ~2 + 2 NB + 1 launches (29 at n = 588): launch-bound (~4.4 us each) rather than flop-bound
 // (68 MFLOP), 25.9 ms -> ~0.3 ms per solve against the single-workgroup global-memory Cholesky it replaces.
 #include "ba_common.h"
+#include "ba_step_body.h"
 #include "imu_dual.h"
 
 #define BB 48                 // block size: 8 cameras
@@ -33,65 +34,26 @@ struct BigBufs {
     double* Ad;      // [n][6] banded factorisation: the damped matrix's entries inside the cameras' own 6 x 6 blocks, (hi, lo) at [hi][lo % 6]
 };
 
-__device__ __forceinline__ double rl64(double v, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
 // ------------------------------------------------------------------ prologue
 __global__ __launch_bounds__(1024) void ba_big_prologue(BaDims d, BaBufs b, BaOpt opt, BigBufs g, int band)
 {
     const int n = d.n, tid = threadIdx.x, nt = blockDim.x;
     __shared__ BaState st;
     __shared__ double red[16];
-    if (tid == 0) { st = *b.st; *g.fail = 0; }
-    __syncthreads();
-    if (st.done) return;
-    for (int i = tid; i < BA_NSLOT * BA_SLOT_STRIDE; i += nt) b.pt_scal[i] = 0.0;     // K8 of this iteration accumulates here
-    // fold the BA_UREP replicas of the camera-side accumulators into replica 0
-    for (size_t i = tid; i < b.cam_stride; i += nt) {
-        double v = 0.0;
-        for (int r = 0; r < BA_UREP; r++) v += b.rhs[(size_t)r * b.cam_stride + i];
-        // U | gc are only accumulated on fresh iterations (K5 skips its first pass after a rejected step)
-        if ((int)i >= n) { if (st.fresh) b.Ukeep[i - n] = v; else v = b.Ukeep[i - n]; }
-        b.rhs[i] = v;
-    }
+    if (!ba_step_begin(d, b, &st, g.fail)) return;
     __syncthreads();
     // (1) fresh linearisation: cost at x, Jacobi scaling of the camera blocks, gradient test
+    double cost = 0.0, gm = 0.0;
     if (st.fresh) {
-        if (tid < 64) {
-            const double c = slot_sum(b.scal, 0);
-            if (tid == 0) {
-                st.x_cost = c;
-                if (st.iter == 0) st.initial_cost = st.x_cost;
-            }
-        }
+        if (tid < 64) cost = slot_sum(b.scal, 0);
         if (!st.have_scale)
             for (int i = tid; i < n; i += nt) {
                 const double h = b.U[(i / 6) * 36 + (i % 6) * 7];
                 b.sc[i] = opt.jacobi ? 1.0 / (1.0 + sqrt(h)) : 1.0;
             }
-        double gm = 0.0;
         for (int i = tid; i < n; i += nt) gm = fmax(gm, fabs(b.gc[i]));
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) gm = fmax(gm, __shfl_down(gm, off, 64));
-        if ((tid & 63) == 0) red[tid >> 6] = gm;
-        __syncthreads();
-        double gslots = 0.0;
-        if (tid < 64) gslots = slot_max_all(b);
-        if (tid == 0) {
-            double gg = gslots;
-            for (int w = 0; w < (nt + 63) / 64; w++) gg = fmax(gg, red[w]);
-            if (!isfinite(st.x_cost)) { st.done = 1; st.termination = RS_BA_FAILURE; }
-            else if (gg <= opt.gtol) { st.done = 1; st.termination = RS_BA_CONVERGENCE_GRADIENT; }
-        }
-        __syncthreads();
     }
-    if (tid < 64) { const double f = slot_sum(b.scal, 1); if (f > 0.0 && tid == 0) *g.fail = 1; }   // K5 saw a bad landmark block
-    if (tid == 0) *b.st = st;
-    if (st.done) return;
+    if (!ba_step_gradient_test(b, opt, &st, g.fail, red, gm, cost)) return;
     __syncthreads();
     // (2) damping, right-hand side, and the full symmetric matrix in place (S is accumulated in its upper triangle)
     const double radius = st.radius;
@@ -184,12 +146,12 @@ __global__ __launch_bounds__(256) void ba_big_diag(BaDims d, BaBufs b, BigBufs g
 #pragma unroll
             for (int cc = 0; cc < 16; cc++) {
                 asm volatile("" : "+v"(r));      // per-step lane masks: hoisted, the 3 x 16 compare results lived in SGPR pairs and spilled
-                const double piv = rl64(a[cc], cc);
+                const double piv = readlane_f64(a[cc], cc);
                 bad = bad || !(piv > 0.0) || !isfinite(piv);
                 const double rd = rcp_nr(piv);
                 const double lc = a[cc] * rd;                               // l_{r,cc} for r > cc
 #pragma unroll
-                for (int k = cc + 1; k < 16; k++) a[k] -= lc * rl64(a[cc], k);     // lane k holds a_{k,cc} = l_{k,cc} d_cc
+                for (int k = cc + 1; k < 16; k++) a[k] -= lc * readlane_f64(a[cc], k);     // lane k holds a_{k,cc} = l_{k,cc} d_cc
                 a[cc] = r > cc ? lc : a[cc];
                 my_rd = r == cc ? rd : my_rd;
                 my_piv = r == cc ? piv : my_piv;
@@ -972,7 +934,7 @@ static __device__ __forceinline__ void band_backsub(const BigBufs& g, int n, dou
             for (int t = 0; t < WB; t++) l[t] = Lb[t * WBS + tid];            // column `tid` of the unit-lower block (t > tid is used)
 #pragma unroll
             for (int t = WB - 1; t >= 0; t--) {
-                const double xt = rl64(v, t);
+                const double xt = readlane_f64(v, t);
                 v -= (tid < t) ? l[t] * xt : 0.0;
             }
             if (tid < w) y[c0 + tid] = v;
@@ -1005,7 +967,7 @@ static __device__ __forceinline__ void band_sep_backsub(const BigBufs& g, int n,
         for (int t = 0; t < WB; t++) l[t] = Pm[t * WBS + tid];
 #pragma unroll
         for (int t = WB - 1; t >= 0; t--) {
-            const double xt = rl64(v, t);
+            const double xt = readlane_f64(v, t);
             v -= (tid < t) ? l[t] * xt : 0.0;
         }
         y[s0 + tid] = v;
@@ -1042,7 +1004,7 @@ static __device__ __forceinline__ void band_sep_backsub(const BigBufs& g, int n,
                     for (int t = 0; t < 16; t++) l[t] = Lb[(sd * WB + tc + t) * WBS + lane];
 #pragma unroll
                     for (int t = 15; t >= 0; t--) {
-                        const double xt = rl64(v, tc + t);
+                        const double xt = readlane_f64(v, tc + t);
                         v -= (lane < tc + t) ? l[t] * xt : 0.0;
                     }
                 }
@@ -1140,7 +1102,7 @@ static __device__ __forceinline__ void big_backsub(const BigBufs& g, int n, doub
             double v = tid < w ? y[c0 + tid] : 0.0;
 #pragma unroll
             for (int t = BB - 1; t >= 0; t--) {
-                const double xt = rl64(v, t);
+                const double xt = readlane_f64(v, t);
                 v -= (tid < t) ? l[t] * xt : 0.0;
             }
             if (tid < w) y[c0 + tid] = v;
@@ -1187,44 +1149,12 @@ __global__ __launch_bounds__(1024) void ba_big_finish(BaDims d, BaBufs b, BaOpt 
     if (band == 2) band_sep_backsub(g, n, y, Lb, &s_fail);
     else if (band) band_backsub(g, n, y, Lb);
     else big_backsub(g, n, y, Lb);
-    // delta_c = -x, candidate cameras, camera part of the step scalars (as ba_solve.hip (5))
-    const double* lam = b.rhs;
-    double mcc = 0.0, ssq = 0.0, xsq = 0.0;
+    // delta_c = -x, candidate cameras, camera part of the step scalars
+    double acc[3] = {0.0, 0.0, 0.0};
     bool bad = false;
-    const double* Xc = b.Xc + (size_t)st.cur * d.C * 6;
-    double* Xn = b.Xc + (size_t)(st.cur ^ 1) * d.C * 6;
-    for (int c = tid; c < d.C; c += nt) {
-        const int s = b.slot[c];
-        bool active = false;
-        if (s >= 0)
-            for (int k = 0; k < 6; k++) active = active || b.U[s * 36 + k * 7] > 0.0;
-        for (int k = 0; k < 6; k++) {
-            const double x = Xc[6 * c + k];
-            if (s >= 0) {
-                const double dlt = -y[6 * s + k];
-                if (!isfinite(dlt)) bad = true;
-                mcc += 0.5 * (dlt * dlt * lam[6 * s + k] - dlt * b.gc[6 * s + k]);
-                const double xn = x + dlt;
-                if (active) { ssq += (x - xn) * (x - xn); xsq += x * x; }
-                Xn[6 * c + k] = xn;
-                b.dc[6 * s + k] = dlt;
-            } else {
-                Xn[6 * c + k] = x;
-            }
-        }
-        cam_prepare(Xn + 6 * c, b.prep + ((size_t)(st.cur ^ 1) * d.C + c) * BA_PREP);
-    }
-    mcc = wave_sum(mcc); ssq = wave_sum(ssq); xsq = wave_sum(xsq);
-    if (__any(bad) && (tid & 63) == 0) s_fail = 1;
-    if ((tid & 63) == 0) { red3[tid >> 6][0] = mcc; red3[tid >> 6][1] = ssq; red3[tid >> 6][2] = xsq; }
-    __syncthreads();
-    if (tid == 0) {
-        double a0 = 0, a1 = 0, a2 = 0;
-        for (int w = 0; w < nt / 64; w++) { a0 += red3[w][0]; a1 += red3[w][1]; a2 += red3[w][2]; }
-        st.cam_scal[0] = a0; st.cam_scal[1] = a1; st.cam_scal[2] = a2;
-        st.solver_failed = s_fail;
-        *b.st = st;
-    }
+    for (int c = tid; c < d.C; c += nt) bad |= ba_step_camera(d, b, st, c, y, b.rhs, b.gc, false, acc);
+    ba_step_reduce(&st, &s_fail, red3, acc, bad);
+    if (tid == 0) *b.st = st;
 }
 
 // ------------------------------------------------------------------ host glue
@@ -1241,22 +1171,26 @@ static void big_launch_factor(hipStream_t s, const BaDims& d, const BaBufs& b, c
     }
 }
 
-static void big_carve(char* ws, size_t n, BigBufs* g)
+// The workspace of the blocked solve, stated once: carves the BigBufs out of `ws` in 256-byte steps and returns the bytes
+// they take.  Nothing is dereferenced, so a null `ws` sizes the workspace.
+static size_t big_carve(char* ws, size_t n, BigBufs* g)
 {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     size_t off = 0;
-    g->Ls = (double*)(ws + off); off += al(sizeof(double) * n * n);
-    g->M = (double*)(ws + off); off += al(sizeof(double) * BB * BB);
-    g->dv = (double*)(ws + off); off += al(sizeof(double) * n);
-    g->yf = (double*)(ws + off); off += al(sizeof(double) * n);
-    g->fail = (int*)(ws + off); off += 256;
-    g->sep = (double*)(ws + off); off += al(sizeof(double) * 2 * (64 * 64 + 64));
-    g->Ad = (double*)(ws + off);
+    auto take = [&](size_t bytes) { char* p = ws ? ws + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
+    g->Ls = (double*)take(sizeof(double) * n * n);
+    g->M = (double*)take(sizeof(double) * BB * BB);
+    g->dv = (double*)take(sizeof(double) * n);
+    g->yf = (double*)take(sizeof(double) * n);
+    g->fail = (int*)take(sizeof(int));
+    g->sep = (double*)take(sizeof(double) * 2 * (WB * WB + WB));
+    g->Ad = (double*)take(sizeof(double) * 6 * n);
+    return off;
 }
 
 size_t ba_big_bytes(int n)
 {
-    return sizeof(double) * ((size_t)n * n + BB * BB + 2 * (size_t)n + 2 * (64 * 64 + 64) + 6 * (size_t)n) + 256 * 8;
+    BigBufs g;
+    return big_carve(nullptr, (size_t)n, &g);
 }
 
 // largest camera span (slots) whose block band fits the one-launch factorisation: 6 span + 5 <= WB columns
@@ -1322,16 +1256,8 @@ __global__ __launch_bounds__(512) void ba_imu_prologue(BaDims d, BaBufs b, BaOpt
     __shared__ BaState st;
     __shared__ double red[16];
     __shared__ double s_cost;
-    if (tid == 0) { st = *b.st; *g.fail = 0; s_cost = 0.0; }
-    __syncthreads();
-    if (st.done) return;
-    for (int i = tid; i < BA_NSLOT * BA_SLOT_STRIDE; i += nt) b.pt_scal[i] = 0.0;     // K8 of this round accumulates here
-    for (size_t i = tid; i < b.cam_stride; i += nt) {                                  // fold the accumulator replicas
-        double v = 0.0;
-        for (int r = 0; r < BA_UREP; r++) v += b.rhs[(size_t)r * b.cam_stride + i];
-        if ((int)i >= n6) { if (st.fresh) b.Ukeep[i - n6] = v; else v = b.Ukeep[i - n6]; }
-        b.rhs[i] = v;
-    }
+    if (tid == 0) s_cost = 0.0;
+    if (!ba_step_begin(d, b, &st, g.fail)) return;
     for (size_t i = tid; i < (size_t)N * N; i += nt) b.imu.A[i] = 0.0;
     for (int i = tid; i < N; i += nt) b.imu.gtot[i] = 0.0;
     __syncthreads();
@@ -1398,27 +1324,9 @@ __global__ __launch_bounds__(512) void ba_imu_prologue(BaDims d, BaBufs b, BaOpt
         b.imu.yv[i] = gi + (i < n6 ? b.rhs[i] : 0.0);
         gm = fmax(gm, fabs(gi));
     }
-    if (st.fresh) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) gm = fmax(gm, __shfl_down(gm, off, 64));
-        if ((tid & 63) == 0) red[tid >> 6] = gm;
-        __syncthreads();
-        double cslots = 0.0, gslots = 0.0;
-        if (tid < 64) { cslots = slot_sum(b.scal, 0); gslots = slot_max_all(b); }
-        if (tid == 0) {
-            st.x_cost = cslots + s_cost;
-            if (st.iter == 0) st.initial_cost = st.x_cost;
-            double gg = gslots;
-            for (int w = 0; w < (nt + 63) / 64; w++) gg = fmax(gg, red[w]);
-            if (!isfinite(st.x_cost)) { st.done = 1; st.termination = RS_BA_FAILURE; }
-            else if (gg <= opt.gtol) { st.done = 1; st.termination = RS_BA_CONVERGENCE_GRADIENT; }
-        }
-    }
-    __syncthreads();
-    if (tid < 64) { const double f = slot_sum(b.scal, 1); if (f > 0.0 && tid == 0) *g.fail = 1; }   // K5 saw a bad landmark block
-    if (tid == 0) *b.st = st;
-    if (st.done) return;
-    __syncthreads();
+    double cost = 0.0;
+    if (st.fresh && tid < 64) cost = slot_sum(b.scal, 0) + s_cost;       // the factors' cost is a camera-side term
+    if (!ba_step_gradient_test(b, opt, &st, g.fail, red, gm, cost)) return;
 }
 
 // the lower triangle of the damped matrix: inertial part (already there) + U + S_schur (pose part) + Lambda.  A grid of
@@ -1458,46 +1366,28 @@ __global__ __launch_bounds__(1024) void ba_imu_finish(BaDims d, BaBufs b, BaOpt 
         return;
     }
     big_backsub(g, N, y, Lb);
-    double mcc = 0.0, ssq = 0.0, xsq = 0.0;
+    double acc[3] = {0.0, 0.0, 0.0};
     bool bad = false;
-    const double* Xc = b.Xc + (size_t)st.cur * d.C * 6;
-    double* Xn = b.Xc + (size_t)(st.cur ^ 1) * d.C * 6;
+    const double* Xn = b.Xc + (size_t)(st.cur ^ 1) * d.C * 6;
     const double* Xv = b.imu.Xv + (size_t)st.cur * d.C * 9;
     double* Xvn = b.imu.Xv + (size_t)(st.cur ^ 1) * d.C * 9;
     for (int c = tid; c < d.C; c += nt) {
-        const int s = b.slot[c], q = b.imu.inert_slot[c];
-        bool active = q >= 0;                               // a frame with an inertial block is in the problem
-        if (s >= 0)
-            for (int k = 0; k < 6; k++) active = active || b.U[s * 36 + k * 7] > 0.0;
-        for (int k = 0; k < 6; k++) {
-            const double x = Xc[6 * c + k];
-            if (s >= 0) {
-                const double dlt = -y[6 * s + k];
-                if (!isfinite(dlt)) bad = true;
-                mcc += 0.5 * (dlt * dlt * b.imu.lam[6 * s + k] - dlt * b.imu.gtot[6 * s + k]);
-                const double xn = x + dlt;
-                if (active) { ssq += (x - xn) * (x - xn); xsq += x * x; }
-                Xn[6 * c + k] = xn;
-                b.dc[6 * s + k] = dlt;                       // K8 back-substitutes the points with the pose step
-            } else {
-                Xn[6 * c + k] = x;
-            }
-        }
+        const int q = b.imu.inert_slot[c];
+        bad |= ba_step_camera(d, b, st, c, y, b.imu.lam, b.imu.gtot, q >= 0 /* a frame with an inertial block is in the problem */, acc);
         for (int k = 0; k < 9; k++) {
             const double x = Xv[9 * c + k];
             if (q >= 0) {
                 const int col = n6 + 9 * q + k;
                 const double dlt = -y[col];
                 if (!isfinite(dlt)) bad = true;
-                mcc += 0.5 * (dlt * dlt * b.imu.lam[col] - dlt * b.imu.gtot[col]);
+                acc[0] += 0.5 * (dlt * dlt * b.imu.lam[col] - dlt * b.imu.gtot[col]);
                 const double xn = x + dlt;
-                ssq += (x - xn) * (x - xn); xsq += x * x;
+                acc[1] += (x - xn) * (x - xn); acc[2] += x * x;
                 Xvn[9 * c + k] = xn;
             } else {
                 Xvn[9 * c + k] = x;
             }
         }
-        cam_prepare(Xn + 6 * c, b.prep + ((size_t)(st.cur ^ 1) * d.C + c) * BA_PREP);
     }
     __syncthreads();                                         // candidates written (same workgroup reads them below)
     for (int fi = tid; fi < b.imu.n_fac; fi += nt) {        // cost of the inertial blocks at the candidate (values only)
@@ -1510,44 +1400,34 @@ __global__ __launch_bounds__(1024) void ba_imu_finish(BaDims d, BaBufs b, BaOpt 
         for (int a = 0; a < 6; a++) c += 0.5 * rw[a] * rw[a];
         atomicAdd(&s_cand, c);
     }
-    mcc = wave_sum(mcc); ssq = wave_sum(ssq); xsq = wave_sum(xsq);
-    if (__any(bad) && (tid & 63) == 0) s_fail = 1;
-    if ((tid & 63) == 0) { red3[tid >> 6][0] = mcc; red3[tid >> 6][1] = ssq; red3[tid >> 6][2] = xsq; }
-    __syncthreads();
-    if (tid == 0) {
-        double a0 = 0, a1 = 0, a2 = 0;
-        for (int w = 0; w < nt / 64; w++) { a0 += red3[w][0]; a1 += red3[w][1]; a2 += red3[w][2]; }
-        st.cam_scal[0] = a0; st.cam_scal[1] = a1; st.cam_scal[2] = a2; st.cam_scal[3] = s_cand;
-        st.solver_failed = s_fail;
-        *b.st = st;
-    }
+    ba_step_reduce(&st, &s_fail, red3, acc, bad);
+    if (tid == 0) { st.cam_scal[3] = s_cand; *b.st = st; }
+}
+
+// The inertial buffers behind the BigBufs region of `ws`, stated once: carves them and returns the bytes of both regions;
+// *d_fac and *d_inert are the device addresses the host uploads to.  A null `ws` sizes the workspace.
+size_t ba_inertial_carve(char* ws, int N, int n_fac, int C, BaImu* imu, ImuFactorDev** d_fac, int32_t** d_inert)
+{
+    size_t off = ba_big_bytes(N);
+    auto take = [&](size_t bytes) { char* p = ws ? ws + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
+    imu->A = (double*)take(sizeof(double) * (size_t)N * N);
+    imu->yv = (double*)take(sizeof(double) * ((size_t)N + 1));
+    imu->lam = (double*)take(sizeof(double) * ((size_t)N + 1));
+    imu->sc = (double*)take(sizeof(double) * ((size_t)N + 1));
+    imu->gtot = (double*)take(sizeof(double) * ((size_t)N + 1));
+    imu->Jf = (double*)take(sizeof(double) * (size_t)(n_fac + 1) * 9 * IMU_NP);
+    imu->fac = *d_fac = (ImuFactorDev*)take(sizeof(ImuFactorDev) * (size_t)(n_fac + 1));
+    imu->inert_slot = *d_inert = (int32_t*)take(sizeof(int32_t) * (size_t)(C + 1));
+    imu->Xv = (double*)take(sizeof(double) * (BA_MAXSETS + 1) * 9 * (size_t)(C + 1));      // one buffer per state slot
+    return off;
 }
 
 size_t ba_inertial_bytes(int N, int n_fac, int C)
 {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    return ba_big_bytes(N) + al(sizeof(double) * (size_t)N * N) + 4 * al(sizeof(double) * ((size_t)N + 1)) +
-           al(sizeof(double) * (size_t)(n_fac + 1) * 9 * IMU_NP) + al(sizeof(ImuFactorDev) * (size_t)(n_fac + 1)) +
-           al(sizeof(int32_t) * (size_t)(C + 1)) + al(sizeof(double) * (BA_MAXSETS + 1) * 9 * (size_t)(C + 1)) + 256;      // Xv: one buffer per state slot
-}
-
-// carves the inertial buffers out of `ws` (after the BigBufs region); returns the device addresses the host uploads to
-void ba_inertial_carve(char* ws, int N, int n_fac, int C, BaImu* imu, ImuFactorDev** d_fac, int32_t** d_inert)
-{
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t off = ba_big_bytes(N);
-    off = al(off);
-    imu->A = (double*)(ws + off); off += al(sizeof(double) * (size_t)N * N);
-    imu->yv = (double*)(ws + off); off += al(sizeof(double) * ((size_t)N + 1));
-    imu->lam = (double*)(ws + off); off += al(sizeof(double) * ((size_t)N + 1));
-    imu->sc = (double*)(ws + off); off += al(sizeof(double) * ((size_t)N + 1));
-    imu->gtot = (double*)(ws + off); off += al(sizeof(double) * ((size_t)N + 1));
-    imu->Jf = (double*)(ws + off); off += al(sizeof(double) * (size_t)(n_fac + 1) * 9 * IMU_NP);
-    *d_fac = (ImuFactorDev*)(ws + off); off += al(sizeof(ImuFactorDev) * (size_t)(n_fac + 1));
-    *d_inert = (int32_t*)(ws + off); off += al(sizeof(int32_t) * (size_t)(C + 1));
-    imu->Xv = (double*)(ws + off);
-    imu->fac = *d_fac;
-    imu->inert_slot = *d_inert;
+    BaImu imu;
+    ImuFactorDev* d_fac;
+    int32_t* d_inert;
+    return ba_inertial_carve(nullptr, N, n_fac, C, &imu, &d_fac, &d_inert);
 }
 
 int ba_launch_reduced_solve_inertial(rs_context* ctx, const BaDims& d, const BaBufs& b, const BaOpt& opt, char* ws)

@@ -15,14 +15,6 @@
 
 typedef __attribute__((ext_vector_type(4))) double d4;
 
-// broadcast one lane's double to the wave (lane is wave-uniform)
-__device__ __forceinline__ double readlane_f64(double v, int lane)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
 // 1/x from v_rcp_f64 + one Newton step
 __device__ __forceinline__ double fast_rcp(double x)
 {

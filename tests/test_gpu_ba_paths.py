@@ -166,3 +166,23 @@ def test_ba_path(ctx, rs, synth, name):
     assert counts == e_counts
     assert sched == e_sched and sched1 == e_sched1
     assert np.allclose(cost, e_cost, rtol=1e-9, atol=0.0) and np.allclose(cost1, e_cost1, rtol=1e-9, atol=0.0)
+
+
+def test_no_free_camera_against_the_oracle(ctx, synth, oracle):
+    """The values of the path without a free camera (n = 0: only the landmarks move), against the CPU oracle; the case
+    above pins its kernels and its cost alone.  A clean, well-conditioned window: the oracle ends on termination 1 after
+    5 iterations with 4 successful steps (an accepted step, a rejected step and a convergence exit, 47.666137 ->
+    17.646648), and 1e-13 relative on its input points moves its result by 6e-13 at most, 3e-8 of the tolerance below —
+    which is the plain-window parity tolerance (test_gpu_parity.py)."""
+    w = synth.make_ba_window(n_kf=3, n_points=60, outlier_frac=0.0, pixel_noise=0.3, rot_noise_deg=0.2, config_id=23)
+    free = np.zeros_like(w["cam_free"])
+    dc, dp = ctx.dev(w["cams"]), ctx.dev(w["points"])
+    s = ctx.bundle_adjust(dc, free, dp, ctx.dev(w["obs_ptr"]), ctx.dev(w["obs_cam"]), ctx.dev(w["obs_uv"]), w["K"])
+    _, rp, r = oracle.bundle_adjust(w["cams"], free, w["points"], w["obs_ptr"], w["obs_cam"], w["obs_uv"], w["K"])
+    print({k: s[k] for k in ("termination", "iterations", "successful_steps", "initial_cost", "final_cost")}, r,
+          float(np.abs(dp.cpu().numpy() - rp).max()))
+    for k in ("termination", "iterations", "successful_steps"):
+        assert s[k] == r[k], k
+    assert np.array_equal(dc.cpu().numpy(), np.asarray(w["cams"], np.float64))
+    assert np.allclose(dp.cpu().numpy(), rp, rtol=1e-6, atol=1e-7)
+    assert np.isclose(s["final_cost"], r["final_cost"], rtol=1e-7, atol=0.0)
