@@ -6,21 +6,28 @@
 // MapPoint::avg_viewing_normal / observed_distance_range (src/MapPoint.cpp:24-45)
 // and KDTree2D::radius_search (src/KDTree.cpp:45-82).
 //
-// K2: eight lanes per map point when the frame's KD-tree fits in LDS (k2_reproj_match_grouped below, the default),
-// one lane per point otherwise (k2_reproj_match).  Projection and the three f32 gates, then the
-// KD-tree radius search walked with an explicit stack kept in LDS, visiting
-// nodes in exactly the reference's recursion order (node, near child, far
-// child) so that "first candidate wins ties" is preserved.  Every accepted
-// candidate is compared against all observations of the point with 8 xor +
-// 8 v_bcnt.  The winner per point goes into a packed 64-bit atomicMin on the
-// keypoint's slot (dist << 32 | map order), which reproduces the reference's
-// sequential strict-'<' proposal table: min distance, earliest point on ties.
-// K3: one workgroup decodes the table and emits accepted_matches() in
-// ascending keypoint order.
+// K2 is two kernels with identical outputs: eight lanes per map point when the frame's KD-tree fits in LDS
+// (k2_reproj_match_grouped, the default), one lane per point otherwise or under k2_mode 1 (k2_reproj_match).  They differ
+// in how a point's observations are spread over lanes — the accumulation of the viewing normal and the descriptor
+// compares of phase B — and share every other step, each defined once below:
+//   k2_stage_tree   the frame's KD-tree into LDS, one K2Node per node
+//   k2_project      Camera::project + is_in_image (tri_core.h's f32 forms)
+//   k2_view_gates   the viewing-angle and distance-range gates, given the accumulated normal and range
+//   K2_WALK         the radius search with an explicit stack in LDS, visiting nodes in exactly the reference's recursion
+//                   order (node, near child, far child) so that "first candidate wins ties" is preserved
+//   k2_candidate    what the walk does with an in-range, open keypoint: queue it for phase B, or compare it on the spot
+//   K2Lds           a point's columns of the workgroup's LDS tables; k2_lds_bytes is their size on the host
+// Every candidate is compared against all observations of the point with 8 xor + 8 v_bcnt, every comparison a strict
+// '<'.  The winner per point goes into a packed 64-bit atomicMin on the keypoint's slot (dist << 32 | map order), which
+// reproduces the reference's sequential strict-'<' proposal table: min distance, earliest point on ties.
+// K3: one workgroup decodes the table and emits accepted_matches() in ascending keypoint order.
 // Built with -ffp-contract=off so the f32 gates execute the oracle's operations.
 #include "common.h"
+#include "tri_core.h"
 
-#define K2_THREADS 128
+#define K2_THREADS 128           // one lane per point
+#define K2G 8                    // lanes per point of the grouped kernel
+#define K2G_THREADS 512          // its workgroup: 64 map points (256 / 1024 threads: slower)
 #define K2_STACK 40
 #define K2_PRE 8         // observations of a map point whose centre / descriptor row are preloaded
 #define K2_MAXC 16       // in-radius candidates queued per map point before their descriptors are compared (phase B)
@@ -50,17 +57,6 @@ struct K2Map {
     const float* kf_centers;
     const uint4* pool;
 };
-
-__device__ __forceinline__ float dot3f(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
-__device__ __forceinline__ void normalize3f(float* v)
-{
-    const float n = dot3f(v, v);
-    if (n > 0.0f) {
-        const float s = sqrtf(n);
-        v[0] = v[0] / s; v[1] = v[1] / s; v[2] = v[2] / s;
-    }
-}
 
 __device__ __forceinline__ int hamming256(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1)
 {
@@ -126,27 +122,207 @@ __device__ __forceinline__ void k3_accept_body(unsigned long long* __restrict__ 
 //   kp       keypoint index | (already matched && !replace) << 31   (:65, :81 become a sign test)
 struct K2Node { float x, y; unsigned lr; int kp; };
 
+// Dynamic LDS of a workgroup that holds `pts` map points: [K2_STACK][pts] traversal stacks, [K2_MAXC][pts] candidate
+// queue, [K2_MAXC][pts] running minima of the queued candidates, then the tree.  A K2Lds is ONE point's column of the
+// three tables: entry i of a table is table[i * pts].
+#define K2_COL_INTS (K2_STACK + 2 * K2_MAXC)
+extern __shared__ __attribute__((aligned(16))) int k2_lds[];
+
+struct K2Lds {
+    int* stack;
+    int* queue;
+    int* qmin;
+    K2Node* tree;
+    int pts;
+};
+
+__device__ __forceinline__ K2Lds k2_lds_view(int pts, int col)
+{
+    K2Lds L;
+    L.pts = pts;
+    L.stack = k2_lds + col;
+    L.queue = L.stack + K2_STACK * pts;
+    L.qmin = L.queue + K2_MAXC * pts;
+    L.tree = (K2Node*)(k2_lds + K2_COL_INTS * pts);
+    return L;
+}
+
+static size_t k2_lds_bytes(int pts, int nodes) { return sizeof(int) * K2_COL_INTS * pts + sizeof(K2Node) * (size_t)nodes; }
+
+// The frame's KD-tree into LDS by a workgroup of THREADS (a constant: blockDim.x would cost registers).  Eight nodes per
+// thread and pass in three phases — the index loads, the loads that depend on them, the LDS writes — so that all loads of
+// a phase are in flight together.
+template <int THREADS>
+__device__ __forceinline__ void k2_stage_tree(const K2Frame& f, int replace, K2Node* tree)
+{
+    for (int base = threadIdx.x; base < f.n_keypoints; base += 8 * THREADS) {
+        int kpi[8], l[8], r[8];
+        float x[8], y[8];
+        bool taken[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int i = base + q * THREADS;
+            kpi[q] = 0; l[q] = -1; r[q] = -1; x[q] = 0.f; y[q] = 0.f;
+            if (i < f.n_keypoints) {
+                if (f.packed) {        // packed once per frame (rs_kdtree_pack): straight copies instead of dependent gathers
+                    const float4 nd = f.packed[i];
+                    kpi[q] = ((const int*)(f.packed + f.n_keypoints))[i];
+                    x[q] = nd.x; y[q] = nd.y; l[q] = __float_as_int(nd.z); r[q] = __float_as_int(nd.w);
+                } else {
+                    kpi[q] = f.kd_node_kp[i]; l[q] = f.kd_left[i]; r[q] = f.kd_right[i];
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const bool in = base + q * THREADS < f.n_keypoints;
+            taken[q] = in && !replace && f.kp_matched[kpi[q]] != 0;
+            if (in && !f.packed) { const float2 k = f.kp[kpi[q]]; x[q] = k.x; y[q] = k.y; }
+        }
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int i = base + q * THREADS;
+            if (i < f.n_keypoints) {
+                K2Node nd;
+                nd.x = x[q]; nd.y = y[q];
+                nd.lr = (unsigned)(l[q] & 0xFFFF) | ((unsigned)(r[q] & 0xFFFF) << 16);
+                nd.kp = kpi[q] | (taken[q] ? (int)0x80000000 : 0);
+                tree[i] = nd;
+            }
+        }
+    }
+}
+
+// Camera::project (src/Camera.cpp:25-32) and is_in_image (:34-37, src/MapMatcher.cpp:58); false: not in the image.
+// T is the kernel's own copy of f.T: each kernel reads the pose in its body, where it is used.  With f.T itself handed
+// to these helpers the compiler reads all of K2Frame into SGPRs at kernel entry, and k2_reproj_match spills.
+__device__ __forceinline__ bool k2_project(const K2Frame& f, const float* T, const float* X, float& u, float& v)
+{
+    const TriParams k = {f.fx, f.fy, f.cx, f.cy, 0.0f, 0.0f};
+    const float2 uv = project_f32(k, T, X);
+    u = uv.x; v = uv.y;
+    return u >= 0.0f && u < (float)f.width && v >= 0.0f && v < (float)f.height;
+}
+
+// The viewing gates once the point's observations are accumulated (src/MapPoint.cpp:24-45): `normal` the sum of the unit
+// rays from the observing keyframes, nearest / furthest their distance range; center = Frame::camera_center.
+__device__ __forceinline__ bool k2_view_gates(float* normal, float nearest, float furthest, const float* X, const float* center)
+{
+    const float ray[3] = {X[0] - center[0], X[1] - center[1], X[2] - center[2]};
+    normalize3f(normal);
+    float rn[3] = {ray[0], ray[1], ray[2]};
+    normalize3f(rn);
+    if (dot3f(normal, rn) < 0.5f) return false;                         // :62-66
+    const float distance = sqrtf(dot3f(ray, ray));
+    return !(distance < nearest / 2.0f || distance > furthest * 1.25f);  // :69-73
+}
+
+// An in-range, open keypoint met by the walk (src/MapMatcher.cpp:84-91).  The first K2_MAXC are QUEUED in visiting
+// order, their descriptors compared in phase B.  (Comparing inside the walk costs one global-memory round trip per
+// iteration in which ANY lane of the wave has a candidate — nearly every one; queued, the round trips are one per four
+// candidates of the busiest lane.)  Candidates beyond K2_MAXC are compared on the spot, against every descriptor of the
+// point o0 .. o1, into a second running best: they come later in visiting order than every queued one, so the queue
+// wins ties when the kernels merge the two.
+__device__ __forceinline__ void k2_candidate(const K2Frame& f, const K2Map& m, int o0, int o1, int kp, const K2Lds& L,
+                                             int& nc, int& over_d, int& over_kp)
+{
+    if (nc < K2_MAXC) { L.queue[nc++ * L.pts] = kp; return; }
+    const uint4 a0 = f.desc[2 * (size_t)kp], a1 = f.desc[2 * (size_t)kp + 1];
+    int d = 0x7fffffff;
+    for (int o = o0; o < o1; o++) {
+        const size_t row = (size_t)m.obs_desc[o];
+        d = min(d, hamming256(a0, a1, m.pool[2 * row], m.pool[2 * row + 1]));
+    }
+    if (d < over_d) { over_d = d; over_kp = kp; }
+}
+
+// KDTree2D::radius_search around (u, v), r = 20 px (src/MapMatcher.cpp:75, src/KDTree.cpp:45-82), by one lane for one
+// point: the near child is visited next without going through the stack, only far children are pushed, with the depth
+// parity of their level.  IN_LDS (a literal): the nodes are L.tree's.  Both children of a node are read while the node is
+// examined (their indices are in the node), so the LDS latency of the next visit overlaps this visit's arithmetic; only
+// a node popped from the stack pays a read of its own.  Otherwise (trees too large for LDS) the same walk fetches each
+// node from global memory when it is visited.
+// A macro over the kernel's f, m, replace, o0, o1, u, v, L, nc, over_d and over_kp, not a function: as an inlined
+// function the compiler splits this loop into a descent loop inside a pop loop, in which a lane that has to pop waits
+// for the wave's last descent to end (K2 on the benchmark scene: 22.4 us instead of 20.9).
+#define K2_WALK(IN_LDS) do {                                                                                        \
+    const float r2 = 20.0f * 20.0f;                                                                                 \
+    int sp = 0;                                                                                                     \
+    int cur = f.kd_root, odd = 0;                                                                                   \
+    K2Node nd, ndl, ndr;                                                                                            \
+    if (IN_LDS && cur >= 0) nd = L.tree[cur];                                                                       \
+    while (cur >= 0) {                                                                                              \
+        int l, r, kp;                                                                                               \
+        float dx, dy;                                                                                               \
+        if (IN_LDS) {                                                                                               \
+            l = (int)(nd.lr & 0xFFFFu); r = (int)(nd.lr >> 16);                                                     \
+            l = l == 0xFFFF ? -1 : l; r = r == 0xFFFF ? -1 : r;                                                     \
+            ndl = L.tree[l >= 0 ? l : 0]; ndr = L.tree[r >= 0 ? r : 0];                                             \
+            kp = nd.kp;                                                                                             \
+            dx = nd.x - u; dy = nd.y - v;                                                                           \
+        } else {                                                                                                    \
+            kp = f.kd_node_kp[cur];                                                                                 \
+            const float2 q = f.kp[kp];                                                                              \
+            l = f.kd_left[cur]; r = f.kd_right[cur];                                                                \
+            dx = q.x - u; dy = q.y - v;                                                                             \
+        }                                                                                                           \
+        const float d2 = dx * dx + dy * dy;                                                                         \
+        if (d2 <= r2 && (IN_LDS ? kp >= 0 : (replace || !f.kp_matched[kp])))     /* in range and open (:65, :81) */   \
+            k2_candidate(f, m, o0, o1, kp, L, nc, over_d, over_kp);                                                 \
+        const float delta = odd ? dy : dx;                                                                          \
+        const bool left_near = delta > 0;                                                                           \
+        const int near_child = left_near ? l : r;                                                                   \
+        const int far_child = left_near ? r : l;                                                                    \
+        odd ^= 1;                                                                /* depth parity of the children */ \
+        if (delta * delta <= r2 && far_child >= 0 && sp < K2_STACK) L.stack[sp++ * L.pts] = far_child | (odd << 30); \
+        if (near_child >= 0) { cur = near_child; if (IN_LDS) nd = left_near ? ndl : ndr; }                          \
+        else if (sp > 0) {                                                                                          \
+            const int e = L.stack[--sp * L.pts];                                                                    \
+            cur = e & 0x3FFFFFFF; odd = (e >> 30) & 1;                                                              \
+            if (IN_LDS) nd = L.tree[cur];                                                                           \
+        }                                                                                                           \
+        else cur = -1;                                                                                              \
+    }                                                                                                               \
+} while (0)
+
+#ifndef RS_STAMPS
+#define RS_STAMPS 0
+#endif
+#if RS_STAMPS
+// diagnostic build (RS_STAMPS=1 python build.py): phase ends of the first wave of the middle workgroup, 10 ns ticks
+__device__ unsigned long long k2_stamps[8];
+#define K2_STAMP(i) do { if (threadIdx.x == 0 && blockIdx.x == gridDim.x / 2) k2_stamps[i] = wall_clock64(); } while (0)
+#define K2_STAMP0() K2_STAMP(0)
+extern "C" int rs_k2_stamps(unsigned long long* h_out, int reset)
+{
+    if (hipMemcpyFromSymbol(h_out, HIP_SYMBOL(k2_stamps), sizeof(unsigned long long) * 8) != hipSuccess) return RS_ERR_HIP;
+    if (reset) {
+        unsigned long long z[8] = {~0ull, 0, 0, 0, 0, 0, 0, 0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(k2_stamps), z, sizeof z) != hipSuccess) return RS_ERR_HIP;
+    }
+    return RS_OK;
+}
+#else
+#define K2_STAMP(i) do { } while (0)
+#define K2_STAMP0() do { } while (0)
+#endif
+
+// One lane per map point: the lane accumulates the point's observations in batches of K2_PRE, walks the tree (in LDS or,
+// when it does not fit, in global memory) and compares the queued candidates against K2_PRE descriptor rows per pass.
 __global__ __launch_bounds__(K2_THREADS) void k2_reproj_match(K2Frame f, K2Map m, int replace, int max_distance, int tree_in_lds,
                                                              int32_t* __restrict__ point_kp,
                                                              int32_t* __restrict__ point_dist,
                                                              unsigned long long* __restrict__ prop)
 {
-    // dynamic LDS: [K2_STACK][K2_THREADS] traversal stacks, [K2_MAXC][K2_THREADS] candidate queue and the candidates'
-    // running minima, then the tree
-    extern __shared__ __attribute__((aligned(16))) int k2_lds[];
-    int (*stack)[K2_THREADS] = (int (*)[K2_THREADS])k2_lds;
-    int (*queue)[K2_THREADS] = (int (*)[K2_THREADS])(k2_lds + K2_STACK * K2_THREADS);
-    int (*qmin)[K2_THREADS] = (int (*)[K2_THREADS])(k2_lds + (K2_STACK + K2_MAXC) * K2_THREADS);
-    K2Node* tree = (K2Node*)(k2_lds + (K2_STACK + 2 * K2_MAXC) * K2_THREADS);
+    const K2Lds L = k2_lds_view(K2_THREADS, threadIdx.x);
     // this lane's map point: every load that needs only p goes out before the tree is staged
     const int p = blockIdx.x * K2_THREADS + threadIdx.x;
     const bool have = p < m.n_points;
     const int pc = have ? p : 0;
-    const bool elig = have && m.n_points > 0 && m.eligible[pc] != 0;
-    const int o0 = m.n_points > 0 ? m.obs_ptr[pc] : 0, o1 = m.n_points > 0 ? m.obs_ptr[pc + 1] : 0;
+    const bool elig = have && m.eligible[pc] != 0;
+    const int o0 = m.obs_ptr[pc], o1 = m.obs_ptr[pc + 1];
     const int nobs = elig ? o1 - o0 : 0;
-    float X[3] = {0.f, 0.f, 0.f};
-    if (m.n_points > 0) { X[0] = m.pos[3 * (size_t)pc]; X[1] = m.pos[3 * (size_t)pc + 1]; X[2] = m.pos[3 * (size_t)pc + 2]; }
+    const float X[3] = {m.pos[3 * (size_t)pc], m.pos[3 * (size_t)pc + 1], m.pos[3 * (size_t)pc + 2]};
     // the first K2_PRE observations of the point: keyframe centre and descriptor row, loaded as two
     // batches (not as nobs dependent pairs inside the loops below); further observations come in batches of K2_PRE too
     int rowv[K2_PRE];
@@ -168,77 +344,19 @@ __global__ __launch_bounds__(K2_THREADS) void k2_reproj_match(K2Frame f, K2Map m
         }
     }
     if (tree_in_lds) {
-        // eight nodes per thread and pass, all loads of a level issued together
-        for (int base = threadIdx.x; base < f.n_keypoints; base += 8 * K2_THREADS) {
-            int kpi[8], l[8], r[8];
-            float x[8], y[8];
-            bool taken[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                const int i = base + q * K2_THREADS;
-                kpi[q] = 0; l[q] = -1; r[q] = -1; x[q] = 0.f; y[q] = 0.f;
-                if (i < f.n_keypoints) {
-                    if (f.packed) {        // packed once per frame (rs_kdtree_pack): straight copies instead of dependent gathers
-                        const float4 nd = f.packed[i];
-                        kpi[q] = ((const int*)(f.packed + f.n_keypoints))[i];
-                        x[q] = nd.x; y[q] = nd.y; l[q] = __float_as_int(nd.z); r[q] = __float_as_int(nd.w);
-                    } else {
-                        kpi[q] = f.kd_node_kp[i]; l[q] = f.kd_left[i]; r[q] = f.kd_right[i];
-                    }
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                const bool in = base + q * K2_THREADS < f.n_keypoints;
-                taken[q] = in && !replace && f.kp_matched[kpi[q]] != 0;
-                if (in && !f.packed) { const float2 k = f.kp[kpi[q]]; x[q] = k.x; y[q] = k.y; }
-            }
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                const int i = base + q * K2_THREADS;
-                if (i < f.n_keypoints) {
-                    K2Node nd;
-                    nd.x = x[q]; nd.y = y[q];
-                    nd.lr = (unsigned)(l[q] & 0xFFFF) | ((unsigned)(r[q] & 0xFFFF) << 16);
-                    nd.kp = kpi[q] | (taken[q] ? (int)0x80000000 : 0);
-                    tree[i] = nd;
-                }
-            }
-        }
+        k2_stage_tree<K2_THREADS>(f, replace, L.tree);
         __syncthreads();
     }
     int out_kp = -1, out_d = max_distance;
     if (have) do {
         if (!elig) break;
-        const float* T = f.T;
-        // Camera::project (src/Camera.cpp:25-32): K * pose.block<3,4> first, then * homogeneous
-        float uvw[3];
-        {
-            float KP[12];
+        float T[16];                                                     // see k2_project
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                KP[0 * 4 + j] = (f.fx * T[0 * 4 + j] + 0.0f * T[1 * 4 + j]) + f.cx * T[2 * 4 + j];
-                KP[1 * 4 + j] = (0.0f * T[0 * 4 + j] + f.fy * T[1 * 4 + j]) + f.cy * T[2 * 4 + j];
-                KP[2 * 4 + j] = (0.0f * T[0 * 4 + j] + 0.0f * T[1 * 4 + j]) + 1.0f * T[2 * 4 + j];
-            }
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-                uvw[i] = (KP[4 * i] * X[0] + KP[4 * i + 1] * X[1]) + (KP[4 * i + 2] * X[2] + KP[4 * i + 3] * 1.0f);
-        }
+        for (int i = 0; i < 16; i++) T[i] = f.T[i];
         float u, v;
-        if (uvw[2] < 0.0f) { u = -1.0f; v = -1.0f; }
-        else { u = uvw[0] / uvw[2]; v = uvw[1] / uvw[2]; }
-        if (!(u >= 0.0f && u < (float)f.width && v >= 0.0f && v < (float)f.height)) break;   // :58
-
-        // Frame::camera_center = -R^T t (src/Frame.cpp:39-42)
+        if (!k2_project(f, T, X, u, v)) break;
         float center[3];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const float a[3] = {-T[0 * 4 + i], -T[1 * 4 + i], -T[2 * 4 + i]};
-            const float t[3] = {T[3], T[7], T[11]};
-            center[i] = dot3f(a, t);
-        }
-        const float ray[3] = {X[0] - center[0], X[1] - center[1], X[2] - center[2]};
+        camera_center_f32(T, center);
         float normal[3] = {0.0f, 0.0f, 0.0f};
         float nearest = 3.402823466e+38f, furthest = 0.0f;
         auto add_obs = [&](const float Cx, const float Cy, const float Cz) {   // src/MapPoint.cpp:24-45
@@ -268,15 +386,8 @@ __global__ __launch_bounds__(K2_THREADS) void k2_reproj_match(K2Frame f, K2Map m
             for (int j = 0; j < K2_PRE; j++)
                 if (ob + j < nobs) add_obs(Cx[j][0], Cx[j][1], Cx[j][2]);
         }
-        normalize3f(normal);
-        float rn[3] = {ray[0], ray[1], ray[2]};
-        normalize3f(rn);
-        if (dot3f(normal, rn) < 0.5f) break;                             // :62-66
-        const float distance = sqrtf(dot3f(ray, ray));
-        if (distance < nearest / 2.0f || distance > furthest * 1.25f) break;   // :69-73
+        if (!k2_view_gates(normal, nearest, furthest, X, center)) break;
 
-        // KDTree2D::radius_search, r = 20 px (src/MapMatcher.cpp:75, src/KDTree.cpp:45-82)
-        const float r2 = 20.0f * 20.0f;
         int best_kp = 0, best_d = max_distance;
         // One candidate keypoint against every descriptor of the point (:84-91).  The reference keeps a running best with
         // a strict '<' over (candidate, observation) pairs; the winner's keypoint is the FIRST candidate (in visiting
@@ -289,78 +400,10 @@ __global__ __launch_bounds__(K2_THREADS) void k2_reproj_match(K2Frame f, K2Map m
                 if (j < nb) d = min(d, hamming256(a0, a1, b0[j], b1[j]));
             return d;
         };
-        // Phase A: the traversal touches LDS only and QUEUES the candidates in visiting order.  (Comparing descriptors
-        // inside this loop costs one global-memory round trip per iteration in which ANY lane of the wave has a
-        // candidate — nearly every one; queued, the round trips are one per four candidates of the busiest lane.)
-        // The near child is visited next without going through the stack; only far children are pushed.
-        // Candidates beyond K2_MAXC are compared on the spot into a second running best, merged below: they come
-        // later in visiting order than every queued one, so the queue wins ties.
+        // Phase A: the walk queues the candidates
         int nc = 0, over_kp = 0, over_d = max_distance;
-        int sp = 0;
-        int cur = f.kd_root, odd = 0;
-        if (tree_in_lds) {
-            // Both children of a node are read while the node is examined (their indices are in the node), so the LDS
-            // latency of the next visit overlaps this visit's arithmetic; only a node popped from the stack pays a
-            // read of its own.
-            K2Node nd;
-            if (cur >= 0) nd = tree[cur];
-            while (cur >= 0) {
-                int l = (int)(nd.lr & 0xFFFFu), r = (int)(nd.lr >> 16);
-                l = l == 0xFFFF ? -1 : l; r = r == 0xFFFF ? -1 : r;
-                const K2Node ndl = tree[l >= 0 ? l : 0], ndr = tree[r >= 0 ? r : 0];
-                const float dx = nd.x - u, dy = nd.y - v;
-                const float d2 = dx * dx + dy * dy;
-                if (d2 <= r2 && nd.kp >= 0) {                               // in range and open (:65, :81)
-                    const int kp = nd.kp;
-                    if (nc < K2_MAXC) queue[nc++][threadIdx.x] = kp;
-                    else {
-                        const uint4 a0 = f.desc[2 * (size_t)kp], a1 = f.desc[2 * (size_t)kp + 1];
-                        int d = 0x7fffffff;
-                        for (int o = o0; o < o1; o++) {
-                            const size_t row = (size_t)m.obs_desc[o];
-                            d = min(d, hamming256(a0, a1, m.pool[2 * row], m.pool[2 * row + 1]));
-                        }
-                        if (d < over_d) { over_d = d; over_kp = kp; }
-                    }
-                }
-                const float delta = odd ? dy : dx;
-                const bool left_near = delta > 0;
-                const int near_child = left_near ? l : r;
-                const int far_child = left_near ? r : l;
-                odd ^= 1;                                                 // depth parity of the children
-                if (delta * delta <= r2 && far_child >= 0 && sp < K2_STACK) stack[sp++][threadIdx.x] = far_child | (odd << 30);
-                if (near_child >= 0) { cur = near_child; nd = left_near ? ndl : ndr; }
-                else if (sp > 0) { const int e = stack[--sp][threadIdx.x]; cur = e & 0x3FFFFFFF; odd = (e >> 30) & 1; nd = tree[cur]; }
-                else cur = -1;
-            }
-        } else
-        while (cur >= 0) {                                                // trees too large for LDS: the same walk on global memory
-            const int kp = f.kd_node_kp[cur];
-            const float2 q = f.kp[kp];
-            const int l = f.kd_left[cur], r = f.kd_right[cur];
-            const float dx = q.x - u, dy = q.y - v;
-            const float d2 = dx * dx + dy * dy;
-            if (d2 <= r2 && (replace || !f.kp_matched[kp])) {               // :65, :81
-                if (nc < K2_MAXC) queue[nc++][threadIdx.x] = kp;
-                else {
-                    const uint4 a0 = f.desc[2 * (size_t)kp], a1 = f.desc[2 * (size_t)kp + 1];
-                    int d = 0x7fffffff;
-                    for (int o = o0; o < o1; o++) {
-                        const size_t row = (size_t)m.obs_desc[o];
-                        d = min(d, hamming256(a0, a1, m.pool[2 * row], m.pool[2 * row + 1]));
-                    }
-                    if (d < over_d) { over_d = d; over_kp = kp; }
-                }
-            }
-            const float delta = odd ? dy : dx;
-            const int near_child = (delta > 0) ? l : r;
-            const int far_child = (delta > 0) ? r : l;
-            odd ^= 1;
-            if (delta * delta <= r2 && far_child >= 0 && sp < K2_STACK) stack[sp++][threadIdx.x] = far_child | (odd << 30);
-            if (near_child >= 0) cur = near_child;
-            else if (sp > 0) { const int e = stack[--sp][threadIdx.x]; cur = e & 0x3FFFFFFF; odd = (e >> 30) & 1; }
-            else cur = -1;
-        }
+        if (tree_in_lds) K2_WALK(true);
+        else K2_WALK(false);
         // Phase B: K2_PRE descriptor rows of the point per pass (the first pass's row numbers are already here), the
         // queued candidates four at a time (their row loads go out together); each candidate's minimum over the
         // observations accumulates in LDS across passes
@@ -381,7 +424,7 @@ __global__ __launch_bounds__(K2_THREADS) void k2_reproj_match(K2Frame f, K2Map m
                     uint4 a0[4], a1[4];
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
-                        kq[q] = (c + q < nc) ? queue[c + q][threadIdx.x] : -1;
+                        kq[q] = (c + q < nc) ? L.queue[(c + q) * L.pts] : -1;
                         a0[q] = make_uint4(0, 0, 0, 0); a1[q] = a0[q];
                         if (kq[q] >= 0) { a0[q] = f.desc[2 * (size_t)kq[q]]; a1[q] = f.desc[2 * (size_t)kq[q] + 1]; }
                     }
@@ -389,14 +432,14 @@ __global__ __launch_bounds__(K2_THREADS) void k2_reproj_match(K2Frame f, K2Map m
                     for (int q = 0; q < 4; q++)
                         if (kq[q] >= 0) {
                             const int d = rows_min(a0[q], a1[q], b0, b1, nb);
-                            qmin[c + q][threadIdx.x] = ob == 0 ? d : min(d, qmin[c + q][threadIdx.x]);
+                            L.qmin[(c + q) * L.pts] = ob == 0 ? d : min(d, L.qmin[(c + q) * L.pts]);
                         }
                 }
             }
             if (nobs > 0)
                 for (int c = 0; c < nc; c++) {
-                    const int d = qmin[c][threadIdx.x];
-                    if (d < best_d) { best_d = d; best_kp = queue[c][threadIdx.x]; }     // :88-91, visiting order
+                    const int d = L.qmin[c * L.pts];
+                    if (d < best_d) { best_d = d; best_kp = L.queue[c * L.pts]; }       // :88-91, visiting order
                 }
         }
         if (over_d < best_d) { best_d = over_d; best_kp = over_kp; }
@@ -413,37 +456,12 @@ __global__ __launch_bounds__(K2_THREADS) void k2_reproj_match(K2Frame f, K2Map m
     }
 }
 
-// K2g: the same search with EIGHT lanes per map point (trees that fit in LDS).  With one lane per point a 64-wide
-// wave walks 64 trees in lock step and then compares every candidate against the point's descriptors one after the
-// other; here a wave holds 8 points, lane 0 of a group walks the tree and queues the candidates, and the group's lanes
-// each own ONE observation of the point: its keyframe centre (viewing-normal gate) and its descriptor row (loaded
-// before the tree is staged), so a candidate costs one 256-bit compare per lane and a 3-step DPP minimum.
-// Observation order of the normal's f32 sum, visiting order of the candidates and the strict '<' rules are those of
-// k2_reproj_match above — the outputs are bit-identical (tests/test_gpu_parity.py runs both).
-#define K2G 8
-
-#ifndef RS_STAMPS
-#define RS_STAMPS 0
-#endif
-#if RS_STAMPS
-// diagnostic build (RS_STAMPS=1 python build.py): phase ends of the first wave of the middle workgroup, 10 ns ticks
-__device__ unsigned long long k2_stamps[8];
-#define K2_STAMP(i) do { if (threadIdx.x == 0 && blockIdx.x == gridDim.x / 2) k2_stamps[i] = wall_clock64(); } while (0)
-#define K2_STAMP0() K2_STAMP(0)
-extern "C" int rs_k2_stamps(unsigned long long* h_out, int reset)
-{
-    if (hipMemcpyFromSymbol(h_out, HIP_SYMBOL(k2_stamps), sizeof(unsigned long long) * 8) != hipSuccess) return RS_ERR_HIP;
-    if (reset) {
-        unsigned long long z[8] = {~0ull, 0, 0, 0, 0, 0, 0, 0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(k2_stamps), z, sizeof z) != hipSuccess) return RS_ERR_HIP;
-    }
-    return RS_OK;
-}
-#else
-#define K2_STAMP(i) do { } while (0)
-#define K2_STAMP0() do { } while (0)
-#endif
-
+// K2g: EIGHT lanes per map point (trees that fit in LDS).  With one lane per point a 64-wide wave walks 64 trees in lock
+// step and then compares every candidate against the point's descriptors one after the other; here a wave holds 8
+// points, lane 0 of a group walks the tree and queues the candidates, and the group's lanes each own ONE observation of
+// the point: its keyframe centre (viewing-normal gate) and its descriptor row (loaded before the tree is staged), so a
+// candidate costs one 256-bit compare per lane and a 3-step DPP minimum.  The normal's f32 sum is taken in observation
+// order, as k2_reproj_match takes it — the outputs are bit-identical (tests/test_gpu_parity.py runs both).
 __device__ __forceinline__ int group8_min(int v)
 {
     v = min(v, __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, true));     // quad_perm [1,0,3,2]
@@ -452,21 +470,15 @@ __device__ __forceinline__ int group8_min(int v)
     return v;
 }
 
-template <int K2G_THREADS_T>
-__global__ __launch_bounds__(K2G_THREADS_T) void k2_reproj_match_grouped(K2Frame f, K2Map m, int replace, int max_distance,
-                                                                       int32_t* __restrict__ point_kp,
-                                                                       int32_t* __restrict__ point_dist,
-                                                                       unsigned long long* __restrict__ prop)
+__global__ __launch_bounds__(K2G_THREADS) void k2_reproj_match_grouped(K2Frame f, K2Map m, int replace, int max_distance,
+                                                                     int32_t* __restrict__ point_kp,
+                                                                     int32_t* __restrict__ point_dist,
+                                                                     unsigned long long* __restrict__ prop)
 {
-    // dynamic LDS: [K2_STACK][K2G_PTS] traversal stacks, [K2_MAXC][K2G_PTS] candidate queue and minima, then the tree
-    constexpr int K2G_PTS = K2G_THREADS_T / K2G;
-    extern __shared__ __attribute__((aligned(16))) int k2_lds[];
-    int (*stack)[K2G_PTS] = (int (*)[K2G_PTS])k2_lds;
-    int (*queue)[K2G_PTS] = (int (*)[K2G_PTS])(k2_lds + K2_STACK * K2G_PTS);
-    int (*qmin)[K2G_PTS] = (int (*)[K2G_PTS])(k2_lds + (K2_STACK + K2_MAXC) * K2G_PTS);
-    K2Node* tree = (K2Node*)(k2_lds + (K2_STACK + 2 * K2_MAXC) * K2G_PTS);
+    constexpr int K2G_PTS = K2G_THREADS / K2G;
     K2_STAMP0();
     const int g = threadIdx.x / K2G, sub = threadIdx.x % K2G;
+    const K2Lds L = k2_lds_view(K2G_PTS, g);
     const int p = blockIdx.x * K2G_PTS + g;
     const bool have = p < m.n_points;
     const int pc = have ? p : 0;
@@ -493,42 +505,7 @@ __global__ __launch_bounds__(K2G_THREADS_T) void k2_reproj_match_grouped(K2Frame
             b2 = m.pool[2 * row1]; b3 = m.pool[2 * row1 + 1];
         }
     }
-    for (int base = threadIdx.x; base < f.n_keypoints; base += 8 * K2G_THREADS_T) {
-        int kpi[8], l[8], r[8];
-        float x[8], y[8];
-        bool taken[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int i = base + q * K2G_THREADS_T;
-            kpi[q] = 0; l[q] = -1; r[q] = -1; x[q] = 0.f; y[q] = 0.f;
-            if (i < f.n_keypoints) {
-                if (f.packed) {
-                    const float4 nd = f.packed[i];
-                    kpi[q] = ((const int*)(f.packed + f.n_keypoints))[i];
-                    x[q] = nd.x; y[q] = nd.y; l[q] = __float_as_int(nd.z); r[q] = __float_as_int(nd.w);
-                } else {
-                    kpi[q] = f.kd_node_kp[i]; l[q] = f.kd_left[i]; r[q] = f.kd_right[i];
-                }
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const bool in = base + q * K2G_THREADS_T < f.n_keypoints;
-            taken[q] = in && !replace && f.kp_matched[kpi[q]] != 0;
-            if (in && !f.packed) { const float2 k = f.kp[kpi[q]]; x[q] = k.x; y[q] = k.y; }
-        }
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int i = base + q * K2G_THREADS_T;
-            if (i < f.n_keypoints) {
-                K2Node nd;
-                nd.x = x[q]; nd.y = y[q];
-                nd.lr = (unsigned)(l[q] & 0xFFFF) | ((unsigned)(r[q] & 0xFFFF) << 16);
-                nd.kp = kpi[q] | (taken[q] ? (int)0x80000000 : 0);
-                tree[i] = nd;
-            }
-        }
-    }
+    k2_stage_tree<K2G_THREADS>(f, replace, L.tree);
     K2_STAMP(1);
     __syncthreads();
     K2_STAMP(2);
@@ -536,33 +513,13 @@ __global__ __launch_bounds__(K2G_THREADS_T) void k2_reproj_match_grouped(K2Frame
     int out_kp = -1, out_d = max_distance;
     if (have) do {
         if (!elig) break;
-        const float* T = f.T;
-        float uvw[3];                                                    // Camera::project (src/Camera.cpp:25-32)
-        {
-            float KP[12];
+        float T[16];                                                     // see k2_project
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                KP[0 * 4 + j] = (f.fx * T[0 * 4 + j] + 0.0f * T[1 * 4 + j]) + f.cx * T[2 * 4 + j];
-                KP[1 * 4 + j] = (0.0f * T[0 * 4 + j] + f.fy * T[1 * 4 + j]) + f.cy * T[2 * 4 + j];
-                KP[2 * 4 + j] = (0.0f * T[0 * 4 + j] + 0.0f * T[1 * 4 + j]) + 1.0f * T[2 * 4 + j];
-            }
-#pragma unroll
-            for (int i = 0; i < 3; i++)
-                uvw[i] = (KP[4 * i] * X[0] + KP[4 * i + 1] * X[1]) + (KP[4 * i + 2] * X[2] + KP[4 * i + 3] * 1.0f);
-        }
+        for (int i = 0; i < 16; i++) T[i] = f.T[i];
         float u, v;
-        if (uvw[2] < 0.0f) { u = -1.0f; v = -1.0f; }
-        else { u = uvw[0] / uvw[2]; v = uvw[1] / uvw[2]; }
-        if (!(u >= 0.0f && u < (float)f.width && v >= 0.0f && v < (float)f.height)) break;   // :58
-
-        float center[3];                                                 // Frame::camera_center (src/Frame.cpp:39-42)
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const float a[3] = {-T[0 * 4 + i], -T[1 * 4 + i], -T[2 * 4 + i]};
-            const float t[3] = {T[3], T[7], T[11]};
-            center[i] = dot3f(a, t);
-        }
-        const float ray[3] = {X[0] - center[0], X[1] - center[1], X[2] - center[2]};
+        if (!k2_project(f, T, X, u, v)) break;
+        float center[3];
+        camera_center_f32(T, center);
         float normal[3] = {0.0f, 0.0f, 0.0f};
         float nearest = 3.402823466e+38f, furthest = 0.0f;
         for (int ob = 0; ob < nobs; ob += K2G) {                          // src/MapPoint.cpp:24-45, eight observations per pass
@@ -586,52 +543,11 @@ __global__ __launch_bounds__(K2G_THREADS_T) void k2_reproj_match_grouped(K2Frame
                 }
             }
         }
-        normalize3f(normal);
-        float rn[3] = {ray[0], ray[1], ray[2]};
-        normalize3f(rn);
-        if (dot3f(normal, rn) < 0.5f) break;                             // :62-66
-        const float distance = sqrtf(dot3f(ray, ray));
-        if (distance < nearest / 2.0f || distance > furthest * 1.25f) break;   // :69-73
+        if (!k2_view_gates(normal, nearest, furthest, X, center)) break;
 
         K2_STAMP(3);
-        // KDTree2D::radius_search (src/MapMatcher.cpp:75, src/KDTree.cpp:45-82) by lane 0 of the group
-        const float r2 = 20.0f * 20.0f;
         int nc = 0, over_kp = 0, over_d = max_distance;
-        if (sub == 0) {
-            int sp = 0;
-            int cur = f.kd_root, odd = 0;
-            K2Node nd;
-            if (cur >= 0) nd = tree[cur];
-            while (cur >= 0) {
-                int l = (int)(nd.lr & 0xFFFFu), r = (int)(nd.lr >> 16);
-                l = l == 0xFFFF ? -1 : l; r = r == 0xFFFF ? -1 : r;
-                const K2Node ndl = tree[l >= 0 ? l : 0], ndr = tree[r >= 0 ? r : 0];
-                const float dx = nd.x - u, dy = nd.y - v;
-                const float d2 = dx * dx + dy * dy;
-                if (d2 <= r2 && nd.kp >= 0) {                               // in range and open (:65, :81)
-                    const int kp = nd.kp;
-                    if (nc < K2_MAXC) queue[nc++][g] = kp;
-                    else {                                                  // crowded neighbourhoods: on the spot, after every queued one
-                        const uint4 a0 = f.desc[2 * (size_t)kp], a1 = f.desc[2 * (size_t)kp + 1];
-                        int d = 0x7fffffff;
-                        for (int o = o0; o < o1; o++) {
-                            const size_t row = (size_t)m.obs_desc[o];
-                            d = min(d, hamming256(a0, a1, m.pool[2 * row], m.pool[2 * row + 1]));
-                        }
-                        if (d < over_d) { over_d = d; over_kp = kp; }
-                    }
-                }
-                const float delta = odd ? dy : dx;
-                const bool left_near = delta > 0;
-                const int near_child = left_near ? l : r;
-                const int far_child = left_near ? r : l;
-                odd ^= 1;
-                if (delta * delta <= r2 && far_child >= 0 && sp < K2_STACK) stack[sp++][g] = far_child | (odd << 30);
-                if (near_child >= 0) { cur = near_child; nd = left_near ? ndl : ndr; }
-                else if (sp > 0) { const int e = stack[--sp][g]; cur = e & 0x3FFFFFFF; odd = (e >> 30) & 1; nd = tree[cur]; }
-                else cur = -1;
-            }
-        }
+        if (sub == 0) K2_WALK(true);                                     // lane 0 of the group
         K2_STAMP(4);
         nc = __shfl(nc, 0, K2G);
         over_d = __shfl(over_d, 0, K2G);
@@ -651,7 +567,7 @@ __global__ __launch_bounds__(K2G_THREADS_T) void k2_reproj_match_grouped(K2Frame
                     uint4 a0[4], a1[4];
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
-                        kq[q] = queue[min(c + q, nc - 1)][g];
+                        kq[q] = L.queue[min(c + q, nc - 1) * L.pts];
                         a0[q] = f.desc[2 * (size_t)kq[q]]; a1[q] = f.desc[2 * (size_t)kq[q] + 1];
                     }
 #pragma unroll
@@ -659,7 +575,7 @@ __global__ __launch_bounds__(K2G_THREADS_T) void k2_reproj_match_grouped(K2Frame
                         const int d = group8_min(mine ? hamming256(a0[q], a1[q], r0, r1) : 0x7fffffff);
                         if (c + q < nc) {
                             if (ob == 0) { if (d < best_d) { best_d = d; best_kp = kq[q]; } }   // :88-91, visiting order
-                            if (nobs > K2G) qmin[c + q][g] = ob == 0 ? d : min(d, qmin[c + q][g]);
+                            if (nobs > K2G) L.qmin[(c + q) * L.pts] = ob == 0 ? d : min(d, L.qmin[(c + q) * L.pts]);
                         }
                     }
                 }
@@ -667,8 +583,8 @@ __global__ __launch_bounds__(K2G_THREADS_T) void k2_reproj_match_grouped(K2Frame
             if (nobs > K2G) {                                             // more than eight observations: minima over all passes
                 best_kp = 0; best_d = max_distance;
                 for (int c = 0; c < nc; c++) {
-                    const int d = qmin[c][g];
-                    if (d < best_d) { best_d = d; best_kp = queue[c][g]; }
+                    const int d = L.qmin[c * L.pts];
+                    if (d < best_d) { best_d = d; best_kp = L.queue[c * L.pts]; }
                 }
             }
         }
@@ -752,15 +668,14 @@ static int reproj_match_impl(rs_context* ctx, const rs_frame_view* fr, const rs_
         const int tree_in_lds = N <= K2_MAX_LDS_NODES ? 1 : 0;
         rs_prof_scope ps(ctx, "K2_reproj_match");
         if (tree_in_lds && ctx->k2_mode == 0) {                           // eight lanes per map point
-            const int th = 512, pts = th / K2G;                           // 64 map points per workgroup (256 / 1024 threads: slower)
-            const size_t lds = sizeof(int) * (K2_STACK + 2 * K2_MAXC) * pts + sizeof(K2Node) * (size_t)N;
-            auto kern = k2_reproj_match_grouped<512>;
+            const int pts = K2G_THREADS / K2G;
+            const size_t lds = k2_lds_bytes(pts, N);
             if (lds > 48 * 1024)
-                RS_HIP(ctx, rs_lds_attr((const void*)kern, lds));
-            hipLaunchKernelGGL(kern, dim3((P + pts - 1) / pts), dim3(th), lds,
+                RS_HIP(ctx, rs_lds_attr((const void*)k2_reproj_match_grouped, lds));
+            hipLaunchKernelGGL(k2_reproj_match_grouped, dim3((P + pts - 1) / pts), dim3(K2G_THREADS), lds,
                                ctx->stream, f, m, replace, max_distance, d_point_kp, d_point_dist, prop);
         } else {
-            const size_t lds = sizeof(int) * (K2_STACK + 2 * K2_MAXC) * K2_THREADS + (tree_in_lds ? sizeof(K2Node) * (size_t)N : 0);
+            const size_t lds = k2_lds_bytes(K2_THREADS, tree_in_lds ? N : 0);
             if (lds > 48 * 1024)
                 RS_HIP(ctx, rs_lds_attr((const void*)k2_reproj_match, lds));
             hipLaunchKernelGGL(k2_reproj_match, dim3((P + K2_THREADS - 1) / K2_THREADS), dim3(K2_THREADS), lds,

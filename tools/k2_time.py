@@ -1,5 +1,9 @@
 #!/usr/bin/env python3
-"""Times K2 (rs_reproj_match) alone on the benchmark scene (20 KF / 10 k landmarks / 2000 keypoints)."""
+"""Times K2 (rs_reproj_match) alone on the benchmark scene (20 KF / 10 k landmarks / 2000 keypoints).
+
+    python tools/k2_time.py [n_keypoints]
+
+More than 6144 keypoints do not fit in LDS: both k2_mode values then run the one-lane kernel's walk over global memory."""
 import importlib
 import os
 import sys
@@ -10,9 +14,10 @@ pkg = importlib.import_module("racing-slam_amd")
 rs, synth = pkg.rsgpu, pkg.synth
 import torch  # noqa: E402
 
+n_keypoints = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
 ctx = rs.Context(0)
 w = synth.make_ba_window()
-frame, mp = synth.make_match_scene(w, n_keypoints=2000, kdtree_build=rs.kdtree_build)
+frame, mp = synth.make_match_scene(w, n_keypoints=n_keypoints, kdtree_build=rs.kdtree_build)
 fv, keep_f = ctx.make_frame_view(frame, pack=True)
 mv, keep_m = ctx.make_map_view(mp)
 for mode in (0, 1):                                  # eight lanes per map point / one lane per point
@@ -26,5 +31,9 @@ for mode in (0, 1):                                  # eight lanes per map point
         ctx.reproj_match(fv, mv, out=out)
     ctx.synchronize()
     p = ctx.prof_end()
-    print("k2_mode", mode, {k: round(1e3 * v[1] / v[0], 2) for k, v in p.items()}, "matches", int(out["count"].item()))
+    n = int(out["count"].item())
+    sums = [int(out[k][:m].to(torch.int64).sum().item()) for k, m in (("point_kp", mv.n_points), ("point_dist", mv.n_points),
+                                                                       ("match_kp", n), ("match_point", n))]
+    print("n_keypoints", n_keypoints, "k2_mode", mode, {k: round(1e3 * v[1] / v[0], 2) for k, v in p.items()},
+          "matches", n, "sums", sums, flush=True)
 ctx.close()
