@@ -353,14 +353,16 @@ extern "C" int rs_vocabulary_load_text(rs_context* ctx, const char* path, rs_voc
     while (!lines.empty() && blank(lines.back())) lines.pop_back();
     if (lines.size() < 2) return rs_fail(ctx, RS_ERR_INVALID, "%s: no nodes", path);
     if (lines.size() > BOW_MAX_NODES) return rs_fail(ctx, RS_ERR_UNSUPPORTED, "%s: more than %d nodes", path, BOW_MAX_NODES);
-    // a line that ends early fails its own count: nothing is read across a '\n'
+    // a line that ends early fails its own count: nothing is read across a '\n'.  A field ends at a blank or at the end of
+    // its line, so "7x" is no number and the integer part of a weight is no byte of a line that lacks one
+    auto ends = [](const char* p) { return *p == ' ' || *p == '\t' || *p == '\n' || *p == '\r' || *p == '\0'; };
     auto ints = [&](const char*& p, long* v, int count) {
         for (int i = 0; i < count; i++) {
             while (*p == ' ' || *p == '\t') p++;
             if (*p == '\n' || *p == '\r' || *p == '\0') return false;
             char* e = nullptr;
             v[i] = strtol(p, &e, 10);
-            if (e == p) return false;
+            if (e == p || !ends(e)) return false;
             p = e;
         }
         return true;
@@ -379,7 +381,7 @@ extern "C" int rs_vocabulary_load_text(rs_context* ctx, const char* path, rs_voc
         while (*p == ' ' || *p == '\t') p++;
         char* e = nullptr;
         if (*p != '\n' && *p != '\r' && *p != '\0') weight[i] = strtod(p, &e);
-        if (!e || e == p) return rs_fail(ctx, RS_ERR_INVALID, "%s: line %zu has no weight", path, i + 1);
+        if (!e || e == p || !ends(e)) return rs_fail(ctx, RS_ERR_INVALID, "%s: line %zu has no weight", path, i + 1);
         if (v[0] < 0 || v[0] > 0x7FFFFFFF) return rs_fail(ctx, RS_ERR_INVALID, "%s: line %zu: parent %ld", path, i + 1, v[0]);
         parent[i] = (int32_t)v[0];
         leaf[i] = v[1] > 0;

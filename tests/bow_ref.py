@@ -6,7 +6,9 @@ What it restates (reference lines):
         line per node after the root, "parent is_leaf b0 .. b31 weight"; node ids are line numbers, a node's children
         are in file order (= ascending id), leaves become words 0 .. W-1 in file order.  The reference's
         while(!f.eof()) loop makes one extra node from the empty last line; that is NOT restated: a trailing blank
-        line is ignored.
+        line is ignored.  A line is read with operator>>: any run of blanks separates fields and whatever follows
+        the weight is ignored; a line with fewer fields, a field that is no number or a byte outside 0 .. 255 (which
+        the reference would take without a word) raises ValueError here.
   TemplatedVocabulary.h:1218-1259  descent of one feature: from the root to the child of smallest Hamming distance,
         strict '<' (the first child among equals), until a leaf; the word is the leaf's word id, with its weight.
   TemplatedVocabulary.h:1066-1122  transform: stopped words (weight <= 0) dropped; TF_IDF / TF add the weight once per
@@ -107,10 +109,13 @@ def parse_text(path):
     is_leaf = np.zeros(n, bool)
     for i in range(1, n):
         t = lines[i].split()
-        if len(t) != 35:
+        if len(t) < 35:                                         # (fields past the weight are not read, as in the reference)
             raise ValueError(f"line {i + 1}: {len(t)} fields")
         parent[i], is_leaf[i] = int(t[0]), int(t[1]) > 0
-        desc[i] = [int(v) for v in t[2:34]]
+        row = [int(v) for v in t[2:34]]
+        if min(row) < 0 or max(row) > 255:
+            raise ValueError(f"line {i + 1}: a descriptor byte outside 0 .. 255")
+        desc[i] = row
         weight[i] = float(t[34])
     return Vocabulary(k, L, weighting, scoring, parent, desc, weight, is_leaf)
 

@@ -5,6 +5,7 @@ Word ids, occurrence counts and word lists are integers: exact equality.  Values
 (every term is a positive weight; any summation order of at most 8192 of them is within (n-1) 2^-53 ~ 9.1e-13 of the exact
 sum, so count x weight and tree reductions are allowed).  Scores: absolute error <= 1e-11, the same bound carried
 through |v-w| - v - w with sum v = sum w = 1.
+The LDS prefix boundary, vectors wider than 1000 words and the score's shape edges are in tests/test_gpu_bow_envelope.py.
 """
 import functools
 import importlib
