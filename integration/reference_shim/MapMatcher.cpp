@@ -7,8 +7,6 @@
 // log + empty result — instead of feeding float descriptors to a Hamming kernel.
 #include "MapMatcher.h"
 
-#include <unordered_map>
-
 #include "Camera.h"
 #include "Frame.h"
 #include "Map.h"
@@ -20,7 +18,7 @@ namespace {
 
 bool orb_rows(const cv::Mat& d, cv::NormTypes norm, const char* who)
 {
-    if (norm == cv::NORM_HAMMING && (d.empty() || (d.type() == CV_8U && d.cols == RS_DESC_BYTES && d.isContinuous()))) return true;
+    if (norm == cv::NORM_HAMMING && rs_shim::orb_layout(d)) return true;
     std::printf("%s: the GPU path matches 32-byte ORB descriptors under NORM_HAMMING only (norm %d, type %d, cols %d)\n",
                 who, (int)norm, d.empty() ? -1 : d.type(), d.empty() ? 0 : d.cols);
     return false;
@@ -50,37 +48,16 @@ std::vector<MapPointMatch> reproj(const Camera& camera, float max_distance, cv::
     const cv::Mat& fd = frame.features().descriptors;
     if (N == 0 || !orb_rows(fd, norm, "MapMatcher::match")) return {};
     FrameArrays fa(frame);
-    std::vector<float> pos(3 * P), centers;
-    std::vector<uint8_t> eligible(P), pool;
-    std::vector<int32_t> obs_ptr(P + 1, 0), obs_kf, obs_desc, pool_off;
-    std::unordered_map<const KeyFrame*, int> kf_id;
-    for (size_t p = 0; p < P; p++) {
-        MapPoint* mp = points[p];
-        bool run = mp != nullptr && !frame.is_matched(*mp);                               // :53, :121-123
-        if (run && required_observer != nullptr && !mp->is_observed_by(required_observer)) run = false;   // :169
-        eligible[p] = run;
-        if (mp) for (int k = 0; k < 3; k++) pos[3 * p + k] = mp->position()[k];
-        if (run)
-            for (const auto& [kf, idx] : mp->observations()) {
-                auto it = kf_id.find(kf);
-                if (it == kf_id.end()) {
-                    const cv::Mat& d = kf->features().descriptors;                        // N x 32 CV_8U, row-contiguous
-                    if (!orb_rows(d, norm, "MapMatcher::match (key frame)")) return {};
-                    it = kf_id.emplace(kf, (int)kf_id.size()).first;
-                    const Eigen::Vector3f c = kf->camera_center();
-                    centers.insert(centers.end(), {c.x(), c.y(), c.z()});
-                    pool_off.push_back((int32_t)(pool.size() / RS_DESC_BYTES));
-                    pool.insert(pool.end(), d.ptr<uint8_t>(0), d.ptr<uint8_t>(0) + (size_t)d.rows * RS_DESC_BYTES);
-                }
-                obs_kf.push_back(it->second);
-                obs_desc.push_back(pool_off[it->second] + (int32_t)idx);
-            }
-        obs_ptr[p + 1] = (int32_t)obs_kf.size();
+    // map side (rs_marshal.h); a key frame whose descriptors are not 32-byte ORB rows refuses the whole call
+    const rs_marshal::MatchArrays m = rs_marshal::flatten_match(frame, points, required_observer, Access{});
+    if (m.refused) {
+        std::printf("MapMatcher::match (key frame): the GPU path matches 32-byte ORB descriptors only (CV_8U, %d columns, continuous)\n", RS_DESC_BYTES);
+        return {};
     }
     Stage stage;
-    DevBuf<float> d_kp(fa.kp), d_pos(pos), d_centers(centers);
-    DevBuf<uint8_t> d_desc(fd.ptr<uint8_t>(0), N * RS_DESC_BYTES), d_matched(fa.matched), d_elig(eligible), d_pool(pool);
-    DevBuf<int32_t> d_nk(fa.node_kp), d_l(fa.left), d_r(fa.right), d_optr(obs_ptr), d_okf(obs_kf), d_odesc(obs_desc);
+    DevBuf<float> d_kp(fa.kp), d_pos(m.pos), d_centers(m.centers);
+    DevBuf<uint8_t> d_desc(fd.ptr<uint8_t>(0), N * RS_DESC_BYTES), d_matched(fa.matched), d_elig(m.eligible), d_pool(m.pool);
+    DevBuf<int32_t> d_nk(fa.node_kp), d_l(fa.left), d_r(fa.right), d_optr(m.obs_ptr), d_okf(m.obs_kf), d_odesc(m.obs_desc);
     rs_frame_view fv{};
     pose_to_row_major(frame.pose(), fv.pose);
     float K[4];

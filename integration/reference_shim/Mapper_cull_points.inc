@@ -15,33 +15,17 @@ double reprojection_sums[2] = {0.0, 0.0};
 {
     using namespace rs_shim;
     std::vector<MapPoint*> order(local.begin(), local.end());
-    std::vector<float> pos, uv, poses;
-    std::vector<int32_t> obs_ptr{0}, obs_pose;
-    std::unordered_map<const KeyFrame*, int32_t> pose_row;
-    for (MapPoint* p : order) {
-        for (int k = 0; k < 3; k++) pos.push_back(p->position()[k]);
-        for (const auto& [kf, idx] : p->observations()) {
-            auto it = pose_row.find(kf);
-            if (it == pose_row.end()) {
-                it = pose_row.emplace(kf, (int32_t)pose_row.size()).first;
-                append_row_major(kf->pose(), poses);
-            }
-            obs_pose.push_back(it->second);
-            uv.push_back(kf->keypoint(idx).pt.x);
-            uv.push_back(kf->keypoint(idx).pt.y);
-        }
-        obs_ptr.push_back((int32_t)obs_pose.size());
-    }
+    const rs_marshal::PointErrorArrays e = rs_marshal::flatten_point_errors(order, Access{});
     const size_t P = order.size();
-    if (P > 0 && !obs_pose.empty()) {
+    if (P > 0 && !e.obs_pose.empty()) {
         float K[4];
         intrinsics(m_camera.get_intrinsic_matrix(), K);
         Stage stage;
-        DevBuf<float> d_pos(pos), d_uv(uv), d_poses(poses), d_mean(P);
-        DevBuf<int32_t> d_ptr(obs_ptr), d_op(obs_pose), d_idx(P), d_cnt(1);
+        DevBuf<float> d_pos(e.pos), d_uv(e.uv), d_poses(e.poses), d_mean(P);
+        DevBuf<int32_t> d_ptr(e.obs_ptr), d_op(e.obs_pose), d_idx(P), d_cnt(1);
         DevBuf<uint8_t> d_cull(P);
         DevBuf<double> d_sums(2);
-        if (ok(rs_point_errors(context(), (int)P, d_pos.p, d_ptr.p, d_op.p, d_uv.p, d_poses.p, (int)pose_row.size(), K,
+        if (ok(rs_point_errors(context(), (int)P, d_pos.p, d_ptr.p, d_op.p, d_uv.p, d_poses.p, e.n_poses, K,
                                MAX_POINT_REPROJECTION_ERROR, d_mean.p, d_cull.p, d_idx.p, d_cnt.p, d_sums.p), "rs_point_errors")) {
             const auto hn = d_cnt.fetch(1);
             const auto hidx = d_idx.fetch(P);

@@ -11,7 +11,6 @@
 #include "Optimization.h"
 
 #include <algorithm>
-#include <unordered_map>
 
 #include "Camera.h"
 #include "Frame.h"
@@ -22,8 +21,6 @@
 namespace slam::optimization {
 
 namespace {
-constexpr size_t MIN_OBSERVATIONS_TO_OPTIMIZE = 2;
-
 void intrinsics(const Camera& camera, float K[4]) { rs_shim::intrinsics(camera.get_intrinsic_matrix(), K); }
 
 // imu::Preintegrated (Eigen, column-major) -> rs_imu_factor (row-major)
@@ -70,14 +67,8 @@ bool report(const char* what, const rs_ba_summary& s)
 bool refine_pose(Frame& frame, const Camera& camera, const InertialConstraint& inertial)
 {
     using namespace rs_shim;
-    std::vector<double> pts;
-    std::vector<float> uv;
-    for (const auto& m : frame.map_matches()) {
-        if (m.point.observations().size() < MIN_OBSERVATIONS_TO_OPTIMIZE) continue;
-        for (int k = 0; k < 3; k++) pts.push_back((double)m.point.position()[k]);
-        uv.push_back(frame.keypoint(m.keypoint_index).pt.x);
-        uv.push_back(frame.keypoint(m.keypoint_index).pt.y);
-    }
+    const rs_marshal::RefineArrays r = rs_marshal::flatten_refine(frame, Access{});
+    const std::vector<float>& uv = r.uv;
     if (uv.empty()) return false;
     float T[16], K[4];
     double cam[6];
@@ -85,7 +76,7 @@ bool refine_pose(Frame& frame, const Camera& camera, const InertialConstraint& i
     rs_pack_pose(T, cam);
     intrinsics(camera, K);
     Stage stage;
-    DevBuf<double> dp(pts);
+    DevBuf<double> dp(r.pts);
     DevBuf<float> duv(uv);
     rs_ba_summary s{};
     // the InertialConstraint (:231-258): an enabled InertialDelta wins over a RotationPrior, a disabled one is nothing
@@ -123,45 +114,15 @@ bool bundle_adjust(const std::vector<FrameConfig>& frames, const Camera& camera,
 {
     using namespace rs_shim;
     const size_t C = frames.size();
-    std::vector<double> cams(6 * C);
-    std::vector<uint8_t> cam_free(C);
-    for (size_t c = 0; c < C; c++) {
-        float T[16];
-        pose_to_row_major(frames[c].frame->pose(), T);
-        rs_pack_pose(T, &cams[6 * c]);
-        cam_free[c] = frames[c].optimize;
-    }
-    std::vector<MapPoint*> free_pts;
-    std::unordered_map<const MapPoint*, int> pid;
-    for (const auto& fc : frames) {
-        if (!fc.optimize) continue;
-        for (auto m : fc.frame->map_matches()) {
-            if (m.point.observations().size() < MIN_OBSERVATIONS_TO_OPTIMIZE) continue;
-            if (pid.emplace(&m.point, (int)free_pts.size()).second) free_pts.push_back(&m.point);
-        }
-    }
-    const size_t P = free_pts.size();
-    std::vector<std::vector<std::pair<int, cv::Point2f>>> per_point(P);
-    for (size_t c = 0; c < C; c++)
-        for (const auto& m : frames[c].frame->map_matches()) {
-            auto it = pid.find(&m.point);
-            if (it != pid.end()) per_point[it->second].emplace_back((int)c, frames[c].frame->keypoint(m.keypoint_index).pt);
-        }
-    std::vector<int32_t> obs_ptr(P + 1, 0), obs_cam;
-    std::vector<float> obs_uv;
-    std::vector<double> pts(3 * P);
-    for (size_t p = 0; p < P; p++) {
-        for (int k = 0; k < 3; k++) pts[3 * p + k] = (double)free_pts[p]->position()[k];
-        for (const auto& [c, px] : per_point[p]) { obs_cam.push_back(c); obs_uv.push_back(px.x); obs_uv.push_back(px.y); }
-        obs_ptr[p + 1] = (int32_t)obs_cam.size();
-    }
-    if (P == 0 || obs_cam.empty()) return false;
+    const auto b = rs_marshal::flatten_ba(frames, Access{});
+    const size_t P = b.free_pts.size();
+    if (P == 0 || b.obs_cam.empty()) return false;
     float K[4];
     intrinsics(camera, K);
     Stage stage;
-    DevBuf<double> dc(cams), dp(pts);
-    DevBuf<int32_t> dptr(obs_ptr), dcam(obs_cam);
-    DevBuf<float> duv(obs_uv);
+    DevBuf<double> dc(b.cams), dp(b.pts);
+    DevBuf<int32_t> dptr(b.obs_ptr), dcam(b.obs_cam);
+    DevBuf<float> duv(b.obs_uv);
     rs_ba_summary s{};
     // IMU factor pairs between consecutive optimised frames (:317-346); none when the input is not usable
     std::vector<rs_imu_factor> factors;
@@ -175,7 +136,7 @@ bool bundle_adjust(const std::vector<FrameConfig>& frames, const Camera& camera,
             factors.push_back(to_factor(imu::preintegrate(samples, inertial.noise, frames[i].frame->inertial().bias), inertial.noise, (int)i, (int)(i + 1)));
         }
     const double gravity[3] = {inertial.gravity[0], inertial.gravity[1], inertial.gravity[2]};
-    if (!ok(rs_bundle_adjust_inertial(context(), (int)C, (int)P, (int)obs_cam.size(), dc.p, cam_free.data(), dp.p, dptr.p, dcam.p, duv.p, K,
+    if (!ok(rs_bundle_adjust_inertial(context(), (int)C, (int)P, (int)b.obs_cam.size(), dc.p, b.cam_free.data(), dp.p, dptr.p, dcam.p, duv.p, K,
                                       velocity.data(), bias.data(), factors.data(), (int)factors.size(), gravity, nullptr, &s),
             "rs_bundle_adjust_inertial"))
         return false;
@@ -191,7 +152,7 @@ bool bundle_adjust(const std::vector<FrameConfig>& frames, const Camera& camera,
             frames[c].frame->set_pose(pose_from_row_major(T));
             unpack_inertial(&velocity[3 * c], &bias[6 * c], *frames[c].frame);      // :366 (unchanged values without factors)
         }
-    for (size_t p = 0; p < P; p++) free_pts[p]->set_position(Eigen::Vector3f((float)hp[3 * p], (float)hp[3 * p + 1], (float)hp[3 * p + 2]));
+    for (size_t p = 0; p < P; p++) b.free_pts[p]->set_position(Eigen::Vector3f((float)hp[3 * p], (float)hp[3 * p + 1], (float)hp[3 * p + 2]));
     return true;
 }
 
@@ -202,11 +163,11 @@ bool pose_graph(const std::vector<std::shared_ptr<KeyFrame>>& key_frames, const 
     if (key_frames.size() < 3 || loops.empty()) return false;                                           // :546-548
     const size_t n = key_frames.size();
     std::vector<float> before(16 * n), after(16 * n), r_delta(9 * n);
-    std::unordered_map<const Frame*, int32_t> slot;
-    slot.reserve(n);
+    rs_shim::PtrIndex slot(rs_shim::PtrIndex::FRAMES, n);
     for (size_t i = 0; i < n; i++) {
         rs_shim::pose_to_row_major(key_frames[i]->pose(), &before[16 * i]);
-        slot[key_frames[i].get()] = (int32_t)i;
+        bool fresh;
+        slot.find_or_insert(static_cast<const Frame*>(key_frames[i].get()), (int)i, &fresh);
     }
     std::vector<rs_pose_graph_edge> edges(loops.size());
     for (size_t l = 0; l < loops.size(); l++) {
@@ -237,11 +198,11 @@ bool pose_graph(const std::vector<std::shared_ptr<KeyFrame>>& key_frames, const 
         KeyFrame* owner = nullptr;
         for (const auto& [observer, _] : point.observations())
             if (owner == nullptr || observer->index() < owner->index()) owner = observer;
-        const auto it = slot.find(owner);
-        if (it == slot.end()) continue;
+        const int owner_index = slot.find(static_cast<const Frame*>(owner));
+        if (owner_index < 0) continue;
         const Eigen::Vector3f p = point.position();
         moved.push_back(&point);
-        owner_slot.push_back(it->second);
+        owner_slot.push_back(owner_index);
         positions.insert(positions.end(), {p[0], p[1], p[2]});
     }
     {

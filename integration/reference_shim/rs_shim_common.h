@@ -3,8 +3,10 @@
 // These files include the reference's own headers plus Eigen / OpenCV, none of which exists in this repository's build
 // image: they are the binding a maintainer of GregVS/Racing-SLAM adds to that tree.  Here they are
 // syntax-checked against the reference's real headers with stand-in Eigen / OpenCV declarations
-// (tests/test_shim_syntax.py), and the same marshalling is compiled, run and checked on plain types in
-// racing-slam_amd/host/slam_host.cpp.  The only dependency besides the reference tree is include/rsgpu.h.
+// (integration/check_shim_syntax.py, tests/test_shim_syntax.py).  The pointer graph -> SoA flattening is not theirs: it
+// is the templates of rs_marshal.h, the same source that racing-slam_amd/host/slam_host.cpp instantiates on plain types
+// and that is compiled, run, tested and timed there; `Access` below is how those templates read the reference's objects.
+// The only dependencies besides the reference tree are include/rsgpu.h and rs_marshal.h.
 #pragma once
 #include <Eigen/Dense>
 #include <cmath>
@@ -12,9 +14,14 @@
 #include <cstdlib>
 #include <vector>
 
+#include "Frame.h"
+#include "MapPoint.h"
+#include "rs_marshal.h"
 #include "rsgpu.h"
 
 namespace rs_shim {
+
+using rs_marshal::PtrIndex;
 
 inline rs_context* context()
 {
@@ -81,5 +88,39 @@ inline void intrinsics(const Eigen::Matrix3f& M, float K[4])
 {
     K[0] = M(0, 0); K[1] = M(1, 1); K[2] = M(0, 2); K[3] = M(1, 2);
 }
+
+// 32-byte ORB rows (or no rows at all): the only descriptor layout the Hamming kernels take
+inline bool orb_layout(const cv::Mat& d) { return d.empty() || (d.type() == CV_8U && d.cols == RS_DESC_BYTES && d.isContinuous()); }
+
+// How the flatten templates of rs_marshal.h read the reference's objects (Eigen / OpenCV).
+struct Access {
+    using Point = slam::MapPoint;
+    static void position(const slam::MapPoint& p, float out[3]) { for (int k = 0; k < 3; k++) out[k] = p.position()[k]; }
+    static void pose_row_major(const slam::Frame& f, float out[16]) { pose_to_row_major(f.pose(), out); }
+    static void center(const slam::Frame& f, float out[3]) { const Eigen::Vector3f c = f.camera_center(); out[0] = c.x(); out[1] = c.y(); out[2] = c.z(); }
+    static void keypoint(const slam::Frame& f, size_t i, float out[2]) { out[0] = f.keypoint(i).pt.x; out[1] = f.keypoint(i).pt.y; }
+    static bool descriptor_rows(const slam::Frame& f, const uint8_t*& rows, size_t& n_rows)
+    {
+        const cv::Mat& d = f.features().descriptors;            // N x 32 CV_8U, row-contiguous
+        if (!orb_layout(d)) return false;
+        rows = d.ptr<uint8_t>(0); n_rows = (size_t)d.rows;
+        return true;
+    }
+    static size_t n_matches(const slam::Frame& f) { return f.num_map_matches(); }
+    template <typename Fn>
+    static void for_each_match(const slam::Frame& f, Fn fn)
+    {
+        for (const auto& m : f.map_matches()) fn(m.point, m.keypoint_index);     // ascending keypoint index, src/Frame.cpp:154-174
+    }
+    template <typename Fn>
+    static void for_each_observation(const slam::MapPoint& p, Fn fn)
+    {
+        for (const auto& [kf, idx] : p.observations()) fn(kf, idx);
+    }
+    static size_t n_observations(const slam::MapPoint& p) { return p.observations().size(); }
+    static const void* observations_address(const slam::MapPoint& p) { return p.observations().empty() ? nullptr : &*p.observations().begin(); }
+    static bool is_matched(const slam::Frame& f, const slam::MapPoint& p) { return f.is_matched(p); }
+    static bool is_observed_by(const slam::MapPoint& p, slam::KeyFrame* kf) { return p.is_observed_by(kf); }
+};
 
 }  // namespace rs_shim

@@ -1,6 +1,7 @@
 // slam_host.cpp — marshalling of the host mirror (slam_host.h) onto the C-ABI of librsgpu.so.
 // Pointer graph -> SoA, upload, ONE C-ABI call per interface function, download.
 #include "slam_host.h"
+#include "../../integration/reference_shim/rs_marshal.h"
 
 #include <hip/hip_runtime_api.h>
 
@@ -77,76 +78,38 @@ bool rs_ok(int rc, const char* what)
 
 rs_ba_summary g_summary{};
 
-// Pointer -> dense index, for flattening the reference's pointer graph (MapPoint has no id: src/MapPoint.h:12-39).  Open
-// addressing over a power-of-two table of {key, value, generation} entries (one cache line per probe), multiplicative hash
-// of the address; the table is kept between calls and "cleared" by bumping the generation — std::unordered_map (a node per
-// entry, cleared and rebuilt per call) spent 50 - 100 ns per operation and build_local_window + bundle_adjust make ~10^5 of
-// them per key frame; allocating and zeroing a fresh 0.8 MB table per call cost another 0.2 ms.
-class PtrIndex {
-  public:
-    // a table for about `expected` distinct keys (it grows by itself beyond that)
-    explicit PtrIndex(std::vector<char>& storage, size_t expected) : m_store(storage)
+// How the flatten templates of rs_marshal.h read the mirror's objects (the shims' Access reads the reference's:
+// integration/reference_shim/rs_shim_common.h).  PtrIndex's tables are thread_local in that header: the flattening is
+// re-entrant across threads; the Session (one context, one staging pool) still serves one caller at a time.
+struct HostAccess {
+    using Point = MapPoint;
+    static void position(const MapPoint& p, float out[3]) { out[0] = p.position().x; out[1] = p.position().y; out[2] = p.position().z; }
+    static void pose_row_major(const Frame& f, float out[16]) { std::memcpy(out, f.pose().data(), 16 * sizeof(float)); }
+    static void center(const Frame& f, float out[3]) { const Vec3f c = f.camera_center(); out[0] = c.x; out[1] = c.y; out[2] = c.z; }
+    static void keypoint(const Frame& f, size_t i, float out[2]) { out[0] = f.keypoint(i).pt.x; out[1] = f.keypoint(i).pt.y; }
+    static bool descriptor_rows(const Frame& f, const uint8_t*& rows, size_t& n_rows)
     {
-        size_t cap = 64;
-        while (cap < 2 * expected + 2) cap <<= 1;
-        Header* h = header();
-        if (!h || h->cap < cap) {
-            m_store.assign(sizeof(Header) + cap * sizeof(Entry), 0);
-            h = header();
-            h->cap = cap; h->gen = 0;
-        }
-        if (++h->gen == 0) {                                   // generation wrapped: really clear
-            std::memset(entries(), 0, h->cap * sizeof(Entry));
-            h->gen = 1;
-        }
-        m_gen = h->gen; m_mask = h->cap - 1; m_e = entries(); m_used = 0;
+        rows = f.features().descriptors.data(); n_rows = f.features().descriptors.size() / RS_DESC_BYTES;
+        return true;
     }
-    // index of p, inserting it with value `fresh` if absent; *inserted says which
-    int find_or_insert(const void* p, int fresh, bool* inserted)
+    static size_t n_matches(const Frame& f) { return f.num_map_matches(); }
+    template <typename Fn>
+    static void for_each_match(const Frame& f, Fn fn)
     {
-        size_t h = slot(p);
-        while (m_e[h].gen == m_gen && m_e[h].key != p) h = (h + 1) & m_mask;
-        if (m_e[h].gen == m_gen) { *inserted = false; return m_e[h].val; }
-        m_e[h].key = p; m_e[h].val = fresh; m_e[h].gen = m_gen; *inserted = true;
-        if (2 * ++m_used > m_mask) grow();
-        return fresh;
+        const std::vector<MapPoint*>& tab = f.match_table();   // ascending keypoint index, as map_matches(): no list is built
+        for (size_t k = 0; k < tab.size(); k++)
+            if (tab[k]) fn(*tab[k], k);
     }
-    int find(const void* p) const
+    template <typename Fn>
+    static void for_each_observation(const MapPoint& p, Fn fn)
     {
-        size_t h = slot(p);
-        while (m_e[h].gen == m_gen && m_e[h].key != p) h = (h + 1) & m_mask;
-        return m_e[h].gen == m_gen ? m_e[h].val : -1;
+        for (const auto& o : p.observations()) fn(o.first, o.second);
     }
-
-  private:
-    struct Entry { const void* key; int val; unsigned gen; };
-    struct Header { size_t cap; unsigned gen; unsigned pad; };
-    Header* header() { return m_store.size() >= sizeof(Header) ? reinterpret_cast<Header*>(m_store.data()) : nullptr; }
-    Entry* entries() { return reinterpret_cast<Entry*>(m_store.data() + sizeof(Header)); }
-    size_t slot(const void* p) const { return (size_t)(((uintptr_t)p >> 4) * 0x9E3779B97F4A7C15ull >> 20) & m_mask; }
-    void grow()
-    {
-        std::vector<Entry> live;
-        for (size_t i = 0; i <= m_mask; i++)
-            if (m_e[i].gen == m_gen) live.push_back(m_e[i]);
-        const size_t cap = 2 * (m_mask + 1);
-        m_store.assign(sizeof(Header) + cap * sizeof(Entry), 0);
-        Header* h = header();
-        h->cap = cap; h->gen = 1;
-        m_gen = 1; m_mask = cap - 1; m_e = entries();
-        for (const Entry& e : live) {
-            size_t q = slot(e.key);
-            while (m_e[q].gen == m_gen) q = (q + 1) & m_mask;
-            m_e[q] = Entry{e.key, e.val, m_gen};
-        }
-    }
-    std::vector<char>& m_store;
-    Entry* m_e = nullptr;
-    size_t m_mask = 0, m_used = 0;
-    unsigned m_gen = 0;
+    static size_t n_observations(const MapPoint& p) { return p.observations().size(); }
+    static const void* observations_address(const MapPoint& p) { return p.observations().data(); }
+    static bool is_matched(const Frame& f, const MapPoint& p) { return f.is_matched(p); }
+    static bool is_observed_by(const MapPoint& p, const KeyFrame* kf) { return p.is_observed_by(kf); }
 };
-// storage of the tables, kept between calls (the callers are single-threaded: SURVEY.md 8b)
-std::vector<char> g_pid_store, g_fid_store;
 
 }  // namespace
 
@@ -279,42 +242,13 @@ std::vector<MapPointMatch> MapMatcher::match(const Frame& frame, const std::vect
         kp[2 * i] = frame.keypoint(i).pt.x; kp[2 * i + 1] = frame.keypoint(i).pt.y;
         matched[i] = frame.is_matched(i) ? 1 : 0;
     }
-    // map side: positions, eligibility (the pointer-set tests of :53, :121-123, :169), observation CSR,
-    // keyframe table and descriptor pool
-    std::vector<float> pos(3 * P), centers;
-    std::vector<uint8_t> eligible(P), pool;
-    std::vector<int32_t> obs_ptr(P + 1, 0), obs_kf, obs_desc;
-    std::unordered_map<const KeyFrame*, int> kf_id;
-    std::vector<int> kf_pool_off;
-    for (size_t p = 0; p < P; p++) {
-        const MapPoint* mp = points[p];
-        bool ok = mp != nullptr;
-        if (ok && frame.is_matched(*mp)) ok = false;
-        if (ok && required_observer && !mp->is_observed_by(required_observer)) ok = false;
-        eligible[p] = ok ? 1 : 0;
-        if (mp) { pos[3 * p] = mp->position().x; pos[3 * p + 1] = mp->position().y; pos[3 * p + 2] = mp->position().z; }
-        if (ok) {
-            for (const auto& o : mp->observations()) {
-                auto it = kf_id.find(o.first);
-                if (it == kf_id.end()) {
-                    it = kf_id.emplace(o.first, (int)kf_id.size()).first;
-                    const Vec3f c = o.first->camera_center();
-                    centers.insert(centers.end(), {c.x, c.y, c.z});
-                    kf_pool_off.push_back((int)(pool.size() / 32));
-                    const auto& d = o.first->features().descriptors;
-                    pool.insert(pool.end(), d.begin(), d.end());
-                }
-                obs_kf.push_back(it->second);
-                obs_desc.push_back(kf_pool_off[it->second] + (int)o.second);
-            }
-        }
-        obs_ptr[p + 1] = (int32_t)obs_kf.size();
-    }
+    // map side: positions, eligibility, observation CSR, keyframe table and descriptor pool
+    const rs_marshal::MatchArrays m = rs_marshal::flatten_match(frame, points, required_observer, HostAccess{});
     StageScope stage;
-    DevBuf<float> d_kp(kp), d_pos(pos), d_centers(centers);
-    DevBuf<uint8_t> d_desc(frame.features().descriptors), d_matched(matched), d_elig(eligible), d_pool(pool);
-    DevBuf<int32_t> d_nk(frame.kd_node_kp()), d_l(frame.kd_left()), d_r(frame.kd_right()), d_optr(obs_ptr), d_okf(obs_kf),
-        d_odesc(obs_desc);
+    DevBuf<float> d_kp(kp), d_pos(m.pos), d_centers(m.centers);
+    DevBuf<uint8_t> d_desc(frame.features().descriptors), d_matched(matched), d_elig(m.eligible), d_pool(m.pool);
+    DevBuf<int32_t> d_nk(frame.kd_node_kp()), d_l(frame.kd_left()), d_r(frame.kd_right()), d_optr(m.obs_ptr), d_okf(m.obs_kf),
+        d_odesc(m.obs_desc);
     rs_frame_view fv{};
     std::memcpy(fv.pose, frame.pose().data(), sizeof fv.pose);
     fv.fx = m_camera.fx(); fv.fy = m_camera.fy(); fv.cx = m_camera.cx(); fv.cy = m_camera.cy();
@@ -478,30 +412,15 @@ CullResult point_errors(const std::vector<MapPoint*>& points, const Camera& came
     const size_t P = points.size();
     if (P == 0) return out;
     rs_context* ctx = Session::get().ctx();
-    std::vector<float> pos(3 * P), uv, poses;
-    std::vector<int32_t> obs_ptr(P + 1, 0), obs_pose;
-    std::vector<const KeyFrame*> frames;                      // pose table: one entry per observing key frame
-    for (size_t p = 0; p < P; p++) {
-        const Vec3f& X = points[p]->position();
-        pos[3 * p] = X.x; pos[3 * p + 1] = X.y; pos[3 * p + 2] = X.z;
-        for (const auto& ob : points[p]->observations()) {
-            size_t f = 0;
-            while (f < frames.size() && frames[f] != ob.first) f++;
-            if (f == frames.size()) { frames.push_back(ob.first); poses.insert(poses.end(), ob.first->pose().begin(), ob.first->pose().end()); }
-            obs_pose.push_back((int32_t)f);
-            const Vec2f px = ob.first->keypoint(ob.second).pt;
-            uv.push_back(px.x); uv.push_back(px.y);
-        }
-        obs_ptr[p + 1] = (int32_t)obs_pose.size();
-    }
-    if (obs_pose.empty()) { out.mean_error.assign(P, 0.0f); return out; }
+    const rs_marshal::PointErrorArrays e = rs_marshal::flatten_point_errors(points, HostAccess{});
+    if (e.obs_pose.empty()) { out.mean_error.assign(P, 0.0f); return out; }
     StageScope stage;
-    DevBuf<float> d_pos(pos), d_uv(uv), d_poses(poses), d_mean(P);
-    DevBuf<int32_t> d_ptr(obs_ptr), d_op(obs_pose), d_idx(P), d_cnt(1);
+    DevBuf<float> d_pos(e.pos), d_uv(e.uv), d_poses(e.poses), d_mean(P);
+    DevBuf<int32_t> d_ptr(e.obs_ptr), d_op(e.obs_pose), d_idx(P), d_cnt(1);
     DevBuf<uint8_t> d_cull(P);
     DevBuf<double> d_sums(2);
     const float K[4] = {camera.fx(), camera.fy(), camera.cx(), camera.cy()};
-    if (!rs_ok(rs_point_errors(ctx, (int)P, d_pos.get(), d_ptr.get(), d_op.get(), d_uv.get(), d_poses.get(), (int)frames.size(), K,
+    if (!rs_ok(rs_point_errors(ctx, (int)P, d_pos.get(), d_ptr.get(), d_op.get(), d_uv.get(), d_poses.get(), e.n_poses, K,
                                max_mean_error, d_mean.get(), d_cull.get(), d_idx.get(), d_cnt.get(), d_sums.get()), "rs_point_errors"))
         return out;
     out.mean_error = d_mean.fetch(P);
@@ -526,18 +445,13 @@ const rs_ba_summary& last_summary() { return g_summary; }
 bool refine_pose(Frame& frame, const Camera& camera)
 {
     rs_context* ctx = Session::get().ctx();
-    std::vector<double> pts;
-    std::vector<float> uv;
-    for (const auto& m : frame.map_matches()) {
-        if (m.point.observations().size() < 2) continue;       // MIN_OBSERVATIONS_TO_OPTIMIZE, :98,:206
-        pts.insert(pts.end(), {m.point.position().x, m.point.position().y, m.point.position().z});
-        uv.insert(uv.end(), {frame.keypoint(m.keypoint_index).pt.x, frame.keypoint(m.keypoint_index).pt.y});
-    }
+    const rs_marshal::RefineArrays r = rs_marshal::flatten_refine(frame, HostAccess{});    // MIN_OBSERVATIONS_TO_OPTIMIZE, :98,:206
+    const std::vector<float>& uv = r.uv;
     if (uv.empty()) return false;                              // :227-229
     double cam[6];
     rs_pack_pose(frame.pose().data(), cam);
     StageScope stage;
-    DevBuf<double> dp(pts);
+    DevBuf<double> dp(r.pts);
     DevBuf<float> duv(uv);
     const float K[4] = {camera.fx(), camera.fy(), camera.cx(), camera.cy()};
     if (!rs_ok(rs_refine_pose(ctx, cam, dp.get(), duv.get(), (int)(uv.size() / 2), K, nullptr, &g_summary), "rs_refine_pose")) return false;
@@ -555,56 +469,15 @@ bool bundle_adjust(const std::vector<FrameConfig>& frames, const Camera& camera,
 {
     rs_context* ctx = Session::get().ctx();
     const size_t C = frames.size();
-    std::vector<double> cams(6 * C);
-    std::vector<uint8_t> cam_free(C);
-    for (size_t c = 0; c < C; c++) { rs_pack_pose(frames[c].frame->pose().data(), &cams[6 * c]); cam_free[c] = frames[c].optimize ? 1 : 0; }
-    // free points: matched by an optimised frame, >= 2 observations (:287-302), in first-seen order
-    std::vector<MapPoint*> free_pts;
-    std::vector<std::vector<MapPointMatch>> matches(C);          // (map_matches() builds a list: once per frame)
-    size_t n_matches = 0;
-    for (size_t c = 0; c < C; c++) { matches[c] = frames[c].frame->map_matches(); n_matches += matches[c].size(); }
-    PtrIndex pid(g_pid_store, n_matches / 2 + 16);
-    for (size_t c = 0; c < C; c++) {
-        if (!frames[c].optimize) continue;
-        for (const auto& m : matches[c]) {
-            if (m.point.observations().size() < 2) continue;
-            bool fresh = false;
-            pid.find_or_insert(&m.point, (int)free_pts.size(), &fresh);
-            if (fresh) free_pts.push_back(&m.point);
-        }
-    }
-    const size_t P = free_pts.size();
-    // residual blocks: every listed frame (free or fixed) x its matched free points (:304-315), CSR by point, frames in
-    // list order within a point: one pass resolves the matches to point ids, a count / prefix / fill builds the CSR
-    struct Hit { int point, cam; Vec2f uv; };
-    std::vector<Hit> hits;
-    hits.reserve(n_matches);
-    std::vector<int32_t> obs_ptr(P + 1, 0);
-    for (size_t c = 0; c < C; c++)
-        for (const auto& m : matches[c]) {
-            const int id = pid.find(&m.point);
-            if (id < 0) continue;
-            hits.push_back(Hit{id, (int)c, frames[c].frame->keypoint(m.keypoint_index).pt});
-            obs_ptr[(size_t)id + 1]++;
-        }
-    for (size_t p = 0; p < P; p++) obs_ptr[p + 1] += obs_ptr[p];
-    std::vector<int32_t> obs_cam(hits.size()), fill(obs_ptr.begin(), obs_ptr.end() - 1);
-    std::vector<float> obs_uv(2 * hits.size());
-    for (const Hit& h : hits) {                                  // (hits are in frame order: so is every point's slice)
-        const size_t o = (size_t)fill[(size_t)h.point]++;
-        obs_cam[o] = h.cam; obs_uv[2 * o] = h.uv.x; obs_uv[2 * o + 1] = h.uv.y;
-    }
-    std::vector<double> pts(3 * P);
-    for (size_t p = 0; p < P; p++) {
-        pts[3 * p] = free_pts[p]->position().x; pts[3 * p + 1] = free_pts[p]->position().y; pts[3 * p + 2] = free_pts[p]->position().z;
-    }
-    if (P == 0 || obs_cam.empty()) return false;
+    const auto b = rs_marshal::flatten_ba(frames, HostAccess{});
+    const size_t P = b.free_pts.size();
+    if (P == 0 || b.obs_cam.empty()) return false;
     StageScope stage;
-    DevBuf<double> dc(cams), dp(pts);
-    DevBuf<int32_t> dptr(obs_ptr), dcam(obs_cam);
-    DevBuf<float> duv(obs_uv);
+    DevBuf<double> dc(b.cams), dp(b.pts);
+    DevBuf<int32_t> dptr(b.obs_ptr), dcam(b.obs_cam);
+    DevBuf<float> duv(b.obs_uv);
     const float K[4] = {camera.fx(), camera.fy(), camera.cx(), camera.cy()};
-    if (!rs_ok(rs_bundle_adjust(ctx, (int)C, (int)P, (int)obs_cam.size(), dc.get(), cam_free.data(), dp.get(), dptr.get(), dcam.get(),
+    if (!rs_ok(rs_bundle_adjust(ctx, (int)C, (int)P, (int)b.obs_cam.size(), dc.get(), b.cam_free.data(), dp.get(), dptr.get(), dcam.get(),
                                 duv.get(), K, nullptr, &g_summary), "rs_bundle_adjust"))
         return false;
     std::printf("bundle_adjust: iterations %d, cost %.6e -> %.6e, termination %d\n", g_summary.iterations,
@@ -615,7 +488,7 @@ bool bundle_adjust(const std::vector<FrameConfig>& frames, const Camera& camera,
     const auto hp = dp.download(3 * P);
     for (size_t c = 0; c < C; c++)
         if (frames[c].optimize) { Mat4f T; rs_unpack_pose(&hc[6 * c], T.data()); frames[c].frame->set_pose(T); }   // :363-368
-    for (size_t p = 0; p < P; p++) free_pts[p]->set_position(Vec3f{(float)hp[3 * p], (float)hp[3 * p + 1], (float)hp[3 * p + 2]});
+    for (size_t p = 0; p < P; p++) b.free_pts[p]->set_position(Vec3f{(float)hp[3 * p], (float)hp[3 * p + 1], (float)hp[3 * p + 2]});
     return true;
 }
 
@@ -624,49 +497,12 @@ std::vector<FrameConfig> build_local_window(const std::vector<std::shared_ptr<Ke
                                             size_t window_size, bool fix_oldest)
 {
     const int n = (int)key_frames.size();
-    int new_index = -1;
-    PtrIndex fid(g_fid_store, (size_t)n);
-    size_t n_matches = 0;
-    for (int i = 0; i < n; i++) {
-        bool fresh;
-        fid.find_or_insert(static_cast<const Frame*>(key_frames[(size_t)i].get()), i, &fresh);
-        if (key_frames[(size_t)i].get() == &new_frame) new_index = i;
-        n_matches += key_frames[(size_t)i]->num_map_matches();
-    }
-    PtrIndex pid(g_pid_store, (n_matches + new_frame.num_map_matches()) / 2 + 16);
-    std::vector<const MapPoint*> pts;
-    std::vector<int32_t> frame_ptr((size_t)n + 2, 0), frame_pt;
-    frame_pt.reserve(n_matches + new_frame.num_map_matches());
-    auto add_frame = [&](const Frame& f, int slot) {
-        const std::vector<MapPoint*>& tab = f.match_table();   // ascending keypoint index, as map_matches()
-        for (size_t k = 0; k < tab.size(); k++) {
-            const MapPoint* mp = tab[k];
-            if (!mp) continue;
-            bool fresh = false;
-            const int id = pid.find_or_insert(mp, (int)pts.size(), &fresh);
-            if (fresh) pts.push_back(mp);
-            frame_pt.push_back(id);
-        }
-        frame_ptr[(size_t)slot + 1] = (int32_t)frame_pt.size();
-    };
-    for (int i = 0; i < n; i++) add_frame(*key_frames[(size_t)i], i);
-    if (new_index < 0) add_frame(new_frame, n); else frame_ptr[(size_t)n + 1] = frame_ptr[(size_t)n];
-    std::vector<int32_t> pt_ptr(pts.size() + 1, 0), pt_obs;
-    pt_obs.reserve(frame_pt.size());
-    for (size_t p = 0; p < pts.size(); p++) {
-        if (p + 8 < pts.size()) __builtin_prefetch(pts[p + 8]);                   // (the points are scattered heap objects)
-        if (p + 4 < pts.size()) __builtin_prefetch(pts[p + 4]->observations().data());
-        for (const auto& o : pts[p]->observations()) {
-            const int f = fid.find(static_cast<const Frame*>(o.first));
-            if (f >= 0) pt_obs.push_back(f);
-        }
-        pt_ptr[p + 1] = (int32_t)pt_obs.size();
-    }
+    const rs_marshal::WindowArrays w = rs_marshal::flatten_local_window(key_frames, new_frame, HostAccess{});
     std::vector<int32_t> of((size_t)n + 1);
     std::vector<uint8_t> oo((size_t)n + 1);
     int32_t cnt = 0;
-    if (rs_build_local_window(n, new_index, (int)window_size, fix_oldest ? 1 : 0, frame_ptr.data(), frame_pt.data(), pt_ptr.data(),
-                              pt_obs.data(), of.data(), oo.data(), &cnt) != RS_OK)
+    if (rs_build_local_window(n, w.new_index, (int)window_size, fix_oldest ? 1 : 0, w.frame_ptr.data(), w.frame_pt.data(), w.pt_ptr.data(),
+                              w.pt_obs.data(), of.data(), oo.data(), &cnt) != RS_OK)
         return {};
     std::vector<FrameConfig> out;
     for (int i = 0; i < cnt; i++) {

@@ -4,7 +4,6 @@ loader round trip; and the new symbols of the C ABI without a GPU."""
 import ctypes as C
 import importlib
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -12,8 +11,9 @@ import pytest
 
 import bow_ref as B
 
+from host_build import build_host_binary
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "host_cpp", "test_bow_host.bin")
 SYMBOLS = ("rs_vocabulary_create", "rs_vocabulary_load_text", "rs_vocabulary_info", "rs_vocabulary_arrays", "rs_vocabulary_destroy",
            "rs_bow_create", "rs_bow_destroy", "rs_bow_transform", "rs_bow_download", "rs_bow_database_create",
            "rs_bow_database_destroy", "rs_bow_database_add", "rs_bow_database_score", "rs_bow_database_counts",
@@ -21,16 +21,7 @@ SYMBOLS = ("rs_vocabulary_create", "rs_vocabulary_load_text", "rs_vocabulary_inf
 
 
 def build_bow_host(rs):
-    rs.load()
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    srcs = [os.path.join(ROOT, "tests", "host_cpp", "test_bow_host.cpp"), os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.cpp")]
-    deps = srcs + [os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.h"), os.path.join(ROOT, "include", "rsgpu.h"),
-                   os.path.join(ROOT, "racing-slam_amd", "librsgpu.so")]
-    if os.path.exists(BIN) and all(os.path.getmtime(d) <= os.path.getmtime(BIN) for d in deps):
-        return BIN
-    subprocess.check_call([hipcc, "-O2", "-std=c++17", "-Wall", "-o", BIN] + srcs + [
-        "-L" + os.path.join(ROOT, "racing-slam_amd"), "-lrsgpu", "-Wl,-rpath," + os.path.join(ROOT, "racing-slam_amd"), "-lm"])
-    return BIN
+    return build_host_binary(rs, "test_bow_host")
 
 
 def test_library_exports_the_bow_symbols(rs):

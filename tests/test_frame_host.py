@@ -4,27 +4,18 @@ compares, over two video frames, the session's frame with rs_frame_create on the
 rs_frame_download and equal rs_map_match results."""
 import importlib
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from host_build import build_host_binary
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "host_cpp", "test_frame_host.bin")
 
 
 def build_frame_host(rs):
-    rs.load()
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    srcs = [os.path.join(ROOT, "tests", "host_cpp", "test_frame_host.cpp"), os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.cpp")]
-    deps = srcs + [os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.h"), os.path.join(ROOT, "include", "rsgpu.h"),
-                   os.path.join(ROOT, "racing-slam_amd", "librsgpu.so")]
-    if os.path.exists(BIN) and all(os.path.getmtime(d) <= os.path.getmtime(BIN) for d in deps):
-        return BIN
-    subprocess.check_call([hipcc, "-O2", "-std=c++17", "-Wall", "-o", BIN] + srcs + [
-        "-L" + os.path.join(ROOT, "racing-slam_amd"), "-lrsgpu", "-Wl,-rpath," + os.path.join(ROOT, "racing-slam_amd"), "-lm"])
-    return BIN
+    return build_host_binary(rs, "test_frame_host")
 
 
 def test_frame_host_mirror_compiles(rs):

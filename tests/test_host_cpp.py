@@ -6,43 +6,19 @@ import subprocess
 
 import pytest
 
+from host_build import build_host_binary
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "host_cpp", "test_host.bin")
 
 
 def build_host_test(rs, oracle):
-    rs.load()
-    oracle.lib()
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    srcs = [os.path.join(ROOT, "tests", "host_cpp", "test_host.cpp"), os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.cpp")]
-    deps = srcs + [os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.h"), os.path.join(ROOT, "include", "rsgpu.h"),
-                   os.path.join(ROOT, "racing-slam_amd", "librsgpu.so"), os.path.join(ROOT, "oracle", "liboracle.so")]
-    if os.path.exists(BIN) and all(os.path.getmtime(d) <= os.path.getmtime(BIN) for d in deps):
-        return BIN
-    cmd = [hipcc, "-O2", "-std=c++17", "-Wall", "-o", BIN] + srcs + [
-        "-L" + os.path.join(ROOT, "racing-slam_amd"), "-lrsgpu", "-L" + os.path.join(ROOT, "oracle"), "-loracle",
-        "-Wl,-rpath," + os.path.join(ROOT, "racing-slam_amd"), "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lm"]
-    subprocess.check_call(cmd)
-    return BIN
-
-
-BENCH_BIN = os.path.join(ROOT, "tests", "host_cpp", "bench_boundary.bin")
+    return build_host_binary(rs, "test_host", oracle)
 
 
 def build_boundary_bench(rs):
     """tests/host_cpp/bench_boundary.cpp: the caller's view of the drop-in (host objects in, host results out), timed.
     No oracle in it: it is a measurement of the product path (bench.py --boundary runs it)."""
-    rs.load()
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    srcs = [os.path.join(ROOT, "tests", "host_cpp", "bench_boundary.cpp"), os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.cpp")]
-    deps = srcs + [os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.h"), os.path.join(ROOT, "include", "rsgpu.h"),
-                   os.path.join(ROOT, "racing-slam_amd", "librsgpu.so")]
-    if os.path.exists(BENCH_BIN) and all(os.path.getmtime(d) <= os.path.getmtime(BENCH_BIN) for d in deps):
-        return BENCH_BIN
-    cmd = [hipcc, "-O2", "-std=c++17", "-Wall", "-o", BENCH_BIN] + srcs + [
-        "-L" + os.path.join(ROOT, "racing-slam_amd"), "-lrsgpu", "-Wl,-rpath," + os.path.join(ROOT, "racing-slam_amd"), "-lm"]
-    subprocess.check_call(cmd)
-    return BENCH_BIN
+    return build_host_binary(rs, "bench_boundary")
 
 
 def test_host_mirror_compiles_and_links(rs, oracle):

@@ -2,30 +2,21 @@
 rs_loop_update_streak against the restatement tests/loop_ref.py, over scripted query sequences.  No GPU."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 
 import loop_ref as L
 
+from host_build import build_host_binary
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "host_cpp", "test_loop_host.bin")
 SYMBOLS = ("rs_loop_verifier_create", "rs_loop_verifier_destroy", "rs_map_verify_loop", "rs_loop_verifier_download",
            "rs_loop_best_candidate", "rs_loop_update_streak")
 
 
 def build_loop_host(rs):
-    rs.load()
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    srcs = [os.path.join(ROOT, "tests", "host_cpp", "test_loop_host.cpp"), os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.cpp")]
-    deps = srcs + [os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.h"), os.path.join(ROOT, "include", "rsgpu.h"),
-                   os.path.join(ROOT, "racing-slam_amd", "librsgpu.so")]
-    if os.path.exists(BIN) and all(os.path.getmtime(d) <= os.path.getmtime(BIN) for d in deps):
-        return BIN
-    subprocess.check_call([hipcc, "-O2", "-std=c++17", "-Wall", "-o", BIN] + srcs + [
-        "-L" + os.path.join(ROOT, "racing-slam_amd"), "-lrsgpu", "-Wl,-rpath," + os.path.join(ROOT, "racing-slam_amd"), "-lm"])
-    return BIN
+    return build_host_binary(rs, "test_loop_host")
 
 
 def V(ok, inliers, pose=None):

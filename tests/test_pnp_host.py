@@ -4,7 +4,6 @@ symbols of the C ABI without a GPU."""
 import ctypes as C
 import importlib
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -12,23 +11,15 @@ import pytest
 
 import pnp_ref as P
 
+from host_build import build_host_binary
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "host_cpp", "test_pnp_host.bin")
 SYMBOLS = ("rs_pnp_estimator_create", "rs_pnp_estimator_destroy", "rs_estimate_pose_pnp", "rs_pnp_estimator_stats",
            "rs_pnp_hypotheses")
 
 
 def build_pnp_host(rs):
-    rs.load()
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    srcs = [os.path.join(ROOT, "tests", "host_cpp", "test_pnp_host.cpp"), os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.cpp")]
-    deps = srcs + [os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.h"), os.path.join(ROOT, "include", "rsgpu.h"),
-                   os.path.join(ROOT, "racing-slam_amd", "librsgpu.so")]
-    if os.path.exists(BIN) and all(os.path.getmtime(d) <= os.path.getmtime(BIN) for d in deps):
-        return BIN
-    subprocess.check_call([hipcc, "-O2", "-std=c++17", "-Wall", "-o", BIN] + srcs + [
-        "-L" + os.path.join(ROOT, "racing-slam_amd"), "-lrsgpu", "-Wl,-rpath," + os.path.join(ROOT, "racing-slam_amd"), "-lm"])
-    return BIN
+    return build_host_binary(rs, "test_pnp_host")
 
 
 def test_library_exports_the_pnp_symbols(rs):

@@ -3,7 +3,6 @@ mirror of the reference's src/PoseEstimation.h — built against librsgpu and ch
 tests/essential_ref.py, including the reference's std::mt19937(0) pairs of the known-rotation form."""
 import importlib
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -11,21 +10,13 @@ import pytest
 
 import essential_ref as R
 
+from host_build import build_host_binary
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "host_cpp", "test_pose_host.bin")
 
 
 def build_pose_host(rs):
-    rs.load()
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    srcs = [os.path.join(ROOT, "tests", "host_cpp", "test_pose_host.cpp"), os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.cpp")]
-    deps = srcs + [os.path.join(ROOT, "racing-slam_amd", "host", "slam_host.h"), os.path.join(ROOT, "include", "rsgpu.h"),
-                   os.path.join(ROOT, "racing-slam_amd", "librsgpu.so")]
-    if os.path.exists(BIN) and all(os.path.getmtime(d) <= os.path.getmtime(BIN) for d in deps):
-        return BIN
-    subprocess.check_call([hipcc, "-O2", "-std=c++17", "-Wall", "-o", BIN] + srcs + [
-        "-L" + os.path.join(ROOT, "racing-slam_amd"), "-lrsgpu", "-Wl,-rpath," + os.path.join(ROOT, "racing-slam_amd"), "-lm"])
-    return BIN
+    return build_host_binary(rs, "test_pose_host")
 
 
 def mt19937_pairs(n, iterations=200):
