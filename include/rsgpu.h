@@ -546,7 +546,9 @@ int rs_triangulate_matches_batch(rs_context* ctx, int batch,
  *     :277-288;
  * then the selection :291-304: candidates with parallax <= required in track order, and, while
  * fewer than min_new_points, the remaining candidates by parallax cosine ascending (ties: track
- * order; std::sort leaves them unspecified upstream).
+ * order; std::sort leaves them unspecified upstream).  A NaN cosine (a non-finite pixel: every gate
+ * is a comparison that NaN fails, so the track is a candidate with a NaN point) sorts after every
+ * number, NaN among NaN in track order: the key is a total order, where std::sort's `<` is none.
  * Outputs, all device: d_status[t] 0 none / 1 candidate / 2 inconsistent; d_xyz[t][3];
  * d_parallax_cos[t]; d_required_cos[t]; d_accepted[0..counts[0]) track indices in creation order
  * (the last counts[1] of them are the top-up); d_inconsistent[0..counts[2]); d_counts[3].

@@ -12,7 +12,8 @@
  * requirement min(cos 1 deg, cos(0.2 * turned)), :277-288.  Then the selection :291-304:
  * every candidate at or below its requirement, in order; if fewer than the quota (100), the
  * rest sorted by parallax cosine ascending tops it up.  The reference sorts with std::sort
- * (order of equal cosines unspecified); here ties keep candidate order.
+ * (order of equal cosines unspecified, and no order at all with a NaN among them); here ties keep
+ * candidate order and a NaN cosine sorts after every number (the order rs_triangulate_tracks documents).
  * The host-side filters of :247-250 (key point already matched, empty track) arrive as `skip`.
  * float math: Eigen expressions restated operation by operation as in triangulate.c /
  * reproj_match.c; acosf / cosf are libm's (the GPU's differ in the last ulp: DESIGN.md §2). */
@@ -147,11 +148,14 @@ int orc_triangulate_tracks(int n_tracks, const float* track_uv, const uint8_t* s
         }
         int top = 0;
         if (na < min_new_points && nr > 0) {
-            /* stable insertion sort by parallax cosine ascending (ties keep candidate order) */
+            /* stable insertion sort by the total order of rs_triangulate_tracks: parallax cosine ascending, a NaN
+             * cosine after every number, ties (and NaN among NaN) in candidate order.  A bare `>` is no order
+             * once a NaN is among the keys: it would leave the NaN candidate wherever it stood. */
             for (int i = 1; i < nr; i++) {
                 const int32_t v = rej[i];
+                const float kv = parallax_cos[v];
                 int j = i - 1;
-                while (j >= 0 && parallax_cos[rej[j]] > parallax_cos[v]) { rej[j + 1] = rej[j]; j--; }
+                while (j >= 0 && (parallax_cos[rej[j]] > kv || (isnan(parallax_cos[rej[j]]) && !isnan(kv)))) { rej[j + 1] = rej[j]; j--; }
                 rej[j + 1] = v;
             }
             top = min_new_points - na < nr ? min_new_points - na : nr;
