@@ -746,6 +746,92 @@ int rs_map_cull_points(rs_context* ctx, rs_map* map, const int32_t* h_kfs, int n
                        float max_mean_error, int apply, int32_t* h_removed, float* h_removed_xyz, int capacity,
                        int* h_n_removed, int* h_n_local);
 
+/* ---- Mapper::fuse_loop (src/Mapper.cpp:41-77,176-220) on the resident map: after rs_map_verify_loop accepted a candidate
+ * and rs_map_pose_graph moved the map, the duplicated points are fused; rs_map_bundle_adjust with the oldest window frame
+ * fixed follows (Mapper::bundle_adjust(query, true)).
+ *
+ * Two orders that the reference leaves unspecified are fixed here:
+ *   source order       the old points compete for a keypoint in ascending point slot (map order), earliest wins (the
+ *                      reference builds its list from an unordered_set);
+ *   covisible ranking  shared count descending, key-frame handle ascending (the reference sorts an unordered_map by count).
+ * Agreement with a particular standard library is not claimed.
+ *
+ * Outcome of one (keypoint, point) entry, by Mapper::fuse_match's branches: */
+enum {
+    RS_FUSE_SKIPPED = 0,        /* keypoint outside the key frame, or the point is dead or unknown: a no-op (the reference
+                                   would follow a dangling pointer) */
+    RS_FUSE_ASSOCIATED = 1,     /* the keypoint was free: the point is associated with it */
+    RS_FUSE_POINT_MATCHED = 2,  /* the keypoint was free but the key frame already matches the point */
+    RS_FUSE_SAME = 3,           /* the keypoint already holds that point */
+    RS_FUSE_OLD = 4,            /* the keypoint's point is an old point: nothing is fused */
+    RS_FUSE_FUSED = 5           /* the keypoint's point was fused into the entry's point and removed */
+};
+/* Map::fuse (src/Map.cpp:78-95): every observation of `discarded`, in its insertion order, moves to `kept` unless the
+ * observer already sees `kept`; `discarded` hands over its track-consistent flag and is removed.  Host only, O(observations).
+ * kept == discarded is a no-op.  RS_ERR_INVALID: a dead or unknown slot. */
+int rs_map_fuse_points(rs_map* map, int kept, int discarded);
+/* Diagnostics, host only.  The observations of a point slot as (key frame, keypoint) in INSERTION order — the order the
+ * viewing normal is summed in — and a key frame's keypoint -> point table (-1 = unmatched).  *h_n = how many there are;
+ * the first min(*h_n, capacity) are copied (the arrays may be NULL with capacity 0).  A removed slot has no observations.
+ * RS_ERR_INVALID: a slot the map never had / an unknown key frame, a null count. */
+int rs_map_get_observations(const rs_map* map, int point, int32_t* h_kf, int32_t* h_kp, int capacity, int* h_n);
+int rs_map_get_keyframe_matches(const rs_map* map, int kf, int32_t* h_kp_point, int capacity, int* h_n);
+
+#define RS_FUSE_MAX_WINDOW 64
+#define RS_FUSE_MAX_COVISIBLE 64
+#define RS_FUSE_MAX_INLIERS 8192
+typedef struct rs_fuse_options {
+    float intrinsics[4];        /* fx fy cx cy */
+    int width, height;
+    int max_distance;           /* descriptor gate of match_for_fuse; the reference's extractor: 64 */
+    int min_shared;             /* MIN_LOOP_COVISIBLE = 15 */
+    int max_covisible;          /* LOOP_COVISIBLE_KFS = 20; 0 .. RS_FUSE_MAX_COVISIBLE */
+    int check;                  /* 1: refuse (RS_ERR_INTERNAL, map unchanged) a map whose tables and observation lists disagree;
+                                   compare the device's old frames with the host ranking and the device's final working
+                                   state with the replayed mirror (one more read-back) */
+    int32_t* h_sources; int capacity_sources;       /* optional (NULL): receives the sources, ascending slot (first capacity) */
+    int32_t* h_removed; int capacity_removed;       /* optional (NULL): receives the removed slots in the order they were fused */
+} rs_fuse_options;
+typedef struct rs_fuse_report {
+    int n_old_frames;                               /* 1 + covisibles */
+    int32_t old_frames[RS_FUSE_MAX_COVISIBLE + 1];  /* the candidate first, then by rank */
+    int n_sources;                                  /* old points = the sources of match_for_fuse */
+    int outcomes[6];                                /* entries per RS_FUSE_* outcome, inliers and window together */
+    int n_removed;                                  /* fused-away points (= outcomes[RS_FUSE_FUSED]) */
+    int device_state_mismatches;                    /* check = 1: differing words; -1 = not checked */
+} rs_fuse_report;                                   /* outputs only: the call writes every field and reads none */
+/* Mapper::fuse_loop.  h_inlier_kp / h_inlier_point [n_inliers]: rs_loop_verifier_download's inlier list (keypoint of the
+ * query, point slot).  h_window_kfs [n_window]: the caller's bundle-adjustment window in its order (the policy `first = size -
+ * BA_WINDOW` stays with the caller, as in rs_map_cull_points).
+ *   1  prologue on the device image: shared counts per key frame (one lane per candidate keypoint walks its point's
+ *      observation row), the ranking above in one workgroup, a flag per point slot from the old frames' table rows, the
+ *      sources by one ordered compaction; read-back 1: the old frames and the number of sources S.
+ *   2  the inliers, on the host mirror, in list order (each an O(1) edit).
+ *   3  per window key frame that is not an old frame, in order, with no host synchronisation between frames: its KD-tree
+ *      from its pool keypoints, the sources' eligibility from the CURRENT source rows, rs_reproj_match (replace = 1) on the
+ *      source view, then the fuses of the accepted matches applied to the device's working state (source observation rows
+ *      rebuilt dense by count / scan / copy / append into the other of two buffers; the key-frame tables; an alive copy).
+ *      Appended observations keep the discarded point's observation order.
+ *   4  read-back 2: the accepted (keypoint, point) pairs of every frame.  The mirror replays them and recomputes every
+ *      outcome; the image is re-flattened at its next use, as after every edit.
+ * So: two synchronisations per call plus the map's lazy upload (twice when the inliers edited the map); a third read-back
+ * with options->check.  Scratch is allocated on first use at a given size and kept: the first call at a size also
+ * synchronises where it allocates (its scratch, rs_reproj_match's proposal table), and the staging pool is drained once
+ * between stage 1 and stage 3; none of this lies between two window frames.
+ * Journal (each array optional, NULL = not wanted): section 0 = the inliers, section 1 + w = window entry w (empty for an old
+ * frame); h_section_ptr [n_window + 2]; entry e = (h_kp[e], h_point[e], h_outcome[e]).  *h_n_entries = the total; when
+ * capacity is smaller the first `capacity` entries are copied and the map is edited all the same.
+ * Envelope: key frames (query, candidate, window) of at most 8192 keypoints, n_window 0 .. RS_FUSE_MAX_WINDOW, max_covisible
+ * 0 .. RS_FUSE_MAX_COVISIBLE, n_inliers 0 .. RS_FUSE_MAX_INLIERS; outside it RS_ERR_UNSUPPORTED.  RS_ERR_INVALID with the
+ * map unchanged: an unknown key frame, a key frame listed twice in the window, a null argument, a map of another context.
+ * Every argument check runs before the first edit or launch. */
+int rs_map_fuse_loop(rs_context* ctx, rs_map* map, int query_kf, int candidate_kf,
+                     const int32_t* h_inlier_kp, const int32_t* h_inlier_point, int n_inliers,
+                     const int32_t* h_window_kfs, int n_window,
+                     const rs_fuse_options* options, rs_fuse_report* report,
+                     int32_t* h_section_ptr, int32_t* h_kp, int32_t* h_point, int32_t* h_outcome, int capacity,
+                     int* h_n_entries);
+
 /* Throughput mode: B INDEPENDENT windows (several sessions / maps served by one GPU) in one call.  A local-window
  * solve is a chain of small dependent launches that leaves most of the 256 CUs idle.
  *   grid mode (default)  every kernel of the solve runs ONCE for all windows (grid z = window, per-window arguments in a

@@ -40,6 +40,7 @@ SOURCES = [
     ("ba_round.hip", ["-munsafe-fp-atomics"]),
     ("map.hip", []),
     ("map_keyframe.hip", ["-ffp-contract=off"]),
+    ("map_fuse.hip", []),
     ("frame.hip", ["-ffp-contract=off"]),
     ("frame_matches.hip", ["-ffp-contract=off"]),
     ("track_store.hip", ["-ffp-contract=off"]),

@@ -129,6 +129,25 @@ rs_context* rs_map_context(const rs_map* m);
 // key frame kf of the mirror: keypoints, first pool row, keypoints with a map match; false = no such key frame
 bool rs_map_loop_keyframe(const rs_map* m, int kf, int* n, int* pool_row, int* n_matched);
 
+// What map_fuse.hip reads and writes of an rs_map (map.hip: rs_map_fuse_sync).  The image's key-frame tables are the fuse's working
+// tables: the caller marks them dirty before its first launch.
+struct MapMirror;
+struct rs_map_fuse_view {
+    rs_context* ctx = nullptr;
+    MapMirror* mirror = nullptr;
+    void** scratch = nullptr;               // rs_map::fuse
+    const float* d_pos = nullptr; const uint8_t* d_alive = nullptr;
+    const int32_t *d_obs_ptr = nullptr, *d_obs_kf = nullptr, *d_obs_desc = nullptr;
+    const float* d_centres = nullptr; const uint8_t* d_pool = nullptr; const float* d_kp_pool = nullptr;
+    int32_t* d_kp_point = nullptr;
+    size_t n_obs = 0, pool_rows = 0;
+};
+int rs_map_fuse_sync(rs_map* m, int sync, rs_map_fuse_view* out);
+void rs_map_fuse_release(void* scratch);      // map_fuse.hip
+// frame.hip: a device-built frame refilled from n keypoints / descriptor rows on the device, n known to the host (d_count[0] == n):
+// the three launches of rs_frame_assign_device without its synchronisation
+int rs_frame_assign_enqueue(rs_context* ctx, rs_frame* f, const float* d_pt, const int32_t* d_count, const uint8_t* d_desc, int n);
+
 // What frame_matches.hip reads and writes of an rs_map (map.hip: rs_map_track_sync brings the device image up to date first).
 struct rs_map_track_view {
     int n_kf = 0;                           // key frames

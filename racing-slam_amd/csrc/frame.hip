@@ -202,6 +202,33 @@ extern "C" int rs_frame_create_device(rs_context* ctx, int max_points, rs_frame*
     return RS_OK;
 }
 
+// the three launches of an assign on the context stream; rank tiles cover the first rank_n keypoints (cap when n is on the device only)
+static int frame_enqueue(rs_context* ctx, rs_frame* f, const float* d_pt_a, const int32_t* d_count_a, const float* d_pt_b,
+                         const int32_t* d_count_b, const uint8_t* d_desc, int rank_n)
+{
+    hipStream_t s = ctx->stream;
+    const int cap = f->cap;
+    {
+        rs_prof_scope ps(ctx, "KF_frame_gather");
+        hipLaunchKernelGGL(k_frame_gather, dim3((2 * cap + 255) / 256), dim3(256), 0, s, cap, (const uint32_t*)d_pt_a, d_count_a,
+                           (const uint32_t*)d_pt_b, d_count_b, d_desc, ((uintptr_t)d_desc & 15) == 0 ? 1 : 0, (uint32_t*)f->d_kp, f->d_desc,
+                           f->d_rank, f->d_n, f->d_kp_point);
+    }
+    if (rank_n > 0) {
+        rs_prof_scope ps(ctx, "KF_frame_rank");
+        const int tiles = (rank_n + 255) / 256;
+        hipLaunchKernelGGL(k_frame_rank, dim3(tiles, tiles), dim3(256), 0, s, f->d_n, (const uint32_t*)f->d_kp, f->d_rank);
+    }
+    {
+        rs_prof_scope ps(ctx, "KF_frame_build");
+        const size_t lds = frame_build_lds(cap);
+        if (lds > 48 * 1024) RS_HIP(ctx, rs_lds_attr((const void*)k_frame_build, lds));
+        hipLaunchKernelGGL(k_frame_build, dim3(1), dim3(FB_THREADS), lds, s, f->d_n, f->d_rank, (const uint2*)f->d_kp, f->d_kd, (uint4*)f->d_packed);
+    }
+    RS_HIP(ctx, hipGetLastError());
+    return RS_OK;
+}
+
 extern "C" int rs_frame_assign_device(rs_context* ctx, rs_frame* f, const float* d_pt_a, const int32_t* d_count_a, const float* d_pt_b,
                                       const int32_t* d_count_b, const uint8_t* d_desc, int* h_n)
 {
@@ -213,25 +240,9 @@ extern "C" int rs_frame_assign_device(rs_context* ctx, rs_frame* f, const float*
     RS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const int cap = f->cap;
-    {
-        rs_prof_scope ps(ctx, "KF_frame_gather");
-        hipLaunchKernelGGL(k_frame_gather, dim3((2 * cap + 255) / 256), dim3(256), 0, s, cap, (const uint32_t*)d_pt_a, d_count_a,
-                           (const uint32_t*)d_pt_b, d_count_b, d_desc, ((uintptr_t)d_desc & 15) == 0 ? 1 : 0, (uint32_t*)f->d_kp, f->d_desc,
-                           f->d_rank, f->d_n, f->d_kp_point);
-    }
+    const int rc = frame_enqueue(ctx, f, d_pt_a, d_count_a, d_pt_b, d_count_b, d_desc, cap);
+    if (rc) return rc;
     RS_HIP(ctx, hipMemcpyAsync(f->h_n, f->d_n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    {
-        rs_prof_scope ps(ctx, "KF_frame_rank");
-        const int tiles = (cap + 255) / 256;
-        hipLaunchKernelGGL(k_frame_rank, dim3(tiles, tiles), dim3(256), 0, s, f->d_n, (const uint32_t*)f->d_kp, f->d_rank);
-    }
-    {
-        rs_prof_scope ps(ctx, "KF_frame_build");
-        const size_t lds = frame_build_lds(cap);
-        if (lds > 48 * 1024) RS_HIP(ctx, rs_lds_attr((const void*)k_frame_build, lds));
-        hipLaunchKernelGGL(k_frame_build, dim3(1), dim3(FB_THREADS), lds, s, f->d_n, f->d_rank, (const uint2*)f->d_kp, f->d_kd, (uint4*)f->d_packed);
-    }
-    RS_HIP(ctx, hipGetLastError());
     // the one host synchronisation: rs_map_match sizes its launches and rs_map_add_keyframe books pool rows by the host-side n
     RS_HIP(ctx, hipStreamSynchronize(s));
     const int n = *f->h_n;
@@ -239,6 +250,16 @@ extern "C" int rs_frame_assign_device(rs_context* ctx, rs_frame* f, const float*
     f->n = n;
     f->kd_root = n > 0 ? n / 2 : -1;
     if (h_n) *h_n = n;
+    return RS_OK;
+}
+
+int rs_frame_assign_enqueue(rs_context* ctx, rs_frame* f, const float* d_pt, const int32_t* d_count, const uint8_t* d_desc, int n)
+{
+    if (!ctx || !f || f->ctx != ctx || f->cap <= 0 || n < 0 || n > f->cap || !d_pt || !d_count || !d_desc) return RS_ERR_INVALID;
+    const int rc = frame_enqueue(ctx, f, d_pt, d_count, nullptr, nullptr, d_desc, n);      // the host knows n: no rank tile beyond it
+    if (rc) return rc;
+    f->n = n;
+    f->kd_root = n > 0 ? n / 2 : -1;
     return RS_OK;
 }
 

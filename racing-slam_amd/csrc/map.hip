@@ -49,6 +49,7 @@ struct rs_map : MapMirror {
     // the tracker's per-frame stages (frame_matches.hip)
     uint8_t* d_consistent = nullptr; uint32_t* d_mark = nullptr;    // [cap_points] both; d_mark all zero between calls
     double* d_gather = nullptr;                     // pts [8192][3] f64 | uv [8192][2] f32 | n: the refit's gathered problem
+    void* fuse = nullptr;                           // scratch of rs_map_fuse_loop (map_fuse.hip owns and frees it)
 };
 
 // (struct rs_frame: common.h — frame.hip fills one from device arrays)
@@ -89,6 +90,7 @@ extern "C" int rs_map_destroy(rs_map* m)
                     (void*)m->d_centres, (void*)m->d_pool, (void*)m->d_elig, (void*)m->d_flag, (void*)m->d_out, (void*)m->d_kp_pool,
                     (void*)m->d_win, (void*)m->d_kp_point, (void*)m->d_consistent, (void*)m->d_mark, (void*)m->d_gather, (void*)m->d_poses})
         if (p) (void)hipFree(p);
+    rs_map_fuse_release(m->fuse);
     delete m;
     return RS_OK;
 }
@@ -347,6 +349,50 @@ int rs_map_loop_sync(rs_map* m, rs_map_loop_view* out)
 }
 
 rs_context* rs_map_context(const rs_map* m) { return m->ctx; }
+
+// map_fuse.hip's window into the map: the mirror, and (sync != 0, a map with at least one point slot) the device image with the
+// key-frame tables brought up to date
+int rs_map_fuse_sync(rs_map* m, int sync, rs_map_fuse_view* out)
+{
+    *out = rs_map_fuse_view{};
+    out->ctx = m->ctx; out->mirror = m; out->scratch = &m->fuse;
+    if (!sync) return RS_OK;
+    rs_map_loop_view lv;
+    const int rc = rs_map_loop_sync(m, &lv);
+    if (rc) return rc;
+    out->d_pos = m->d_pos; out->d_alive = m->d_alive; out->d_obs_ptr = m->d_obs_ptr; out->d_obs_kf = m->d_obs_kf;
+    out->d_obs_desc = m->d_obs_desc; out->d_centres = m->d_centres; out->d_pool = m->d_pool; out->d_kp_pool = m->d_kp_pool;
+    out->d_kp_point = m->d_kp_point; out->n_obs = m->n_obs; out->pool_rows = m->pool_rows;
+    return RS_OK;
+}
+
+extern "C" int rs_map_fuse_points(rs_map* m, int kept, int discarded)
+{
+    if (!m) return RS_ERR_INVALID;
+    return mirror_fuse(m, kept, discarded);
+}
+
+extern "C" int rs_map_get_observations(const rs_map* m, int point, int32_t* h_kf, int32_t* h_kp, int capacity, int* h_n)
+{
+    if (!m || !h_n || point < 0 || point >= (int)m->alive.size()) return RS_ERR_INVALID;
+    const auto& v = m->obs[(size_t)point];
+    *h_n = (int)v.size();
+    for (size_t i = 0; i < v.size() && (int)i < capacity; i++) {
+        if (h_kf) h_kf[i] = v[i].kf;
+        if (h_kp) h_kp[i] = v[i].kp;
+    }
+    return RS_OK;
+}
+
+extern "C" int rs_map_get_keyframe_matches(const rs_map* m, int kf, int32_t* h_kp_point, int capacity, int* h_n)
+{
+    if (!m || !h_n || !mirror_kf_ok(m, kf)) return RS_ERR_INVALID;
+    const auto& t = m->kfs[(size_t)kf].kp_point;
+    *h_n = (int)t.size();
+    for (size_t i = 0; i < t.size() && (int)i < capacity; i++)
+        if (h_kp_point) h_kp_point[i] = t[i];
+    return RS_OK;
+}
 
 extern "C" int rs_map_set_track_consistent(rs_map* m, int point)
 {

@@ -168,3 +168,126 @@ static inline int mirror_add_track_points(MapMirror* m, int kf, const rs_track_r
     }
     return RS_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ loop fusion
+// The invariant every edit above keeps: table[kf][kp] == p exactly when (kf, kp) is an observation of the alive point p, and a
+// point has at most one observation per key frame.
+static inline bool mirror_consistent(const MapMirror* m)
+{
+    size_t in_tables = 0, in_rows = 0;
+    for (size_t k = 0; k < m->kfs.size(); k++)
+        for (int i = 0; i < m->kfs[k].n; i++) {
+            const int p = m->kfs[k].kp_point[(size_t)i];
+            if (p < 0) continue;
+            in_tables++;
+            if (!mirror_point_ok(m, p)) return false;
+            int found = 0;
+            for (const MapObs& o : m->obs[(size_t)p]) found += (o.kf == (int)k && o.kp == i) ? 1 : 0;
+            if (found != 1) return false;
+        }
+    for (size_t p = 0; p < m->obs.size(); p++) {
+        if (!m->alive[p] && !m->obs[p].empty()) return false;
+        for (size_t a = 0; a < m->obs[p].size(); a++) {
+            const MapObs& o = m->obs[p][a];
+            if (!mirror_kf_ok(m, o.kf) || o.kp < 0 || o.kp >= m->kfs[(size_t)o.kf].n) return false;
+            for (size_t b = a + 1; b < m->obs[p].size(); b++)
+                if (m->obs[p][b].kf == o.kf) return false;
+        }
+        in_rows += m->obs[p].size();
+    }
+    return in_tables == in_rows;
+}
+
+// Frame::is_matched(point): the key frame's table names the point somewhere
+static inline bool mirror_kf_matches(const MapMirror* m, int kf, int point)
+{
+    for (const int32_t p : m->kfs[(size_t)kf].kp_point)
+        if (p == point) return true;
+    return false;
+}
+
+// Map::fuse (src/Map.cpp:78-95): the observations of `discarded` move to `kept`, in discarded's observation order, unless
+// the observer already sees `kept`; `discarded` hands over its track_consistent flag (:91-93) and is removed.  The loop
+// walks a COPY of the list, as the reference does: every turn erases from the original.
+static inline int mirror_fuse(MapMirror* m, int kept, int discarded)
+{
+    if (!mirror_point_ok(m, kept) || !mirror_point_ok(m, discarded)) return RS_ERR_INVALID;
+    if (kept == discarded) return RS_OK;                                  // :80-82
+    const std::vector<MapObs> observations = m->obs[(size_t)discarded];
+    for (const MapObs& o : observations) {
+        mirror_remove_observation(m, discarded, o.kf);                    // :85
+        if (mirror_observed_by(m, kept, o.kf) || m->kfs[(size_t)o.kf].kp_point[(size_t)o.kp] >= 0 || mirror_kf_matches(m, o.kf, kept))
+            continue;                                                     // :86-88
+        mirror_add_observation(m, kept, o.kf, o.kp);                      // :89
+    }
+    if (m->consistent[(size_t)discarded]) mirror_set_track_consistent(m, kept);
+    return mirror_remove_point(m, discarded);                             // :94
+}
+
+// Mapper::fuse_match (src/Mapper.cpp:176-196) for keypoint kp of key frame kf and the point `kept`; is_old [n_flags] marks
+// the loop's old points.  Returns the outcome (RS_FUSE_*); *removed = the discarded slot of a fuse, else -1.  An entry
+// whose keypoint is outside the key frame or whose point is dead or unknown is a no-op (the reference would follow a
+// dangling pointer).
+static inline int mirror_fuse_match(MapMirror* m, int kf, int kp, int kept, const uint8_t* is_old, size_t n_flags, int* removed)
+{
+    if (removed) *removed = -1;
+    if (!mirror_kf_ok(m, kf) || kp < 0 || kp >= m->kfs[(size_t)kf].n || !mirror_point_ok(m, kept)) return RS_FUSE_SKIPPED;
+    const int existing = m->kfs[(size_t)kf].kp_point[(size_t)kp];
+    if (existing < 0) {                                                   // :184-190
+        if (mirror_kf_matches(m, kf, kept)) return RS_FUSE_POINT_MATCHED;
+        mirror_add_observation(m, kept, kf, kp);
+        return RS_FUSE_ASSOCIATED;
+    }
+    if (existing == kept) return RS_FUSE_SAME;                            // :192
+    if ((size_t)existing < n_flags && is_old[(size_t)existing]) return RS_FUSE_OLD;
+    if (mirror_fuse(m, kept, existing) != RS_OK) return RS_FUSE_SKIPPED;
+    if (removed) *removed = existing;
+    return RS_FUSE_FUSED;
+}
+
+// loop_covisibles (src/Mapper.cpp:41-66): the candidate, then at most max_covisible key frames that share at least
+// min_shared of the candidate's points, ranked by shared count descending, key-frame handle ascending (the reference
+// sorts an unordered_map by count alone: ties are unspecified upstream).  The candidate's own observations do not count.
+static inline void mirror_loop_old_frames(const MapMirror* m, int candidate, int min_shared, int max_covisible, std::vector<int32_t>* out)
+{
+    out->assign(1, candidate);
+    const size_t KF = m->kfs.size();
+    std::vector<int32_t> shared(KF, 0);
+    for (const int32_t p : m->kfs[(size_t)candidate].kp_point) {
+        if (p < 0) continue;
+        for (const MapObs& o : m->obs[(size_t)p])
+            if (o.kf != candidate) shared[(size_t)o.kf]++;
+    }
+    for (int r = 0; r < max_covisible; r++) {
+        int best = -1;
+        for (size_t k = 0; k < KF; k++)
+            if (shared[k] > 0 && shared[k] >= min_shared && (best < 0 || shared[k] > shared[(size_t)best])) best = (int)k;
+        if (best < 0) break;
+        out->push_back(best);
+        shared[(size_t)best] = 0;
+    }
+}
+
+// loop_points (src/Mapper.cpp:68-77) as a flag per point slot
+static inline void mirror_loop_points(const MapMirror* m, const std::vector<int32_t>& old_frames, std::vector<uint8_t>* is_old)
+{
+    is_old->assign(m->alive.size(), 0);
+    for (const int32_t kf : old_frames)
+        for (const int32_t p : m->kfs[(size_t)kf].kp_point)
+            if (p >= 0) (*is_old)[(size_t)p] = 1;
+}
+
+// One journal section — the (keypoint, point) pairs of key frame kf, in order — applied to the mirror.  Every outcome is
+// recomputed here: the section supplies matches, not decisions.  outcomes [n] (NULL = not wanted); the discarded slots of
+// the fuses are appended to *removed (NULL = not wanted); counts [6] are incremented per outcome.
+static inline void mirror_replay_fuse(MapMirror* m, int kf, const int32_t* kp, const int32_t* point, int n, const uint8_t* is_old,
+                                      size_t n_flags, int32_t* outcomes, std::vector<int32_t>* removed, int counts[6])
+{
+    for (int i = 0; i < n; i++) {
+        int gone = -1;
+        const int oc = mirror_fuse_match(m, kf, kp[i], point[i], is_old, n_flags, &gone);
+        if (outcomes) outcomes[i] = oc;
+        if (counts) counts[oc]++;
+        if (gone >= 0 && removed) removed->push_back(gone);
+    }
+}

@@ -1294,4 +1294,94 @@ bool insert_key_frame(rs_context* ctx, rs_map* map, DeviceTracks* tracks, const 
     return done(true);
 }
 
+bool close_loop(rs_context* ctx, rs_map* map, const std::vector<LoopConstraint>& loops, const std::vector<int32_t>& window,
+                const Camera& camera, int max_descriptor_distance, bool four_dof, const double gravity[3], bool bundle_adjust, bool check,
+                LoopClosure* out)
+{
+    LoopClosure r;
+    const auto done = [&](bool ok) { if (out) *out = std::move(r); return ok; };
+    const auto fail = [&](int rc, const char* what) {
+        std::printf("%s failed (status %d): %s\n", what, rc, ctx ? rs_last_error(ctx) : "no context");
+        return done(false);
+    };
+    if (loops.empty() || window.empty()) return fail(RS_ERR_INVALID, "close_loop: no constraint or no window");
+    int counts[4] = {0, 0, 0, 0};
+    int rc = rs_map_counts(map, counts);
+    if (rc != RS_OK) return fail(rc, "rs_map_counts");
+    const int cap = counts[0], n_kf = counts[3];
+    std::vector<rs_pose_graph_edge> edges(loops.size());
+    for (size_t i = 0; i < loops.size(); i++) {
+        edges[i].from = (int32_t)loops[i].from;
+        edges[i].to = (int32_t)loops[i].to;
+        for (int k = 0; k < 16; k++) edges[i].relative[k] = loops[i].relative[(size_t)k];
+    }
+    const double zero[3] = {0.0, 0.0, 0.0};
+    r.graph_poses.assign(16 * (size_t)std::max(n_kf, 1), 0.0f);
+    rc = rs_map_pose_graph(ctx, map, edges.data(), (int)edges.size(), four_dof ? 1 : 0, gravity ? gravity : zero, nullptr, r.graph_poses.data(),
+                           nullptr, &r.graph);                                                                 // src/Slam.cpp:262-268
+    if (rc != RS_OK) return fail(rc, "rs_map_pose_graph");
+    r.closed = r.graph.usable != 0;
+    if (!r.closed) return done(true);
+    const LoopConstraint& loop = loops.back();
+    const int query = (int)loop.from, C = (int)window.size();
+    if ((int)loop.to < n_kf) {                                                                                 // :275-279
+        std::vector<int32_t> ikp, ipt;
+        for (const auto& m : loop.inlier_matches) { ikp.push_back(m.first); ipt.push_back(m.second); }
+        rs_fuse_options opt{};
+        opt.intrinsics[0] = camera.fx(); opt.intrinsics[1] = camera.fy(); opt.intrinsics[2] = camera.cx(); opt.intrinsics[3] = camera.cy();
+        opt.width = camera.get_width(); opt.height = camera.get_height();
+        opt.max_distance = max_descriptor_distance; opt.min_shared = 15; opt.max_covisible = 20; opt.check = check ? 1 : 0;
+        r.sources.assign((size_t)std::max(cap, 1), -1);
+        r.removed.assign((size_t)std::max(cap, 1), -1);
+        opt.h_sources = r.sources.data(); opt.capacity_sources = cap;
+        opt.h_removed = r.removed.data(); opt.capacity_removed = cap;
+        size_t room = ikp.size();
+        for (const int32_t kf : window) {
+            int n = 0;
+            if (rs_map_get_keyframe_matches(map, kf, nullptr, 0, &n) == RS_OK) room += (size_t)n;
+        }
+        r.section_ptr.assign((size_t)C + 2, 0);
+        r.journal_kp.assign(std::max<size_t>(room, 1), 0);
+        r.journal_point = r.journal_kp;
+        r.journal_outcome = r.journal_kp;
+        int n_entries = 0;
+        rc = rs_map_fuse_loop(ctx, map, query, (int)loop.to, ikp.data(), ipt.data(), (int)ikp.size(), window.data(), C, &opt, &r.fuse,
+                              r.section_ptr.data(), r.journal_kp.data(), r.journal_point.data(), r.journal_outcome.data(), (int)room, &n_entries);
+        if (rc != RS_OK) return fail(rc, "rs_map_fuse_loop");
+        r.sources.resize((size_t)std::min(r.fuse.n_sources, cap));
+        r.removed.resize((size_t)std::min(r.fuse.n_removed, cap));
+        r.journal_kp.resize((size_t)n_entries); r.journal_point.resize((size_t)n_entries); r.journal_outcome.resize((size_t)n_entries);
+        std::printf("Fused loop: %d old frames, %d sources, %d fused, %d associated\n", r.fuse.n_old_frames, r.fuse.n_sources,
+                    r.fuse.outcomes[RS_FUSE_FUSED], r.fuse.outcomes[RS_FUSE_ASSOCIATED]);
+    }
+    if (bundle_adjust) {                                                                                       // :280-282, Mapper.cpp:364-394
+        const float K[4] = {camera.fx(), camera.fy(), camera.cx(), camera.cy()};
+        std::vector<uint8_t> free_flags((size_t)C, 1);
+        free_flags[0] = 0;                                                  // fix_oldest
+        std::vector<int32_t> anchors;
+        std::vector<float> before;
+        for (int c = 1; c < C; c++) {
+            if (window[(size_t)c] < 0 || window[(size_t)c] >= n_kf) return fail(RS_ERR_INVALID, "close_loop: window");
+            anchors.push_back(window[(size_t)c]);
+            before.insert(before.end(), r.graph_poses.begin() + 16 * (long)window[(size_t)c], r.graph_poses.begin() + 16 * (long)window[(size_t)c] + 16);
+        }
+        r.poses.assign(16 * (size_t)C, 0.0f);
+        r.adjusted.assign((size_t)std::max(cap, 1), 0);
+        r.adjusted_xyz.assign(3 * (size_t)std::max(cap, 1), 0.0f);
+        int n = 0;
+        rc = rs_map_bundle_adjust(ctx, map, window.data(), free_flags.data(), C, K, nullptr, &r.adjust, r.poses.data(), r.adjusted.data(),
+                                  r.adjusted_xyz.data(), cap, &n);
+        if (rc != RS_OK) return fail(rc, "rs_map_bundle_adjust");
+        r.adjusted.resize((size_t)std::min(n, cap));
+        r.adjusted_xyz.resize(3 * r.adjusted.size());
+        r.reanchored.assign((size_t)std::max(cap, 1), 0);
+        r.reanchored_xyz.assign(3 * (size_t)std::max(cap, 1), 0.0f);
+        rc = rs_map_reanchor(ctx, map, anchors.data(), before.data(), (int)anchors.size(), r.reanchored.data(), r.reanchored_xyz.data(), cap, &n);
+        if (rc != RS_OK) return fail(rc, "rs_map_reanchor");
+        r.reanchored.resize((size_t)std::min(n, cap));
+        r.reanchored_xyz.resize(3 * r.reanchored.size());
+    }
+    return done(true);
+}
+
 }  // namespace slam

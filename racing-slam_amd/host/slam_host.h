@@ -522,4 +522,27 @@ class LoopStreak {
     bool m_new_loop = false;
 };
 
+// Slam::step's "LOOP CLOSED" branch (src/Slam.cpp:260-283) on the resident map, next to insert_key_frame: three calls,
+// rs_map_pose_graph -> rs_map_fuse_loop (Mapper::fuse_loop with the newest constraint's candidate and inliers) ->
+// rs_map_bundle_adjust with the oldest window frame fixed (Mapper::bundle_adjust(query, true)) and its re-anchoring tail,
+// rs_map_reanchor.  Nothing walks map objects on the host.
+struct LoopClosure {
+    bool closed = false;                         // optimization::pose_graph's result; false: nothing after it ran
+    rs_ba_summary graph{};
+    std::vector<float> graph_poses;              // [key frames][16] after the pose graph
+    rs_fuse_report fuse{};
+    std::vector<int32_t> sources, removed;       // the old points; the fused-away points in order
+    std::vector<int32_t> section_ptr, journal_kp, journal_point, journal_outcome;      // rs_map_fuse_loop's journal
+    rs_ba_summary adjust{};
+    std::vector<float> poses;                    // [window][16] after the adjustment
+    std::vector<int32_t> adjusted; std::vector<float> adjusted_xyz;
+    std::vector<int32_t> reanchored; std::vector<float> reanchored_xyz;
+};
+// loops: every constraint so far, the new one last (LoopStreak::constraints(); from / to are key-frame handles of `map`);
+// window: the caller's bundle-adjustment window in order, the query last (`first = size - BA_WINDOW` stays with the caller);
+// check: rs_fuse_options::check.  False on failure (logged); a pose graph that is not usable is no failure (closed = false).
+bool close_loop(rs_context* ctx, rs_map* map, const std::vector<LoopConstraint>& loops, const std::vector<int32_t>& window,
+                const Camera& camera, int max_descriptor_distance, bool four_dof, const double gravity[3], bool bundle_adjust, bool check,
+                LoopClosure* out);
+
 }  // namespace slam

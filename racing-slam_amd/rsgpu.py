@@ -25,6 +25,7 @@ EXPORTS = [
     "rs_track_store_query", "rs_needs_key_frame", "rs_track_store_triangulate", "rs_track_store_erase_inconsistent",
     "rs_track_store_download", "rs_track_store_download_packed",
     "rs_map_insert_keyframe", "rs_map_add_track_points", "rs_map_reanchor", "rs_map_cull_points",
+    "rs_map_fuse_points", "rs_map_get_observations", "rs_map_get_keyframe_matches", "rs_map_fuse_loop",
     "rs_map_add_keyframe", "rs_map_set_keyframe_pose", "rs_map_add_point", "rs_map_set_position", "rs_map_remove_point",
     "rs_map_add_observation", "rs_map_remove_observation", "rs_map_counts", "rs_map_get_positions", "rs_map_match", "rs_map_pose_graph", "rs_pose_graph", "rs_pose_relative", "rs_transform_points", "rs_map_bundle_adjust", "rs_map_window", "rs_triangulate", "rs_triangulate_host", "rs_triangulate_matches", "rs_triangulate_matches_batch", "rs_triangulate_tracks", "rs_parallax_requirements", "rs_point_errors", "rs_ba_default_options",
     "rs_bundle_adjust", "rs_bundle_adjust_batch", "rs_ba_get_trace", "rs_ba_get_stats", "rs_ba_get_cameras", "rs_reanchor_points", "rs_reanchor_points_host_poses", "rs_refine_pose", "rs_bundle_adjust_inertial", "rs_refine_pose_inertial", "rs_pack_pose", "rs_unpack_pose", "rs_pack_poses", "rs_unpack_poses", "rs_build_local_window",
@@ -1447,6 +1448,20 @@ class TrackStore:
 SIGHTING_DTYPE = np.dtype([("frame", np.int32), ("x", np.float32), ("y", np.float32), ("kf", np.int32), ("kp", np.int32)])
 
 
+FUSE_MAX_COVISIBLE = 64
+
+
+class FuseOptions(C.Structure):
+    _fields_ = [("intrinsics", C.c_float * 4), ("width", C.c_int), ("height", C.c_int), ("max_distance", C.c_int),
+                ("min_shared", C.c_int), ("max_covisible", C.c_int), ("check", C.c_int),
+                ("h_sources", C.c_void_p), ("capacity_sources", C.c_int), ("h_removed", C.c_void_p), ("capacity_removed", C.c_int)]
+
+
+class FuseReport(C.Structure):
+    _fields_ = [("n_old_frames", C.c_int), ("old_frames", C.c_int32 * (FUSE_MAX_COVISIBLE + 1)), ("n_sources", C.c_int),
+                ("outcomes", C.c_int * 6), ("n_removed", C.c_int), ("device_state_mismatches", C.c_int)]
+
+
 class ResidentMap:
     """Thin wrapper of rs_map: every method is one C-ABI call."""
 
@@ -1667,3 +1682,64 @@ class ResidentMap:
                 return dict(points=pts[:n.value].copy(), positions=xyz[:n.value].copy(), obs_ptr=ptr[:n.value + 1].copy(),
                             obs_cam=cam[:m.value].copy(), obs_uv=uv[:m.value].copy())
             cap_p, cap_o = n.value, m.value
+
+    # -- Mapper::fuse_loop on the resident map
+    def fuse_points(self, kept, discarded):
+        """rs_map_fuse_points (Map::fuse)"""
+        self.ctx._check(self.lib.rs_map_fuse_points(self.h, int(kept), int(discarded)), "rs_map_fuse_points")
+
+    def observations(self, point):
+        """rs_map_get_observations: [(key frame, keypoint)] in insertion order"""
+        n = C.c_int(0)
+        self.ctx._check(self.lib.rs_map_get_observations(self.h, int(point), None, None, 0, C.byref(n)), "rs_map_get_observations")
+        kf, kp = np.zeros(max(n.value, 1), np.int32), np.zeros(max(n.value, 1), np.int32)
+        self.ctx._check(self.lib.rs_map_get_observations(self.h, int(point), kf.ctypes.data_as(C.c_void_p), kp.ctypes.data_as(C.c_void_p),
+                                                         n.value, C.byref(n)), "rs_map_get_observations")
+        return [(int(a), int(b)) for a, b in zip(kf[:n.value], kp[:n.value])]
+
+    def keyframe_matches(self, kf):
+        """rs_map_get_keyframe_matches: the key frame's keypoint -> point table"""
+        n = C.c_int(0)
+        self.ctx._check(self.lib.rs_map_get_keyframe_matches(self.h, int(kf), None, 0, C.byref(n)), "rs_map_get_keyframe_matches")
+        tab = np.full(max(n.value, 1), -1, np.int32)
+        self.ctx._check(self.lib.rs_map_get_keyframe_matches(self.h, int(kf), tab.ctypes.data_as(C.c_void_p), n.value, C.byref(n)),
+                        "rs_map_get_keyframe_matches")
+        return tab[:n.value].copy()
+
+    def fuse_loop(self, query, candidate, inliers, window, K, width, height, max_distance=64, min_shared=15, max_covisible=20,
+                  check=False, journal=True, capacity=None, raise_on_error=True):
+        """rs_map_fuse_loop.  inliers: [(keypoint, point)].  Returns dict(status, old_frames, sources, sections (a list of
+        [(keypoint, point, outcome)] per section; None with journal=False), n_entries, outcomes, removed,
+        device_state_mismatches).  capacity: the room of the journal arrays (default: every possible entry)."""
+        ik = np.ascontiguousarray([i[0] for i in inliers], np.int32)
+        ip = np.ascontiguousarray([i[1] for i in inliers], np.int32)
+        win = np.ascontiguousarray(window, np.int32)
+        c = self.counts()
+        opt = FuseOptions(width=int(width), height=int(height), max_distance=int(max_distance), min_shared=int(min_shared),
+                          max_covisible=int(max_covisible), check=int(bool(check)))
+        for i in range(4):
+            opt.intrinsics[i] = float(K[i])
+        src, rem = np.full(max(c["slots"], 1), -1, np.int32), np.full(max(c["slots"], 1), -1, np.int32)
+        opt.h_sources, opt.capacity_sources, opt.h_removed, opt.capacity_removed = src.ctypes.data, len(src), rem.ctypes.data, len(rem)
+        rep = FuseReport()
+        # a section has at most min(sources, keypoints of the frame) entries: a source is accepted by at most one keypoint,
+        # and a key frame inside the envelope has at most 8192
+        cap = len(ik) + len(win) * min(c["slots"], 8192) if capacity is None else int(capacity)
+        sec = np.zeros(len(win) + 2, np.int32)
+        jk, jp, jo = (np.zeros(max(cap, 1), np.int32) for _ in range(3))
+        n = C.c_int(0)
+        ptr = (lambda a: a.ctypes.data_as(C.c_void_p)) if journal else (lambda a: None)
+        rc = self.lib.rs_map_fuse_loop(self.ctx.h, self.h, int(query), int(candidate), ik.ctypes.data_as(C.c_void_p), ip.ctypes.data_as(C.c_void_p),
+                                       len(ik), win.ctypes.data_as(C.c_void_p), len(win), C.byref(opt), C.byref(rep), ptr(sec), ptr(jk), ptr(jp),
+                                       ptr(jo), cap if journal else 0, C.byref(n))
+        if raise_on_error:
+            self.ctx._check(rc, "rs_map_fuse_loop")
+        if rc != 0:
+            return dict(status=rc)
+        sections = None
+        if journal:
+            k = min(n.value, max(cap, 0))
+            sections = [[(int(jk[e]), int(jp[e]), int(jo[e])) for e in range(min(sec[i], k), min(sec[i + 1], k))] for i in range(len(sec) - 1)]
+        return dict(status=rc, old_frames=[int(v) for v in rep.old_frames[:rep.n_old_frames]], sources=src[:rep.n_sources].copy(),
+                    sections=sections, n_entries=n.value, outcomes=[int(v) for v in rep.outcomes], removed=rem[:rep.n_removed].copy(),
+                    device_state_mismatches=rep.device_state_mismatches)

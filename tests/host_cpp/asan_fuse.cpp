@@ -1,0 +1,173 @@
+// asan_fuse.cpp — the mirror edits of rs_map_fuse_points and rs_map_fuse_loop (csrc/map_mirror.h: plain C++, no GPU, no HIP)
+// in a program of its own, built with -fsanitize=address,undefined by tests/test_fuse_host.py.  mirror_fuse walks a copy of
+// the discarded point's observation list while every turn erases from the original; journal sections and flag tables live in
+// exactly-sized heap blocks, so an index one past any of them aborts here.  Results are checked against Map::fuse's and
+// Mapper::fuse_match's rules.
+#include <cstdio>
+#include <memory>
+#include <vector>
+
+#include "../../racing-slam_amd/csrc/map_mirror.h"
+
+static int g_bad = 0;
+static void expect_true(bool ok, const char* what)
+{
+    if (!ok) { g_bad++; std::printf("FAILED: %s\n", what); }
+}
+
+template <class T> static std::unique_ptr<T[]> exact(const std::vector<T>& v)
+{
+    std::unique_ptr<T[]> p(new T[v.size() ? v.size() : 1]);
+    for (size_t i = 0; i < v.size(); i++) p[i] = v[i];
+    return p;
+}
+
+static int add_keyframe(MapMirror* m, int n)
+{
+    MapKeyFrame k;
+    k.n = n;
+    k.kp.assign(2 * (size_t)n, 0.f);
+    k.kp_point.assign((size_t)n, -1);
+    for (int i = 0; i < 16; i++) k.pose[i] = i % 5 == 0 ? 1.f : 0.f;
+    m->kfs.push_back(k);
+    return (int)m->kfs.size() - 1;
+}
+
+static size_t n_obs(const MapMirror& m)
+{
+    size_t c = 0;
+    for (const auto& v : m.obs) c += v.size();
+    return c;
+}
+
+static bool consistent(const MapMirror& m)
+{
+    size_t in_tables = 0;
+    for (size_t k = 0; k < m.kfs.size(); k++)
+        for (int i = 0; i < m.kfs[k].n; i++) {
+            const int p = m.kfs[k].kp_point[(size_t)i];
+            if (p < 0) continue;
+            in_tables++;
+            if (!mirror_point_ok(&m, p)) return false;
+            bool found = false;
+            for (const auto& o : m.obs[(size_t)p]) found = found || (o.kf == (int)k && o.kp == i);
+            if (!found) return false;
+        }
+    return in_tables == n_obs(m);
+}
+
+static bool row_is(const MapMirror& m, int p, const std::vector<MapObs>& want)
+{
+    if (m.obs[(size_t)p].size() != want.size()) return false;
+    for (size_t i = 0; i < want.size(); i++)
+        if (m.obs[(size_t)p][i].kf != want[i].kf || m.obs[(size_t)p][i].kp != want[i].kp) return false;
+    return true;
+}
+
+int main()
+{
+    MapMirror m;
+    const float x[3] = {1.f, 2.f, 3.f};
+    for (int k = 0; k < 5; k++) add_keyframe(&m, 4);
+    for (int p = 0; p < 8; p++) mirror_add_point(&m, x);
+    // kept = 0 seen by key frames 0 and 2; discarded = 1 seen by 1, 2, 3 (in that order) and track-consistent
+    mirror_add_observation(&m, 0, 0, 0);
+    mirror_add_observation(&m, 0, 2, 3);                                     // the last keypoint
+    mirror_add_observation(&m, 1, 1, 1);
+    mirror_add_observation(&m, 1, 2, 0);
+    mirror_add_observation(&m, 1, 3, 3);
+    mirror_set_track_consistent(&m, 1);
+
+    // ---- Map::fuse
+    expect_true(mirror_fuse(&m, 0, 0) == RS_OK && n_obs(m) == 5, "kept == discarded is a no-op");
+    expect_true(mirror_fuse(&m, 0, 8) == RS_ERR_INVALID && mirror_fuse(&m, -1, 0) == RS_ERR_INVALID, "unknown slots are refused");
+    expect_true(mirror_fuse(&m, 0, 1) == RS_OK, "fuse");
+    expect_true(row_is(m, 0, {{0, 0}, {2, 3}, {1, 1}, {3, 3}}), "moved in the discarded point's order; the shared observer is skipped");
+    expect_true(!m.alive[1] && m.obs[1].empty() && m.kfs[2].kp_point[0] == -1 && m.kfs[1].kp_point[1] == 0, "discarded is gone, tables follow");
+    expect_true(m.consistent[0] == 1, "track-consistent handed over");
+    expect_true(mirror_fuse(&m, 0, 1) == RS_ERR_INVALID, "a removed slot is refused");
+    expect_true(consistent(m), "consistent after the fuse");
+    // a discarded point without observations
+    expect_true(mirror_fuse(&m, 0, 2) == RS_OK && !m.alive[2] && m.obs[0].size() == 4, "a point nobody observes");
+
+    // ---- Mapper::fuse_match: every outcome, flags in an exactly-sized block shorter than the slot table
+    auto is_old = exact<uint8_t>({1, 0, 0, 0, 1});                            // slots 0 and 4 are old; 5 .. 7 lie beyond the block
+    int gone = 7;
+    mirror_add_observation(&m, 4, 4, 0);
+    mirror_add_observation(&m, 5, 4, 1);
+    mirror_add_observation(&m, 5, 3, 0);
+    expect_true(mirror_fuse_match(&m, 4, 4, 0, is_old.get(), 5, &gone) == RS_FUSE_SKIPPED && gone == -1, "keypoint one past the key frame");
+    expect_true(mirror_fuse_match(&m, 4, -1, 0, is_old.get(), 5, &gone) == RS_FUSE_SKIPPED, "negative keypoint");
+    expect_true(mirror_fuse_match(&m, 5, 0, 0, is_old.get(), 5, &gone) == RS_FUSE_SKIPPED, "unknown key frame");
+    expect_true(mirror_fuse_match(&m, 4, 2, 1, is_old.get(), 5, &gone) == RS_FUSE_SKIPPED, "dead point");
+    expect_true(mirror_fuse_match(&m, 4, 2, 8, is_old.get(), 5, &gone) == RS_FUSE_SKIPPED, "unknown point");
+    expect_true(mirror_fuse_match(&m, 4, 2, 0, is_old.get(), 5, &gone) == RS_FUSE_ASSOCIATED && m.kfs[4].kp_point[2] == 0, "free keypoint");
+    expect_true(mirror_fuse_match(&m, 4, 3, 0, is_old.get(), 5, &gone) == RS_FUSE_POINT_MATCHED && m.kfs[4].kp_point[3] == -1, "the frame matches the point already");
+    expect_true(mirror_fuse_match(&m, 4, 2, 0, is_old.get(), 5, &gone) == RS_FUSE_SAME, "the keypoint holds the point");
+    expect_true(mirror_fuse_match(&m, 4, 0, 0, is_old.get(), 5, &gone) == RS_FUSE_OLD && m.alive[4], "the keypoint's point is old");
+    expect_true(mirror_fuse_match(&m, 4, 1, 0, is_old.get(), 5, &gone) == RS_FUSE_FUSED && gone == 5 && !m.alive[5], "fused (slot beyond the flag block)");
+    expect_true(m.kfs[4].kp_point[1] == -1 && m.kfs[3].kp_point[0] == -1, "both observers of the discarded point already saw the kept one");
+    expect_true(consistent(m), "consistent after fuse_match");
+
+    // ---- a journal section replayed from exactly-sized arrays
+    {
+        mirror_add_observation(&m, 6, 1, 3);
+        auto kp = exact<int32_t>({3, 3, 0, 9});
+        auto pt = exact<int32_t>({4, 4, 4, 4});
+        auto oc = exact<int32_t>({-1, -1, -1, -1});
+        std::vector<int32_t> removed;
+        int counts[6] = {0, 0, 0, 0, 0, 0};
+        mirror_replay_fuse(&m, 1, kp.get(), pt.get(), 4, is_old.get(), 5, oc.get(), &removed, counts);
+        expect_true(oc[0] == RS_FUSE_FUSED && oc[1] == RS_FUSE_SAME && oc[2] == RS_FUSE_POINT_MATCHED && oc[3] == RS_FUSE_SKIPPED, "section outcomes");
+        expect_true(removed == std::vector<int32_t>({6}) && counts[5] == 1 && counts[3] == 1 && counts[2] == 1 && counts[0] == 1, "removed list and counts");
+        mirror_replay_fuse(&m, 1, kp.get(), pt.get(), 0, is_old.get(), 5, nullptr, nullptr, nullptr);
+        expect_true(consistent(m), "consistent after the replay");
+    }
+
+    // ---- loop_covisibles: threshold, cut, tie by handle, the candidate's own observations
+    {
+        MapMirror c;
+        for (int k = 0; k < 6; k++) add_keyframe(&c, 6);
+        for (int p = 0; p < 6; p++) { mirror_add_point(&c, x); mirror_add_observation(&c, p, 0, p); }
+        const int shared[6] = {0, 3, 2, 3, 1, 3};                             // key frames 1, 3, 5 share three points, 2 two, 4 one
+        for (int k = 1; k < 6; k++)
+            for (int p = 0; p < shared[k]; p++) mirror_add_observation(&c, p, k, p);
+        std::vector<int32_t> old;
+        mirror_loop_old_frames(&c, 0, 2, 20, &old);
+        expect_true(old == std::vector<int32_t>({0, 1, 3, 5, 2}), "count descending, handle ascending, threshold 2");
+        mirror_loop_old_frames(&c, 0, 2, 2, &old);
+        expect_true(old == std::vector<int32_t>({0, 1, 3}), "the cut keeps the lower handles of a tie");
+        mirror_loop_old_frames(&c, 0, 2, 0, &old);
+        expect_true(old == std::vector<int32_t>({0}), "max_covisible = 0");
+        mirror_loop_old_frames(&c, 4, 0, 20, &old);
+        expect_true(old.size() == 6 && old[0] == 4, "min_shared = 0 still needs one shared point");
+        std::vector<uint8_t> flags;
+        mirror_loop_points(&c, {0, 4}, &flags);
+        expect_true(flags == std::vector<uint8_t>({1, 1, 1, 1, 1, 1}), "old points of the candidate");
+        mirror_loop_points(&c, {4}, &flags);
+        expect_true(flags == std::vector<uint8_t>({1, 0, 0, 0, 0, 0}), "old points of one key frame");
+    }
+    // ---- the invariant rs_map_fuse_loop's device stage rests on (checked by the call under check = 1), broken by hand
+    {
+        expect_true(mirror_consistent(&m), "the edited mirror is consistent");
+        MapMirror b = m;
+        b.kfs[0].kp_point[1] = 0;                                             // a table entry without its observation
+        expect_true(!mirror_consistent(&b), "a table entry without an observation is seen");
+        b = m;
+        b.obs[0].push_back({4, 3});                                           // an observation without its table entry
+        expect_true(!mirror_consistent(&b), "an observation without a table entry is seen");
+        b = m;
+        b.kfs[0].kp_point[0] = 1;                                             // a table entry naming a removed slot
+        expect_true(!mirror_consistent(&b), "a table entry naming a removed slot is seen");
+        b = m;
+        b.obs[0].push_back({0, 2});
+        b.kfs[0].kp_point[2] = 0;                                             // one point twice in one key frame
+        expect_true(!mirror_consistent(&b), "two observations by one key frame are seen");
+    }
+    for (int p = 0; p < (int)m.alive.size(); p++)
+        if (mirror_point_ok(&m, p)) mirror_remove_point(&m, p);
+    expect_true(n_obs(m) == 0 && m.n_alive == 0 && consistent(m), "everything removed");
+    if (g_bad) return 1;
+    std::printf("asan fuse checks passed\n");
+    return 0;
+}
