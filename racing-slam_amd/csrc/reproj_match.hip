@@ -71,6 +71,44 @@ __device__ __forceinline__ int hamming256(const uint4 a0, const uint4 a1, const 
     return d;
 }
 
+// K3 with the thread's chunk of at most CH keypoints held in registers: the table is read ONCE (one global round trip
+// on the path from kernel start to the last store instead of two), counted, scanned and written from the registers.
+// CH is the smallest of 1, 2, 4, 8 that holds the chunk: the one workgroup issues every load through one CU's
+// address path, where 16 waves x 8 clamped 64-bit loads cost more than the round trip they overlap.
+template <int CH>
+__device__ __forceinline__ void k3_accept_held(unsigned long long* __restrict__ prop, int lo, int hi, int max_distance,
+                                               int32_t* __restrict__ prop_point, int32_t* __restrict__ prop_dist,
+                                               int32_t* __restrict__ match_kp, int32_t* __restrict__ match_point,
+                                               int32_t* __restrict__ match_count)
+{
+    unsigned long long v[CH];
+    int cnt = 0;
+#pragma unroll
+    for (int u = 0; u < CH; u++) v[u] = __builtin_nontemporal_load(&prop[max(min(lo + u, hi - 1), 0)]);   // clamped: no branches
+#pragma unroll
+    for (int u = 0; u < CH; u++) cnt += (lo + u < hi && v[u] != ~0ull) ? 1 : 0;
+    int total;
+    int off = rs_block_exclusive_scan(cnt, &total);
+#pragma unroll
+    for (int u = 0; u < CH; u++) {
+        const int i = lo + u;
+        if (i < hi) {
+            int pt = -1, dist = max_distance;
+            if (v[u] != ~0ull) {
+                pt = (int)(unsigned)(v[u] & 0xFFFFFFFFull);
+                dist = (int)(v[u] >> 32);
+                match_kp[off] = i;                                       // accepted_matches :34-43
+                match_point[off] = pt;
+                off++;
+                prop[i] = ~0ull;
+            }
+            prop_point[i] = pt;
+            prop_dist[i] = dist;
+        }
+    }
+    if (threadIdx.x == 0) *match_count = total;
+}
+
 // Ordered acceptance of the proposal table (accepted_matches, src/MapMatcher.cpp:34-43) by ONE workgroup
 // of any size; resets the table to all-ones for the next call.
 __device__ __forceinline__ void k3_accept_body(unsigned long long* __restrict__ prop, int n, int max_distance,
@@ -79,9 +117,14 @@ __device__ __forceinline__ void k3_accept_body(unsigned long long* __restrict__ 
                                                int32_t* __restrict__ match_count)
 {
     // every thread owns a contiguous chunk of keypoints: count, one workgroup scan, ordered write.
-    // Loads go out in batches of 8 (clamped addresses, no branches) so that their latencies overlap.
     const int T = blockDim.x, chunk = (n + T - 1) / T;
     const int lo = min((int)threadIdx.x * chunk, n), hi = min(lo + chunk, n);
+    // up to 8 keypoints per thread (n <= 8 T; workgroup-uniform): held in registers
+    if (chunk <= 1) return k3_accept_held<1>(prop, lo, hi, max_distance, prop_point, prop_dist, match_kp, match_point, match_count);
+    if (chunk <= 2) return k3_accept_held<2>(prop, lo, hi, max_distance, prop_point, prop_dist, match_kp, match_point, match_count);
+    if (chunk <= 4) return k3_accept_held<4>(prop, lo, hi, max_distance, prop_point, prop_dist, match_kp, match_point, match_count);
+    if (chunk <= 8) return k3_accept_held<8>(prop, lo, hi, max_distance, prop_point, prop_dist, match_kp, match_point, match_count);
+    // larger tables: two passes.  Loads go out in batches of 8 (clamped addresses, no branches) so that their latencies overlap.
     int cnt = 0;
     for (int i0 = lo; i0 < hi; i0 += 8) {
         unsigned long long v[8];

@@ -125,45 +125,142 @@ __global__ __launch_bounds__(64) void k6_tracks(const float2* __restrict__ track
 // Selection by ONE workgroup (:291-304): ordered compaction of the accepted and of the inconsistent tracks,
 // then the quota top-up by rank counting over the rejected candidates (n_rej^2 comparisons; key = (cosine,
 // candidate order), NaN cosines sort last).
+//
+// Up to K6B_CH tracks per thread (8192 tracks with 1024 threads: workgroup-uniform) the thread's status bytes and
+// both cosines are read ONCE, together, and classified in registers; the three ordered compactions share one scan
+// of a packed triple (21 bits per field); and the rejected candidates with their keys stay in LDS for the rank
+// count when there are at most K6B_REJ_LDS of them.  Larger inputs take the two-pass form, larger rejected lists the
+// list in global memory.
+#define K6B_CH 8
+#define K6B_REJ_LDS 2048
+#define K6B_FIELD 21
+
+// kj (candidate j) sorts before ki (candidate i):  kj < ki, or equal (or both unordered) and earlier; NaN after everything
+__device__ __forceinline__ bool k6_before(float kj, float ki, int j, int i)
+{
+    return (kj < ki) || (!(ki < kj) && !(kj < ki) && ((kj == kj) == (ki == ki)) && j < i) || ((kj == kj) && !(ki == ki));
+}
+
+// rs_block_exclusive_scan over 64 bits: three 21-bit counters in one pass
+__device__ __forceinline__ unsigned long long k6_block_exclusive_scan64(unsigned long long v, unsigned long long* total)
+{
+    __shared__ unsigned long long k6_scan_w[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    unsigned long long x = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long t = __shfl_up(x, off, 64);
+        if (lane >= off) x += t;
+    }
+    if (lane == 63) k6_scan_w[wave] = x;
+    __syncthreads();
+    unsigned long long pre = 0, tot = 0;
+    for (int w = 0; w < nw; w++) { const unsigned long long c = k6_scan_w[w]; if (w < wave) pre += c; tot += c; }
+    __syncthreads();
+    *total = tot;
+    return pre + x - v;
+}
+
+// The thread's chunk of at most CH tracks (the smallest of 1, 2, 4, 8 that holds it: clamped loads the thread does not
+// need cost the one workgroup more in its CU's address path than the round trip they overlap): classified in registers,
+// one scan, the compacted writes.  Returns the three totals; the rejected go to LDS (*in_lds) or to `rejected`, and
+// only if the top-up will read them.
+template <int CH>
+__device__ __forceinline__ void k6_select_held(const uint8_t* __restrict__ status, const float* __restrict__ pcs,
+                                               const float* __restrict__ rcs, int lo, int hi, int min_new_points,
+                                               int32_t* __restrict__ accepted, int32_t* __restrict__ inconsistent,
+                                               int32_t* __restrict__ rejected, int32_t* rej_t, float* rej_k,
+                                               int* tot_a, int* tot_r, int* tot_i, bool* in_lds)
+{
+    uint8_t st[CH];
+    float pc[CH], rc[CH];
+#pragma unroll
+    for (int u = 0; u < CH; u++) {
+        const int t = max(min(lo + u, hi - 1), 0);                         // clamped: no branches around the loads
+        st[u] = status[t]; pc[u] = pcs[t]; rc[u] = rcs[t];
+    }
+    int cls[CH];                                                           // 0 none, 1 accepted, 2 rejected, 3 inconsistent
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int u = 0; u < CH; u++) {
+        cls[u] = lo + u >= hi ? 0 : st[u] == 2 ? 3 : st[u] == 1 ? (pc[u] <= rc[u] ? 1 : 2) : 0;
+        if (cls[u]) mine += 1ull << (K6B_FIELD * (cls[u] - 1));
+    }
+    unsigned long long tot;
+    const unsigned long long off = k6_block_exclusive_scan64(mine, &tot);
+    const unsigned fm = (1u << K6B_FIELD) - 1;
+    int oa = (int)(off & fm), orj = (int)((off >> K6B_FIELD) & fm), oi = (int)(off >> (2 * K6B_FIELD));
+    *tot_a = (int)(tot & fm); *tot_r = (int)((tot >> K6B_FIELD) & fm); *tot_i = (int)(tot >> (2 * K6B_FIELD));
+    const bool top_up = *tot_a < min_new_points && *tot_r > 0;
+    *in_lds = *tot_r <= K6B_REJ_LDS;
+#pragma unroll
+    for (int u = 0; u < CH; u++) {
+        const int t = lo + u;
+        if (cls[u] == 3) inconsistent[oi++] = t;
+        else if (cls[u] == 1) accepted[oa++] = t;
+        else if (cls[u] == 2) {
+            if (top_up) {
+                if (*in_lds) { rej_t[orj] = t; rej_k[orj] = pc[u]; }
+                else rejected[orj] = t;
+            }
+            orj++;
+        }
+    }
+}
+
 __global__ __launch_bounds__(1024) void k6_select(const uint8_t* __restrict__ status, const float* __restrict__ pcs,
                                                   const float* __restrict__ rcs, int n_tracks, int min_new_points,
                                                   int32_t* __restrict__ accepted, int32_t* __restrict__ inconsistent,
                                                   int32_t* __restrict__ rejected, int32_t* __restrict__ counts)
 {
+    __shared__ int32_t rej_t[K6B_REJ_LDS];
+    __shared__ float rej_k[K6B_REJ_LDS];
     const int T = blockDim.x, chunk = (n_tracks + T - 1) / T;
     const int lo = min((int)threadIdx.x * chunk, n_tracks), hi = min(lo + chunk, n_tracks);
-    int na = 0, nr = 0, ni = 0;
-    for (int t = lo; t < hi; t++) {
-        const int st = status[t];
-        if (st == 2) ni++;
-        else if (st == 1) { if (pcs[t] <= rcs[t]) na++; else nr++; }
-    }
     int tot_a, tot_r, tot_i;
-    int oa = rs_block_exclusive_scan(na, &tot_a);
-    int orj = rs_block_exclusive_scan(nr, &tot_r);
-    int oi = rs_block_exclusive_scan(ni, &tot_i);
-    for (int t = lo; t < hi; t++) {
-        const int st = status[t];
-        if (st == 2) inconsistent[oi++] = t;
-        else if (st == 1) { if (pcs[t] <= rcs[t]) accepted[oa++] = t; else rejected[orj++] = t; }
+    bool in_lds = false;
+#define K6B_HELD(CH) k6_select_held<CH>(status, pcs, rcs, lo, hi, min_new_points, accepted, inconsistent, rejected, rej_t, rej_k, &tot_a, &tot_r, &tot_i, &in_lds)
+    if (chunk <= 1) K6B_HELD(1);
+    else if (chunk <= 2) K6B_HELD(2);
+    else if (chunk <= 4) K6B_HELD(4);
+    else if (chunk <= K6B_CH) K6B_HELD(8);
+#undef K6B_HELD
+    else {
+        int na = 0, nr = 0, ni = 0;
+        for (int t = lo; t < hi; t++) {
+            const int st = status[t];
+            if (st == 2) ni++;
+            else if (st == 1) { if (pcs[t] <= rcs[t]) na++; else nr++; }
+        }
+        int oa = rs_block_exclusive_scan(na, &tot_a);
+        int orj = rs_block_exclusive_scan(nr, &tot_r);
+        int oi = rs_block_exclusive_scan(ni, &tot_i);
+        for (int t = lo; t < hi; t++) {
+            const int st = status[t];
+            if (st == 2) inconsistent[oi++] = t;
+            else if (st == 1) { if (pcs[t] <= rcs[t]) accepted[oa++] = t; else rejected[orj++] = t; }
+        }
     }
     __threadfence_block();
     __syncthreads();
     int top = 0;
     if (tot_a < min_new_points && tot_r > 0) {
         top = min(min_new_points - tot_a, tot_r);
-        for (int i = threadIdx.x; i < tot_r; i += T) {
-            const int ti = rejected[i];
-            const float ki = pcs[ti];
-            int rank = 0;
-            for (int j = 0; j < tot_r; j++) {
-                const float kj = pcs[rejected[j]];
-                // kj sorts before ki:  kj < ki, or equal (or both unordered) and earlier; NaN after everything
-                const bool before = (kj < ki) || (!(ki < kj) && !(kj < ki) && ((kj == kj) == (ki == ki)) && j < i) ||
-                                    ((kj == kj) && !(ki == ki));
-                rank += before ? 1 : 0;
+        if (in_lds) {
+            for (int i = threadIdx.x; i < tot_r; i += T) {
+                const float ki = rej_k[i];
+                int rank = 0;
+                for (int j = 0; j < tot_r; j++) rank += k6_before(rej_k[j], ki, j, i) ? 1 : 0;
+                if (rank < top) accepted[tot_a + rank] = rej_t[i];
             }
-            if (rank < top) accepted[tot_a + rank] = ti;
+        } else {
+            for (int i = threadIdx.x; i < tot_r; i += T) {
+                const int ti = rejected[i];
+                const float ki = pcs[ti];
+                int rank = 0;
+                for (int j = 0; j < tot_r; j++) rank += k6_before(pcs[rejected[j]], ki, j, i) ? 1 : 0;
+                if (rank < top) accepted[tot_a + rank] = ti;
+            }
         }
     }
     if (threadIdx.x == 0) { counts[0] = tot_a + top; counts[1] = top; counts[2] = tot_i; }

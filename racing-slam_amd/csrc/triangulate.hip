@@ -44,16 +44,62 @@ __device__ __forceinline__ void k4_triangulate_body(
     keep[i] = ok ? 1 : 0;
 }
 
+// K4b with the thread's chunk of at most CH correspondences held in registers.  The range is partitioned by the LAUNCH
+// bound, so that the thread's keep bytes, its positions and *d_n are in flight together — one global round trip, one
+// scan, one write phase.  Entries at or beyond *d_n count as not kept (below the launch bound they are valid memory); the
+// ordered compaction does not depend on how the range is cut into chunks.  CH is the smallest of 1, 2, 4, 8 that holds
+// the chunk: the one workgroup issues every load through one CU's address path, and clamped loads it does not need
+// cost more there than the round trip they overlap.
+template <int CH>
+__device__ __forceinline__ void k4_compact_held(const uint8_t* __restrict__ keep, const float* __restrict__ xyz, int lo, int hi,
+                                                const int32_t* __restrict__ d_n, int32_t* __restrict__ out_index,
+                                                float* __restrict__ out_xyz, int32_t* __restrict__ out_count)
+{
+    uint8_t k[CH];
+    float x[CH][3];
+#pragma unroll
+    for (int u = 0; u < CH; u++) {
+        const int i = max(min(lo + u, hi - 1), 0);                         // clamped: no branches around the loads
+        k[u] = keep[i];
+        x[u][0] = xyz[3 * (size_t)i + 0]; x[u][1] = xyz[3 * (size_t)i + 1]; x[u][2] = xyz[3 * (size_t)i + 2];
+    }
+    const int live = d_n ? min(hi, *d_n) : hi;
+    int cnt = 0;
+#pragma unroll
+    for (int u = 0; u < CH; u++) cnt += (lo + u < live && k[u] != 0) ? 1 : 0;
+    int total;
+    int off = rs_block_exclusive_scan(cnt, &total);
+#pragma unroll
+    for (int u = 0; u < CH; u++) {
+        if (lo + u >= live || k[u] == 0) continue;
+        out_index[off] = lo + u;
+        out_xyz[3 * (size_t)off + 0] = x[u][0];
+        out_xyz[3 * (size_t)off + 1] = x[u][1];
+        out_xyz[3 * (size_t)off + 2] = x[u][2];
+        off++;
+    }
+    if (threadIdx.x == 0) *out_count = total;
+}
+
 // Ordered compaction of the kept correspondences (:102) by ONE workgroup of any size.
 __device__ __forceinline__ void k4_compact_body(const uint8_t* __restrict__ keep, const float* __restrict__ xyz,
                                                 int n, const int32_t* __restrict__ d_n,
                                                 int32_t* __restrict__ out_index, float* __restrict__ out_xyz,
                                                 int32_t* __restrict__ out_count)
 {
+    const int T = blockDim.x;
+    if (n <= 8 * T) {                                                      // workgroup-uniform: the launch bound
+        const int chunk = (n + T - 1) / T;
+        const int lo = min((int)threadIdx.x * chunk, n), hi = min(lo + chunk, n);
+        if (chunk <= 1) return k4_compact_held<1>(keep, xyz, lo, hi, d_n, out_index, out_xyz, out_count);
+        if (chunk <= 2) return k4_compact_held<2>(keep, xyz, lo, hi, d_n, out_index, out_xyz, out_count);
+        if (chunk <= 4) return k4_compact_held<4>(keep, xyz, lo, hi, d_n, out_index, out_xyz, out_count);
+        return k4_compact_held<8>(keep, xyz, lo, hi, d_n, out_index, out_xyz, out_count);
+    }
     if (d_n) n = min(n, *d_n);
     // every thread owns a contiguous chunk: count, one workgroup scan, ordered write.  Loads go out in
     // batches (clamped addresses, no branches) so that their latencies overlap.
-    const int T = blockDim.x, chunk = (n + T - 1) / T;
+    const int chunk = (n + T - 1) / T;
     const int lo = min((int)threadIdx.x * chunk, n), hi = min(lo + chunk, n);
     int cnt = 0;
     for (int i0 = lo; i0 < hi; i0 += 16) {
