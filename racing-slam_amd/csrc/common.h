@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/rsgpu.h"
+#include "dev_array.h"
 
 #define RS_WAVE 64
 
@@ -84,17 +85,15 @@ struct rs_context {
     std::vector<rs_context*> batch_lanes;
     std::vector<hipStream_t> batch_streams;
     // proposal table of rs_reproj_match: persistent, always left at all-ones by the accept tail
-    unsigned long long* prop = nullptr;
-    size_t prop_cap = 0;
+    rs_dev_array<unsigned long long> prop;
     hipEvent_t sync_ev = nullptr;       // rs_context_wait_for: "everything enqueued on this context so far"
     void* tri_pin = nullptr;            // pinned in / out block + completion flag of rs_triangulate_host's one-launch path
     int tri_ticket = 0;
-    void* k1_top = nullptr;             // [batch][nq] {best, second} packed keys of rs_match_descriptors; all-ones between calls
-    size_t k1_top_cap = 0;
+    rs_dev_array<uint2> k1_top;         // [batch][nq] {best, second} packed keys of rs_match_descriptors; all-ones between calls
 };
 
-// A frame's keypoints, descriptors and flattened KD-tree on the device (map.hip: built on the host and uploaded by
-// rs_frame_create; frame.hip: filled from device arrays by rs_frame_assign_device).
+// A frame's keypoints, descriptors and flattened KD-tree on the device (frame.hip: built on the host and uploaded by
+// rs_frame_create, or filled from device arrays by rs_frame_assign_device).
 struct rs_frame {
     rs_context* ctx = nullptr;
     int n = 0;
@@ -102,7 +101,6 @@ struct rs_frame {
     uint8_t* d_matched = nullptr;
     void* d_packed = nullptr;           // {x, y, left, right}[n] + keypoint[n]: what K2 stages in LDS (rs_kdtree_pack layout)
     int kd_root = -1;
-    std::vector<float> kp;              // host copy of the keypoints (rs_frame_create only; nothing reads it)
     // rs_frame_create_device: every buffer above holds `cap` keypoints and is refilled by rs_frame_assign_device
     int cap = 0;                        // 0 = built by rs_frame_create: exactly n, not assignable
     uint32_t* d_rank = nullptr;         // [cap] rank_x | rank_y << 16 of the last assign

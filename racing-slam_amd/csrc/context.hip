@@ -60,8 +60,6 @@ extern "C" int rs_context_destroy(rs_context* ctx)
     arena_free(ctx->stage_dev, false);
     arena_free(ctx->stage_pin, true);
     if (ctx->ws) (void)hipFree(ctx->ws);
-    if (ctx->prop) (void)hipFree(ctx->prop);
-    if (ctx->k1_top) (void)hipFree(ctx->k1_top);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->tri_pin) (void)hipHostFree(ctx->tri_pin);
     if (ctx->sync_ev) (void)hipEventDestroy(ctx->sync_ev);
@@ -197,6 +195,25 @@ extern "C" int rs_context_synchronize(rs_context* ctx)
 }
 
 extern "C" const char* rs_last_error(const rs_context* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
+
+// rs_dev_array<T>::reserve past its capacity (dev_array.h).  With nothing to keep the old block is freed first, so that the
+// two never coexist; with entries to keep the new block is made first, and a failure leaves the array as it was.
+int rs_dev_array_grow(rs_context* ctx, void** p, size_t* cap, size_t elem, size_t need, size_t first, size_t keep_entries, rs_grow_policy policy)
+{
+    size_t want = policy == RS_GROW_ROUND_UP ? (need + first - 1) / first * first : (*cap ? *cap : first);
+    while (want < need) want *= 2;
+    void *old = *p, *q = nullptr;
+    if (old) RS_HIP(ctx, hipStreamSynchronize(ctx->stream));          // nothing in flight reads the old block
+    if (old && !keep_entries) { *p = nullptr; *cap = 0; RS_HIP(ctx, hipFree(old)); old = nullptr; }
+    if (hipMalloc(&q, elem * want) != hipSuccess) return rs_fail(ctx, RS_ERR_NOMEM, "device array of %zu entries of %zu bytes", want, elem);
+    if (old && hipMemcpy(q, old, elem * keep_entries, hipMemcpyDeviceToDevice) != hipSuccess) {
+        (void)hipFree(q);
+        return rs_fail(ctx, RS_ERR_HIP, "keeping %zu entries of a device array failed", keep_entries);
+    }
+    if (old) (void)hipFree(old);
+    *p = q; *cap = want;
+    return RS_OK;
+}
 
 int rs_workspace(rs_context* ctx, size_t bytes, void** out)
 {

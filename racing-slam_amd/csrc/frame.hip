@@ -1,6 +1,8 @@
-// frame.hip — an rs_frame (re)filled from DEVICE arrays: the front end's keypoint lists and descriptor rows go into the
-// frame's buffers and its KD-tree is built on the device, bit-identical to what rs_frame_create builds on the host from
-// the same data (rs_kdtree_build, host.cpp; reference src/KDTree.cpp:8-43).
+// frame.hip — rs_frame: keypoints, descriptors and the flattened KD-tree, uploaded once and shared by the match calls of a
+// frame.  rs_frame_create builds the tree on the host (rs_kdtree_build, host.cpp; reference src/Frame.cpp:8-15,
+// src/KDTree.cpp:8-43).  The rest of this file is an rs_frame (re)filled from DEVICE arrays: the front end's keypoint lists
+// and descriptor rows go into the frame's buffers and its KD-tree is built on the device, bit-identical to what
+// rs_frame_create builds from the same data.
 //
 // rs_kdtree_build orders keypoints by the total order (coordinate, keypoint index); the node of a segment [s, e) at depth
 // d is THE element of rank mid = (s + e) / 2 of that segment under axis d % 2, and its node id is mid.  Hence root, left[]
@@ -180,6 +182,62 @@ static size_t frame_build_lds(int cap)
     return 2 * 5 * np + 4 * np + 4 * FB_THREADS;
 }
 
+// The buffers of a frame of `rows` keypoints, its match table at -1 (no map match yet).  An assignable frame
+// (rs_frame_create_device) also gets the rank table, the two count words and d_packed in full.  Both constructors go through
+// here, and on any failure after `new rs_frame` through rs_frame_destroy, which frees whatever was made.
+static int frame_alloc(rs_context* ctx, rs_frame* f, size_t rows, bool assignable)
+{
+    bool ok = hipMalloc((void**)&f->d_kp, sizeof(float) * 2 * rows) == hipSuccess && hipMalloc((void**)&f->d_desc, 32 * rows) == hipSuccess &&
+              hipMalloc((void**)&f->d_kd, sizeof(int32_t) * 3 * rows) == hipSuccess && hipMalloc((void**)&f->d_matched, rows) == hipSuccess &&
+              hipMalloc((void**)&f->d_kp_point, sizeof(int32_t) * rows) == hipSuccess;
+    if (assignable)
+        ok = ok && hipMalloc(&f->d_packed, 20 * rows) == hipSuccess && hipMalloc((void**)&f->d_rank, sizeof(uint32_t) * rows) == hipSuccess &&
+             hipMalloc((void**)&f->d_n, sizeof(int32_t)) == hipSuccess && hipHostMalloc((void**)&f->h_n, sizeof(int32_t)) == hipSuccess;
+    ok = ok && hipMemsetAsync(f->d_kp_point, 0xFF, sizeof(int32_t) * rows, ctx->stream) == hipSuccess;
+    return ok ? RS_OK : rs_fail(ctx, RS_ERR_NOMEM, "frame buffers");
+}
+
+// rs_frame_create's uploads: the caller's arrays, the tree rs_kdtree_build made of them (kd: node_kp | left | right, stride n)
+// and its packed form (rs_kdtree_pack's layout).  Integer and copy work only: nothing here depends on this file's
+// -ffp-contract=off.
+static int frame_upload(rs_context* ctx, rs_frame* f, const float* h_kp, const uint8_t* h_desc, const std::vector<int32_t>& kd)
+{
+    const size_t m = (size_t)f->n;
+    hipStream_t s = ctx->stream;
+    std::vector<int32_t> packed(5 * m);
+    for (size_t i = 0; i < m; i++) {
+        const int32_t kpi = kd[i];
+        memcpy(&packed[4 * i], &h_kp[2 * (size_t)kpi], 8);
+        packed[4 * i + 2] = kd[m + i];
+        packed[4 * i + 3] = kd[2 * m + i];
+        packed[4 * m + i] = kpi;
+    }
+    if (hipMalloc(&f->d_packed, 20 * m) != hipSuccess) return rs_fail(ctx, RS_ERR_NOMEM, "frame buffers");
+    RS_HIP(ctx, hipMemcpyAsync(f->d_kp, h_kp, sizeof(float) * 2 * m, hipMemcpyHostToDevice, s));
+    RS_HIP(ctx, hipMemcpyAsync(f->d_desc, h_desc, 32 * m, hipMemcpyHostToDevice, s));
+    RS_HIP(ctx, hipMemcpyAsync(f->d_kd, kd.data(), sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice, s));
+    RS_HIP(ctx, hipMemcpyAsync(f->d_packed, packed.data(), 20 * m, hipMemcpyHostToDevice, s));
+    RS_HIP(ctx, hipStreamSynchronize(s));       // the sources are the caller's / this call's memory
+    return RS_OK;
+}
+
+extern "C" int rs_frame_create(rs_context* ctx, const float* h_kp, const uint8_t* h_desc, int n, rs_frame** out)
+{
+    if (!ctx || !out || n < 0 || (n > 0 && (!h_kp || !h_desc))) return RS_ERR_INVALID;
+    RS_HIP(ctx, hipSetDevice(ctx->device));
+    rs_frame* f = new rs_frame();
+    f->ctx = ctx;
+    f->n = n;
+    const size_t m = n > 0 ? (size_t)n : 1;
+    std::vector<int32_t> kd(3 * m);
+    if (n > 0) rs_kdtree_build(h_kp, n, kd.data(), kd.data() + m, kd.data() + 2 * m, &f->kd_root);     // src/Frame.cpp:8-15
+    int rc = frame_alloc(ctx, f, m, false);
+    if (!rc && n > 0) rc = frame_upload(ctx, f, h_kp, h_desc, kd);       // (n == 0: no tree, d_packed stays null)
+    if (rc) { rs_frame_destroy(f); return rc; }
+    *out = f;
+    return RS_OK;
+}
+
 extern "C" int rs_frame_create_device(rs_context* ctx, int max_points, rs_frame** out)
 {
     if (!ctx || !out) return RS_ERR_INVALID;
@@ -188,17 +246,23 @@ extern "C" int rs_frame_create_device(rs_context* ctx, int max_points, rs_frame*
     rs_frame* f = new rs_frame();
     f->ctx = ctx;
     f->cap = max_points;
-    const size_t m = (size_t)max_points;
-    if (hipMalloc((void**)&f->d_kp, sizeof(float) * 2 * m) != hipSuccess || hipMalloc((void**)&f->d_desc, 32 * m) != hipSuccess ||
-        hipMalloc((void**)&f->d_kd, sizeof(int32_t) * 3 * m) != hipSuccess || hipMalloc((void**)&f->d_matched, m) != hipSuccess ||
-        hipMalloc(&f->d_packed, 20 * m) != hipSuccess || hipMalloc((void**)&f->d_rank, sizeof(uint32_t) * m) != hipSuccess ||
-        hipMalloc((void**)&f->d_n, sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&f->d_kp_point, sizeof(int32_t) * m) != hipSuccess || hipHostMalloc((void**)&f->h_n, sizeof(int32_t)) != hipSuccess ||
-        hipMemsetAsync(f->d_kp_point, 0xFF, sizeof(int32_t) * m, ctx->stream) != hipSuccess) {       // no map match yet
-        rs_frame_destroy(f);
-        return rs_fail(ctx, RS_ERR_NOMEM, "frame buffers");
-    }
+    const int rc = frame_alloc(ctx, f, (size_t)max_points, true);
+    if (rc) { rs_frame_destroy(f); return rc; }
     *f->h_n = 0;
     *out = f;
+    return RS_OK;
+}
+
+extern "C" int rs_frame_destroy(rs_frame* f)
+{
+    if (!f) return RS_OK;
+    (void)hipSetDevice(f->ctx->device);
+    (void)hipStreamSynchronize(f->ctx->stream);
+    for (void* p : {(void*)f->d_kp, (void*)f->d_desc, (void*)f->d_kd, (void*)f->d_matched, f->d_packed, (void*)f->d_rank, (void*)f->d_n,
+                    (void*)f->d_kp_point})
+        if (p) (void)hipFree(p);
+    if (f->h_n) (void)hipHostFree(f->h_n);
+    delete f;
     return RS_OK;
 }
 

@@ -165,14 +165,10 @@ __global__ __launch_bounds__(1024) void k1_merge_filter(
 // all-ones again.  Growing synchronises the stream.  (loop.hip reserves it at creation so that no call allocates.)
 int rs_k1_reserve(rs_context* ctx, size_t entries)
 {
-    if (entries <= ctx->k1_top_cap) return RS_OK;
-    RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->k1_top) RS_HIP(ctx, hipFree(ctx->k1_top));
-    ctx->k1_top = nullptr; ctx->k1_top_cap = 0;
-    const size_t cap = (entries + 4095) & ~(size_t)4095;
-    if (hipMalloc(&ctx->k1_top, sizeof(uint2) * cap) != hipSuccess) return rs_fail(ctx, RS_ERR_NOMEM, "top-2 table of %zu entries", cap);
-    RS_HIP(ctx, hipMemsetAsync(ctx->k1_top, 0xFF, sizeof(uint2) * cap, ctx->stream));
-    ctx->k1_top_cap = cap;
+    bool fresh = false;
+    const int rc = ctx->k1_top.reserve(ctx, entries, 4096, 0, &fresh, RS_GROW_ROUND_UP);
+    if (rc) return rc;
+    if (fresh) RS_HIP(ctx, hipMemsetAsync(ctx->k1_top, 0xFF, sizeof(uint2) * ctx->k1_top.cap, ctx->stream));
     return RS_OK;
 }
 
@@ -203,7 +199,7 @@ static int knn2_launch(rs_context* ctx, const uint8_t* d_query, int nq, const ui
     if ((size_t)nqb * nsplit * batch > 0x7fffffffu) return rs_fail(ctx, RS_ERR_UNSUPPORTED, "too many query blocks for one launch");
     const int krc = rs_k1_reserve(ctx, (size_t)batch * nq);
     if (krc) return krc;
-    void* ws = ctx->k1_top;
+    uint2* ws = ctx->k1_top;
     {
         rs_prof_scope ps(ctx, "K1_hamming_knn2");
         hipLaunchKernelGGL(k1_hamming_knn2, dim3((unsigned)((size_t)nqb * nsplit * batch)), dim3(64 * K1_WAVES), 0, ctx->stream,

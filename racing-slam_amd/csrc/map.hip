@@ -20,57 +20,40 @@
 // in place, src/Map.cpp:63-76), which is what decides ties between points (src/MapMatcher.cpp:95-97).  Observation order
 // within a point = insertion order (the reference iterates an unordered_map: unspecified upstream).
 //
-// rs_frame is the per-frame counterpart: keypoints, descriptors and the flattened KD-tree (built once, like the
-// reference builds it in the Frame constructor, src/Frame.cpp:8-15) uploaded once and shared by the two match calls of a
-// frame; a frame that becomes a key frame hands its descriptor rows to the pool device-to-device.
+// rs_frame (frame.hip) is the per-frame counterpart; a frame that becomes a key frame hands its descriptor rows and keypoints
+// to the pools device-to-device.
 #include <algorithm>
 
 #include "common.h"
 #include "map_mirror.h"
 
 // (MapObs, MapKeyFrame and the mirror's fields and edits: map_mirror.h)
+#define MAP_FIRST 1024                  // first capacity, in entries, of every array below that has no other (32 pool rows, 64 poses)
+#define MAP_FIRST_POINTS 4096           // ... of the per-point arrays, in slots
+#define MAP_FIRST_OBS 16384             // ... of the per-observation arrays
+
 struct rs_map : MapMirror {
     rs_context* ctx = nullptr;
-    // device image
-    float* d_pos = nullptr; uint8_t* d_alive = nullptr; int32_t* d_obs_ptr = nullptr;
-    int32_t* d_obs_kf = nullptr; int32_t* d_obs_desc = nullptr; float* d_centres = nullptr;
-    float* d_poses = nullptr;                       // [KF][16] the key frames' poses (hipMalloc: 16-byte aligned for load_pose), uploaded with the centres
-    uint8_t* d_pool = nullptr; uint8_t* d_elig = nullptr; uint8_t* d_flag = nullptr;
-    float* d_kp_pool = nullptr;                     // [pool rows][2] keypoints of the key frames, row for row with the descriptor pool
-    size_t cap_kp_pool = 0;
-    int32_t* d_kp_point = nullptr;                  // [pool rows] point slot of each key-frame keypoint or -1, row for row with the pool:
-    size_t cap_kp_point = 0, kp_point_rows = 0;     // rewritten after a topology change by rs_map_loop_sync, its only reader's entry
-    int32_t* d_win = nullptr; size_t cap_win = 0;   // scratch of rs_map_bundle_adjust: pid [P] | obs offset [P]; flags [P] of the key-frame stages
-    size_t cap_points = 0, cap_obs = 0, cap_kf = 0, cap_poses = 0, cap_pool_bytes = 0, pool_rows = 0, n_obs = 0;
-    // scratch for match results
-    int32_t* d_out = nullptr; size_t cap_out = 0;
+    // device image.  Per point slot, reserved together (map_reserve_points); d_flag and d_mark are all zero between calls, and
+    // d_consistent and d_mark belong to the tracker's per-frame stages (frame_matches.hip):
+    rs_dev_array<float> d_pos;
+    rs_dev_array<int32_t> d_obs_ptr;
+    rs_dev_array<uint8_t> d_alive, d_elig, d_flag, d_consistent;
+    rs_dev_array<uint32_t> d_mark;
+    rs_dev_array<int32_t> d_obs_kf, d_obs_desc;     // per observation, reserved together (map_reserve_obs)
+    rs_dev_array<float> d_centres, d_poses;         // [KF][3]; [KF][16] the poses (hipMalloc: 16-byte aligned for load_pose), uploaded with the centres
+    rs_dev_array<uint8_t> d_pool;                   // [pool rows][32] descriptors, append only
+    rs_dev_array<float> d_kp_pool;                  // [pool rows][2] keypoints of the key frames, row for row with the descriptor pool
+    rs_dev_array<int32_t> d_kp_point;               // [pool rows] point slot of each key-frame keypoint or -1, row for row with the pool:
+    size_t kp_point_rows = 0;                       // rewritten after a topology change by rs_map_loop_sync, its only reader's entry
+    rs_dev_array<int32_t> d_win;                    // scratch of rs_map_bundle_adjust: pid [P] | obs offset [P]; flags [P] of the key-frame stages
+    size_t pool_rows = 0, n_obs = 0;
+    rs_dev_array<int32_t> d_out;                    // scratch for match results
     std::vector<int32_t> h_obs_ptr, h_obs_kf, h_obs_desc, h_kp_point;
     std::vector<float> h_centres, h_poses;
-    // the tracker's per-frame stages (frame_matches.hip)
-    uint8_t* d_consistent = nullptr; uint32_t* d_mark = nullptr;    // [cap_points] both; d_mark all zero between calls
-    double* d_gather = nullptr;                     // pts [8192][3] f64 | uv [8192][2] f32 | n: the refit's gathered problem
+    rs_dev_array<double> d_gather;                  // pts [8192][3] f64 | uv [8192][2] f32 | n: the refit's gathered problem
     void* fuse = nullptr;                           // scratch of rs_map_fuse_loop (map_fuse.hip owns and frees it)
 };
-
-// (struct rs_frame: common.h — frame.hip fills one from device arrays)
-
-template <typename T>
-static int grow(rs_context* ctx, T** p, size_t* cap, size_t need, size_t keep_bytes)
-{
-    if (need <= *cap) return RS_OK;
-    size_t want = *cap ? *cap * 2 : 1024;
-    while (want < need) want *= 2;
-    T* q = nullptr;
-    if (hipMalloc((void**)&q, sizeof(T) * want) != hipSuccess) return rs_fail(ctx, RS_ERR_NOMEM, "map buffer of %zu entries", want);
-    if (*p) {
-        RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (keep_bytes) RS_HIP(ctx, hipMemcpy(q, *p, keep_bytes, hipMemcpyDeviceToDevice));
-        RS_HIP(ctx, hipFree(*p));
-    }
-    *p = q;
-    *cap = want;
-    return RS_OK;
-}
 
 extern "C" int rs_map_create(rs_context* ctx, rs_map** out)
 {
@@ -86,66 +69,8 @@ extern "C" int rs_map_destroy(rs_map* m)
     if (!m) return RS_OK;
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->stream);
-    for (void* p : {(void*)m->d_pos, (void*)m->d_alive, (void*)m->d_obs_ptr, (void*)m->d_obs_kf, (void*)m->d_obs_desc,
-                    (void*)m->d_centres, (void*)m->d_pool, (void*)m->d_elig, (void*)m->d_flag, (void*)m->d_out, (void*)m->d_kp_pool,
-                    (void*)m->d_win, (void*)m->d_kp_point, (void*)m->d_consistent, (void*)m->d_mark, (void*)m->d_gather, (void*)m->d_poses})
-        if (p) (void)hipFree(p);
     rs_map_fuse_release(m->fuse);
-    delete m;
-    return RS_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ frames
-extern "C" int rs_frame_create(rs_context* ctx, const float* h_kp, const uint8_t* h_desc, int n, rs_frame** out)
-{
-    if (!ctx || !out || n < 0 || (n > 0 && (!h_kp || !h_desc))) return RS_ERR_INVALID;
-    RS_HIP(ctx, hipSetDevice(ctx->device));
-    rs_frame* f = new rs_frame();
-    f->ctx = ctx;
-    f->n = n;
-    f->kp.assign(h_kp, h_kp + 2 * (size_t)n);
-    const size_t m = n > 0 ? (size_t)n : 1;
-    std::vector<int32_t> kd(3 * m);
-    int32_t root = -1;
-    if (n > 0) rs_kdtree_build(h_kp, n, kd.data(), kd.data() + m, kd.data() + 2 * m, &root);     // src/Frame.cpp:8-15
-    f->kd_root = root;
-    if (hipMalloc((void**)&f->d_kp, sizeof(float) * 2 * m) != hipSuccess || hipMalloc((void**)&f->d_desc, 32 * m) != hipSuccess ||
-        hipMalloc((void**)&f->d_kd, sizeof(int32_t) * 3 * m) != hipSuccess || hipMalloc((void**)&f->d_matched, m) != hipSuccess ||
-        hipMalloc((void**)&f->d_kp_point, sizeof(int32_t) * m) != hipSuccess ||
-        hipMemsetAsync(f->d_kp_point, 0xFF, sizeof(int32_t) * m, ctx->stream) != hipSuccess) {      // no map match yet
-        rs_frame_destroy(f);
-        return rs_fail(ctx, RS_ERR_NOMEM, "frame buffers");
-    }
-    if (n > 0) {
-        RS_HIP(ctx, hipMemcpyAsync(f->d_kp, h_kp, sizeof(float) * 2 * m, hipMemcpyHostToDevice, ctx->stream));
-        RS_HIP(ctx, hipMemcpyAsync(f->d_desc, h_desc, 32 * m, hipMemcpyHostToDevice, ctx->stream));
-        RS_HIP(ctx, hipMemcpyAsync(f->d_kd, kd.data(), sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice, ctx->stream));
-        std::vector<int32_t> packed(5 * m);
-        for (size_t i = 0; i < m; i++) {
-            const int32_t kpi = kd[i];
-            memcpy(&packed[4 * i], &h_kp[2 * (size_t)kpi], 8);
-            packed[4 * i + 2] = kd[m + i];
-            packed[4 * i + 3] = kd[2 * m + i];
-            packed[4 * m + i] = kpi;
-        }
-        if (hipMalloc(&f->d_packed, 20 * m) != hipSuccess) { delete f; return rs_fail(ctx, RS_ERR_NOMEM, "frame buffers"); }
-        RS_HIP(ctx, hipMemcpyAsync(f->d_packed, packed.data(), 20 * m, hipMemcpyHostToDevice, ctx->stream));
-        RS_HIP(ctx, hipStreamSynchronize(ctx->stream));       // the sources are the caller's / this function's memory
-    }
-    *out = f;
-    return RS_OK;
-}
-
-extern "C" int rs_frame_destroy(rs_frame* f)
-{
-    if (!f) return RS_OK;
-    (void)hipSetDevice(f->ctx->device);
-    (void)hipStreamSynchronize(f->ctx->stream);
-    for (void* p : {(void*)f->d_kp, (void*)f->d_desc, (void*)f->d_kd, (void*)f->d_matched, f->d_packed, (void*)f->d_rank, (void*)f->d_n,
-                    (void*)f->d_kp_point})
-        if (p) (void)hipFree(p);
-    if (f->h_n) (void)hipHostFree(f->h_n);
-    delete f;
+    delete m;                           // every device array frees itself
     return RS_OK;
 }
 
@@ -161,15 +86,14 @@ extern "C" int rs_map_add_keyframe(rs_map* m, const rs_frame* f, const float h_p
     rs_context* ctx = m->ctx;
     RS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t rows = m->pool_rows + (size_t)f->n;
-    int rc = grow(ctx, &m->d_pool, &m->cap_pool_bytes, 32 * (rows > 0 ? rows : 1), 32 * m->pool_rows);   // keeps the rows already there
+    int rc = m->d_pool.reserve(ctx, 32 * (rows > 0 ? rows : 1), MAP_FIRST, 32 * m->pool_rows);      // both keep the rows already there
     if (rc) return rc;
-    rc = grow(ctx, &m->d_kp_pool, &m->cap_kp_pool, 2 * (rows > 0 ? rows : 1), sizeof(float) * 2 * m->pool_rows);
+    rc = m->d_kp_pool.reserve(ctx, 2 * (rows > 0 ? rows : 1), MAP_FIRST, 2 * m->pool_rows);
     if (rc) return rc;
     MapKeyFrame k;
     k.n = f->n;
     k.pool_row = (int)m->pool_rows;
     memcpy(k.pose, h_pose, sizeof k.pose);
-    k.kp = f->kp;
     k.kp_point.assign((size_t)f->n, -1);
     if (f->n > 0)
         RS_HIP(ctx, hipMemcpyAsync(m->d_pool + 32 * m->pool_rows, f->d_desc, 32 * (size_t)f->n, hipMemcpyDeviceToDevice, ctx->stream));
@@ -243,6 +167,34 @@ extern "C" int rs_map_get_positions(const rs_map* m, int first, int count, float
 }
 
 // ------------------------------------------------------------------------------------------------ device image
+// The seven per-point arrays for P slots.  Nothing is kept: each is uploaded, recomputed or zeroed after it grew.  d_flag goes
+// first and its new capacity S (4096 doubled) is the slot capacity: every other array is reserved for S slots, not for P, so
+// all hold S of them (d_obs_ptr S + 1: its capacity 4097 doubled as often exceeds it) and none lags behind the others.  d_alive
+// goes last: only when all seven hold S slots does the compare below let a later call pass.
+static int map_reserve_points(rs_map* m, size_t P)
+{
+    if (P <= m->d_alive.cap) return RS_OK;
+    rs_context* ctx = m->ctx;
+    const size_t F = MAP_FIRST_POINTS;
+    bool zero_flag = false, zero_mark = false;
+    int rc;
+    if ((rc = m->d_flag.reserve(ctx, P, F, 0, &zero_flag))) return rc;
+    if (zero_flag) RS_HIP(ctx, hipMemsetAsync(m->d_flag, 0, m->d_flag.cap, ctx->stream));
+    const size_t S = m->d_flag.cap;
+    if ((rc = m->d_mark.reserve(ctx, S, F, 0, &zero_mark))) return rc;
+    if (zero_mark) RS_HIP(ctx, hipMemsetAsync(m->d_mark, 0, sizeof(uint32_t) * m->d_mark.cap, ctx->stream));
+    if ((rc = m->d_pos.reserve(ctx, 3 * S, 3 * F, 0, &m->dirty_positions)) || (rc = m->d_consistent.reserve(ctx, S, F, 0, &m->dirty_consistent)) ||
+        (rc = m->d_obs_ptr.reserve(ctx, S + 1, F + 1)) || (rc = m->d_elig.reserve(ctx, S, F)))
+        return rc;
+    return m->d_alive.reserve(ctx, S, F);
+}
+
+static int map_reserve_obs(rs_map* m, size_t n_obs)      // the two per-observation arrays, uploaded whole after every topology change
+{
+    const int rc = m->d_obs_kf.reserve(m->ctx, n_obs, MAP_FIRST_OBS);
+    return rc ? rc : m->d_obs_desc.reserve(m->ctx, n_obs, MAP_FIRST_OBS);
+}
+
 static int map_sync_device(rs_map* m)
 {
     rs_context* ctx = m->ctx;
@@ -261,37 +213,9 @@ static int map_sync_device(rs_map* m)
         }
         m->h_obs_ptr[P] = (int32_t)m->h_obs_kf.size();
         m->n_obs = m->h_obs_kf.size();
-        if (P > m->cap_points) {
-            // every per-point array is re-uploaded / recomputed / zeroed below: nothing to preserve
-            RS_HIP(ctx, hipStreamSynchronize(s));
-            for (void* q : {(void*)m->d_alive, (void*)m->d_obs_ptr, (void*)m->d_pos, (void*)m->d_elig, (void*)m->d_flag, (void*)m->d_consistent,
-                            (void*)m->d_mark})
-                if (q) RS_HIP(ctx, hipFree(q));
-            m->d_alive = nullptr; m->d_obs_ptr = nullptr; m->d_pos = nullptr; m->d_elig = nullptr; m->d_flag = nullptr;
-            m->d_consistent = nullptr; m->d_mark = nullptr;
-            size_t cap = m->cap_points ? m->cap_points : 4096;
-            while (cap < P) cap *= 2;
-            if (hipMalloc((void**)&m->d_alive, cap) != hipSuccess || hipMalloc((void**)&m->d_obs_ptr, sizeof(int32_t) * (cap + 1)) != hipSuccess ||
-                hipMalloc((void**)&m->d_pos, sizeof(float) * 3 * cap) != hipSuccess || hipMalloc((void**)&m->d_elig, cap) != hipSuccess ||
-                hipMalloc((void**)&m->d_flag, cap) != hipSuccess || hipMalloc((void**)&m->d_consistent, cap) != hipSuccess ||
-                hipMalloc((void**)&m->d_mark, sizeof(uint32_t) * cap) != hipSuccess)
-                return rs_fail(ctx, RS_ERR_NOMEM, "map buffers for %zu points", cap);
-            RS_HIP(ctx, hipMemsetAsync(m->d_flag, 0, cap, s));
-            RS_HIP(ctx, hipMemsetAsync(m->d_mark, 0, sizeof(uint32_t) * cap, s));
-            m->cap_points = cap;
-            m->dirty_positions = m->dirty_consistent = true;
-        }
-        if (m->n_obs > m->cap_obs) {
-            RS_HIP(ctx, hipStreamSynchronize(s));
-            if (m->d_obs_kf) RS_HIP(ctx, hipFree(m->d_obs_kf));
-            if (m->d_obs_desc) RS_HIP(ctx, hipFree(m->d_obs_desc));
-            m->d_obs_kf = nullptr; m->d_obs_desc = nullptr;
-            size_t cap = m->cap_obs ? m->cap_obs : 16384;
-            while (cap < m->n_obs) cap *= 2;
-            if (hipMalloc((void**)&m->d_obs_kf, sizeof(int32_t) * cap) != hipSuccess || hipMalloc((void**)&m->d_obs_desc, sizeof(int32_t) * cap) != hipSuccess)
-                return rs_fail(ctx, RS_ERR_NOMEM, "map buffers for %zu observations", cap);
-            m->cap_obs = cap;
-        }
+        int rc = map_reserve_points(m, P);
+        if (!rc) rc = map_reserve_obs(m, m->n_obs);
+        if (rc) return rc;
         // pageable sources: these three copies complete before returning only because of the synchronisation below
         if (P) RS_HIP(ctx, hipMemcpyAsync(m->d_alive, m->alive.data(), P, hipMemcpyHostToDevice, s));
         RS_HIP(ctx, hipMemcpyAsync(m->d_obs_ptr, m->h_obs_ptr.data(), sizeof(int32_t) * (P + 1), hipMemcpyHostToDevice, s));
@@ -304,18 +228,13 @@ static int map_sync_device(rs_map* m)
     if (m->dirty_centres) {
         m->h_centres.resize(3 * (KF ? KF : 1));
         for (size_t k = 0; k < KF; k++) centre_of(m->kfs[k].pose, &m->h_centres[3 * k]);
-        size_t ck = m->cap_kf;
-        int rc = grow(ctx, &m->d_centres, &ck, 3 * (KF ? KF : 1), 0);
+        int rc = m->d_centres.reserve(ctx, 3 * (KF ? KF : 1), MAP_FIRST);
         if (rc) return rc;
-        m->cap_kf = ck;
         if (KF) RS_HIP(ctx, hipMemcpyAsync(m->d_centres, m->h_centres.data(), sizeof(float) * 3 * KF, hipMemcpyHostToDevice, s));
         // the poses themselves, for the key-frame stages (rs_map_reanchor, rs_map_cull_points)
         m->h_poses.resize(16 * (KF ? KF : 1));
         for (size_t k = 0; k < KF; k++) memcpy(&m->h_poses[16 * k], m->kfs[k].pose, sizeof(float) * 16);
-        size_t cp = m->cap_poses;
-        rc = grow(ctx, &m->d_poses, &cp, 16 * (KF ? KF : 1), 0);
-        if (rc) return rc;
-        m->cap_poses = cp;
+        if ((rc = m->d_poses.reserve(ctx, 16 * (KF ? KF : 1), MAP_FIRST))) return rc;
         if (KF) RS_HIP(ctx, hipMemcpyAsync(m->d_poses, m->h_poses.data(), sizeof(float) * 16 * KF, hipMemcpyHostToDevice, s));
     }
     if (m->dirty_topology || m->dirty_positions || m->dirty_centres) RS_HIP(ctx, hipStreamSynchronize(s));
@@ -333,10 +252,7 @@ int rs_map_loop_sync(rs_map* m, rs_map_loop_view* out)
         rs_context* ctx = m->ctx;
         m->h_kp_point.clear();
         for (const auto& k : m->kfs) m->h_kp_point.insert(m->h_kp_point.end(), k.kp_point.begin(), k.kp_point.end());
-        size_t ck = m->cap_kp_point;
-        rc = grow(ctx, &m->d_kp_point, &ck, m->pool_rows ? m->pool_rows : 1, 0);
-        if (rc) return rc;
-        m->cap_kp_point = ck;
+        if ((rc = m->d_kp_point.reserve(ctx, m->pool_rows ? m->pool_rows : 1, MAP_FIRST))) return rc;
         if (m->pool_rows) {             // pageable source: complete before returning
             RS_HIP(ctx, hipMemcpyAsync(m->d_kp_point, m->h_kp_point.data(), sizeof(int32_t) * m->pool_rows, hipMemcpyHostToDevice, ctx->stream));
             RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -415,13 +331,9 @@ int rs_map_track_sync(rs_map* m, int n_keypoints, rs_map_track_view* out)
         RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
         m->dirty_consistent = false;
     }
-    if (!m->d_gather && hipMalloc((void**)&m->d_gather, (size_t)MAP_GATHER_MAX * 32 + 256) != hipSuccess)
-        return rs_fail(ctx, RS_ERR_NOMEM, "refit scratch");
+    if ((rc = m->d_gather.reserve(ctx, (size_t)MAP_GATHER_MAX * 4 + 32, (size_t)MAP_GATHER_MAX * 4 + 32))) return rc;      // one size, made once
     const size_t N = (size_t)(n_keypoints > 0 ? n_keypoints : 0);
-    size_t co = m->cap_out;
-    rc = grow(ctx, &m->d_out, &co, 2 * P + 4 * N + 1, 0);
-    if (rc) return rc;
-    m->cap_out = co;
+    if ((rc = m->d_out.reserve(ctx, 2 * P + 4 * N + 1, MAP_FIRST))) return rc;
     *out = rs_map_track_view{};
     out->n_kf = (int)m->kfs.size();
     out->mv = rs_map_view{(int)P, m->d_pos, m->d_elig, m->d_obs_ptr, m->d_obs_kf, m->d_obs_desc, m->d_centres, m->d_pool};
@@ -514,10 +426,7 @@ extern "C" int rs_map_match(rs_context* ctx, rs_map* m, rs_frame* f, const float
     const bool listed = n_only > 0;
     const int Pv = listed ? n_only : P;                  // points of the view the matcher runs on
     const size_t need = 2 * (size_t)Pv + 4 * (size_t)N + 1;
-    size_t co = m->cap_out;
-    rc = grow(ctx, &m->d_out, &co, need, 0);
-    if (rc) return rc;
-    m->cap_out = co;
+    if ((rc = m->d_out.reserve(ctx, need, MAP_FIRST))) return rc;
     rc = rs_stage_begin(ctx);
     if (rc) return rc;
     hipStream_t s = ctx->stream;
@@ -705,20 +614,27 @@ struct MapWindow {
     double* pts = nullptr; int32_t *ptr = nullptr, *cam = nullptr, *list = nullptr; float* uv = nullptr;
 };
 
-static int map_window_build(rs_context* ctx, rs_map* m, const std::vector<int32_t>& win, size_t C, MapWindow* w)
+// What map_window_build and map_keyframe_stage start with: the image brought up to date, d_win made, the staging pool begun and
+// the list's table of key frames in it.  d_win is the window build's pid [P] | obs offset [P] | totals [2] and the key-frame
+// stages' selection bytes [P] (nothing else uses it between calls); both size it 2 P + 2 words, so that the two users never
+// reallocate it in turn.
+static int map_stage_begin(rs_context* ctx, rs_map* m, const std::vector<int32_t>& win, int32_t** d_winkf)
 {
-    const size_t P = m->alive.size();
     RS_HIP(ctx, hipSetDevice(ctx->device));
     int rc = map_sync_device(m);
     if (rc) return rc;
-    size_t cw = m->cap_win;
-    rc = grow(ctx, &m->d_win, &cw, 2 * P + 2, 0);
-    if (rc) return rc;
-    m->cap_win = cw;
+    if ((rc = m->d_win.reserve(ctx, 2 * m->alive.size() + 2, MAP_FIRST))) return rc;
     if ((rc = rs_stage_begin(ctx))) return rc;
-    hipStream_t s = ctx->stream;
+    return rs_stage_upload(ctx, win.data(), sizeof(int32_t) * win.size(), (void**)d_winkf);
+}
+
+static int map_window_build(rs_context* ctx, rs_map* m, const std::vector<int32_t>& win, size_t C, MapWindow* w)
+{
+    const size_t P = m->alive.size();
     int32_t* d_winkf = nullptr;
-    if ((rc = rs_stage_upload(ctx, win.data(), sizeof(int32_t) * win.size(), (void**)&d_winkf))) return rc;
+    int rc = map_stage_begin(ctx, m, win, &d_winkf);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
     int32_t *d_pid = m->d_win, *d_off = d_pid + P, *d_tot = d_off + P;
     const int pb = (int)((P + 255) / 256);
     {
@@ -740,7 +656,7 @@ static int map_window_build(rs_context* ctx, rs_map* m, const std::vector<int32_
     {
         rs_prof_scope ps(ctx, "K9_window_build");
         hipLaunchKernelGGL(k_win_fill, dim3(pb), dim3(256), 0, s, (int)P, (int)C, d_pid, d_off, m->d_obs_ptr, m->d_obs_kf, m->d_obs_desc, d_winkf,
-                           m->d_pos, (const float2*)m->d_kp_pool, w->pts, w->list, w->ptr, w->cam, (float2*)w->uv, (int)w->Pf, (int)w->M);
+                           m->d_pos, (const float2*)m->d_kp_pool.p, w->pts, w->list, w->ptr, w->cam, (float2*)w->uv, (int)w->Pf, (int)w->M);
     }
     return RS_OK;
 }
@@ -862,20 +778,10 @@ extern "C" int rs_map_add_track_points(rs_map* m, int kf, const rs_track_results
 // what both device stages start with.  d_out: 2 + 4 P words (rs_kf_launch_*).
 static int map_keyframe_stage(rs_context* ctx, rs_map* m, const std::vector<int32_t>& win, int32_t** d_winkf, uint8_t** d_sel, int32_t** d_out)
 {
-    const size_t P = m->alive.size();
-    RS_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = map_sync_device(m);
+    int rc = map_stage_begin(ctx, m, win, d_winkf);
     if (rc) return rc;
-    // the per-slot selection bytes [P] live in rs_map_bundle_adjust's scratch (nothing else uses it between calls); it is
-    // grown to that call's size, 2 P + 2 words, so that the two users never reallocate it in turn
-    size_t cw = m->cap_win;
-    rc = grow(ctx, &m->d_win, &cw, 2 * P + 2, 0);
-    if (rc) return rc;
-    m->cap_win = cw;
-    if ((rc = rs_stage_begin(ctx))) return rc;
-    if ((rc = rs_stage_upload(ctx, win.data(), sizeof(int32_t) * win.size(), (void**)d_winkf))) return rc;
-    if ((rc = rs_stage_alloc(ctx, sizeof(int32_t) * (2 + 4 * P), (void**)d_out))) return rc;
-    *d_sel = (uint8_t*)m->d_win;                      // (not rs_map::d_flag, the matcher's table that is all zero between calls)
+    if ((rc = rs_stage_alloc(ctx, sizeof(int32_t) * (2 + 4 * m->alive.size()), (void**)d_out))) return rc;
+    *d_sel = (uint8_t*)m->d_win.p;                    // (not rs_map::d_flag, the matcher's table that is all zero between calls)
     return RS_OK;
 }
 

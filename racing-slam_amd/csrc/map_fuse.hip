@@ -36,35 +36,20 @@
 #define FUSE_MAX_KP 8192
 #define FUSE_HDR (RS_FUSE_MAX_COVISIBLE + 3)      // old frames [65] | n_old | S
 
+#define FUSE_FIRST 4096                           // first capacity of the three scratch arrays; nothing in them outlives a call
 struct FuseScratch {
     rs_frame* frame = nullptr;                    // the reusable internal frame of stage 3
-    int32_t* d_pro = nullptr; size_t cap_pro = 0; // prologue: shared [KF] | hdr [FUSE_HDR] | src_slot [P]
-    int32_t* d_win = nullptr; size_t cap_win = 0; // stage 3 (carved in rs_map_fuse_loop)
-    uint8_t* d_u8 = nullptr; size_t cap_u8 = 0;   // is_old [P] | alive copy [P] | eligible [P] | zeros [FUSE_MAX_KP]
+    rs_dev_array<int32_t> d_pro;                  // prologue: shared [KF] | hdr [FUSE_HDR] | src_slot [P]
+    rs_dev_array<int32_t> d_win;                  // stage 3 (carved in rs_map_fuse_loop)
+    rs_dev_array<uint8_t> d_u8;                   // is_old [P] | alive copy [P] | eligible [P] | zeros [FUSE_MAX_KP]
 };
 
-void rs_map_fuse_release(void* scratch)
+void rs_map_fuse_release(void* scratch)           // (rs_map_destroy has made the device current and drained the stream)
 {
     FuseScratch* s = (FuseScratch*)scratch;
     if (!s) return;
     if (s->frame) (void)rs_frame_destroy(s->frame);
-    for (void* p : {(void*)s->d_pro, (void*)s->d_win, (void*)s->d_u8})
-        if (p) (void)hipFree(p);
     delete s;
-}
-
-template <typename T>
-static int fuse_reserve(rs_context* ctx, T** p, size_t* cap, size_t need)
-{
-    if (need <= *cap) return RS_OK;
-    size_t want = *cap ? *cap : 4096;
-    while (want < need) want *= 2;
-    RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (*p) RS_HIP(ctx, hipFree(*p));
-    *p = nullptr; *cap = 0;
-    if (hipMalloc((void**)p, sizeof(T) * want) != hipSuccess) return rs_fail(ctx, RS_ERR_NOMEM, "fuse scratch of %zu entries", want);
-    *cap = want;
-    return RS_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ prologue
@@ -332,8 +317,8 @@ extern "C" int rs_map_fuse_loop(rs_context* ctx, rs_map* map, int query_kf, int 
     if (P > 0) {
         // ---- stage 1: the prologue on the entry image
         if ((rc = rs_map_fuse_sync(map, 1, &mv))) return rc;
-        if ((rc = fuse_reserve(ctx, &fs->d_pro, &fs->cap_pro, (size_t)KF + FUSE_HDR + P))) return rc;
-        if ((rc = fuse_reserve(ctx, &fs->d_u8, &fs->cap_u8, 3 * P + FUSE_MAX_KP))) return rc;
+        if ((rc = fs->d_pro.reserve(ctx, (size_t)KF + FUSE_HDR + P, FUSE_FIRST))) return rc;
+        if ((rc = fs->d_u8.reserve(ctx, 3 * P + FUSE_MAX_KP, FUSE_FIRST))) return rc;
         d_shared = fs->d_pro; d_hdr = d_shared + KF; d_src = d_hdr + FUSE_HDR;
         d_old = fs->d_u8; d_alive_w = d_old + P; d_elig = d_alive_w + P; d_zero = d_elig + P;
         std::vector<int32_t> kf_tab(2 * (size_t)KF);
@@ -416,7 +401,7 @@ extern "C" int rs_map_fuse_loop(rs_context* ctx, rs_map* map, int query_kf, int 
         // ptr x2 [S+1] | add [S] | point_kp [S] | point_dist [S] | prop_point, prop_dist [max_n] | counts [T] | jkp, jview, jpt [sum_n]
         // | view positions [3 S] | rows x2 x (kf, desc) [capO]
         const size_t words = 2 * (Sz + 1) + 3 * Sz + 2 * (size_t)max_n + T + 3 * sum_n + 3 * Sz + 4 * capO;
-        if ((rc = fuse_reserve(ctx, &fs->d_win, &fs->cap_win, words))) return rc;
+        if ((rc = fs->d_win.reserve(ctx, words, FUSE_FIRST))) return rc;
         int32_t* q = fs->d_win;
         d_ptr[0] = q; q += Sz + 1; d_ptr[1] = q; q += Sz + 1;
         int32_t* d_add = q; q += Sz;

@@ -16,7 +16,6 @@ struct MapKeyFrame {
     int n = 0;
     int pool_row = 0;                  // first row of its descriptors in the device pool
     float pose[16];
-    std::vector<float> kp;             // [n][2]
     std::vector<int32_t> kp_point;     // [n] point slot matched by keypoint i or -1 (Frame::map_matches)
 };
 

@@ -683,16 +683,10 @@ static int reproj_match_impl(rs_context* ctx, const rs_frame_view* fr, const rs_
         return rs_fail(ctx, RS_ERR_INVALID, "null output");
     if (P > 0 && (!d_point_kp || !d_point_dist || !mp->d_positions || !mp->d_eligible || !mp->d_obs_ptr))
         return rs_fail(ctx, RS_ERR_INVALID, "null map pointer");
-    if ((size_t)N > ctx->prop_cap) {     // grow-only; all-ones once, every call leaves it all-ones again
-        RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->prop) RS_HIP(ctx, hipFree(ctx->prop));
-        ctx->prop = nullptr; ctx->prop_cap = 0;
-        const size_t cap = ((size_t)N + 4095) & ~(size_t)4095;
-        if (hipMalloc(&ctx->prop, sizeof(unsigned long long) * cap) != hipSuccess)
-            return rs_fail(ctx, RS_ERR_NOMEM, "proposal table of %zu entries", cap);
-        RS_HIP(ctx, hipMemsetAsync(ctx->prop, 0xFF, sizeof(unsigned long long) * cap, ctx->stream));
-        ctx->prop_cap = cap;
-    }
+    bool fresh = false;                  // grow-only, in steps of 4096; all-ones once, every call leaves it all-ones again
+    const int prc = ctx->prop.reserve(ctx, (size_t)N, 4096, 0, &fresh, RS_GROW_ROUND_UP);
+    if (prc) return prc;
+    if (fresh) RS_HIP(ctx, hipMemsetAsync(ctx->prop, 0xFF, sizeof(unsigned long long) * ctx->prop.cap, ctx->stream));
     unsigned long long* prop = ctx->prop;
     if (P > 0) {
         K2Frame f;

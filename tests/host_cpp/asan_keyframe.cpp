@@ -26,7 +26,6 @@ static int add_keyframe(MapMirror* m, int n)
 {
     MapKeyFrame k;
     k.n = n;
-    k.kp.assign(2 * (size_t)n, 0.f);
     k.kp_point.assign((size_t)n, -1);
     for (int i = 0; i < 16; i++) k.pose[i] = i % 5 == 0 ? 1.f : 0.f;
     m->kfs.push_back(k);

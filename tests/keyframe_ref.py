@@ -195,11 +195,12 @@ def build_model(scene, replay=None):
     return model
 
 
-def match_frame_of(model, seed, n=120, extra=10):
+def match_frame_of(model, seed, n=120, extra=10, at=None):
     """A frame that sees some of the map: keypoints at the projections of observed alive points under a pose next to the
-    last key frame's, each with the descriptor of its point's first observation; dict(pose, keypoints, descriptors)."""
+    last key frame's (or to pose_of(at)), each with the descriptor of its point's first observation; dict(pose, keypoints,
+    descriptors)."""
     rng = np.random.default_rng(seed)
-    T = pose_of(model.n_kf(), rng)
+    T = pose_of(model.n_kf() if at is None else at, rng)
     cand = [p for p in model.alive_points() if model.obs[p]]
     pick = rng.permutation(len(cand))[:n]
     kp, de = [], []

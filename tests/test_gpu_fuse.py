@@ -261,6 +261,52 @@ def test_reuse_after_an_insertion_chain(ctx, rs):
         mm.close()
 
 
+def grown_between_fuses(c, model):
+    """The edits between the two fuses of the test below, on the model: a key frame of 1000 keypoints that alone observes 900
+    new points, then 4100 slots nothing observes.  Returns the calls that make them on an rs_map: (op, arguments)."""
+    rng = np.random.default_rng(5)
+    kp = np.stack([rng.uniform(5, 635, 1000), rng.uniform(5, 475, 1000)], 1).astype(np.float32)
+    desc = rng.integers(0, 256, (1000, 32), dtype=np.uint8)
+    kf = model.add_keyframe(kp, desc, model.kf_pose[c["query"]])[0]
+    calls = [("add_keyframe", kp, desc, model.kf_pose[kf])]
+    for i in range(5000):
+        xyz = np.array([rng.uniform(-2, 2), rng.uniform(-1.5, 1.5), rng.uniform(5, 7)], np.float32)
+        p = model.create_point(xyz, [(kf, i)] if i < 900 else [])[0]
+        calls.append(("add_point", xyz, [(p, kf, i)] if i < 900 else []))
+    return calls
+
+
+def test_the_scratch_is_outgrown_between_two_fuses(ctx, rs):
+    """The first fuse, with one window frame on a map of 153 slots, makes the three scratch arrays at their first sizes: the
+    prologue's KF + 68 + P = 231 words in 4096, the 3 P + 8192 = 8651 bytes in 16384 and stage 3's 4135 words in 8192.  The
+    map then grows (grown_between_fuses) and a second fuse, with another candidate and the whole window, needs each of them
+    larger: 5232 words, 23651 bytes, and through the 900 new observations more than 10000 words in stage 3."""
+    c = fuse_cases.general(23)
+    m, ref, _ = check_case(ctx, rs, dict(c, window=c["window"][:1], name="first fuse"), keep=True)
+    model = ref["model"]
+    for call_ in grown_between_fuses(c, model):
+        if call_[0] == "add_keyframe":
+            f = rs.ResidentFrame(ctx, call_[1], call_[2])
+            m.add_keyframe(f, call_[3])
+            f.close()
+        else:
+            m.add_point(call_[1])
+            for p, kf, kp in call_[2]:
+                m.add_observation(p, kf, kp)
+    assert_state(m, model, "grown")
+    c2 = dict(c, model=model, candidate=1, inliers=[], name="second fuse")
+    ref2 = run_ref(c2)
+    got = call(m, c2)
+    assert got["sections"] == ref2["journal"] and got["old_frames"] == ref2["old_frames"] and got["sources"].tolist() == ref2["sources"]
+    assert got["device_state_mismatches"] == 0 and got["n_entries"] > 0
+    assert_state(m, ref2["model"], "second fuse")
+    m2 = build_map(ctx, rs, ref2["model"])
+    for kf in (c["query"], 1):
+        assert probe(ctx, rs, m, ref2["model"], c, kf) == probe(ctx, rs, m2, ref2["model"], c, kf)
+    m2.close()
+    m.close()
+
+
 def test_fuse_points_equals_the_model(ctx, rs):
     """rs_map_fuse_points is Map::fuse: pairs that share observers, pairs that do not, a point with itself, dead slots"""
     c = fuse_cases.general(11)

@@ -7,7 +7,9 @@ point slots: across the block size, k_kf_compact's 1024-slot chunks and the 4096
 has at most one observation per key frame, so these maps reach 6 observations per point; the 40-observation lists are in
 test_long_observation_lists on a map of 40 small key frames.  tests/test_keyframe_cpu.py checks on the CPU that no mean
 error of these maps lies within 1e-3 px of the culling threshold, so the set comparisons test the kernel and not float noise.
-The whole chain through the C++ host form (slam::insert_key_frame) runs in tests/test_keyframe_host.py."""
+The whole chain through the C++ host form (slam::insert_key_frame) runs in tests/test_keyframe_host.py.
+test_every_buffer_of_the_map_is_outgrown_in_use grows one map of 64-keypoint key frames past every first capacity of the
+device image (GROW_STEPS), with the calls above and the other readers of the image in between."""
 import numpy as np
 import pytest
 
@@ -379,6 +381,147 @@ def test_the_calls_in_mapper_insert_order(ctx, rs, oracle):
     assert np.array_equal(got["removed"], want["removed"]) and bits(got["xyz"]) == bits(want["xyz"]) and got["n_removed"] > 0
     c.same_as_rebuilt(kfs)
     c.close()
+
+
+# ------------------------------------------------------------------------------------------ growth
+GROW_KP = 64                            # keypoints per key frame of the growing map
+# (key frames, point slots) after each step, and what the step outgrows of what the uses before it allocated.  First
+# capacities (csrc/map.hip): 1024 entries for the centres [KF][3], the poses [KF][16], d_win [2 P + 2], d_out
+# [2 P + 4 N + 1], d_kp_point [rows] and the two pools (32 bytes, 2 floats a row); 4096 point slots; 16384 observations.
+# Crossed elsewhere on a live map: 4096 slots (test_gpu_track.py), the pools with kept rows and d_kp_point
+# (test_gpu_resident_map_edits.py, test_gpu_loop_envelope.py), the two 4096-entry tables of the context
+# (test_gpu_match_envelope.py's two reuse tests).  Crossed only here: the 65th pose, the 342nd centre, d_win and d_out past
+# 1024 after a use, 16384 observations, and the second doubling of the slots; the fuse scratch in test_gpu_fuse.py.
+GROW_STEPS = [(64, 700),                # the poses fill their 1024 floats and d_kp_point its 4096 rows exactly
+              (65, 700),                # the 65th pose; 4160 rows in d_kp_point; both pools, which keep their rows
+              (65, 1100),               # d_win (2202 words after 2048) and d_out
+              (342, 1100),              # the 342nd centre; the pools and d_kp_point again
+              (342, 4096),              # 4096 slots and 16384 observations: both fit exactly, d_win grows
+              (342, 4097),              # the 4097th slot: the seven per-point arrays; its observations: the two per-observation arrays
+              (342, 8193),              # the slots double again (d_obs_ptr, one entry longer than the rest, must double with them) ...
+              (342, 8194)]              # ... and the next slot fits every one of the seven
+
+
+def growing_scene(seed=31):
+    """342 key frames and 8194 points laid out so that the map can be built in GROW_STEPS' order: a point's observers are
+    the least-filled key frames among those its step already has.  Slots below 1100 have 1 - 3 observers (the single ones
+    are what rs_map_reanchor moves); the later ones 5, then 4, so that slot 4095 brings the count to 16384 exactly; from
+    slot 4097 on one."""
+    rng = np.random.default_rng(seed)
+    n_kf, P = GROW_STEPS[-1]
+    poses = [R.pose_of(0.02 * k) for k in range(n_kf)]
+    pts = np.c_[rng.uniform(-2, 2, P), rng.uniform(-1.5, 1.5, P), rng.uniform(4, 8, P)].astype(np.float32)
+    kf_kp = [[] for _ in range(n_kf)]
+    fill = np.zeros(n_kf, np.int64)
+    obs = [[] for _ in range(P)]
+    for p in range(P):
+        have = next(kf for kf, slots in GROW_STEPS if p < slots)
+        n = 1 + p % 3 if p < 1100 else (5 if p < 3301 else 4 if p < 4097 else 1)
+        bad = rng.random() < 0.25
+        sign = rng.choice([-1.0, 1.0], 2)
+        for kf in sorted(np.argsort(fill[:have], kind="stable")[:n].tolist()):
+            off = sign * rng.uniform(5.0, 12.0, 2) if bad else rng.normal(0, 0.4, 2)
+            kf_kp[kf].append(R.project(poses[kf], pts[p]) + off)
+            obs[p].append((kf, int(fill[kf])))
+            fill[kf] += 1
+    assert fill.max() <= GROW_KP and sum(len(o) for o in obs[:4096]) == 16384
+    for kf in range(n_kf):
+        while len(kf_kp[kf]) < GROW_KP:
+            kf_kp[kf].append(rng.uniform((0, 0), (R.WIDTH, R.HEIGHT)))
+    return dict(poses=poses, points=pts, obs=obs, kf_kp=[np.array(k, np.float32).reshape(-1, 2) for k in kf_kp],
+                kf_desc=[rng.integers(0, 256, (GROW_KP, 32), dtype=np.uint8) for _ in range(n_kf)])
+
+
+def test_every_buffer_of_the_map_is_outgrown_in_use(ctx, rs, oracle):
+    """One map built in GROW_STEPS' order and used after every step, so that each grow-only buffer of the device image is
+    reallocated while the map is live.  A use: counts, positions, two plain matches (the second equal to the first: the flag
+    table came back all zero), a match by observer, match_frame's table (d_mark, the track-consistent flags), the BA window
+    against the model's, a loop verification's gathered rows, slots and positions (the pools' old rows, d_kp_point) against
+    the model, a dry cull and a re-anchor against the oracle; the matches and the window also against a map rebuilt from the
+    model in one go, which never reallocates."""
+    import types
+    from loop_checks import _check
+    from map_model import MapModel
+    s = growing_scene()
+    model, m = MapModel(), rs.ResidentMap(ctx)
+    replay = replay_on(m)
+    ver = ctx.loop_verifier(256, 2, 200)
+    rng = np.random.default_rng(32)
+    probe = None
+
+    def match_frame_table(mm):
+        f = rs.ResidentFrame(ctx, probe["keypoints"], probe["descriptors"])
+        n = mm.match_frame(f, probe["pose"], R.K, R.WIDTH, R.HEIGHT)
+        tab = f.matches()[0].tolist()
+        f.close()
+        return n, tab
+
+    def use(step):
+        n_kf = model.n_kf()
+        assert m.counts() == model.counts() and bits(m.positions()) == bits(model.positions()), step
+        ref = map_of(ctx, rs, model)
+        f = rs.ResidentFrame(ctx, probe["keypoints"], probe["descriptors"])
+        try:
+            first = m.match(f, probe["pose"], R.K, R.WIDTH, R.HEIGHT)
+            again = m.match(f, probe["pose"], R.K, R.WIDTH, R.HEIGHT)
+            want = ref.match(f, probe["pose"], R.K, R.WIDTH, R.HEIGHT)
+            assert len(first[0]) > 20 and all(np.array_equal(a, b) and np.array_equal(a, c) for a, b, c in zip(first, again, want)), step
+            for kf in (0, n_kf - 1):
+                got, want = (mm.match(f, probe["pose"], R.K, R.WIDTH, R.HEIGHT, required_observer=kf) for mm in (m, ref))
+                assert all(np.array_equal(a, b) for a, b in zip(got, want)), (step, kf)
+            assert match_frame_table(m) == match_frame_table(ref), step
+            kfs = np.array([0, 1, n_kf // 2, n_kf - 2, n_kf - 1], np.int32)
+            free = np.array([0, 1, 1, 1, 1], np.uint8)
+            a, b, w = m.window(kfs, free), ref.window(kfs, free), model.ba_window(kfs, free)
+            assert all(np.array_equal(a[k], b[k]) for k in a) and len(a["points"]) > 10, step
+            assert all(np.array_equal(a[k], w[k]) for k in ("points", "obs_ptr", "obs_cam")) and a["obs_uv"].tobytes() == w["obs_uv"].tobytes(), step
+        finally:
+            f.close()
+            ref.close()
+        # the loop view: the oldest and the newest key frame's rows gathered for a query in the middle
+        key_frames = [dict(kp=model.kf_kp[k], desc=model.kf_desc[k], pose=model.kf_pose[k].reshape(4, 4)) for k in range(n_kf)]
+        b = types.SimpleNamespace(s=dict(key_frames=key_frames, query=n_kf // 2, width=R.WIDTH), map=m, pos=model.positions(),
+                                  kp_point=[np.asarray(t, np.int32) for t in model.kp_point])
+        cands = [0, n_kf - 1]
+        _check(ver, b, cands, ver.verify(m, n_kf // 2, cands, R.K, R.WIDTH))
+        assert ver.download(0)["nt"] > 0, step
+        # a dry cull, then a re-anchor after a small move of the listed poses (the image's poses and centres follow)
+        kfs = [int(k) for k in kfs[1:]]
+        want = R.cull(model, kfs, R.K, oracle, apply=False)
+        assert R.cull_margin(want["mean_err"]) >= R.CULL_MARGIN and 0 < len(want["removed"]) < len(want["local"]), step
+        got = m.cull_points(kfs, R.K, apply=False)
+        assert np.array_equal(got["removed"], want["removed"]) and bits(got["xyz"]) == bits(want["xyz"]), step
+        before = np.stack([model.kf_pose[k] for k in kfs]).astype(np.float32)
+        for k in kfs:
+            replay(model.set_pose(k, R.perturb_pose(model.kf_pose[k], rng, angle=2e-4, step=5e-4)))
+        n, slots, xyz = m.reanchor(kfs, before)
+        want_slots, want_xyz = R.reanchor(model, kfs, before, oracle)
+        assert n == len(want_slots) > 0 and np.array_equal(slots, want_slots) and bits(xyz) == bits(want_xyz), step
+        assert bits(m.positions()) == bits(model.positions()), step
+
+    try:
+        for step, (n_kf, P) in enumerate(GROW_STEPS):
+            for k in range(model.n_kf(), n_kf):
+                model.add_keyframe(s["kf_kp"][k], s["kf_desc"][k], s["poses"][k])
+                f = rs.ResidentFrame(ctx, s["kf_kp"][k], s["kf_desc"][k])
+                assert m.add_keyframe(f, model.kf_pose[k]) == k
+                f.close()
+            for p in range(model.n_slots(), P):
+                replay(model.create_point(s["points"][p], s["obs"][p])[1])
+            if probe is None:
+                probe = R.match_frame_of(model, 31, at=0.02 * n_kf)
+            use(step)
+        assert model.counts()["observations"] > 16384 and model.consistent()
+        # the cull applied on the grown map, and a last use of what is left
+        kfs = list(range(300, 342))
+        want = R.cull(model, kfs, R.K, oracle, apply=True)
+        assert R.cull_margin(want["mean_err"]) >= R.CULL_MARGIN and len(want["removed"]) > 100
+        got = m.cull_points(kfs, R.K, apply=True)
+        assert np.array_equal(got["removed"], want["removed"]) and bits(got["xyz"]) == bits(want["xyz"])
+        use("after the cull")
+    finally:
+        ver.close()
+        m.close()
 
 
 # ------------------------------------------------------------------------------------------ refusals

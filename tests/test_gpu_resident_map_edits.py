@@ -217,8 +217,8 @@ def test_edit_sequences_match_the_model(ctx, rs, oracle, synth, seed):
         if i == 150:                                     # a BA, then a key frame larger than the whole pool: it must grow
             check_ba(mi, ctx, rs, oracle, np.arange(mi.model.n_kf()), [0, 0] + [1] * (mi.model.n_kf() - 2))
             mk, mpt = mi.check_match(oracle)
-            # grow() at least doubles, so a key frame with as many rows as the pool holds always outgrows it; its first rows
-            # are the matched frame's, so the matches below are observations at the end of the grown pools
+            # the pools at least double when they grow, so a key frame with as many rows as the pool holds always outgrows it;
+            # its first rows are the matched frame's, so the matches below are observations at the end of the grown pools
             rows = sum(len(k) for k in mi.model.kf_kp)
             big = np.random.default_rng(seed)
             kp = np.concatenate([mi.frame["keypoints"], big.uniform(0, 1920, (rows, 2)).astype(np.float32)])
