@@ -620,6 +620,7 @@ typedef enum rs_ba_termination {
  * reference only sets the iteration cap (src/Optimization.cpp:127-134). */
 typedef struct rs_ba_options {
     int max_num_iterations;             /* BA_ITERATIONS / POSE_ITERATIONS = 10 (:118-119) */
+                                        /* 0 .. 1000; 0: the cost and the gradient at the input, no step (NO_CONVERGENCE, usable) */
     double huber_delta;                 /* sqrt(5.991) (:219,:311) */
     double initial_trust_region_radius; /* 1e4 */
     double max_trust_region_radius;     /* 1e16 */

@@ -733,7 +733,8 @@ static inline BaPath ba_choose_path(const rs_context* ctx, const BaDims& d, int 
 template <class Enqueue>
 static inline int ba_follow_rounds(hipStream_t s, int max_iter, int ns, const BaProgress* const* prog, int n_windows, Enqueue enqueue, int& rounds)
 {
-    const int min_rounds = (max_iter + ns - 1) / ns;
+    // (max_iter 0 still takes one round: its front end evaluates the cost and the gradient at the input and ends the solve)
+    const int min_rounds = max_iter > 0 ? (max_iter + ns - 1) / ns : 1;
     for (rounds = 0; rounds < min_rounds; rounds++)
         if (const int rc = enqueue(rounds)) return rc;
     while (ns > 1 && rounds < max_iter) {

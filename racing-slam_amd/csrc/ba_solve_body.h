@@ -234,6 +234,7 @@ static __device__ __forceinline__ void ba_reduced_solve_lds_body(const BaDims& d
             for (int w = 0; w < nt / 64; w++) g = fmax(g, red[w]);
             if (!isfinite(st.x_cost)) { st.done = 1; st.termination = RS_BA_FAILURE; }
             else if (g <= opt.gtol) { st.done = 1; st.termination = RS_BA_CONVERGENCE_GRADIENT; }
+            else if (st.iter >= opt.max_iter) { st.done = 1; st.termination = RS_BA_NO_CONVERGENCE; }      // max_num_iterations 0: the costs and these two exits, no step
         }
         __syncthreads();
         if (st.done) { if (tid == 0 && set == 0) *b.st = st; publish(BA_HAND_TAKEN, 2ull); return; }      // every set reaches the same verdict

@@ -50,6 +50,7 @@ __device__ __forceinline__ bool ba_step_gradient_test(const BaBufs& b, const BaO
             for (int w = 0; w < (nt + 63) / 64; w++) gg = fmax(gg, red[w]);
             if (!isfinite(st->x_cost)) { st->done = 1; st->termination = RS_BA_FAILURE; }
             else if (gg <= opt.gtol) { st->done = 1; st->termination = RS_BA_CONVERGENCE_GRADIENT; }
+            else if (st->iter >= opt.max_iter) { st->done = 1; st->termination = RS_BA_NO_CONVERGENCE; }   // max_num_iterations 0: the costs and these two exits, no step
         }
     }
     __syncthreads();

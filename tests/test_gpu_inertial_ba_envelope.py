@@ -12,11 +12,11 @@ import numpy as np
 import pytest
 
 import inertial_cases as IC
+from ba_compare import assert_same_solve as _assert_same_solve      # (the contract shared with test_gpu_ba_envelope.py)
 from conftest import to_np
 
 pytestmark = pytest.mark.gpu
 
-SCHEDULE = ("iterations", "successful_steps", "termination", "usable")
 LDS, BIG = "K6i_imu_eliminate", "K7_ba_reduced_solve_inertial"
 INERTIAL = [k for k, c in IC.CASES.items() if c["imu"] is not None]
 VISION = [k for k, c in IC.CASES.items() if c["imu"] is None]
@@ -66,26 +66,6 @@ def _assert_path(g, want):
         assert lds and not big, g["prof"]
     else:
         assert big and not lds, g["prof"]
-
-
-def _close(a, b, rtol, atol=0.0):
-    return np.allclose(a, b, rtol=rtol, atol=atol, equal_nan=True)
-
-
-def _assert_same_solve(g, ref):
-    """g against ref = (cams, points, velocity, bias, summary, trace): the schedule exactly, values within the tolerances of
-    test_gpu_parity.py::test_bundle_adjust_inertial."""
-    rc, rp, rv, rb, rs_, otr = ref
-    s, tr = g["s"], g["tr"]
-    assert tuple(s[k] for k in SCHEDULE) == tuple(rs_[k] for k in SCHEDULE)
-    assert [t["outcome"] for t in tr] == [t["outcome"] for t in otr]
-    for k, tol in (("radius", 1e-7), ("cost", 1e-9), ("candidate_cost", 1e-6), ("model_cost_change", 1e-6), ("x_norm", 1e-6)):
-        assert _close([t[k] for t in tr], [t[k] for t in otr], tol), k
-    assert _close(s["initial_cost"], rs_["initial_cost"], 1e-12) and _close(s["final_cost"], rs_["final_cost"], 1e-8)
-    assert _close(g["c"], rc, 1e-7, 1e-9)
-    assert _close(g["p"], rp, 1e-6, 1e-7)
-    if rv is not None:
-        assert _close(g["v"], rv, 1e-7, 1e-9) and _close(g["b"], rb, 1e-6, 1e-9)
 
 
 def _assert_untouched_where_due(g, w, m):
