@@ -45,11 +45,9 @@ def num_matches(table):
     return int(np.count_nonzero(np.asarray(table) >= 0))
 
 
-def carry(alive, n_obs, consistent, prev_table, next_table, prev_index, inlier_index=None, count=None, max_n=None,
-          min_points=MIN_TRACKED_MAP_POINTS):
-    """Tracker::track_from_last_frame (:197-230).  Returns (next's table, candidates, accepted).  A dead slot in prev's
-    table (undefined behaviour in the reference) is no candidate."""
-    nxt = np.array(next_table, np.int32)
+def carry_candidates(alive, n_obs, consistent, prev_table, n_next, prev_index, inlier_index=None, count=None, max_n=None):
+    """The first loop of Tracker::track_from_last_frame (:204-214): (list position, next's keypoint, point) of every
+    candidate, in list order."""
     prev_index = np.asarray(prev_index, np.int64)
     max_n = len(prev_index) if max_n is None else max_n
     n = clamp_count(count, max_n)
@@ -57,7 +55,7 @@ def carry(alive, n_obs, consistent, prev_table, next_table, prev_index, inlier_i
     cand = []
     for i in range(n):
         j = int(inlier_index[i]) if inlier_index is not None else i
-        if j < 0 or j >= min(max_n, len(nxt)):
+        if j < 0 or j >= min(max_n, n_next):
             continue
         kq = int(prev_index[j])
         if kq < 0 or kq >= len(prev_table):
@@ -67,7 +65,16 @@ def carry(alive, n_obs, consistent, prev_table, next_table, prev_index, inlier_i
             continue
         if n_obs[p] < 2 and not consistent[p]:            # :209
             continue
-        cand.append((j, p))
+        cand.append((i, j, p))
+    return cand
+
+
+def carry(alive, n_obs, consistent, prev_table, next_table, prev_index, inlier_index=None, count=None, max_n=None,
+          min_points=MIN_TRACKED_MAP_POINTS):
+    """Tracker::track_from_last_frame (:197-230).  Returns (next's table, candidates, accepted).  A dead slot in prev's
+    table (undefined behaviour in the reference) is no candidate."""
+    nxt = np.array(next_table, np.int32)
+    cand = [(j, p) for _, j, p in carry_candidates(alive, n_obs, consistent, prev_table, len(nxt), prev_index, inlier_index, count, max_n)]
     if len(cand) < min_points:                            # :216-219
         return nxt, len(cand), 0
     accepted = 0
