@@ -102,8 +102,11 @@ int rs_context_fork(rs_context* ctx, rs_context* const* others, int n);
  * "ba_handoff_timeout_us": how long (1 .. 1000000, default 4000) a workgroup of that fused launch waits for a hand-off
  * word before it gives up; a solve in which that happened is re-run once as separate launches from its untouched
  * inputs (rs_ba_get_stats [4] counts them) — the caller sees the same result either way.
- * "k2_mode": rs_reproj_match — 0 (default) eight lanes per map point where the frame's KD-tree fits in LDS
- * (<= 6144 keypoints), 1 always one lane per point; the outputs are identical.
+ * "k2_mode": rs_reproj_match — 0 (default) eight lanes per map point where the frame has a usable cell grid
+ * (rs_kdtree_grid_build) or its KD-tree fits in LDS (<= 6144 keypoints), 1 always one lane per point walking the tree;
+ * the outputs are identical.
+ * "k2_grid": rs_reproj_match under k2_mode 0 — 1 (default) search the frame's cell grid where it has a usable one,
+ * 0 always walk the KD-tree; the outputs are identical.
  * "ba_batch_mode": how rs_bundle_adjust_batch runs its windows — 0 (default) one launch sequence for all of them
  * where the windows allow it, 1 always the lanes.
  * "gftt_round_launches": rs_detect_features — how many launches of the parallel minimum-distance round (0 .. 12,
@@ -202,11 +205,30 @@ typedef struct rs_frame_view {
                                       20 * n bytes, 16-byte aligned.  A frame is matched at least twice
                                       (src/Tracker.cpp:232-248): packing once saves every workgroup of both calls the
                                       dependent gathers node -> keypoint -> coordinates */
+    const void* d_kd_grid;         /* optional (NULL = none; a zero-initialised view has none): the frame's keypoints in a
+                                      cell grid, built by rs_kdtree_grid_build in this process for this frame */
 } rs_frame_view;
 
 /* Packs the flattened KD-tree of `frame` (its d_keypoints, d_kd_* arrays) into d_packed [n] x 20 bytes for
  * rs_frame_view::d_kd_packed. */
 int rs_kdtree_pack(rs_context* ctx, const rs_frame_view* frame, void* d_packed);
+
+/* The frame's keypoints in a uniform grid of 40-pixel cells over width x height, for rs_frame_view::d_kd_grid: with it
+ * rs_reproj_match finds a point's keypoints within its 20-pixel radius in the cells the disc touches instead of walking
+ * the KD-tree, and decides ties between equally distant keypoints by the order in which the reference's recursion would
+ * have met them, computed from their node ids.  The outputs are identical.  Built once per frame from d_kd_packed
+ * (required) and kd_root; the keypoint positions must not change afterwards, d_kp_matched may (it is read by every
+ * call).  d_grid: rs_kdtree_grid_bytes(n_keypoints, width, height) bytes, 16-byte aligned; the arrangement is a pure
+ * function of the input.  The build also decides whether the grid may stand in for the walk: only if the tree has the
+ * shape rs_kdtree_build gives it (root n / 2, children the mids of the two half ranges), every node lies on the correct
+ * side of each of its ancestors, and every coordinate is finite.  Otherwise (or above 65536 keypoints) the call still
+ * succeeds and rs_reproj_match keeps walking the tree for this frame.  The library remembers the verdict per process, for
+ * every context (a view may be matched on forked child contexts), so the call waits for the build (once per frame); a
+ * pointer it has not built a usable grid at is ignored.  Rebuild, or build an empty frame, at d_grid before its memory
+ * is reused for something else.
+ * "k2_grid" (rs_context_set_int): 1 (default) use a frame's grid under k2_mode 0, 0 never. */
+size_t rs_kdtree_grid_bytes(int n_keypoints, int width, int height);
+int rs_kdtree_grid_build(rs_context* ctx, const rs_frame_view* frame, void* d_grid);
 
 typedef struct rs_map_view {
     int n_points;                  /* candidate points, in MAP ORDER (src/Map.h:66) */

@@ -76,6 +76,7 @@ struct rs_context {
     int ba_fuse_mode = 0;               // local-window BA: 0 = K7 + K8 in one launch when this is the only solve in flight, 1 = never,
                                         // 2 = K7 + K8 in one launch wherever possible, 3 = the whole round (K5 + K7 + K8) wherever possible
     int k2_mode = 0;                    // rs_reproj_match: 0 = eight lanes per map point where the KD-tree fits in LDS, 1 = always one lane per point
+    int k2_grid = 1;                    // rs_reproj_match under k2_mode 0: 1 = the cell-grid kernel where the view carries a usable grid, 0 = never
     int ba_imu_mode = 0;                // inertial solves: 0 = z blocks eliminated around the LDS K7 where possible, 1 = always the N x N blocked solve
     int ba_batch_mode = 0;              // rs_bundle_adjust_batch: 0 = one grid for all windows where possible, 1 = lanes only
     int bow_score_mode = 0;             // rs_bow_database_score: 0 = the query's dense word table, 1 = binary search in its sorted words
@@ -108,9 +109,25 @@ struct rs_frame {
     int32_t* h_n = nullptr;             // pinned word the one read-back per assign lands in
     // Frame::m_map_matches (frame_matches.hip): point slot matched by keypoint i or -1; [cap], or [n] after rs_frame_create
     int32_t* d_kp_point = nullptr;
+    // the keypoints in K2's cell grid (rs_frame_grid): made when a match first asks for it, since only the match knows the
+    // image size; grow-only, rebuilt after every assign
+    rs_dev_array<unsigned char> grid;
+    int grid_w = 0, grid_h = 0;
+    bool grid_built = false;            // the grid holds this frame's keypoints for grid_w x grid_h
+    bool finite = false;                // every keypoint coordinate is known to be finite: the only thing a grid over this library's own tree needs
 };
+// frame.hip: the frame's cell grid for an image of width x height in *d_grid, or null where the frame has none (see `finite`)
+int rs_frame_grid(rs_context* ctx, rs_frame* f, int width, int height, const void** d_grid);
 
 int rs_fail(rs_context* ctx, int code, const char* fmt, ...);
+
+// reproj_match.hip: the cell grids K2 may use in place of its walk, remembered per process (a view travels between contexts).
+// rs_k2_grid_enqueue launches a build on the context stream without waiting for its verdict; a caller that knows the tree to be
+// this library's own over finite coordinates remembers the grid itself.
+int rs_k2_grid_enqueue(rs_context* ctx, int n, int kd_root, const void* d_packed, int width, int height, void* d_grid, bool validate, bool* built);
+void rs_k2_grid_remember(const void* d_grid, int n);
+void rs_k2_grid_forget(const void* d_grid);
+bool rs_k2_grid_usable(const void* d_grid, int n);
 
 // What loop.hip reads of an rs_map (map.hip: rs_map_loop_sync brings the device image up to date first).
 struct rs_map_loop_view {

@@ -164,6 +164,11 @@ extern "C" int rs_context_set_int(rs_context* ctx, const char* name, int value)
         ctx->k2_mode = value;
         return RS_OK;
     }
+    if (strcmp(name, "k2_grid") == 0) {
+        if (value < 0 || value > 1) return rs_fail(ctx, RS_ERR_INVALID, "k2_grid must be 1 (the cell-grid kernel where the frame has a usable grid) or 0 (never)");
+        ctx->k2_grid = value;
+        return RS_OK;
+    }
     if (strcmp(name, "ba_batch_mode") == 0) {
         if (value < 0 || value > 1) return rs_fail(ctx, RS_ERR_INVALID, "ba_batch_mode must be 0 (grid where possible) or 1 (lanes)");
         ctx->ba_batch_mode = value;

@@ -23,6 +23,8 @@
 //                    axis and become the children's `oth`.  floor(log2 n) + 1 levels, segment bounds from n alone.
 #include "common.h"
 
+#include <cmath>
+
 #define FRAME_MAX_POINTS 8192          // the describer's and the detector's envelope
 #define FB_THREADS 1024
 #define FB_PER (FRAME_MAX_POINTS / FB_THREADS)      // consecutive positions per thread of k_frame_build
@@ -53,7 +55,7 @@ __global__ __launch_bounds__(256) void k_frame_gather(int cap, const uint32_t* _
     frame_counts(pt_a ? count_a : nullptr, pt_b ? count_b : nullptr, cap, &na, &nb);
     const int n = na + nb;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t == 0) d_n[0] = n;
+    if (t == 0) { d_n[0] = n; d_n[1] = 0; }              // [1]: every coordinate finite, set by k_frame_build
     if (t < cap) { rank[t] = 0; kp_point[t] = -1; }      // (the match table: no match yet)
     if (t < n) {
         const uint32_t* src = t < na ? pt_a + 2 * (size_t)t : pt_b + 2 * (size_t)(t - na);
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(256) void k_frame_rank(const int32_t* __restrict__ 
 
 // dynamic LDS, in 16-bit words: rank_x [n] | rank_y [n] | three position lists [n] (cur, oth, the one being filled),
 // then as u32 the prefix counts inside each thread's run of positions [n] and the threads' bases [FB_THREADS]
-__global__ __launch_bounds__(FB_THREADS) void k_frame_build(const int32_t* __restrict__ d_n, const uint32_t* __restrict__ rank,
+__global__ __launch_bounds__(FB_THREADS) void k_frame_build(int32_t* __restrict__ d_n, const uint32_t* __restrict__ rank,
                                                            const uint2* __restrict__ kp, int32_t* __restrict__ kd, uint4* __restrict__ packed)
 {
     extern __shared__ __attribute__((aligned(16))) uint16_t fb_lds[];
@@ -163,6 +165,7 @@ __global__ __launch_bounds__(FB_THREADS) void k_frame_build(const int32_t* __res
         uint16_t* t = oth; oth = cur; cur = nxt; nxt = t;
     }
     // every position is a node now: the flat arrays and the packed form, children from the segment alone
+    int nonfinite = 0;
 #pragma unroll
     for (int k = 0; k < FB_PER; k++) {
         const int p = p0 + k;
@@ -173,7 +176,10 @@ __global__ __launch_bounds__(FB_THREADS) void k_frame_build(const int32_t* __res
         kd[p] = node[k]; kd[(size_t)n + p] = left; kd[2 * (size_t)n + p] = right;
         packed[p] = make_uint4(xy.x, xy.y, (uint32_t)left, (uint32_t)right);
         ((int32_t*)(packed + n))[p] = node[k];
+        nonfinite |= ((xy.x & 0x7F800000u) == 0x7F800000u || (xy.y & 0x7F800000u) == 0x7F800000u) ? 1 : 0;
     }
+    nonfinite = __syncthreads_or(nonfinite);
+    if (tid == 0) d_n[1] = nonfinite ? 0 : 1;
 }
 
 static size_t frame_build_lds(int cap)
@@ -192,7 +198,7 @@ static int frame_alloc(rs_context* ctx, rs_frame* f, size_t rows, bool assignabl
               hipMalloc((void**)&f->d_kp_point, sizeof(int32_t) * rows) == hipSuccess;
     if (assignable)
         ok = ok && hipMalloc(&f->d_packed, 20 * rows) == hipSuccess && hipMalloc((void**)&f->d_rank, sizeof(uint32_t) * rows) == hipSuccess &&
-             hipMalloc((void**)&f->d_n, sizeof(int32_t)) == hipSuccess && hipHostMalloc((void**)&f->h_n, sizeof(int32_t)) == hipSuccess;
+             hipMalloc((void**)&f->d_n, 2 * sizeof(int32_t)) == hipSuccess && hipHostMalloc((void**)&f->h_n, 2 * sizeof(int32_t)) == hipSuccess;
     ok = ok && hipMemsetAsync(f->d_kp_point, 0xFF, sizeof(int32_t) * rows, ctx->stream) == hipSuccess;
     return ok ? RS_OK : rs_fail(ctx, RS_ERR_NOMEM, "frame buffers");
 }
@@ -233,6 +239,8 @@ extern "C" int rs_frame_create(rs_context* ctx, const float* h_kp, const uint8_t
     if (n > 0) rs_kdtree_build(h_kp, n, kd.data(), kd.data() + m, kd.data() + 2 * m, &f->kd_root);     // src/Frame.cpp:8-15
     int rc = frame_alloc(ctx, f, m, false);
     if (!rc && n > 0) rc = frame_upload(ctx, f, h_kp, h_desc, kd);       // (n == 0: no tree, d_packed stays null)
+    f->finite = n > 0;
+    for (size_t i = 0; i < 2 * (size_t)n; i++) f->finite = f->finite && std::isfinite(h_kp[i]);
     if (rc) { rs_frame_destroy(f); return rc; }
     *out = f;
     return RS_OK;
@@ -258,6 +266,7 @@ extern "C" int rs_frame_destroy(rs_frame* f)
     if (!f) return RS_OK;
     (void)hipSetDevice(f->ctx->device);
     (void)hipStreamSynchronize(f->ctx->stream);
+    rs_k2_grid_forget(f->grid.p);
     for (void* p : {(void*)f->d_kp, (void*)f->d_desc, (void*)f->d_kd, (void*)f->d_matched, f->d_packed, (void*)f->d_rank, (void*)f->d_n,
                     (void*)f->d_kp_point})
         if (p) (void)hipFree(p);
@@ -272,6 +281,9 @@ static int frame_enqueue(rs_context* ctx, rs_frame* f, const float* d_pt_a, cons
 {
     hipStream_t s = ctx->stream;
     const int cap = f->cap;
+    rs_k2_grid_forget(f->grid.p);      // the grid, if any, is the previous keypoints'
+    f->grid_built = false;
+    f->finite = false;
     {
         rs_prof_scope ps(ctx, "KF_frame_gather");
         hipLaunchKernelGGL(k_frame_gather, dim3((2 * cap + 255) / 256), dim3(256), 0, s, cap, (const uint32_t*)d_pt_a, d_count_a,
@@ -306,13 +318,14 @@ extern "C" int rs_frame_assign_device(rs_context* ctx, rs_frame* f, const float*
     const int cap = f->cap;
     const int rc = frame_enqueue(ctx, f, d_pt_a, d_count_a, d_pt_b, d_count_b, d_desc, cap);
     if (rc) return rc;
-    RS_HIP(ctx, hipMemcpyAsync(f->h_n, f->d_n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    RS_HIP(ctx, hipMemcpyAsync(f->h_n, f->d_n, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     // the one host synchronisation: rs_map_match sizes its launches and rs_map_add_keyframe books pool rows by the host-side n
     RS_HIP(ctx, hipStreamSynchronize(s));
     const int n = *f->h_n;
     if (n < 0 || n > cap) return rs_fail(ctx, RS_ERR_HIP, "rs_frame_assign_device: count %d outside the frame", n);
     f->n = n;
     f->kd_root = n > 0 ? n / 2 : -1;
+    f->finite = n > 0 && f->h_n[1] == 1;
     if (h_n) *h_n = n;
     return RS_OK;
 }
@@ -343,5 +356,28 @@ extern "C" int rs_frame_download(rs_context* ctx, const rs_frame* f, int* h_n, f
         if (h_packed) RS_HIP(ctx, hipMemcpyAsync(h_packed, f->d_packed, 20 * n, hipMemcpyDeviceToHost, s));
     }
     RS_HIP(ctx, hipStreamSynchronize(s));
+    return RS_OK;
+}
+
+// The frame's cell grid for K2 (reproj_match.hip), made on the first match after the frame was filled: the tree is this
+// file's own — implicit shape, every node on the correct side of its ancestors — so finite coordinates are all the grid
+// needs, and those the host knows (rs_frame_create sees them, rs_frame_assign_device reads the verdict back with n).  A
+// frame refilled by rs_frame_assign_enqueue, whose keypoints the host has never seen, has no grid: K2 walks its tree.
+int rs_frame_grid(rs_context* ctx, rs_frame* f, int width, int height, const void** d_grid)
+{
+    *d_grid = nullptr;
+    if (!f->finite || f->n <= 0 || !f->d_packed) return RS_OK;
+    if (!(f->grid_built && f->grid_w == width && f->grid_h == height)) {
+        rs_k2_grid_forget(f->grid.p);
+        f->grid_built = false;
+        const int rc = f->grid.reserve(ctx, rs_kdtree_grid_bytes(f->cap > 0 ? f->cap : f->n, width, height), 4096, 0, nullptr, RS_GROW_ROUND_UP);
+        if (rc) return rc;
+        bool built = false;
+        const int rc2 = rs_k2_grid_enqueue(ctx, f->n, f->kd_root, f->d_packed, width, height, f->grid.p, false, &built);
+        if (rc2 || !built) return rc2;
+        rs_k2_grid_remember(f->grid.p, f->n);
+        f->grid_built = true; f->grid_w = width; f->grid_h = height;
+    }
+    *d_grid = f->grid.p;
     return RS_OK;
 }

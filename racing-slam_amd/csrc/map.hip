@@ -487,6 +487,7 @@ extern "C" int rs_map_match(rs_context* ctx, rs_map* m, rs_frame* f, const float
     fv.d_keypoints = f->d_kp; fv.d_descriptors = f->d_desc; fv.d_kp_matched = d_matched;
     fv.d_kd_node_kp = f->d_kd; fv.d_kd_left = f->d_kd + N; fv.d_kd_right = f->d_kd + 2 * (size_t)N; fv.kd_root = f->kd_root;
     fv.d_kd_packed = f->d_packed;
+    if ((rc = rs_frame_grid(ctx, f, width, height, &fv.d_kd_grid))) return rc;
     rc = rs_reproj_match(ctx, &fv, &mv, replace, max_distance, pk, pd, pp, pdist, mkp, mpt, cnt);
     if (rc) return rc;
     int32_t n_out = 0;

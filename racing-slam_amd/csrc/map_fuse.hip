@@ -445,6 +445,7 @@ extern "C" int rs_map_fuse_loop(rs_context* ctx, rs_map* map, int query_kf, int 
             fv.d_keypoints = f->d_kp; fv.d_descriptors = f->d_desc; fv.d_kp_matched = d_zero;
             fv.d_kd_node_kp = f->d_kd; fv.d_kd_left = f->d_kd + N; fv.d_kd_right = f->d_kd + 2 * (size_t)N; fv.kd_root = f->kd_root;
             fv.d_kd_packed = f->d_packed;
+            if ((rc = rs_frame_grid(ctx, f, opt->width, opt->height, &fv.d_kd_grid))) return rc;      // (none: the host never sees these keypoints)
             rs_map_view sv{S, d_vpos, d_elig, d_ptr[cur], d_vkf[cur], d_vdesc[cur], mv.d_centres, mv.d_pool};
             if ((rc = rs_reproj_match(ctx, &fv, &sv, 1, opt->max_distance, d_pkp, d_pdist, d_pp, d_ppd, d_jkp + joff[t], d_jview + joff[t], d_jcnt + t)))
                 return rc;

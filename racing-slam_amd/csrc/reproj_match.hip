@@ -6,13 +6,17 @@
 // MapPoint::avg_viewing_normal / observed_distance_range (src/MapPoint.cpp:24-45)
 // and KDTree2D::radius_search (src/KDTree.cpp:45-82).
 //
-// K2 is two kernels with identical outputs: eight lanes per map point when the frame's KD-tree fits in LDS
-// (k2_reproj_match_grouped, the default), one lane per point otherwise or under k2_mode 1 (k2_reproj_match).  They differ
+// K2 is three kernels with identical outputs.  Where the frame carries a usable cell grid (rs_kdtree_grid_build, below) a
+// point's candidates come from the grid's cells around its projection (k2_reproj_match_grid, the default: eight lanes per
+// map point, no LDS, ties between equally distant keypoints decided by the reference's visiting order computed from their
+// node ids).  The other two walk the KD-tree: eight lanes per map point when the tree fits in LDS
+// (k2_reproj_match_grouped), one lane per point otherwise or under k2_mode 1 (k2_reproj_match).  Those two differ
 // in how a point's observations are spread over lanes — the accumulation of the viewing normal and the descriptor
-// compares of phase B — and share every other step, each defined once below:
-//   k2_stage_tree   the frame's KD-tree into LDS, one K2Node per node
+// compares of phase B — and share every other step, each defined once below (k2_project and k2_view_gates with the grid
+// kernel too):
 //   k2_project      Camera::project + is_in_image (tri_core.h's f32 forms)
 //   k2_view_gates   the viewing-angle and distance-range gates, given the accumulated normal and range
+//   k2_stage_tree   the frame's KD-tree into LDS, one K2Node per node
 //   K2_WALK         the radius search with an explicit stack in LDS, visiting nodes in exactly the reference's recursion
 //                   order (node, near child, far child) so that "first candidate wins ties" is preserved
 //   k2_candidate    what the walk does with an in-range, open keypoint: queue it for phase B, or compare it on the spot
@@ -24,6 +28,8 @@
 // Built with -ffp-contract=off so the f32 gates execute the oracle's operations.
 #include "common.h"
 #include "tri_core.h"
+
+#include <mutex>
 
 #define K2_THREADS 128           // one lane per point
 #define K2G 8                    // lanes per point of the grouped kernel
@@ -647,6 +653,215 @@ __global__ __launch_bounds__(K2G_THREADS) void k2_reproj_match_grouped(K2Frame f
     K2_STAMP(6);
 }
 
+// ------------------------------------------------------------------------------------------------ the cell grid
+// A frame's keypoints in a uniform grid over the image, built once per frame (rs_kdtree_grid_build) from the packed tree:
+//   K2Grid header | cell_start[nx * ny + 1] (padded to 16 bytes) | entries[n] {x, y, keypoint, node id} | build scratch [2 n]
+// entries are sorted by cell (row-major), inside a cell by node id: a pure function of the input.  A coordinate's cell
+// is floor(c * K2_CELL_INV) clamped into the grid — monotone in c, so a keypoint within 20 px of (u, v) lies in the cell
+// range of [u - 20.5, u + 20.5] x [v - 20.5, v + 20.5] whatever the grid's extent (keypoints outside it sit in border
+// cells), and that range spans at most 3 cells per axis.  The exact dx * dx + dy * dy <= 400 test of the walk decides.
+#define K2_CELL 40
+#define K2_CELL_INV 0.025f
+#define K2_GRID_MAX_N 65536        // the build ranks entries inside their cell by counting pairs
+#define K2_GRID_MAX_DIM 256        // cells per axis; a larger image gets wider border cells
+#define K2_GRID_MAX_IMAGE 65536    // pixels per axis up to which the 0.5 px margin above covers the f32 rounding of u -+ 20
+#define K2C_THREADS 256            // the grid kernel's workgroup: 32 map points (no LDS, no barrier: any size would do)
+
+struct K2Grid { int nx, ny, cell, n, usable, pad[3]; };
+
+static inline int k2_grid_dim(int pixels)
+{
+    if (pixels <= 0) return 1;
+    const int d = pixels / K2_CELL + 1;
+    return d > K2_GRID_MAX_DIM ? K2_GRID_MAX_DIM : d;
+}
+__host__ __device__ static inline size_t k2_grid_start_ints(int nx, int ny) { return ((size_t)nx * ny + 1 + 3) & ~(size_t)3; }
+
+__device__ __forceinline__ int k2_cell_of(float c, int cells)
+{
+    return (int)fminf(fmaxf(floorf(c * K2_CELL_INV), 0.0f), (float)(cells - 1));
+}
+
+// Which of two in-radius nodes the reference's recursion (src/KDTree.cpp:52-82) reaches first; true: node b before the
+// running best a.  Node ids are positions mid = (start + end) / 2 of the implicit tree, so the lowest common ancestor L
+// is integer arithmetic on a, b and n.  L == a or L == b: the ancestor comes first.  Otherwise the node in L's near
+// subtree, near being the left child when L.coord[depth % 2] - query > 0 in f32, as K2_WALK computes delta.
+__device__ __forceinline__ bool k2_visited_before(int b, int a, int n, const float4* __restrict__ packed, float u, float v)
+{
+    int s = 0, e = n, odd = 0, L;
+    for (;;) {
+        L = (s + e) >> 1;
+        if (a == L) return false;
+        if (b == L) return true;
+        if ((a < L) != (b < L)) break;
+        if (a < L) e = L; else s = L + 1;
+        odd ^= 1;
+    }
+    const float4 nd = packed[L];
+    const float delta = odd ? nd.y - v : nd.x - u;
+    return (b < L) == (delta > 0);
+}
+
+// K2c: eight lanes per map point as in k2_reproj_match_grouped, the candidates from the frame's cell grid instead of a
+// walk: the cell ranges of the at most 3 rows (one contiguous range per row), their entries eight per step and one per
+// lane, the in-radius ones up to four at a time through the 256-bit compare.  The running best resolves an equal
+// distance on the spot by k2_visited_before: the recursion order is total, so the result is the walk's.  No LDS.
+__global__ __launch_bounds__(K2C_THREADS) void k2_reproj_match_grid(K2Frame f, K2Map m, const int* __restrict__ grid, int replace,
+                                                                   int max_distance, int32_t* __restrict__ point_kp,
+                                                                   int32_t* __restrict__ point_dist,
+                                                                   unsigned long long* __restrict__ prop)
+{
+    constexpr int PTS = K2C_THREADS / K2G;
+    K2_STAMP0();
+    const int g = threadIdx.x / K2G, sub = threadIdx.x % K2G;
+    const int p = blockIdx.x * PTS + g;
+    const bool have = p < m.n_points;
+    const int pc = have ? p : 0;
+    const bool elig = have && m.eligible[pc] != 0;
+    const int o0 = m.obs_ptr[pc], o1 = m.obs_ptr[pc + 1];
+    const int nobs = elig ? o1 - o0 : 0;
+    const float X[3] = {m.pos[3 * (size_t)pc], m.pos[3 * (size_t)pc + 1], m.pos[3 * (size_t)pc + 2]};
+    // this lane's observations of the first sixteen (sub and sub + 8): keyframe centre and descriptor row
+    float C0[3] = {0.f, 0.f, 0.f}, C1[3] = {0.f, 0.f, 0.f};
+    uint4 b0 = make_uint4(0, 0, 0, 0), b1 = b0, b2 = b0, b3 = b0;
+    const bool h0 = sub < nobs, h1 = K2G + sub < nobs;
+    {
+        const int kf0 = h0 ? m.obs_kf[o0 + sub] : 0, kf1 = h1 ? m.obs_kf[o0 + K2G + sub] : 0;
+        const size_t row0 = h0 ? (size_t)m.obs_desc[o0 + sub] : 0, row1 = h1 ? (size_t)m.obs_desc[o0 + K2G + sub] : 0;
+        if (h0) {
+            const float* C = m.kf_centers + 3 * (size_t)kf0;
+            C0[0] = C[0]; C0[1] = C[1]; C0[2] = C[2];
+            b0 = m.pool[2 * row0]; b1 = m.pool[2 * row0 + 1];
+        }
+        if (h1) {
+            const float* C = m.kf_centers + 3 * (size_t)kf1;
+            C1[0] = C[0]; C1[1] = C[1]; C1[2] = C[2];
+            b2 = m.pool[2 * row1]; b3 = m.pool[2 * row1 + 1];
+        }
+    }
+    K2_STAMP(1);
+    // everything below is uniform within a group of eight lanes except where `sub` appears
+    int out_kp = -1, out_d = max_distance;
+    if (have) do {
+        if (!elig) break;
+        float T[16];                                                     // see k2_project
+#pragma unroll
+        for (int i = 0; i < 16; i++) T[i] = f.T[i];
+        float u, v;
+        if (!k2_project(f, T, X, u, v)) break;
+        // the disc's cells: lane r < 3 reads the range of row cy0 + r.  These loads and the first eight entries need only
+        // (u, v): they are under way while the viewing gates are computed
+        const int nx = grid[0], ny = grid[1];
+        const int* __restrict__ cell_start = grid + sizeof(K2Grid) / sizeof(int);
+        const uint4* __restrict__ entries = (const uint4*)(cell_start + k2_grid_start_ints(nx, ny));
+        const int cx0 = k2_cell_of(u - 20.5f, nx), cx1 = k2_cell_of(u + 20.5f, nx);
+        const int cy0 = k2_cell_of(v - 20.5f, ny), cy1 = k2_cell_of(v + 20.5f, ny);
+        int rs = 0, re = 0;
+        if (sub < 3 && cy0 + sub <= cy1) {
+            const int row = (cy0 + sub) * nx;
+            rs = cell_start[row + cx0]; re = cell_start[row + cx1 + 1];
+        }
+        const int s0 = __shfl(rs, 0, K2G), s1 = __shfl(rs, 1, K2G), s2 = __shfl(rs, 2, K2G);
+        const int l0 = __shfl(re, 0, K2G) - s0, l01 = l0 + __shfl(re, 1, K2G) - s1, total = l01 + __shfl(re, 2, K2G) - s2;
+        auto entry_at = [&](int idx) {
+            uint4 e = make_uint4(0, 0, 0, 0);
+            if (idx < total) e = entries[idx < l0 ? s0 + idx : (idx < l01 ? s1 + (idx - l0) : s2 + (idx - l01))];
+            return e;
+        };
+        uint4 ent = entry_at(sub);
+        K2_STAMP(2);
+        float center[3];
+        camera_center_f32(T, center);
+        float normal[3] = {0.0f, 0.0f, 0.0f};
+        float nearest = 3.402823466e+38f, furthest = 0.0f;
+        for (int ob = 0; ob < nobs; ob += K2G) {                          // src/MapPoint.cpp:24-45, eight observations per pass
+            float Cx[3] = {ob == 0 ? C0[0] : C1[0], ob == 0 ? C0[1] : C1[1], ob == 0 ? C0[2] : C1[2]};
+            if (ob > K2G && ob + sub < nobs) {
+                const float* C = m.kf_centers + 3 * (size_t)m.obs_kf[o0 + ob + sub];
+                Cx[0] = C[0]; Cx[1] = C[1]; Cx[2] = C[2];
+            }
+            float d[3] = {X[0] - Cx[0], X[1] - Cx[1], X[2] - Cx[2]};
+            const float dist = sqrtf(dot3f(d, d));
+            normalize3f(d);
+            normalize3f(d);
+#pragma unroll
+            for (int j = 0; j < K2G; j++) {                               // summed in observation order by every lane
+                const float dj0 = __shfl(d[0], j, K2G), dj1 = __shfl(d[1], j, K2G), dj2 = __shfl(d[2], j, K2G);
+                const float distj = __shfl(dist, j, K2G);
+                if (ob + j < nobs) {
+                    nearest = distj < nearest ? distj : nearest;
+                    furthest = furthest < distj ? distj : furthest;
+                    normal[0] += dj0; normal[1] += dj1; normal[2] += dj2;
+                }
+            }
+        }
+        if (!k2_view_gates(normal, nearest, furthest, X, center)) break;
+        K2_STAMP(3);
+
+        const float r2 = 20.0f * 20.0f;
+        const int first_lane = (int)(threadIdx.x & 63u) & ~(K2G - 1);
+        int best_kp = 0, best_node = 0, best_d = max_distance;
+        for (int base = 0; base < total; base += K2G) {
+            if (base > 0) ent = entry_at(base + sub);
+            bool in = false;
+            if (base + sub < total) {
+                const float dx = __uint_as_float(ent.x) - u, dy = __uint_as_float(ent.y) - v;
+                const float d2 = dx * dx + dy * dy;
+                in = d2 <= r2;                                            // in range (:65)
+            }
+            unsigned mask = (unsigned)(__ballot(in) >> first_lane) & 0xFFu;
+            if (base == 0) K2_STAMP(4);                                   // the first eight entries are here
+            while (mask) {                                                // the group's in-radius entries, four per round trip
+                int kq[4], nq[4];
+                bool val[4], open[4];
+                uint4 a0[4], a1[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    val[q] = mask != 0;
+                    const int src = val[q] ? __ffs(mask) - 1 : 0;
+                    mask &= mask - 1;
+                    kq[q] = __shfl((int)ent.z, src, K2G);
+                    nq[q] = __shfl((int)ent.w, src, K2G);
+                    a0[q] = make_uint4(0, 0, 0, 0); a1[q] = a0[q];
+                    open[q] = false;
+                    if (val[q]) {
+                        a0[q] = f.desc[2 * (size_t)kq[q]]; a1[q] = f.desc[2 * (size_t)kq[q] + 1];
+                        open[q] = replace || !f.kp_matched[kq[q]];       // read live (:65, :81): it changes between the calls of a frame
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    if (!val[q]) continue;
+                    int d = h0 ? hamming256(a0[q], a1[q], b0, b1) : 0x7fffffff;
+                    if (h1) d = min(d, hamming256(a0[q], a1[q], b2, b3));
+                    for (int ob = 2 * K2G; ob < nobs; ob += K2G)          // long-lived points: this lane's further rows
+                        if (ob + sub < nobs) {
+                            const size_t row = (size_t)m.obs_desc[o0 + ob + sub];
+                            d = min(d, hamming256(a0[q], a1[q], m.pool[2 * row], m.pool[2 * row + 1]));
+                        }
+                    d = group8_min(d);
+                    // :88-91: the first candidate in visiting order among those at the minimal distance
+                    if (open[q] && (d < best_d || (d == best_d && d < max_distance && k2_visited_before(nq[q], best_node, f.n_keypoints, f.packed, u, v)))) {
+                        best_d = d; best_kp = kq[q]; best_node = nq[q];
+                    }
+                }
+            }
+        }
+        K2_STAMP(5);
+        if (best_d < max_distance) {
+            out_kp = best_kp;
+            out_d = best_d;
+            // :95-97 sequential strict-'<' over map order == atomicMin of (dist, map order)
+            if (sub == 0) atomicMin(&prop[best_kp], ((unsigned long long)(unsigned)best_d << 32) | (unsigned)(m.point_base + p));
+        }
+    } while (0);
+    if (have && sub == 0) {
+        point_kp[p] = out_kp;
+        point_dist[p] = out_d;
+    }
+    K2_STAMP(6);
+}
+
 // K3: one workgroup decodes the proposal table, compacts the accepted matches in order and resets the table
 // (tried as a tail of K2's last workgroup: no cheaper than this launch)
 __global__ __launch_bounds__(1024) void k3_accept(unsigned long long* __restrict__ prop, int n,
@@ -704,7 +919,12 @@ static int reproj_match_impl(rs_context* ctx, const rs_frame_view* fr, const rs_
         m.pool = (const uint4*)mp->d_desc_pool;
         const int tree_in_lds = N <= K2_MAX_LDS_NODES ? 1 : 0;
         rs_prof_scope ps(ctx, "K2_reproj_match");
-        if (tree_in_lds && ctx->k2_mode == 0) {                           // eight lanes per map point
+        if (ctx->k2_mode == 0 && ctx->k2_grid && f.packed && rs_k2_grid_usable(fr->d_kd_grid, N) && fr->width <= K2_GRID_MAX_IMAGE &&
+            fr->height <= K2_GRID_MAX_IMAGE) {                            // eight lanes per map point, candidates from the cell grid
+            const int pts = K2C_THREADS / K2G;
+            hipLaunchKernelGGL(k2_reproj_match_grid, dim3((P + pts - 1) / pts), dim3(K2C_THREADS), 0, ctx->stream, f, m,
+                               (const int*)fr->d_kd_grid, replace, max_distance, d_point_kp, d_point_dist, prop);
+        } else if (tree_in_lds && ctx->k2_mode == 0) {                    // eight lanes per map point
             const int pts = K2G_THREADS / K2G;
             const size_t lds = k2_lds_bytes(pts, N);
             if (lds > 48 * 1024)
@@ -777,5 +997,174 @@ extern "C" int rs_kdtree_pack(rs_context* ctx, const rs_frame_view* fr, void* d_
     hipLaunchKernelGGL(k2_pack_tree, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, (const float2*)fr->d_keypoints,
                        fr->d_kd_node_kp, fr->d_kd_left, fr->d_kd_right, (float4*)d_packed);
     RS_HIP(ctx, hipGetLastError());
+    return RS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ rs_kdtree_grid_build
+// Three small launches, once per frame.  k2_grid_classify_rank also decides `usable` when asked to: the grid kernel may stand
+// in for the walk only if (a) the tree has the implicit shape (children are the mids of the node's half ranges), (b) every
+// node lies on the correct side of each ancestor on that ancestor's axis (left: coord <= ancestor's, right: >=), so that the
+// walk's pruning never hides an in-radius node and k2_visited_before's order is the recursion's, and (c) every coordinate
+// is finite (a NaN sends the reference's walk right and makes it miss the left subtree).
+__global__ __launch_bounds__(256) void k2_grid_init(int* __restrict__ grid, int nx, int ny, int n, int* __restrict__ rank)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) {
+        K2Grid h = {nx, ny, K2_CELL, n, 1, {0, 0, 0}};
+        *(K2Grid*)grid = h;
+    }
+    if (i < nx * ny + 1) grid[sizeof(K2Grid) / sizeof(int) + i] = 0;
+    if (i < n) rank[i] = 0;
+}
+
+// Tiles of 256 nodes i x 256 nodes j with j0 <= i0: rank[i] = #{j < i in i's cell}, one integer atomic per tile (exact,
+// order-free).  The tiles of the first column also count their nodes into the cells and, if `validate`, check them.
+__global__ __launch_bounds__(256) void k2_grid_classify_rank(int* __restrict__ grid, int nx, int ny, int n, const float4* __restrict__ packed,
+                                                             int validate, int* __restrict__ cell_of_node, int* __restrict__ rank)
+{
+    __shared__ int cj[256];
+    const int i0 = blockIdx.x * 256, j0 = blockIdx.y * 256;
+    if (j0 > i0 || i0 >= n) return;
+    const int t = threadIdx.x;
+    cj[t] = -1;
+    if (j0 + t < n) {
+        const float4 q = packed[j0 + t];
+        cj[t] = k2_cell_of(q.y, ny) * nx + k2_cell_of(q.x, nx);
+    }
+    __syncthreads();
+    const int i = i0 + t;
+    if (i >= n) return;
+    const float4 nd = packed[i];
+    const int ci = k2_cell_of(nd.y, ny) * nx + k2_cell_of(nd.x, nx), lim = min(256, i - j0);
+    int cnt = 0;
+    for (int q = 0; q < lim; q++) cnt += cj[q] == ci ? 1 : 0;
+    if (cnt) atomicAdd(&rank[i], cnt);
+    if (j0 != 0) return;
+    cell_of_node[i] = ci;
+    atomicAdd(&grid[sizeof(K2Grid) / sizeof(int) + ci + 1], 1);
+    if (!validate) return;
+    const int kp = ((const int*)(packed + n))[i];
+    bool ok = isfinite(nd.x) && isfinite(nd.y) && (unsigned)kp < (unsigned)n;
+    int s = 0, e = n, odd = 0, mid;
+    for (;;) {                                                            // root -> i by arithmetic: at most log2(n) + 1 ancestors
+        mid = (s + e) >> 1;
+        if (mid == i) break;
+        const float4 a = packed[mid];
+        const float ca = odd ? a.y : a.x, cn = odd ? nd.y : nd.x;
+        if (i < mid) { ok = ok && cn <= ca; e = mid; }
+        else { ok = ok && cn >= ca; s = mid + 1; }
+        odd ^= 1;
+    }
+    const int left = s < mid ? (s + mid) >> 1 : -1, right = mid + 1 < e ? (mid + 1 + e) >> 1 : -1;
+    ok = ok && __float_as_int(nd.z) == left && __float_as_int(nd.w) == right;
+    if (!ok) ((K2Grid*)grid)->usable = 0;
+}
+
+// One workgroup: cell_start[k] = number of keypoints in cells < k, in place over the counts at [k + 1]; then every node
+// into its cell's range at its rank.
+__global__ __launch_bounds__(1024) void k2_grid_scan_scatter(int* __restrict__ grid, int nx, int ny, int n, const float4* __restrict__ packed,
+                                                             const int* __restrict__ cell_of_node, const int* __restrict__ rank)
+{
+    const int cells = nx * ny;
+    int* cs = grid + sizeof(K2Grid) / sizeof(int);
+    {
+        int* c1 = cs + 1;
+        const int chunk = (cells + 1023) / 1024, lo = min((int)threadIdx.x * chunk, cells), hi = min(lo + chunk, cells);
+        int sum = 0;
+        for (int k = lo; k < hi; k++) sum += c1[k];
+        int total;
+        int run = rs_block_exclusive_scan(sum, &total);
+        for (int k = lo; k < hi; k++) { run += c1[k]; c1[k] = run; }
+    }
+    __syncthreads();
+    uint4* entries = (uint4*)(cs + k2_grid_start_ints(nx, ny));
+    for (int i = threadIdx.x; i < n; i += 1024) {
+        const float4 nd = packed[i];
+        const int pos = min(cs[cell_of_node[i]] + rank[i], n - 1);        // (always below n: the counts are these cells')
+        entries[pos] = make_uint4(__float_as_uint(nd.x), __float_as_uint(nd.y), (uint32_t)((const int*)(packed + n))[i], (uint32_t)i);
+    }
+}
+
+extern "C" size_t rs_kdtree_grid_bytes(int n_keypoints, int width, int height)
+{
+    const size_t n = n_keypoints > 0 ? (size_t)n_keypoints : 0;
+    return sizeof(K2Grid) + sizeof(int) * k2_grid_start_ints(k2_grid_dim(width), k2_grid_dim(height)) + 16 * n + 8 * n;
+}
+
+// Which grids may stand in for the walk is host knowledge (the kernel is chosen at launch), kept per process, not per
+// context: a frame's view is handed to forked child contexts (the benchmark's front end runs its two matches on two of them).
+static std::mutex k2_grids_mutex;
+static std::vector<std::pair<const void*, int>> k2_grids;      // {grid, n}
+
+static void k2_grid_forget_locked(const void* d_grid)
+{
+    for (size_t i = 0; i < k2_grids.size();)
+        if (k2_grids[i].first == d_grid) k2_grids.erase(k2_grids.begin() + (long)i); else i++;
+}
+
+void rs_k2_grid_forget(const void* d_grid)
+{
+    std::lock_guard<std::mutex> lock(k2_grids_mutex);
+    k2_grid_forget_locked(d_grid);
+}
+
+void rs_k2_grid_remember(const void* d_grid, int n)
+{
+    std::lock_guard<std::mutex> lock(k2_grids_mutex);
+    k2_grid_forget_locked(d_grid);
+    if (k2_grids.size() >= 4096) k2_grids.erase(k2_grids.begin());      // a forgotten grid only means the walk
+    k2_grids.push_back({d_grid, n});
+}
+
+bool rs_k2_grid_usable(const void* d_grid, int n)
+{
+    if (!d_grid) return false;
+    std::lock_guard<std::mutex> lock(k2_grids_mutex);
+    for (const auto& g : k2_grids)
+        if (g.first == d_grid) return g.second == n;
+    return false;
+}
+
+// the launches, on the context stream; false in *built: no grid for this frame (too many keypoints, or the root is not n / 2).
+// validate 0: the caller knows the tree to be this library's own over finite coordinates.
+int rs_k2_grid_enqueue(rs_context* ctx, int n, int kd_root, const void* d_packed, int width, int height, void* d_grid, bool validate, bool* built)
+{
+    *built = false;
+    if (n <= 0 || n > K2_GRID_MAX_N || kd_root != n / 2) return RS_OK;
+    const int nx = k2_grid_dim(width), ny = k2_grid_dim(height);
+    int* grid = (int*)d_grid;
+    const float4* packed = (const float4*)d_packed;
+    int* cell_of_node = (int*)((char*)d_grid + rs_kdtree_grid_bytes(n, width, height) - 8 * (size_t)n), *rank = cell_of_node + n;
+    hipStream_t s = ctx->stream;
+    rs_prof_scope ps(ctx, "K2g_grid_build");
+    const int nb = (n + 255) / 256, most = max(n, nx * ny + 1);
+    hipLaunchKernelGGL(k2_grid_init, dim3((most + 255) / 256), dim3(256), 0, s, grid, nx, ny, n, rank);
+    hipLaunchKernelGGL(k2_grid_classify_rank, dim3(nb, nb), dim3(256), 0, s, grid, nx, ny, n, packed, validate ? 1 : 0, cell_of_node, rank);
+    hipLaunchKernelGGL(k2_grid_scan_scatter, dim3(1), dim3(1024), 0, s, grid, nx, ny, n, packed, (const int*)cell_of_node, (const int*)rank);
+    RS_HIP(ctx, hipGetLastError());
+    *built = true;
+    return RS_OK;
+}
+
+extern "C" int rs_kdtree_grid_build(rs_context* ctx, const rs_frame_view* fr, void* d_grid)
+{
+    if (!ctx || !fr) return RS_ERR_INVALID;
+    const int n = fr->n_keypoints;
+    if (n < 0) return rs_fail(ctx, RS_ERR_INVALID, "negative size");
+    if (!d_grid) return rs_fail(ctx, RS_ERR_INVALID, "null pointer");
+    if (((uintptr_t)d_grid) & 15) return rs_fail(ctx, RS_ERR_INVALID, "d_grid must be 16-byte aligned");
+    rs_k2_grid_forget(d_grid);
+    if (n == 0) return RS_OK;
+    if (!fr->d_kd_packed) return rs_fail(ctx, RS_ERR_INVALID, "rs_kdtree_grid_build needs the frame's d_kd_packed");
+    if (((uintptr_t)fr->d_kd_packed) & 15) return rs_fail(ctx, RS_ERR_INVALID, "d_kd_packed must be 16-byte aligned");
+    RS_HIP(ctx, hipSetDevice(ctx->device));
+    bool built = false;
+    int rc = rs_k2_grid_enqueue(ctx, n, fr->kd_root, fr->d_kd_packed, fr->width, fr->height, d_grid, true, &built);
+    if (rc || !built) return rc;
+    // once per frame: whether the grid may stand in for the walk is decided on the device and remembered on the host
+    K2Grid h;
+    RS_HIP(ctx, hipMemcpyAsync(&h, d_grid, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (h.usable) rs_k2_grid_remember(d_grid, n);
     return RS_OK;
 }

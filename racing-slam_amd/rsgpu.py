@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("RS_LIB") or ("librsgpu_stamps.so"
 EXPORTS = [
     "rs_abi_version", "rs_context_create", "rs_context_destroy", "rs_context_set_stream", "rs_context_wait_for", "rs_context_fork",
     "rs_context_synchronize", "rs_context_set_int", "rs_stage_begin", "rs_stage_alloc", "rs_stage_upload", "rs_stage_download", "rs_stage_sync", "rs_last_error", "rs_hamming_knn2", "rs_match_descriptors",
-    "rs_kdtree_build", "rs_kdtree_pack", "rs_reproj_match", "rs_reproj_match_sharded", "rs_map_create", "rs_map_destroy", "rs_frame_create", "rs_frame_destroy",
+    "rs_kdtree_build", "rs_kdtree_pack", "rs_kdtree_grid_bytes", "rs_kdtree_grid_build", "rs_reproj_match", "rs_reproj_match_sharded", "rs_map_create", "rs_map_destroy", "rs_frame_create", "rs_frame_destroy",
     "rs_frame_create_device", "rs_frame_assign_device", "rs_frame_download",
     "rs_frame_matches_clear", "rs_frame_matches_add", "rs_frame_matches_download",
     "rs_map_set_track_consistent", "rs_map_carry_matches", "rs_map_refine_pose", "rs_map_match_frame",
@@ -64,6 +64,8 @@ def load():
         _lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
         _lib.rs_last_error.restype = C.c_char_p
         _lib.rs_last_error.argtypes = [C.c_void_p]
+        if hasattr(_lib, "rs_kdtree_grid_bytes"):        # (an A/B library named by RS_LIB may predate the cell grid)
+            _lib.rs_kdtree_grid_bytes.restype = C.c_size_t
     return _lib
 
 
@@ -72,7 +74,7 @@ class FrameView(C.Structure):
                 ("cy", C.c_float), ("width", C.c_int), ("height", C.c_int), ("n_keypoints", C.c_int),
                 ("d_keypoints", C.c_void_p), ("d_descriptors", C.c_void_p), ("d_kp_matched", C.c_void_p),
                 ("d_kd_node_kp", C.c_void_p), ("d_kd_left", C.c_void_p), ("d_kd_right", C.c_void_p),
-                ("kd_root", C.c_int), ("d_kd_packed", C.c_void_p)]
+                ("kd_root", C.c_int), ("d_kd_packed", C.c_void_p), ("d_kd_grid", C.c_void_p)]
 
 
 class MapView(C.Structure):
@@ -458,10 +460,18 @@ class Context:
             setattr(fv, name, keep[name].data_ptr())
         fv.kd_root = int(frame["kd_root"])
         fv.d_kd_packed = None
+        fv.d_kd_grid = None
         if pack and fv.n_keypoints > 0:        # once per frame: shared by the match calls of that frame
             keep["d_kd_packed"] = self.empty((5 * fv.n_keypoints,), self.torch.int32)
             self._check(self.lib.rs_kdtree_pack(self.h, C.byref(fv), _dp(keep["d_kd_packed"])), "rs_kdtree_pack")
             fv.d_kd_packed = keep["d_kd_packed"].data_ptr()
+            if os.environ.get("RS_LIB") and not hasattr(self.lib, "rs_kdtree_grid_build"):
+                return fv, keep
+            # and its cell grid (rs_kdtree_grid_build): what K2 searches instead of walking the tree, where the tree allows it
+            nbytes = self.lib.rs_kdtree_grid_bytes(fv.n_keypoints, fv.width, fv.height)
+            keep["d_kd_grid"] = self.empty(((nbytes + 15) // 16 * 4,), self.torch.int32)
+            self._check(self.lib.rs_kdtree_grid_build(self.h, C.byref(fv), _dp(keep["d_kd_grid"])), "rs_kdtree_grid_build")
+            fv.d_kd_grid = keep["d_kd_grid"].data_ptr()
         return fv, keep
 
     def make_map_view(self, mp):

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Phase stamps of the grouped K2 (build with RS_STAMPS=1): phase ends of one wave of the middle workgroup, relative to
-its start, in microseconds: [staged-loads issued, tree staged, gates, traversal, compare, outputs]."""
+"""Phase stamps of K2 (build with RS_STAMPS=1): phase ends of one wave of the middle workgroup, relative to its start, in
+microseconds.  The cell-grid kernel (the default): [observation loads issued, cell ranges read and first entries issued,
+gates, first entries arrived, entries compared, outputs]; with the argument k2_grid=0 the grouped walk kernel:
+[staged-loads issued, tree staged, gates, traversal, compare, outputs]."""
 import ctypes as C
 import importlib
 import os
@@ -12,6 +14,8 @@ pkg = importlib.import_module("racing-slam_amd")
 rs, synth = pkg.rsgpu, pkg.synth
 
 ctx = rs.Context(0)
+for k, v in (a.split("=") for a in sys.argv[1:] if "=" in a):
+    ctx.set_int(k, int(v))
 w = synth.make_ba_window()
 frame, mp = synth.make_match_scene(w, n_keypoints=2000, kdtree_build=rs.kdtree_build)
 fv, keep_f = ctx.make_frame_view(frame, pack=True)
