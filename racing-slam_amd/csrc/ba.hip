@@ -443,7 +443,7 @@ static BaLayout ba_layout(const BaDims& d, int ns, int max_iter, size_t n_ranks,
     BaLayout L;
     const size_t n = (size_t)d.n, C = (size_t)d.C, P = (size_t)d.P, nb = (size_t)ns + 1;
     size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return o; };
+    auto carve = [&](size_t bytes) { size_t o = off; off += rs_align256(bytes); return o; };
     L.Xc = carve(sizeof(double) * nb * C * 6); L.Xp = carve(sizeof(double) * nb * P * 3);
     L.prep = carve(sizeof(double) * nb * C * BA_PREP); L.slot = carve(sizeof(int32_t) * C);
     L.sc = carve(sizeof(double) * (n + 1)); L.sp = carve(sizeof(double) * P * 3);
@@ -805,9 +805,9 @@ static int ba_solve_once(rs_context* ctx, const rs_ba_problem& q, const rs_ba_op
     const size_t n_ranks = rs_comm_active(ctx) ? (size_t)ctx->n_ranks : 1;
     const BaLayout L = ba_layout(d, path.ns, opt.max_iter, n_ranks, path.use_mfma ? ba_group_bytes(d.P, d.Cf, d.M) : 16, path.srep);
     const size_t o_big = L.bytes;
-    const size_t big_bytes = align_up(in ? ba_inertial_bytes(d.n + 9 * Ci, in->n_factors, d.C) : (path.solve_big ? ba_big_bytes(d.n) : 16), 256);
+    const size_t big_bytes = rs_align256(in ? ba_inertial_bytes(d.n + 9 * Ci, in->n_factors, d.C) : (path.solve_big ? ba_big_bytes(d.n) : 16));
     const size_t o_zacc = o_big + big_bytes;
-    const size_t ws_bytes = o_zacc + (path.imu_lds ? align_up(sizeof(double) * ba_imu_lds_total_doubles(Ci, d.n, path.ns), 256) : 0);
+    const size_t ws_bytes = o_zacc + (path.imu_lds ? rs_align256(sizeof(double) * ba_imu_lds_total_doubles(Ci, d.n, path.ns)) : 0);
     void* wsv = nullptr;
     rc = rs_workspace_quiet(ctx, ws_bytes, &wsv);      // (this solve keeps its own account of what it leaves behind: ba_enqueue_setup)
     if (rc) return rc;
@@ -971,7 +971,7 @@ static int ba_solve_batch_grid(rs_context* ctx, int B, const rs_ba_problem* Q, c
     if (opt.max_iter < 1 || opt.max_iter > 1000) return 1;
     std::vector<BaWin> wins((size_t)B);
     std::vector<size_t> ws_off((size_t)B), pin_off((size_t)B);
-    size_t ws_total = align_up(sizeof(BaWin) * (size_t)B, 256), pin_total = 0;
+    size_t ws_total = rs_align256(sizeof(BaWin) * (size_t)B), pin_total = 0;
     int max_P = 0, max_items = 0, max_n = 0, max_C = 0, ns = 1;
     size_t k5_lds = 0, k8_lds = 0;
     std::vector<BaLayout> lay((size_t)B);
@@ -1001,7 +1001,7 @@ static int ba_solve_batch_grid(rs_context* ctx, int B, const rs_ba_problem* Q, c
     if (rc) { *rc_out = rc; return 0; }
     char* ws = (char*)wsv;
     void* pinv = nullptr;
-    const size_t pin_wins = align_up(pin_total, 256);
+    const size_t pin_wins = rs_align256(pin_total);
     rc = rs_pinned(ctx, pin_wins + sizeof(BaWin) * (size_t)B, &pinv);
     if (rc) { *rc_out = rc; return 0; }
     char* pin = (char*)pinv;

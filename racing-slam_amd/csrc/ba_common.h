@@ -601,7 +601,7 @@ void ba_launch_backsub_batch(hipStream_t s, const BaWin* d_wins, int B, int it, 
 void ba_group_set_items(BaGroup* g, int P, bool throughput, int batch_item = 0);   // landmarks per item: 32 (or batch_item) in throughput mode, else as ba_group_carve chose
 
 size_t ba_group_bytes(int P, int Cf, int M);
-void ba_group_carve(char* base, int P, int Cf, int M, BaGroup* g);
+size_t ba_group_carve(char* base, int P, int Cf, int M, BaGroup* g);
 void ba_group_zero_range(const BaGroup& g, int32_t** ptr, int* count);
 int ba_launch_grouping(rs_context* ctx, const BaDims& d, const BaBufs& b, const BaGroup& g);
 bool ba_setup_fusable(const BaDims& d, const BaGroup& g);

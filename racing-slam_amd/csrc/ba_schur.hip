@@ -288,10 +288,8 @@ __global__ __launch_bounds__(64 * SCH_WAVES) void ba_schur_mfma_batch(const BaWi
 // ------------------------------------------------------------------ host glue
 size_t ba_group_bytes(int P, int Cf, int M)
 {
-    const size_t nb = ((size_t)Cf * Cf + 2) * GRP_REP;
-    const size_t ni = ((size_t)P + 31) / 32 + 1;                 // (the smallest item: 32 landmarks, throughput mode)
-    return 256 * 10 + sizeof(int32_t) * (2 * (size_t)P + 2 * nb + 16 + (size_t)M) + sizeof(int4) * (size_t)P +
-           sizeof(uint64_t) * (2 * (size_t)P + 2 * ni);
+    BaGroup g;
+    return ba_group_carve(nullptr, P, Cf, M, &g);
 }
 
 // The whole grouping in ONE workgroup (a launch costs ~4 us on this GPU; a local window has ~10^4
@@ -379,30 +377,31 @@ void ba_group_zero_range(const BaGroup& g, int32_t** ptr, int* count)
     *count = (int)(g.maxspan - g.hist) + 1;      // histogram, cursors and the span word behind them
 }
 
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 // landmarks per item of a single solve: 40 while that keeps the items within ONE shift of 256 workgroups, 64 beyond.  (48 / 56
 // are there as "ba_item_landmarks": 3 us per launch faster at 11 - 14 k landmarks when the items' camera unions are small, 10 us
 // slower when they are not — the 8 x 8-tile class deals its 36 tiles to the workgroup's waves, and 6 waves carry 6 each.)
 static int ba_default_item(int P) { return P <= 256 * IT_L_SMALL ? IT_L_SMALL : IT_L; }
 
-void ba_group_carve(char* base, int P, int Cf, int M, BaGroup* g)
+// The grouping's buffers, stated once: carves them out of `base` and returns the bytes they take; a null `base` sizes them.
+size_t ba_group_carve(char* base, int P, int Cf, int M, BaGroup* g)
 {
     const size_t nb = ((size_t)Cf * Cf + 2) * GRP_REP;
-    const size_t ni_max = ((size_t)P + 31) / 32 + 1;
+    const size_t ni_max = ((size_t)P + 31) / 32 + 1;                 // (the smallest item: 32 landmarks, throughput mode)
     g->it_l = ba_default_item(P);
     const size_t ni = P > 0 ? ((size_t)P + g->it_l - 1) / g->it_l : 1;     // an empty landmark shard keeps one (empty) item:
-    size_t off = 0;                                                            // its workgroup runs the round's decision
-    g->sorted = (int32_t*)(base + off); off += al256(sizeof(int32_t) * P);
-    g->bucket = (int32_t*)(base + off); off += al256(sizeof(int32_t) * P);
-    g->hist = (int32_t*)(base + off); off += al256(sizeof(int32_t) * nb);
-    g->cursor = (int32_t*)(base + off); off += al256(sizeof(int32_t) * (nb + 16));
-    g->maxspan = g->cursor + nb;
-    g->mask = (uint64_t*)(base + off); off += al256(sizeof(uint64_t) * 2 * P);
-    g->item_mask = (uint64_t*)(base + off); off += al256(sizeof(uint64_t) * 2 * ni_max);
-    g->lm = (int4*)(base + off); off += al256(sizeof(int4) * P);
-    g->obs_cs = (int32_t*)(base + off); off += al256(sizeof(int32_t) * M);
+    rs_carve c(base);                                                          // its workgroup runs the round's decision
+    g->sorted = c.take<int32_t>(P);
+    g->bucket = c.take<int32_t>(P);
+    g->hist = c.take<int32_t>(nb);
+    g->cursor = c.take<int32_t>(nb + 16);
+    g->maxspan = base ? g->cursor + nb : nullptr;
+    g->mask = c.take<uint64_t>(2 * (size_t)P);
+    g->item_mask = c.take<uint64_t>(2 * ni_max);
+    g->lm = c.take<int4>(P);
+    g->obs_cs = c.take<int32_t>(M);
     g->n_items = (int)ni;
     g->n_buckets = Cf * Cf;           // + 1 bucket for landmarks without a free camera
+    return c.bytes();
 }
 
 int ba_launch_grouping(rs_context* ctx, const BaDims& d, const BaBufs& b, const BaGroup& g)

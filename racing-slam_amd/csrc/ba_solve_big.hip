@@ -1175,16 +1175,15 @@ static void big_launch_factor(hipStream_t s, const BaDims& d, const BaBufs& b, c
 // they take.  Nothing is dereferenced, so a null `ws` sizes the workspace.
 static size_t big_carve(char* ws, size_t n, BigBufs* g)
 {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = ws ? ws + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
-    g->Ls = (double*)take(sizeof(double) * n * n);
-    g->M = (double*)take(sizeof(double) * BB * BB);
-    g->dv = (double*)take(sizeof(double) * n);
-    g->yf = (double*)take(sizeof(double) * n);
-    g->fail = (int*)take(sizeof(int));
-    g->sep = (double*)take(sizeof(double) * 2 * (WB * WB + WB));
-    g->Ad = (double*)take(sizeof(double) * 6 * n);
-    return off;
+    rs_carve c(ws);
+    g->Ls = c.take<double>(n * n);
+    g->M = c.take<double>(BB * BB);
+    g->dv = c.take<double>(n);
+    g->yf = c.take<double>(n);
+    g->fail = c.take<int>(1);
+    g->sep = c.take<double>(2 * (WB * WB + WB));
+    g->Ad = c.take<double>(6 * n);
+    return c.bytes();
 }
 
 size_t ba_big_bytes(int n)
@@ -1408,18 +1407,18 @@ __global__ __launch_bounds__(1024) void ba_imu_finish(BaDims d, BaBufs b, BaOpt 
 // *d_fac and *d_inert are the device addresses the host uploads to.  A null `ws` sizes the workspace.
 size_t ba_inertial_carve(char* ws, int N, int n_fac, int C, BaImu* imu, ImuFactorDev** d_fac, int32_t** d_inert)
 {
-    size_t off = ba_big_bytes(N);
-    auto take = [&](size_t bytes) { char* p = ws ? ws + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
-    imu->A = (double*)take(sizeof(double) * (size_t)N * N);
-    imu->yv = (double*)take(sizeof(double) * ((size_t)N + 1));
-    imu->lam = (double*)take(sizeof(double) * ((size_t)N + 1));
-    imu->sc = (double*)take(sizeof(double) * ((size_t)N + 1));
-    imu->gtot = (double*)take(sizeof(double) * ((size_t)N + 1));
-    imu->Jf = (double*)take(sizeof(double) * (size_t)(n_fac + 1) * 9 * IMU_NP);
-    imu->fac = *d_fac = (ImuFactorDev*)take(sizeof(ImuFactorDev) * (size_t)(n_fac + 1));
-    imu->inert_slot = *d_inert = (int32_t*)take(sizeof(int32_t) * (size_t)(C + 1));
-    imu->Xv = (double*)take(sizeof(double) * (BA_MAXSETS + 1) * 9 * (size_t)(C + 1));      // one buffer per state slot
-    return off;
+    rs_carve c(ws);
+    c.off = ba_big_bytes(N);
+    imu->A = c.take<double>((size_t)N * N);
+    imu->yv = c.take<double>((size_t)N + 1);
+    imu->lam = c.take<double>((size_t)N + 1);
+    imu->sc = c.take<double>((size_t)N + 1);
+    imu->gtot = c.take<double>((size_t)N + 1);
+    imu->Jf = c.take<double>((size_t)(n_fac + 1) * 9 * IMU_NP);
+    imu->fac = *d_fac = c.take<ImuFactorDev>((size_t)(n_fac + 1));
+    imu->inert_slot = *d_inert = c.take<int32_t>((size_t)(C + 1));
+    imu->Xv = c.take<double>((BA_MAXSETS + 1) * 9 * (size_t)(C + 1));      // one buffer per state slot
+    return c.bytes();
 }
 
 size_t ba_inertial_bytes(int N, int n_fac, int C)

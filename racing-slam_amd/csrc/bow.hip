@@ -44,6 +44,7 @@
 struct rs_vocabulary {
     rs_context* ctx = nullptr;
     int k = 0, L = 0, weighting = 0, scoring = 0, n_nodes = 0, n_words = 0;
+    rs_dev_block block;
     uint4* d_desc = nullptr;            // [n_nodes][2], breadth-first order
     int2* d_info = nullptr;             // [n_nodes] {first child, children}; a leaf: {word id, 0}
     double* d_word_weight = nullptr;    // [n_words]
@@ -56,6 +57,7 @@ struct rs_bow {
     rs_context* ctx = nullptr;
     rs_vocabulary* voc = nullptr;
     int max_points = 0;
+    rs_dev_block block;
     int32_t* d_feat_word = nullptr;     // [max_points] word of every feature of the last transform
     int32_t* d_words = nullptr;         // [max_points] the vector: sorted unique words,
     int32_t* d_counts = nullptr;        //              their occurrences
@@ -69,6 +71,7 @@ struct rs_bow_database {
     rs_context* ctx = nullptr;
     rs_vocabulary* voc = nullptr;
     int max_entries = 0, max_total_words = 0;
+    rs_dev_block block;
     int32_t* d_ptr = nullptr;           // [max_entries + 1] CSR offsets
     int32_t* d_words = nullptr;         // [max_total_words]
     double* d_values = nullptr;
@@ -251,14 +254,6 @@ __global__ __launch_bounds__(64 * BOW_SCORE_WAVES) void bow_score(const int32_t*
 __global__ void bow_set_int(int32_t* p, int32_t v) { *p = v; }
 
 // ------------------------------------------------------------------------------------------------ vocabulary
-static void vocabulary_free(rs_vocabulary* v)
-{
-    if (v->d_desc) (void)hipFree(v->d_desc);
-    if (v->d_info) (void)hipFree(v->d_info);
-    if (v->d_word_weight) (void)hipFree(v->d_word_weight);
-    delete v;
-}
-
 // h_is_leaf (NULL = not checked): the text file's leaf flags
 static int vocabulary_build(rs_context* ctx, int k, int L, int weighting, int scoring, int n_nodes, const int32_t* h_parent,
                             const uint8_t* h_desc, const double* h_weight, const uint8_t* h_is_leaf, rs_vocabulary** out)
@@ -307,15 +302,16 @@ static int vocabulary_build(rs_context* ctx, int k, int L, int weighting, int sc
     rs_vocabulary* v = new rs_vocabulary();
     v->ctx = ctx;
     v->k = k; v->L = L; v->weighting = weighting; v->scoring = scoring; v->n_nodes = n_nodes; v->n_words = n_words;
-    if (hipMalloc(&v->d_desc, 32 * n) != hipSuccess || hipMalloc(&v->d_info, sizeof(int2) * n) != hipSuccess ||
-        hipMalloc(&v->d_word_weight, sizeof(double) * (size_t)n_words) != hipSuccess) {
-        vocabulary_free(v);
-        return rs_fail(ctx, RS_ERR_NOMEM, "vocabulary of %d nodes", n_nodes);
-    }
+    const int rc = v->block.carve(ctx, "vocabulary", [&](rs_carve& c) {
+        v->d_desc = c.take<uint4>(2 * n);
+        v->d_info = c.take<int2>(n);
+        v->d_word_weight = c.take<double>((size_t)n_words);
+    });
+    if (rc != RS_OK) { delete v; return rc; }
     if (hipMemcpy(v->d_desc, desc.data(), 32 * n, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(v->d_info, info.data(), sizeof(int2) * n, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(v->d_word_weight, ww.data(), sizeof(double) * (size_t)n_words, hipMemcpyHostToDevice) != hipSuccess) {
-        vocabulary_free(v);
+        delete v;
         return rs_fail(ctx, RS_ERR_HIP, "vocabulary upload failed");
     }
     v->parent.assign(h_parent, h_parent + n);
@@ -412,24 +408,9 @@ extern "C" int rs_vocabulary_arrays(const rs_vocabulary* voc, int32_t* h_parent,
     return RS_OK;
 }
 
-extern "C" int rs_vocabulary_destroy(rs_vocabulary* voc)
-{
-    if (!voc) return RS_OK;
-    (void)hipSetDevice(voc->ctx->device);
-    (void)hipStreamSynchronize(voc->ctx->stream);
-    vocabulary_free(voc);
-    return RS_OK;
-}
+extern "C" int rs_vocabulary_destroy(rs_vocabulary* voc) { return rs_drain_and_delete(voc); }
 
 // ------------------------------------------------------------------------------------------------ rs_bow
-static void bow_free(rs_bow* b)
-{
-    void* p[] = {b->d_feat_word, b->d_words, b->d_counts, b->d_values, b->d_hdr, b->d_norm, b->d_lookup};
-    for (void* q : p)
-        if (q) (void)hipFree(q);
-    delete b;
-}
-
 extern "C" int rs_bow_create(rs_context* ctx, rs_vocabulary* voc, int max_points, rs_bow** out_bow)
 {
     if (!ctx || !out_bow) return RS_ERR_INVALID;
@@ -443,30 +424,27 @@ extern "C" int rs_bow_create(rs_context* ctx, rs_vocabulary* voc, int max_points
     b->voc = voc;
     b->max_points = max_points;
     const size_t m = (size_t)max_points, W = (size_t)voc->n_words;
-    if (hipMalloc(&b->d_feat_word, 4 * m) != hipSuccess || hipMalloc(&b->d_words, 4 * m) != hipSuccess ||
-        hipMalloc(&b->d_counts, 4 * m) != hipSuccess || hipMalloc(&b->d_values, 8 * m) != hipSuccess ||
-        hipMalloc(&b->d_hdr, 8) != hipSuccess || hipMalloc(&b->d_norm, 8) != hipSuccess || hipMalloc(&b->d_lookup, 4 * W) != hipSuccess) {
-        bow_free(b);
-        return rs_fail(ctx, RS_ERR_NOMEM, "bag-of-words scratch for %d points and %zu words", max_points, W);
-    }
+    const int rc = b->block.carve(ctx, "bag-of-words scratch", [&](rs_carve& c) {
+        b->d_feat_word = c.take<int32_t>(m);
+        b->d_words = c.take<int32_t>(m);
+        b->d_counts = c.take<int32_t>(m);
+        b->d_values = c.take<double>(m);
+        b->d_hdr = c.take<int32_t>(2);
+        b->d_norm = c.take<double>(1);
+        b->d_lookup = c.take<int32_t>(W);
+    });
+    if (rc != RS_OK) { delete b; return rc; }
     // an empty vector: on the context stream, ahead of the first transform
     if (hipMemsetAsync(b->d_hdr, 0, 8, ctx->stream) != hipSuccess || hipMemsetAsync(b->d_norm, 0, 8, ctx->stream) != hipSuccess ||
         hipMemsetAsync(b->d_lookup, 0, 4 * W, ctx->stream) != hipSuccess) {
-        bow_free(b);
+        delete b;
         return rs_fail(ctx, RS_ERR_HIP, "bag-of-words scratch could not be cleared");
     }
     *out_bow = b;
     return RS_OK;
 }
 
-extern "C" int rs_bow_destroy(rs_bow* bow)
-{
-    if (!bow) return RS_OK;
-    (void)hipSetDevice(bow->ctx->device);
-    (void)hipStreamSynchronize(bow->ctx->stream);
-    bow_free(bow);
-    return RS_OK;
-}
+extern "C" int rs_bow_destroy(rs_bow* bow) { return rs_drain_and_delete(bow); }
 
 extern "C" int rs_bow_transform(rs_context* ctx, rs_bow* bow, const uint8_t* d_desc, const int32_t* d_count, int max_n, int32_t* d_word)
 {
@@ -512,14 +490,6 @@ extern "C" int rs_bow_download(rs_context* ctx, const rs_bow* bow, int32_t* h_wo
 }
 
 // ------------------------------------------------------------------------------------------------ database
-static void database_free(rs_bow_database* db)
-{
-    if (db->d_ptr) (void)hipFree(db->d_ptr);
-    if (db->d_words) (void)hipFree(db->d_words);
-    if (db->d_values) (void)hipFree(db->d_values);
-    delete db;
-}
-
 extern "C" int rs_bow_database_create(rs_context* ctx, rs_vocabulary* voc, int max_entries, int max_total_words, rs_bow_database** out_db)
 {
     if (!ctx || !out_db) return RS_ERR_INVALID;
@@ -536,27 +506,21 @@ extern "C" int rs_bow_database_create(rs_context* ctx, rs_vocabulary* voc, int m
     db->max_total_words = max_total_words;
     db->ptr.reserve((size_t)max_entries + 1);
     db->ptr.push_back(0);
-    if (hipMalloc(&db->d_ptr, 4 * ((size_t)max_entries + 1)) != hipSuccess || hipMalloc(&db->d_words, 4 * (size_t)max_total_words) != hipSuccess ||
-        hipMalloc(&db->d_values, 8 * (size_t)max_total_words) != hipSuccess) {
-        database_free(db);
-        return rs_fail(ctx, RS_ERR_NOMEM, "database of %d entries and %d words", max_entries, max_total_words);
-    }
+    const int rc = db->block.carve(ctx, "bag-of-words database", [&](rs_carve& c) {
+        db->d_ptr = c.take<int32_t>((size_t)max_entries + 1);
+        db->d_words = c.take<int32_t>((size_t)max_total_words);
+        db->d_values = c.take<double>((size_t)max_total_words);
+    });
+    if (rc != RS_OK) { delete db; return rc; }
     if (hipMemsetAsync(db->d_ptr, 0, 4, ctx->stream) != hipSuccess) {
-        database_free(db);
+        delete db;
         return rs_fail(ctx, RS_ERR_HIP, "database could not be cleared");
     }
     *out_db = db;
     return RS_OK;
 }
 
-extern "C" int rs_bow_database_destroy(rs_bow_database* db)
-{
-    if (!db) return RS_OK;
-    (void)hipSetDevice(db->ctx->device);
-    (void)hipStreamSynchronize(db->ctx->stream);
-    database_free(db);
-    return RS_OK;
-}
+extern "C" int rs_bow_database_destroy(rs_bow_database* db) { return rs_drain_and_delete(db); }
 
 extern "C" int rs_bow_database_add(rs_context* ctx, rs_bow_database* db, const rs_bow* bow, int32_t* h_entry)
 {

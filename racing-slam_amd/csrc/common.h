@@ -98,6 +98,8 @@ struct rs_context {
 struct rs_frame {
     rs_context* ctx = nullptr;
     int n = 0;
+    rs_dev_block block;                 // every device array below but the grid
+    rs_pin_block pin;                   // h_n
     float* d_kp = nullptr; uint8_t* d_desc = nullptr; int32_t* d_kd = nullptr;   // node_kp | left | right, stride n
     uint8_t* d_matched = nullptr;
     void* d_packed = nullptr;           // {x, y, left, right}[n] + keypoint[n]: what K2 stages in LDS (rs_kdtree_pack layout)
@@ -120,6 +122,16 @@ struct rs_frame {
 int rs_frame_grid(rs_context* ctx, rs_frame* f, int width, int height, const void** d_grid);
 
 int rs_fail(rs_context* ctx, int code, const char* fmt, ...);
+// the whole of a *_destroy whose object holds only owners (dev_array.h): make the device current, drain the stream, delete
+template <class T>
+static inline int rs_drain_and_delete(T* o)
+{
+    if (!o) return RS_OK;
+    (void)hipSetDevice(o->ctx->device);
+    (void)hipStreamSynchronize(o->ctx->stream);
+    delete o;
+    return RS_OK;
+}
 
 // reproj_match.hip: the cell grids K2 may use in place of its walk, remembered per process (a view travels between contexts).
 // rs_k2_grid_enqueue launches a build on the context stream without waiting for its verdict; a caller that knows the tree to be

@@ -268,7 +268,7 @@ int rs_pinned(rs_context* ctx, size_t bytes, void** out)
 // and every copy is asynchronous on the context stream.
 static int arena_take(rs_context* ctx, rs_arena& a, bool pinned, size_t bytes, void** out)
 {
-    const size_t need = (bytes + 255) & ~(size_t)255;
+    const size_t need = rs_align256(bytes);
     if (a.used + need > a.cap) {
         size_t want = a.cap ? a.cap * 2 : (size_t)1 << 20;
         while (want < a.used + need) want *= 2;

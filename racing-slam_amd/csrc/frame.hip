@@ -188,19 +188,27 @@ static size_t frame_build_lds(int cap)
     return 2 * 5 * np + 4 * np + 4 * FB_THREADS;
 }
 
-// The buffers of a frame of `rows` keypoints, its match table at -1 (no map match yet).  An assignable frame
-// (rs_frame_create_device) also gets the rank table, the two count words and d_packed in full.  Both constructors go through
-// here, and on any failure after `new rs_frame` through rs_frame_destroy, which frees whatever was made.
+// The buffers of a frame of `rows` keypoints, its match table at -1 (no map match yet).  A frame with a tree has d_packed (one
+// of no keypoints has none); an assignable frame (rs_frame_create_device) also gets the rank table, the two count words and
+// the pinned word.  Both constructors go through here.
 static int frame_alloc(rs_context* ctx, rs_frame* f, size_t rows, bool assignable)
 {
-    bool ok = hipMalloc((void**)&f->d_kp, sizeof(float) * 2 * rows) == hipSuccess && hipMalloc((void**)&f->d_desc, 32 * rows) == hipSuccess &&
-              hipMalloc((void**)&f->d_kd, sizeof(int32_t) * 3 * rows) == hipSuccess && hipMalloc((void**)&f->d_matched, rows) == hipSuccess &&
-              hipMalloc((void**)&f->d_kp_point, sizeof(int32_t) * rows) == hipSuccess;
-    if (assignable)
-        ok = ok && hipMalloc(&f->d_packed, 20 * rows) == hipSuccess && hipMalloc((void**)&f->d_rank, sizeof(uint32_t) * rows) == hipSuccess &&
-             hipMalloc((void**)&f->d_n, 2 * sizeof(int32_t)) == hipSuccess && hipHostMalloc((void**)&f->h_n, 2 * sizeof(int32_t)) == hipSuccess;
-    ok = ok && hipMemsetAsync(f->d_kp_point, 0xFF, sizeof(int32_t) * rows, ctx->stream) == hipSuccess;
-    return ok ? RS_OK : rs_fail(ctx, RS_ERR_NOMEM, "frame buffers");
+    int rc = f->block.carve(ctx, "frame buffers", [&](rs_carve& c) {
+        f->d_kp = c.take<float>(2 * rows);
+        f->d_desc = c.take<uint8_t>(32 * rows);
+        f->d_kd = c.take<int32_t>(3 * rows);
+        f->d_matched = c.take<uint8_t>(rows);
+        f->d_kp_point = c.take<int32_t>(rows);
+        if (assignable || f->n > 0) f->d_packed = c.take<uint8_t>(20 * rows);
+        if (assignable) {
+            f->d_rank = c.take<uint32_t>(rows);
+            f->d_n = c.take<int32_t>(2);
+        }
+    });
+    if (!rc && assignable) rc = f->pin.carve(ctx, "frame count word", [&](rs_carve& c) { f->h_n = c.take<int32_t>(2); });
+    if (rc) return rc;
+    RS_HIP(ctx, hipMemsetAsync(f->d_kp_point, 0xFF, sizeof(int32_t) * rows, ctx->stream));
+    return RS_OK;
 }
 
 // rs_frame_create's uploads: the caller's arrays, the tree rs_kdtree_build made of them (kd: node_kp | left | right, stride n)
@@ -218,7 +226,6 @@ static int frame_upload(rs_context* ctx, rs_frame* f, const float* h_kp, const u
         packed[4 * i + 3] = kd[2 * m + i];
         packed[4 * m + i] = kpi;
     }
-    if (hipMalloc(&f->d_packed, 20 * m) != hipSuccess) return rs_fail(ctx, RS_ERR_NOMEM, "frame buffers");
     RS_HIP(ctx, hipMemcpyAsync(f->d_kp, h_kp, sizeof(float) * 2 * m, hipMemcpyHostToDevice, s));
     RS_HIP(ctx, hipMemcpyAsync(f->d_desc, h_desc, 32 * m, hipMemcpyHostToDevice, s));
     RS_HIP(ctx, hipMemcpyAsync(f->d_kd, kd.data(), sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice, s));
@@ -267,10 +274,6 @@ extern "C" int rs_frame_destroy(rs_frame* f)
     (void)hipSetDevice(f->ctx->device);
     (void)hipStreamSynchronize(f->ctx->stream);
     rs_k2_grid_forget(f->grid.p);
-    for (void* p : {(void*)f->d_kp, (void*)f->d_desc, (void*)f->d_kd, (void*)f->d_matched, f->d_packed, (void*)f->d_rank, (void*)f->d_n,
-                    (void*)f->d_kp_point})
-        if (p) (void)hipFree(p);
-    if (f->h_n) (void)hipHostFree(f->h_n);
     delete f;
     return RS_OK;
 }

@@ -52,7 +52,7 @@ enum {
 struct rs_detector {
     rs_context* ctx = nullptr;
     int width = 0, height = 0, max_corners = 0;
-    void* d_buf = nullptr;          // everything below, one allocation
+    rs_dev_block block;             // everything below
     uint8_t* d_mask = nullptr;      // replenish mask [h][w]
     uint8_t* d_state = nullptr;     // 0 not a candidate, 1 undecided, 2 accepted, 3 rejected [h][w]
     float* d_eig = nullptr;         // [h][w]
@@ -465,34 +465,21 @@ extern "C" int rs_detector_create(rs_context* ctx, int width, int height, int ma
     d->max_corners = max_corners;
     const size_t px = (size_t)width * height;
     const size_t nc = (size_t)std::max(width - 2, 1) * std::max(height - 2, 1);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t o_state = up(px), o_eig = o_state + up(px), o_cand = o_eig + up(4 * px), o_acc = o_cand + up(4 * nc),
-                 o_work = o_acc + up(8 * nc), o_ctr = o_work + up(8 * nc), total = o_ctr + up(4 * C_COUNT);
-    if (hipMalloc(&d->d_buf, total) != hipSuccess) {
-        delete d;
-        return rs_fail(ctx, RS_ERR_NOMEM, "detector scratch of %zu bytes", total);
-    }
-    uint8_t* b = (uint8_t*)d->d_buf;
-    d->d_mask = b;
-    d->d_state = b + o_state;
-    d->d_eig = (float*)(b + o_eig);
-    d->d_cand = (int32_t*)(b + o_cand);
-    d->d_acc = (unsigned long long*)(b + o_acc);
-    d->d_work = (unsigned long long*)(b + o_work);
-    d->d_ctr = (uint32_t*)(b + o_ctr);
+    const int rc = d->block.carve(ctx, "detector scratch", [&](rs_carve& c) {
+        d->d_mask = c.take<uint8_t>(px);
+        d->d_state = c.take<uint8_t>(px);
+        d->d_eig = c.take<float>(px);
+        d->d_cand = c.take<int32_t>(nc);
+        d->d_acc = c.take<unsigned long long>(nc);
+        d->d_work = c.take<unsigned long long>(nc);
+        d->d_ctr = c.take<uint32_t>(C_COUNT);
+    });
+    if (rc != RS_OK) { delete d; return rc; }
     *out = d;
     return RS_OK;
 }
 
-extern "C" int rs_detector_destroy(rs_detector* d)
-{
-    if (!d) return RS_OK;
-    (void)hipSetDevice(d->ctx->device);
-    (void)hipStreamSynchronize(d->ctx->stream);
-    if (d->d_buf) (void)hipFree(d->d_buf);
-    delete d;
-    return RS_OK;
-}
+extern "C" int rs_detector_destroy(rs_detector* d) { return rs_drain_and_delete(d); }
 
 static int detector_check(rs_context* ctx, const rs_detector* det, const rs_image* img)
 {

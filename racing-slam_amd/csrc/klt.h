@@ -22,7 +22,7 @@ struct rs_image {
     rs_context* ctx = nullptr;
     int width = 0, height = 0, max_level = 0, win = 0;
     KltPyr pyr{};
-    void* d_buf = nullptr;          // every level, one allocation
+    rs_dev_block block;             // every level and d_stage
     uint8_t* d_stage = nullptr;     // raw upload of a host frame (width * height * 3 bytes)
     bool valid = false;             // a frame has been uploaded
 };

@@ -322,7 +322,6 @@ extern "C" int rs_image_create(rs_context* ctx, int width, int height, int max_l
     KltPyr& P = im->pyr;
     P.pad = win;
     P.levels = klt_num_levels(width, height, win, max_level) + 1;
-    size_t off[KLT_MAX_LEVELS][2], total = 0;
     int w = width, h = height;
     for (int l = 0; l < P.levels; l++) {
         KltLevel& L = P.lv[l];
@@ -330,37 +329,23 @@ extern "C" int rs_image_create(rs_context* ctx, int width, int height, int max_l
         L.h = h;
         L.pitch = w + 2 * win;
         L.rows = h + 2 * win;
-        const size_t px = (size_t)L.pitch * L.rows;
-        off[l][0] = total;
-        total += (px + 255) / 256 * 256;
-        off[l][1] = total;
-        total += (4 * px + 255) / 256 * 256;
         w = (w + 1) / 2;
         h = (h + 1) / 2;
     }
-    if (hipMalloc(&im->d_buf, total) != hipSuccess || hipMalloc((void**)&im->d_stage, (size_t)width * height * 3) != hipSuccess) {
-        if (im->d_buf) (void)hipFree(im->d_buf);
-        delete im;
-        return rs_fail(ctx, RS_ERR_NOMEM, "image pyramid of %zu bytes", total);
-    }
-    for (int l = 0; l < P.levels; l++) {
-        P.lv[l].img = (uint8_t*)im->d_buf + off[l][0];
-        P.lv[l].der = (short2*)((uint8_t*)im->d_buf + off[l][1]);
-    }
+    const int rc = im->block.carve(ctx, "image pyramid", [&](rs_carve& c) {
+        for (int l = 0; l < P.levels; l++) {
+            const size_t px = (size_t)P.lv[l].pitch * P.lv[l].rows;
+            P.lv[l].img = c.take<uint8_t>(px);
+            P.lv[l].der = c.take<short2>(px);
+        }
+        im->d_stage = c.take<uint8_t>((size_t)width * height * 3);
+    });
+    if (rc != RS_OK) { delete im; return rc; }
     *out = im;
     return RS_OK;
 }
 
-extern "C" int rs_image_destroy(rs_image* im)
-{
-    if (!im) return RS_OK;
-    (void)hipSetDevice(im->ctx->device);
-    (void)hipStreamSynchronize(im->ctx->stream);
-    if (im->d_buf) (void)hipFree(im->d_buf);
-    if (im->d_stage) (void)hipFree(im->d_stage);
-    delete im;
-    return RS_OK;
-}
+extern "C" int rs_image_destroy(rs_image* im) { return rs_drain_and_delete(im); }
 
 extern "C" int rs_image_levels(const rs_image* im, int* h_levels, int* h_sizes)
 {
@@ -512,7 +497,7 @@ extern "C" int rs_track_features(rs_context* ctx, const rs_image* prev, const rs
     }
     if (!d_prev_pts || !d_kept_index || !d_kept_pt) return rs_fail(ctx, RS_ERR_INVALID, "null pointer");
     void* ws = nullptr;
-    const size_t pt_bytes = (sizeof(float2) * (size_t)n + 255) / 256 * 256;
+    const size_t pt_bytes = rs_align256(sizeof(float2) * (size_t)n);
     if ((rc = rs_workspace(ctx, pt_bytes + (size_t)n, &ws))) return rc;
     float2* d_next = (float2*)ws;
     uint8_t* d_keep = (uint8_t*)ws + pt_bytes;

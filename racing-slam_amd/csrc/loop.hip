@@ -60,8 +60,8 @@ struct LoopPinned {                         // what the verdict kernel writes in
 struct rs_loop_verifier {
     rs_context* ctx = nullptr;
     int max_points = 0, max_candidates = 0, max_hyp = 0;
-    void* slab = nullptr;                   // every LoopChain buffer
-    void* pinned = nullptr;
+    rs_dev_block slab;                      // every LoopChain buffer
+    rs_pin_block pinned;                    // what `pin` points into
     LoopChain chain[LOOP_MAX_CANDIDATES];
     LoopPinned pin = {};
     rs_pnp_estimator* est[LOOP_MAX_CANDIDATES] = {};
@@ -181,8 +181,6 @@ __global__ __launch_bounds__(LOOP_BLOCK) void loop_verdict(LoopArgs a, int max_p
 }
 
 // ------------------------------------------------------------------------------------------------ C-ABI
-static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // The child contexts of the forked form, the default: own stream, own K1 table sized for max_points.  Created with the
 // verifier, so that no call allocates.
 static int loop_children(rs_loop_verifier* v, int n)
@@ -217,8 +215,6 @@ extern "C" int rs_loop_verifier_destroy(rs_loop_verifier* v)
         if (v->child[c]) rs_context_destroy(v->child[c]);
         if (v->child_stream[c]) (void)hipStreamDestroy(v->child_stream[c]);
     }
-    if (v->slab) (void)hipFree(v->slab);
-    if (v->pinned) (void)hipHostFree(v->pinned);
     delete v;
     return RS_OK;
 }
@@ -238,38 +234,32 @@ extern "C" int rs_loop_verifier_create(rs_context* ctx, int max_points, int max_
     v->max_candidates = max_candidates;
     v->max_hyp = max_hypotheses;
     const size_t m = (size_t)max_points, C = (size_t)max_candidates;
-    const size_t b_rows = up256(32 * m), b_pos = up256(12 * m), b_i = up256(4 * m), b_scal = up256(4 * LS_WORDS), b_pose = up256(64),
-                 b_u8 = up256(m);
-    const size_t per = b_rows + b_pos + 5 * b_i + b_scal + b_pose + b_u8;
-    const size_t pin_bytes = up256(sizeof(rs_loop_result) * C) + up256(4 * C) + 3 * up256(4 * C * m);
-    int rc = RS_OK;
-    if (hipMalloc(&v->slab, per * C) != hipSuccess || hipHostMalloc(&v->pinned, pin_bytes, hipHostMallocDefault) != hipSuccess)
-        rc = rs_fail(ctx, RS_ERR_NOMEM, "loop verifier scratch for %d points, %d candidates", max_points, max_candidates);
-    if (!rc && hipMemsetAsync(v->slab, 0, per * C, ctx->stream) != hipSuccess) rc = rs_fail(ctx, RS_ERR_HIP, "hipMemsetAsync");
-    if (!rc) {
-        memset(v->pinned, 0, pin_bytes);
-        char* p = (char*)v->pinned;
-        v->pin.result = (rs_loop_result*)p; p += up256(sizeof(rs_loop_result) * C);
-        v->pin.gathered = (int32_t*)p; p += up256(4 * C);
-        v->pin.query_kp = (int32_t*)p; p += up256(4 * C * m);
-        v->pin.point = (int32_t*)p; p += up256(4 * C * m);
-        v->pin.cand_kp = (int32_t*)p;
-    }
-    for (size_t c = 0; c < C && !rc; c++) {
-        char* p = (char*)v->slab + per * c;
-        LoopChain& k = v->chain[c];
-        k.rows = (uint8_t*)p; p += b_rows;
-        k.pos = (float*)p; p += b_pos;
-        k.kp = (int32_t*)p; p += b_i;
-        k.slot = (int32_t*)p; p += b_i;
-        k.mq = (int32_t*)p; p += b_i;
-        k.mt = (int32_t*)p; p += b_i;
-        k.inlier_index = (int32_t*)p; p += b_i;
-        k.scal = (int32_t*)p; p += b_scal;
-        k.pose = (float*)p; p += b_pose;
-        k.inlier = (uint8_t*)p;
-        rc = rs_pnp_estimator_create(ctx, max_points, max_hypotheses, &v->est[c]);
-    }
+    int rc = v->slab.carve(ctx, "loop verifier scratch", [&](rs_carve& s) {
+        for (size_t c = 0; c < C; c++) {
+            LoopChain& k = v->chain[c];
+            k.rows = s.take<uint8_t>(32 * m);
+            k.pos = s.take<float>(3 * m);
+            k.kp = s.take<int32_t>(m);
+            k.slot = s.take<int32_t>(m);
+            k.mq = s.take<int32_t>(m);
+            k.mt = s.take<int32_t>(m);
+            k.inlier_index = s.take<int32_t>(m);
+            k.scal = s.take<int32_t>(LS_WORDS);
+            k.pose = s.take<float>(16);
+            k.inlier = s.take<uint8_t>(m);
+        }
+    });
+    if (!rc)
+        rc = v->pinned.carve(ctx, "loop verifier results", [&](rs_carve& p) {
+            v->pin.result = p.take<rs_loop_result>(C);
+            v->pin.gathered = p.take<int32_t>(C);
+            v->pin.query_kp = p.take<int32_t>(C * m);
+            v->pin.point = p.take<int32_t>(C * m);
+            v->pin.cand_kp = p.take<int32_t>(C * m);
+        });
+    if (!rc && hipMemsetAsync(v->slab.p, 0, v->slab.bytes, ctx->stream) != hipSuccess) rc = rs_fail(ctx, RS_ERR_HIP, "hipMemsetAsync");
+    if (!rc) memset(v->pinned.p, 0, v->pinned.bytes);
+    for (size_t c = 0; c < C && !rc; c++) rc = rs_pnp_estimator_create(ctx, max_points, max_hypotheses, &v->est[c]);
     if (!rc) rc = loop_children(v, max_candidates);
     if (!rc) rc = rs_k1_reserve(ctx, m);
     if (!rc && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = rs_fail(ctx, RS_ERR_HIP, "hipStreamSynchronize");

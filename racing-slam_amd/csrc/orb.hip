@@ -38,6 +38,7 @@
 struct rs_describer {
     rs_context* ctx = nullptr;
     int width = 0, height = 0, max_points = 0;
+    rs_dev_block block;
     uint8_t* d_blur = nullptr;      // the blurred level 0 [h][w]
 };
 
@@ -175,23 +176,13 @@ extern "C" int rs_describer_create(rs_context* ctx, int width, int height, int m
     d->width = width;
     d->height = height;
     d->max_points = max_points;
-    if (hipMalloc(&d->d_blur, (size_t)width * height) != hipSuccess) {
-        delete d;
-        return rs_fail(ctx, RS_ERR_NOMEM, "describer plane of %zu bytes", (size_t)width * height);
-    }
+    const int rc = d->block.carve(ctx, "describer plane", [&](rs_carve& c) { d->d_blur = c.take<uint8_t>((size_t)width * height); });
+    if (rc != RS_OK) { delete d; return rc; }
     *out = d;
     return RS_OK;
 }
 
-extern "C" int rs_describer_destroy(rs_describer* d)
-{
-    if (!d) return RS_OK;
-    (void)hipSetDevice(d->ctx->device);
-    (void)hipStreamSynchronize(d->ctx->stream);
-    if (d->d_blur) (void)hipFree(d->d_blur);
-    delete d;
-    return RS_OK;
-}
+extern "C" int rs_describer_destroy(rs_describer* d) { return rs_drain_and_delete(d); }
 
 static int describer_check(rs_context* ctx, const rs_describer* d, const rs_image* img)
 {

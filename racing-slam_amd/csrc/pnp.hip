@@ -657,22 +657,21 @@ __global__ __launch_bounds__(256) void pnp_final(int max_n, double fx, double fy
 }
 
 // ------------------------------------------------------------------------------------------------ C-ABI
-static bool pnp_alloc(rs_pnp_estimator* e, size_t m, hipStream_t stream)
+static void pnp_layout(rs_pnp_estimator* e, rs_carve& c)
 {
-    return hipMalloc(&e->x, 5 * m * sizeof(double)) == hipSuccess && hipMalloc(&e->fin, m) == hipSuccess &&
-           hipMalloc(&e->mask, 2 * m) == hipSuccess && hipMalloc(&e->st, sizeof(PnpState)) == hipSuccess &&
-           hipMemsetAsync(e->st, 0, sizeof(PnpState), stream) == hipSuccess;
+    const size_t m = e->max_points;
+    e->x = c.take<double>(5 * m);
+    e->fin = c.take<uint8_t>(m);
+    e->mask = c.take<uint8_t>(2 * m);
+    e->st = c.take<PnpState>(1);
 }
 
 extern "C" int rs_pnp_estimator_create(rs_context* ctx, int max_points, int max_hypotheses, rs_pnp_estimator** out)
 {
-    return ransac_create(ctx, max_points, max_hypotheses, out, 4, 4, 12, "pnp", pnp_alloc, rs_pnp_estimator_destroy);
+    return ransac_create(ctx, max_points, max_hypotheses, out, 4, 4, 12, "pnp estimator scratch", pnp_layout);
 }
 
-extern "C" int rs_pnp_estimator_destroy(rs_pnp_estimator* e)
-{
-    return e ? ransac_destroy(e, {e->x, e->fin, e->mask, e->st}) : RS_OK;
-}
+extern "C" int rs_pnp_estimator_destroy(rs_pnp_estimator* e) { return rs_drain_and_delete(e); }
 
 extern "C" int rs_estimate_pose_pnp(rs_context* ctx, rs_pnp_estimator* e, const float* d_object, const int32_t* d_object_index,
                                     const float* d_pixels, const int32_t* d_pixel_index, const int32_t* d_count, int max_n,

@@ -782,23 +782,23 @@ __global__ __launch_bounds__(256) void kr_final(int max_n, Rot9 R, float focal, 
 }
 
 // ------------------------------------------------------------------------------------------------ C-ABI
-static bool pose_alloc(rs_pose_estimator* e, size_t m, hipStream_t stream)
+static void pose_layout(rs_pose_estimator* e, rs_carve& c)
 {
-    return hipMalloc(&e->x, 4 * m * sizeof(double)) == hipSuccess && hipMalloc(&e->pix, 2 * m * sizeof(float2)) == hipSuccess &&
-           hipMalloc(&e->fin, m) == hipSuccess && hipMalloc(&e->mask, 2 * m) == hipSuccess &&
-           hipMalloc(&e->rays, 9 * m * sizeof(float)) == hipSuccess && hipMalloc(&e->st, sizeof(PoseState)) == hipSuccess &&
-           hipMemsetAsync(e->st, 0, sizeof(PoseState), stream) == hipSuccess;
+    const size_t m = e->max_points;
+    e->x = c.take<double>(4 * m);
+    e->pix = c.take<float2>(2 * m);
+    e->fin = c.take<uint8_t>(m);
+    e->mask = c.take<uint8_t>(2 * m);
+    e->rays = c.take<float>(9 * m);
+    e->st = c.take<PoseState>(1);
 }
 
 extern "C" int rs_pose_estimator_create(rs_context* ctx, int max_points, int max_hypotheses, rs_pose_estimator** out)
 {
-    return ransac_create(ctx, max_points, max_hypotheses, out, 5, 10, 9, "pose", pose_alloc, rs_pose_estimator_destroy);
+    return ransac_create(ctx, max_points, max_hypotheses, out, 5, 10, 9, "pose estimator scratch", pose_layout);
 }
 
-extern "C" int rs_pose_estimator_destroy(rs_pose_estimator* e)
-{
-    return e ? ransac_destroy(e, {e->x, e->pix, e->fin, e->mask, e->rays, e->st}) : RS_OK;
-}
+extern "C" int rs_pose_estimator_destroy(rs_pose_estimator* e) { return rs_drain_and_delete(e); }
 
 extern "C" int rs_estimate_pose(rs_context* ctx, rs_pose_estimator* e, const float* d_pts_from, const int32_t* d_from_index,
                                 const float* d_pts_to, const int32_t* d_count, int max_n, const float* h_intrinsics,

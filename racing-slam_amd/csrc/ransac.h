@@ -8,11 +8,10 @@
 //   the stop      after each round of RANSAC_ROUND: drawn >= log(1 - confidence) / log(1 - w^S), w = best count / n
 //                 (tests/essential_ref.needed_hypotheses)
 //   the inliers   the u8 mask over max_n and the ascending index list
-// and, on the host, the table's allocation / release / download and the argument checks of the entry points.
+// and, on the host, the table's layout / first fill / download and the argument checks of the entry points.
 #pragma once
 #include <algorithm>
 #include <cmath>
-#include <initializer_list>
 
 #include "common.h"
 
@@ -124,18 +123,22 @@ struct RansacEstimator {                // what rs_pose_estimator and rs_pnp_est
     rs_context* ctx = nullptr;
     int max_points = 0, max_hyp = 0;
     RansacTable t = {};                 // [max_hyp] entries
+    rs_dev_block block;                 // the table and the stage's own arrays
 };
 
-// allocates the table for H hypotheses and fills it as a call's reset would (models 0); synchronises the stream
-static inline bool ransac_table_alloc(RansacTable* t, size_t H, int S, int M, int D, hipStream_t stream)
+// the stage's state at zero and the table as a call's reset would leave it (models 0); synchronises the stream
+template <class E>
+static inline int ransac_first_fill(rs_context* ctx, E* e, size_t H, int S, int M, int D)
 {
-    const size_t ns = S * H * sizeof(int32_t), nn = H * sizeof(int32_t), nc = M * H * sizeof(int32_t),
-                 nm = (size_t)M * D * H * sizeof(double);
-    return hipMalloc(&t->samples, ns) == hipSuccess && hipMalloc(&t->nmod, nn) == hipSuccess &&
-           hipMalloc(&t->models, nm) == hipSuccess && hipMalloc(&t->scores, nc) == hipSuccess &&
-           hipMemsetAsync(t->samples, 0xFF, ns, stream) == hipSuccess && hipMemsetAsync(t->nmod, 0xFF, nn, stream) == hipSuccess &&
-           hipMemsetAsync(t->scores, 0, nc, stream) == hipSuccess && hipMemsetAsync(t->models, 0, nm, stream) == hipSuccess &&
-           hipStreamSynchronize(stream) == hipSuccess;
+    const RansacTable& t = e->t;
+    hipStream_t stream = ctx->stream;
+    RS_HIP(ctx, hipMemsetAsync(e->st, 0, sizeof *e->st, stream));
+    RS_HIP(ctx, hipMemsetAsync(t.samples, 0xFF, S * H * sizeof(int32_t), stream));
+    RS_HIP(ctx, hipMemsetAsync(t.nmod, 0xFF, H * sizeof(int32_t), stream));
+    RS_HIP(ctx, hipMemsetAsync(t.scores, 0, M * H * sizeof(int32_t), stream));
+    RS_HIP(ctx, hipMemsetAsync(t.models, 0, (size_t)M * D * H * sizeof(double), stream));
+    RS_HIP(ctx, hipStreamSynchronize(stream));
+    return RS_OK;
 }
 
 // the body of rs_*_hypotheses: the whole table to the host arrays that are not null
@@ -155,10 +158,11 @@ static inline int ransac_table_download(rs_context* ctx, const RansacEstimator* 
     return RS_OK;
 }
 
-// rs_*_estimator_create: a new E with its table; own(e, max_points, stream) allocates and clears what the stage adds
+// rs_*_estimator_create: a new E with one block; own(e, carver) lays out what the stage adds (its state e->st included),
+// the table follows it
 template <class E>
-static inline int ransac_create(rs_context* ctx, int max_points, int max_hypotheses, E** out, int S, int M, int D, const char* stage,
-                                bool (*own)(E*, size_t, hipStream_t), int (*destroy)(E*))
+static inline int ransac_create(rs_context* ctx, int max_points, int max_hypotheses, E** out, int S, int M, int D, const char* what,
+                                void (*own)(E*, rs_carve&))
 {
     if (!ctx || !out) return RS_ERR_INVALID;
     *out = nullptr;
@@ -170,25 +174,17 @@ static inline int ransac_create(rs_context* ctx, int max_points, int max_hypothe
     e->ctx = ctx;
     e->max_points = max_points;
     e->max_hyp = max_hypotheses;
-    if (!own(e, max_points, ctx->stream) || !ransac_table_alloc(&e->t, max_hypotheses, S, M, D, ctx->stream)) {
-        destroy(e);
-        return rs_fail(ctx, RS_ERR_NOMEM, "%s estimator scratch for %d points, %d hypotheses", stage, max_points, max_hypotheses);
-    }
+    const size_t H = max_hypotheses;
+    int rc = e->block.carve(ctx, what, [&](rs_carve& c) {
+        own(e, c);
+        e->t.samples = c.take<int32_t>(S * H);
+        e->t.nmod = c.take<int32_t>(H);
+        e->t.models = c.take<double>((size_t)M * D * H);
+        e->t.scores = c.take<int32_t>(M * H);
+    });
+    if (rc == RS_OK) rc = ransac_first_fill(ctx, e, H, S, M, D);
+    if (rc != RS_OK) { delete e; return rc; }
     *out = e;
-    return RS_OK;
-}
-
-// rs_*_estimator_destroy: own = the stage's device pointers
-template <class E>
-static inline int ransac_destroy(E* e, std::initializer_list<void*> own)
-{
-    (void)hipSetDevice(e->ctx->device);
-    (void)hipStreamSynchronize(e->ctx->stream);
-    for (void* q : own)
-        if (q) (void)hipFree(q);
-    for (void* q : {(void*)e->t.samples, (void*)e->t.nmod, (void*)e->t.models, (void*)e->t.scores})
-        if (q) (void)hipFree(q);
-    delete e;
     return RS_OK;
 }
 

@@ -405,7 +405,7 @@ static int refine_pose_solve(rs_context* ctx, double h_camera[6], const double* 
     if (in) {
         const size_t ext_off = 512;
         void* wsv = nullptr;
-        rc = rs_workspace(ctx, ext_off + ((sizeof(RpInertial) + 255) & ~(size_t)255), &wsv);
+        rc = rs_workspace(ctx, ext_off + rs_align256(sizeof(RpInertial)), &wsv);
         if (rc) return rc;
         d_ext = (RpInertial*)((char*)wsv + ext_off);
     }

@@ -30,7 +30,8 @@ struct TsSighting { int32_t frame; float x, y; int32_t kf; int32_t kp; };      /
 struct rs_track_store {
     rs_context* ctx = nullptr;
     int cap = 0, max_s = 0;
-    void* d_block = nullptr;                    // every device array below is a piece of it
+    rs_dev_block block;                         // every device array below is a piece of it
+    rs_pin_block pin;                           // h_pin
     int32_t* d_kp_row = nullptr;                // [cap] keypoint of the current frame -> row or -1
     uint8_t* d_used = nullptr;                  // [cap] row in use
     unsigned long long* d_id = nullptr;         // [cap] per row
@@ -38,7 +39,7 @@ struct rs_track_store {
     int32_t* d_count = nullptr;                 // [cap] sightings held
     TsSighting* d_sight = nullptr;              // [cap][max_s]
     unsigned long long* d_next_id = nullptr;    // [1]
-    int32_t* d_query = nullptr;                 // [6]
+    int32_t* d_query = nullptr;                 // [6] of 8
     // rs_triangulate_tracks' inputs and outputs for the tracks of the last pack
     int32_t* d_order = nullptr;                 // [cap] row of packed track t
     float* d_track_uv = nullptr; uint8_t* d_skip = nullptr; int32_t* d_sight_ptr = nullptr; int32_t* d_sight_pose = nullptr;
@@ -362,8 +363,6 @@ extern "C" int rs_track_store_destroy(rs_track_store* s)
         (void)hipSetDevice(s->ctx->device);
         (void)hipStreamSynchronize(s->ctx->stream);
     }
-    if (s->d_block) (void)hipFree(s->d_block);
-    if (s->h_pin) (void)hipHostFree(s->h_pin);
     delete s;
     return RS_OK;
 }
@@ -381,32 +380,36 @@ extern "C" int rs_track_store_create(rs_context* ctx, int max_points, int max_si
     s->ctx = ctx; s->cap = max_points; s->max_s = max_sightings;
     const size_t cap = (size_t)max_points, all = cap * (size_t)max_sightings;
     s->result_ints = 8 + 10 * cap + 1 + 2 * all;
-    // the pieces, 256-byte aligned, in the order of the members
-    const size_t bytes[] = {4 * cap, cap, 8 * cap, 4 * cap, 4 * cap, sizeof(TsSighting) * all, 8, 4 * 8,
-                            4 * cap, 8 * cap, cap, 4 * (cap + 1), 4 * all, 8 * all, cap, 12 * cap, 4 * cap, 4 * cap, 4 * cap, 4 * cap, 4 * 4,
-                            4 * s->result_ints};
-    size_t off[sizeof bytes / sizeof bytes[0] + 1] = {0};
-    for (size_t i = 0; i < sizeof bytes / sizeof bytes[0]; i++) off[i + 1] = off[i] + ((bytes[i] + 255) & ~(size_t)255);
-    const size_t total = off[sizeof bytes / sizeof bytes[0]];
-    if (hipMalloc(&s->d_block, total) != hipSuccess || hipHostMalloc((void**)&s->h_pin, 4 * (8 + s->result_ints), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        rs_track_store_destroy(s);
-        return rs_fail(ctx, RS_ERR_NOMEM, "rs_track_store_create: %zu bytes", total);
-    }
-    char* b = (char*)s->d_block;
-    int i = 0;
-    s->d_kp_row = (int32_t*)(b + off[i++]); s->d_used = (uint8_t*)(b + off[i++]); s->d_id = (unsigned long long*)(b + off[i++]);
-    s->d_row_kp = (int32_t*)(b + off[i++]); s->d_count = (int32_t*)(b + off[i++]); s->d_sight = (TsSighting*)(b + off[i++]);
-    s->d_next_id = (unsigned long long*)(b + off[i++]); s->d_query = (int32_t*)(b + off[i++]);
-    s->d_order = (int32_t*)(b + off[i++]); s->d_track_uv = (float*)(b + off[i++]); s->d_skip = (uint8_t*)(b + off[i++]);
-    s->d_sight_ptr = (int32_t*)(b + off[i++]); s->d_sight_pose = (int32_t*)(b + off[i++]); s->d_sight_uv = (float*)(b + off[i++]);
-    s->d_status = (uint8_t*)(b + off[i++]); s->d_xyz = (float*)(b + off[i++]); s->d_pc = (float*)(b + off[i++]); s->d_rc = (float*)(b + off[i++]);
-    s->d_accepted = (int32_t*)(b + off[i++]); s->d_inconsistent = (int32_t*)(b + off[i++]); s->d_counts = (int32_t*)(b + off[i++]);
-    s->d_result = (int32_t*)(b + off[i++]);
-    hipError_t e = hipMemsetAsync(s->d_block, 0, total, ctx->stream);
+    int rc = s->block.carve(ctx, "rs_track_store_create: device block", [&](rs_carve& c) {
+        s->d_kp_row = c.take<int32_t>(cap);
+        s->d_used = c.take<uint8_t>(cap);
+        s->d_id = c.take<unsigned long long>(cap);
+        s->d_row_kp = c.take<int32_t>(cap);
+        s->d_count = c.take<int32_t>(cap);
+        s->d_sight = c.take<TsSighting>(all);
+        s->d_next_id = c.take<unsigned long long>(1);
+        s->d_query = c.take<int32_t>(8);
+        s->d_order = c.take<int32_t>(cap);
+        s->d_track_uv = c.take<float>(2 * cap);
+        s->d_skip = c.take<uint8_t>(cap);
+        s->d_sight_ptr = c.take<int32_t>(cap + 1);
+        s->d_sight_pose = c.take<int32_t>(all);
+        s->d_sight_uv = c.take<float>(2 * all);
+        s->d_status = c.take<uint8_t>(cap);
+        s->d_xyz = c.take<float>(3 * cap);
+        s->d_pc = c.take<float>(cap);
+        s->d_rc = c.take<float>(cap);
+        s->d_accepted = c.take<int32_t>(cap);
+        s->d_inconsistent = c.take<int32_t>(cap);
+        s->d_counts = c.take<int32_t>(4);
+        s->d_result = c.take<int32_t>(s->result_ints);
+    });
+    if (!rc) rc = s->pin.carve(ctx, "rs_track_store_create: pinned block", [&](rs_carve& c) { s->h_pin = c.take<int32_t>(8 + s->result_ints); });
+    if (rc) { rs_track_store_destroy(s); return rc; }
+    hipError_t e = hipMemsetAsync(s->block.p, 0, s->block.bytes, ctx->stream);
     if (e == hipSuccess) e = rs_lds_attr((const void*)k_ts_carry, 13 * (size_t)TS_MAX);
     if (e == hipSuccess) e = rs_lds_attr((const void*)k_ts_pack, 8 * (size_t)TS_MAX);
-    int rc = e == hipSuccess ? rs_track_store_clear(ctx, s) : rs_fail(ctx, RS_ERR_HIP, "rs_track_store_create: %s", hipGetErrorString(e));
+    rc = e == hipSuccess ? rs_track_store_clear(ctx, s) : rs_fail(ctx, RS_ERR_HIP, "rs_track_store_create: %s", hipGetErrorString(e));
     if (rc) { rs_track_store_destroy(s); return rc; }
     *out = s;
     return RS_OK;

@@ -481,7 +481,7 @@ extern "C" int rs_reanchor_points_host_poses(rs_context* ctx, int n, const int32
         const int rc = rs_workspace(ctx, 2 * bytes + 256, &ws);
         if (rc) return rc;
         float* d_before = (float*)ws;
-        float* d_after = (float*)((char*)ws + ((bytes + 255) & ~(size_t)255));
+        float* d_after = (float*)((char*)ws + rs_align256(bytes));
         RS_HIP(ctx, hipMemcpyAsync(d_before, h_poses_before, bytes, hipMemcpyHostToDevice, ctx->stream));
         RS_HIP(ctx, hipMemcpyAsync(d_after, h_poses_after, bytes, hipMemcpyHostToDevice, ctx->stream));
         RS_HIP(ctx, hipStreamSynchronize(ctx->stream));          // pageable sources: the copies have read them
