@@ -38,7 +38,7 @@
 #include "ba_backsub_body.h"
 #include "ba_init_body.h"
 #include "ba_step_body.h"
-#include "imu_dual.h"
+#include "ba_blocks.h"
 
 // ---------------------------------------------------------------------- K0 (body: ba_init_body.h)
 __global__ void ba_init(BaDims d, BaBufs b, BaOpt opt, const double* __restrict__ cams_in,
@@ -392,8 +392,6 @@ extern "C" int rs_prof_counters(rs_context* ctx, uint64_t* h_out, int n)
     return RS_OK;
 }
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // the inertial residual blocks of one solve (null for a vision-only solve)
 struct BaInertialArgs {
     double* h_velocity;            // [C][3] in/out
@@ -429,62 +427,6 @@ void imu_whitener(const double cov[81], double W[81])
             for (int k = 0; k < i; k++) t -= L[i * 9 + k] * W[k * 9 + c];
             W[i * 9 + c] = t / L[i * 9 + i];
         }
-}
-
-// Workspace layout of one window (all offsets multiples of 256 B) and the BaBufs pointers into it: shared by the single
-// solve and by every window of a batched solve.
-struct BaLayout {
-    size_t Xc, Xp, prep, slot, sc, sp, Vinv, gp, lamp, Vc, Ukeep, acc, pts, dc, st, set, trace, dbg, fre, grp;
-    size_t bytes;                       // end of the common part (callers may carve more behind it)
-    size_t acc_count, cam_stride, pts_block;
-};
-static BaLayout ba_layout(const BaDims& d, int ns, int max_iter, size_t n_ranks, size_t grp_bytes, int srep = 1)
-{
-    BaLayout L;
-    const size_t n = (size_t)d.n, C = (size_t)d.C, P = (size_t)d.P, nb = (size_t)ns + 1;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += rs_align256(bytes); return o; };
-    L.Xc = carve(sizeof(double) * nb * C * 6); L.Xp = carve(sizeof(double) * nb * P * 3);
-    L.prep = carve(sizeof(double) * nb * C * BA_PREP); L.slot = carve(sizeof(int32_t) * C);
-    L.sc = carve(sizeof(double) * (n + 1)); L.sp = carve(sizeof(double) * P * 3);
-    L.Vinv = carve(sizeof(double) * ns * P * 6); L.gp = carve(sizeof(double) * P * 3);
-    L.lamp = carve(sizeof(double) * ns * P * 3);
-    L.Vc = carve(sizeof(double) * P * 6); L.Ukeep = carve(sizeof(double) * ((size_t)d.Cf * 36 + n + 1));
-    L.cam_stride = (size_t)ns * n + (size_t)d.Cf * 36 + n;
-    L.acc_count = (size_t)srep * ns * n * n + (size_t)BA_UREP * L.cam_stride + (1 + n_ranks) * (size_t)BA_NSLOT * BA_SLOT_STRIDE;
-    L.acc = carve(sizeof(double) * L.acc_count);
-    L.pts_block = (size_t)ns * BA_NSLOT * BA_SLOT_STRIDE;
-    L.pts = carve(sizeof(double) * 2 * L.pts_block); L.dc = carve(sizeof(double) * ns * BA_DC_STRIDE(n));
-    L.st = carve(sizeof(BaState) * 2);
-    L.set = carve(sizeof(BaSetOut) * 2 * BA_MAXSETS);
-    L.trace = carve(sizeof(BaTrace) * (size_t)(max_iter + 1));
-    L.dbg = carve(sizeof(unsigned long long) * BA_DBG_WORDS);
-    L.fre = carve(C);
-    L.grp = carve(grp_bytes);
-    L.bytes = off;
-    return L;
-}
-// pointers of round parity 0 (the double-buffered blocks are re-pointed per round); rank = this rank's gradient-max block
-static void ba_bind(BaBufs& b, char* ws, const BaLayout& L, const BaDims& d, int ns, int n_ranks, int rank, int srep = 1)
-{
-    const size_t n = (size_t)d.n;
-    b.ns = ns;
-    b.srep = srep; b.s_rep_stride = (size_t)ns * n * n;
-    b.Xc = (double*)(ws + L.Xc); b.Xp = (double*)(ws + L.Xp); b.prep = (double*)(ws + L.prep);
-    b.slot = (int32_t*)(ws + L.slot); b.sc = (double*)(ws + L.sc); b.sp = (double*)(ws + L.sp);
-    b.Vinv = (double*)(ws + L.Vinv); b.gp = (double*)(ws + L.gp); b.lamp = (double*)(ws + L.lamp);
-    b.Vc = (double*)(ws + L.Vc); b.Ukeep = (double*)(ws + L.Ukeep);
-    b.acc = (double*)(ws + L.acc); b.acc_count = L.acc_count;
-    b.S = b.acc; b.rhs = b.S + (size_t)srep * ns * n * n; b.U = b.rhs + (size_t)ns * n; b.gc = b.U + (size_t)d.Cf * 36;
-    b.cam_stride = L.cam_stride; b.scal = b.rhs + (size_t)BA_UREP * L.cam_stride;
-    b.gmax_all = b.scal + (size_t)BA_NSLOT * BA_SLOT_STRIDE; b.gmax_blocks = n_ranks; b.decided = 0;
-    b.gmax = b.gmax_all + (size_t)rank * BA_NSLOT * BA_SLOT_STRIDE;
-    b.pt_scal = (double*)(ws + L.pts); b.pt_prev = b.pt_scal; b.dc = (double*)(ws + L.dc);
-    b.st = (BaState*)(ws + L.st); b.st_prev = b.st;
-    b.trace = (BaTrace*)(ws + L.trace);
-    b.set_out = (BaSetOut*)(ws + L.set); b.set_prev = b.set_out;
-    b.dbg = (unsigned long long*)(ws + L.dbg);
-    b.hand_timeout = BA_HAND_TIMEOUT_TICKS;
 }
 
 // Solves of this process that are between entry and return right now (any context, any thread).  A solve that has the
@@ -546,27 +488,6 @@ static void ba_choose_fusion(const rs_context* ctx, const BaDims& d, const BaBuf
                   ba_solve_backsub_workgroups(d, b, ctx->n_cu) <= ctx->n_cu;
 }
 
-// Offsets into the pinned block of one window.  The single solve keeps its slot and free-camera tables (windows of more
-// than 64 cameras upload them from here) behind the summary and the inertial state at the end; a window of the grid batch
-// has neither, and whole 64-byte lines per part.  `key`: a word of the progress line's unused half (span / lost-key reads).
-struct BaPinned { size_t st, slot, fre, prog, key, trace, cams, vb, bytes; };
-static BaPinned ba_pinned_single(size_t C, int max_iter, bool inertial)
-{
-    BaPinned p;
-    p.st = 0; p.slot = sizeof(BaState); p.fre = p.slot + sizeof(int32_t) * C;
-    p.prog = align_up(p.fre + C, 64); p.key = p.prog + 32; p.trace = p.prog + 64;
-    p.cams = p.trace + sizeof(BaTrace) * (size_t)(max_iter + 1); p.vb = align_up(p.cams + sizeof(double) * 6 * C, 64);
-    p.bytes = p.vb + (inertial ? sizeof(double) * 9 * C : 0);
-    return p;
-}
-static BaPinned ba_pinned_batch(size_t C, int max_iter)
-{
-    BaPinned p;
-    p.st = p.slot = p.fre = 0; p.prog = align_up(sizeof(BaState), 64); p.key = p.prog + 32; p.trace = p.prog + 64;
-    p.cams = p.trace + align_up(sizeof(BaTrace) * (size_t)(max_iter + 1), 64); p.vb = p.bytes = p.cams + align_up(sizeof(double) * 6 * C, 64);
-    return p;
-}
-
 // A 64-bit key every rank holds, MIN-reduced over the ranks and read by the host (the stream is drained when it returns).
 static int ba_min_key_to_host(rs_context* ctx, unsigned long long* d_key, volatile unsigned long long* h_key)
 {
@@ -610,7 +531,7 @@ static int ba_choose_band(rs_context* ctx, const BaPath& path, bool inertial, co
 // Inertial blocks onto the device: the carve behind the common workspace, the whitened factors, the inertial slots and the
 // velocity | bias state of both parities.  fac_host, xv_host and inert are pageable sources of asynchronous copies: the
 // caller keeps them alive until it has synchronised (the copies complete before the call returns — it waits for finalize).
-static int ba_inertial_upload(rs_context* ctx, const BaInertialArgs& in, const BaDims& d, BaBufs& b, const BaPath& path, char* ws_big, char* ws_zacc,
+static int ba_inertial_upload(rs_context* ctx, const BaInertialArgs& in, const BaDims& d, BaBufs& b, const BaPath& path, char* ws_big, double* ws_zacc,
                               const std::vector<int32_t>& inert, int Ci, std::vector<ImuFactorDev>& fac_host, std::vector<double>& xv_host)
 {
     hipStream_t s = ctx->stream;
@@ -620,7 +541,7 @@ static int ba_inertial_upload(rs_context* ctx, const BaInertialArgs& in, const B
     ba_inertial_carve(ws_big, N_in, in.n_factors, d.C, &b.imu, &d_fac, &d_inert);
     b.imu.n_fac = in.n_factors; b.imu.Ci = Ci; b.imu.N = N_in;
     if (path.imu_lds) {
-        b.imu.zacc = (double*)ws_zacc;
+        b.imu.zacc = ws_zacc;
         b.imu.zacc_n = (int)ba_imu_lds_zacc_doubles(Ci, d.n);
         RS_HIP(ctx, hipMemsetAsync(b.imu.zacc, 0, sizeof(double) * (size_t)b.imu.zacc_n, s));
     }
@@ -663,26 +584,24 @@ static int ba_prepare_kernels(rs_context* ctx, const BaDims& d, const BaPath& pa
 // second — two instead of four (*fused).  The count adds into a histogram that must be zero when the launch starts: the
 // finalize kernel of the previous solve leaves it so, and the context remembers that (grp_zero_ptr) unless the workspace was
 // reallocated or another caller asked for workspace bytes reaching into it since (ws_dirty_hi); otherwise one memset.
-static int ba_enqueue_setup(rs_context* ctx, const rs_ba_problem& q, const BaDims& d, const BaBufs& b, const BaOpt& opt, const BaGroup& grp, bool use_mfma,
-                            const char* ws, unsigned long long free_mask, int from_mask, uint8_t* d_cam_free, int32_t* zero_ptr, int zero_n, bool* fused)
+static int ba_enqueue_setup(rs_context* ctx, const BaWin& w, const BaOpt& opt, bool use_mfma, const void* ws, int from_mask, bool* fused)
 {
     hipStream_t s = ctx->stream;
-    *fused = use_mfma && ba_setup_fusable(d, grp);
+    *fused = use_mfma && ba_setup_fusable(w.d, w.g);
     if (*fused) {
-        const bool known_zero = ctx->grp_zero_ptr == zero_ptr && ctx->grp_zero_n == zero_n &&
-                                ctx->ws_dirty_hi <= (size_t)((char*)zero_ptr - ws);
+        const bool known_zero = ctx->grp_zero_ptr == w.zero_ptr && ctx->grp_zero_n == w.zero_n &&
+                                ctx->ws_dirty_hi <= (size_t)((const char*)w.zero_ptr - (const char*)ws);
         ctx->grp_zero_ptr = nullptr;                                  // (until this solve's finalize kernel is enqueued)
-        if (!known_zero) RS_HIP(ctx, hipMemsetAsync(zero_ptr, 0, sizeof(int32_t) * (size_t)zero_n, s));
-        ba_launch_setup_fused(ctx, d, b, opt, grp, (const double*)q.d_cameras, (const double*)q.d_points, free_mask, from_mask, d_cam_free);
+        if (!known_zero) RS_HIP(ctx, hipMemsetAsync(w.zero_ptr, 0, sizeof(int32_t) * (size_t)w.zero_n, s));
+        ba_launch_setup_fused(ctx, w.d, w.b, opt, w.g, w.cams_in, w.pts_in, w.free_mask, from_mask, w.cam_free);
     } else {
         ctx->grp_zero_ptr = nullptr;
         {
             rs_prof_scope ps(ctx, "K0_ba_init");
-            hipLaunchKernelGGL(ba_init, dim3(64), dim3(256), 0, s, d, b, opt, (const double*)q.d_cameras, (const double*)q.d_points,
-                               free_mask, from_mask, d_cam_free, zero_ptr, zero_n);
+            hipLaunchKernelGGL(ba_init, dim3(64), dim3(256), 0, s, w.d, w.b, opt, w.cams_in, w.pts_in, w.free_mask, from_mask, w.cam_free, w.zero_ptr, w.zero_n);
         }
         if (use_mfma) {
-            const int rc = ba_launch_grouping(ctx, d, b, grp);
+            const int rc = ba_launch_grouping(ctx, w.d, w.b, w.g);
             if (rc) return rc;
         }
     }
@@ -692,17 +611,39 @@ static int ba_enqueue_setup(rs_context* ctx, const rs_ba_problem& q, const BaDim
 
 // Double-buffered state / step-scalar / set blocks: round `it` works on [it & 1] and reads [(it + 1) & 1].  last: the
 // finalize launch (round index = rounds enqueued) only reads the blocks of the round before it.
-struct BaRoundBases {
-    BaState* st; double* pts; BaSetOut* set; size_t pts_block;
-};
-static void ba_point_round(BaBufs& b, const BaRoundBases& r, int it, bool last = false)
+static void ba_point_round(BaWin& w, int it, bool last = false)
 {
-    b.st = r.st + (it & 1); b.st_prev = r.st + ((it + 1) & 1);
-    b.pt_prev = r.pts + (size_t)((it + 1) & 1) * r.pts_block;
-    b.set_prev = r.set + (size_t)((it + 1) & 1) * BA_MAXSETS;
+    BaBufs& b = w.b;
+    b.st = w.st_base + (it & 1); b.st_prev = w.st_base + ((it + 1) & 1);
+    b.pt_prev = w.pts_base + (size_t)((it + 1) & 1) * w.pts_block;
+    b.set_prev = w.set_base + (size_t)((it + 1) & 1) * BA_MAXSETS;
     if (last) return;
-    b.pt_scal = r.pts + (size_t)(it & 1) * r.pts_block;
-    b.set_out = r.set + (size_t)(it & 1) * BA_MAXSETS;
+    b.pt_scal = w.pts_base + (size_t)(it & 1) * w.pts_block;
+    b.set_out = w.set_base + (size_t)(it & 1) * BA_MAXSETS;
+}
+
+// One window bound to its part of the workspace and of the pinned block (sized by the same two layouts on a null carver):
+// the single solve and every window of the grid batch go through here.  w.d and w.free_mask are the caller's (ba_dims_from);
+// the rest of w comes in zeroed and is filled, w.b at round parity 0, and the progress line is reset.  dev / host: carvers
+// on the blocks, advanced by this window's pieces.
+static BaExtra ba_bind_window(const rs_ba_problem& q, const BaWinAsk& a, rs_carve& dev, rs_carve& host, BaWin& w)
+{
+    BaBufs& b = w.b;
+    BaExtra x;
+    b.obs_ptr = q.d_obs_ptr; b.obs_cam = q.d_obs_cam; b.obs_uv = (const float2*)q.d_obs_uv;
+    b.hand_timeout = BA_HAND_TIMEOUT_TICKS;
+    ba_window_layout(dev, a, w, x);
+    ba_pinned_layout(host, a, w, x);
+    if (a.use_mfma) {
+        ba_group_carve(x.grp, w.d.P, w.d.Cf, w.d.M, &w.g);
+        if (a.items >= 0) ba_group_set_items(&w.g, w.d.P, true, a.items);
+        ba_group_zero_range(w.g, &w.zero_ptr, &w.zero_n);
+    }
+    b.obs_cs = w.g.obs_cs;                                  // (null on the generic path)
+    w.prog->round = 0; w.prog->done = 0; w.prog->iter = 0;
+    b.prog = w.prog;
+    w.cams_in = w.cams_out = q.d_cameras; w.pts_in = w.pts_out = q.d_points;
+    return x;
 }
 
 // K7 of a round, with K8 inside when path.fuse78
@@ -723,27 +664,27 @@ static int ba_enqueue_reduced_solve(rs_context* ctx, const BaDims& d, const BaBu
 }
 
 // One round of the single solve: K5 [C1] K7 K8 [C2], or fewer launches where the path fuses them
-static int ba_enqueue_round(rs_context* ctx, const BaDims& d, BaBufs& b, const BaOpt& opt, const BaGroup& grp, const BaPath& path,
-                            const BaRoundBases& bases, bool inertial, char* ws_big, int it)
+static int ba_enqueue_round(rs_context* ctx, BaWin& w, const BaOpt& opt, const BaPath& path, bool inertial, char* ws_big, int it)
 {
     hipStream_t s = ctx->stream;
-    const int pblocks = d.P > 0 ? (d.P + BA_THREADS - 1) / BA_THREADS : 1;      // (an empty shard still runs the round's decision)
-    ba_point_round(b, bases, it);
+    BaBufs& b = w.b;
+    const int pblocks = w.d.P > 0 ? (w.d.P + BA_THREADS - 1) / BA_THREADS : 1;      // (an empty shard still runs the round's decision)
+    ba_point_round(w, it);
     if (path.fuse_round) {
         rs_prof_scope ps(ctx, "K578_ba_round");
-        ba_launch_round(s, d, b, opt, grp, it);
+        ba_launch_round(s, w.d, b, opt, w.g, it);
         return RS_OK;
     }
     if (path.use_mfma) {
         rs_prof_scope ps(ctx, "K5_ba_schur_mfma");
         // more items than compute units: the round's decision once, in front, instead of in every item's prologue
-        b.decided = grp.n_items > ctx->n_cu ? 1 : 0;
+        b.decided = w.g.n_items > ctx->n_cu ? 1 : 0;
         if (b.decided) ba_launch_decide(s, b, opt, it);
-        ba_launch_schur(s, d, b, opt, grp, it);
+        ba_launch_schur(s, w.d, b, opt, w.g, it);
         b.decided = 0;
     } else {
         rs_prof_scope ps(ctx, "K5_ba_linearize_schur");
-        hipLaunchKernelGGL(ba_linearize_schur, dim3(pblocks), dim3(BA_THREADS), sizeof(double) * (size_t)d.Cf * 42, s, d, b, opt, it);
+        hipLaunchKernelGGL(ba_linearize_schur, dim3(pblocks), dim3(BA_THREADS), sizeof(double) * (size_t)w.d.Cf * 42, s, w.d, b, opt, it);
     }
     if (rs_comm_active(ctx)) {
         rs_prof_scope ps(ctx, "C1_allreduce_system");
@@ -751,14 +692,14 @@ static int ba_enqueue_round(rs_context* ctx, const BaDims& d, BaBufs& b, const B
         const int rc = rs_allreduce_f64(ctx, b.acc, b.acc_count, false);
         if (rc) return rc;
     }
-    const int rc = ba_enqueue_reduced_solve(ctx, d, b, opt, path, inertial, ws_big);
+    const int rc = ba_enqueue_reduced_solve(ctx, w.d, b, opt, path, inertial, ws_big);
     if (rc) return rc;
     if (path.fuse78) { /* K8 ran inside the K7 launch */ }
-    else if (path.k8_lds) { rs_prof_scope ps(ctx, "K8_ba_backsub_cost"); ba_launch_backsub(s, d, b); }
-    else { rs_prof_scope ps(ctx, "K8_ba_backsub_cost_global"); hipLaunchKernelGGL(ba_backsub_cost, dim3(pblocks), dim3(BA_THREADS), 0, s, d, b); }
+    else if (path.k8_lds) { rs_prof_scope ps(ctx, "K8_ba_backsub_cost"); ba_launch_backsub(s, w.d, b); }
+    else { rs_prof_scope ps(ctx, "K8_ba_backsub_cost_global"); hipLaunchKernelGGL(ba_backsub_cost, dim3(pblocks), dim3(BA_THREADS), 0, s, w.d, b); }
     if (rs_comm_active(ctx)) {
         rs_prof_scope ps(ctx, "C2_allreduce_cost");
-        return rs_allreduce_f64(ctx, b.pt_scal, bases.pts_block, false);
+        return rs_allreduce_f64(ctx, b.pt_scal, w.pts_block, false);
     }
     return RS_OK;
 }
@@ -787,10 +728,11 @@ static int ba_solve_once(rs_context* ctx, const rs_ba_problem& q, const rs_ba_op
     RS_HIP(ctx, hipSetDevice(ctx->device));
 
     // dimensions, inertial slots, kernel path
-    BaDims d;
+    BaWin w;
+    memset(&w, 0, sizeof w);
+    BaDims& d = w.d;
     std::vector<int32_t> slot(q.n_cameras), inert(q.n_cameras, -1);
-    unsigned long long free_mask = 0;
-    const bool supported = ba_dims_from(q, options, d, slot.data(), &free_mask);
+    const bool supported = ba_dims_from(q, options, d, slot.data(), &w.free_mask);
     const BaOpt opt = ba_opt_from(options);
     if (opt.max_iter < 0 || opt.max_iter > 1000) return rs_fail(ctx, RS_ERR_INVALID, "max_num_iterations out of range");
     if (!supported) return rs_fail(ctx, RS_ERR_UNSUPPORTED, "more than 484 free cameras");
@@ -800,116 +742,93 @@ static int ba_solve_once(rs_context* ctx, const rs_ba_problem& q, const rs_ba_op
     BaPath path = ba_choose_path(ctx, d, opt.max_iter, in != nullptr, Ci, imu_chain, in ? BA_CALIBRATED_SETS : BA_DEFAULT_SETS,
                                  in ? BA_CALIBRATED_SETS : BA_MAXSETS);
 
-    // workspace: the common layout, then the blocked / inertial solve's part and the accumulators of the inertial elimination
-    const size_t C = (size_t)d.C;
-    const size_t n_ranks = rs_comm_active(ctx) ? (size_t)ctx->n_ranks : 1;
-    const BaLayout L = ba_layout(d, path.ns, opt.max_iter, n_ranks, path.use_mfma ? ba_group_bytes(d.P, d.Cf, d.M) : 16, path.srep);
-    const size_t o_big = L.bytes;
-    const size_t big_bytes = rs_align256(in ? ba_inertial_bytes(d.n + 9 * Ci, in->n_factors, d.C) : (path.solve_big ? ba_big_bytes(d.n) : 16));
-    const size_t o_zacc = o_big + big_bytes;
-    const size_t ws_bytes = o_zacc + (path.imu_lds ? rs_align256(sizeof(double) * ba_imu_lds_total_doubles(Ci, d.n, path.ns)) : 0);
-    void* wsv = nullptr;
-    rc = rs_workspace_quiet(ctx, ws_bytes, &wsv);      // (this solve keeps its own account of what it leaves behind: ba_enqueue_setup)
-    if (rc) return rc;
-    char* ws = (char*)wsv;
-    BaBufs b;
-    memset(&b.imu, 0, sizeof b.imu);
-    b.obs_ptr = q.d_obs_ptr; b.obs_cam = q.d_obs_cam; b.obs_uv = (const float2*)q.d_obs_uv;
-    ba_bind(b, ws, L, d, path.ns, (int)n_ranks, rs_comm_active(ctx) ? ctx->rank : 0, path.srep);
-    const BaRoundBases bases = {b.st, b.pt_scal, b.set_out, L.pts_block};
+    // the window on its workspace and pinned block; behind the common workspace the blocked / inertial solve's part and the
+    // accumulators of the inertial elimination
+    const bool comm = rs_comm_active(ctx);
+    const BaWinAsk ask = {path.ns, opt.max_iter, comm ? ctx->n_ranks : 1, comm ? ctx->rank : 0, path.srep,
+                          path.use_mfma ? ba_group_bytes(d.P, d.Cf, d.M) : 16,
+                          in ? ba_inertial_bytes(d.n + 9 * Ci, in->n_factors, d.C) : (path.solve_big ? ba_big_bytes(d.n) : 16),
+                          path.imu_lds ? ba_imu_lds_total_doubles(Ci, d.n, path.ns) : 0, true, in != nullptr, path.use_mfma, ctx->ba_item ? ctx->ba_item : -1};
+    BaBufs& b = w.b;
+    BaExtra x;
+    rs_carve ws_size, pin_size;
+    ba_window_layout(ws_size, ask, w, x);
+    ba_pinned_layout(pin_size, ask, w, x);
+    void *ws = nullptr, *pin = nullptr;
+    // (this solve keeps its own account of what it leaves behind in the workspace: ba_enqueue_setup)
+    if ((rc = rs_workspace_quiet(ctx, ws_size.bytes(), &ws)) || (rc = rs_pinned(ctx, pin_size.bytes(), &pin))) return rc;
+    ctx->ba_cams = nullptr; ctx->ba_cams_n = 0; ctx->ba_trace_n = 0;
+    rs_carve dev(ws), host(pin);
+    x = ba_bind_window(q, ask, dev, host, w);
+    if (path.ns == 1) b.prog = nullptr;     // (one set per round: the kernels publish no progress; w.prog only names the line whose pad is the completion flag)
 #if RS_STAMPS
     RS_HIP(ctx, hipMemsetAsync(b.dbg, 0, sizeof(unsigned long long) * BA_DBG_WORDS, ctx->stream));
 #endif
     ctx->ba_cache = b.dbg;
-
-    // pinned block
-    const BaPinned pl = ba_pinned_single(C, opt.max_iter, in != nullptr);
-    void* pinv = nullptr;
-    rc = rs_pinned(ctx, pl.bytes, &pinv);
-    if (rc) return rc;
-    char* pin = (char*)pinv;
-    double* h_vb = in ? (double*)(pin + pl.vb) : nullptr;
-    ctx->ba_cams = nullptr; ctx->ba_cams_n = 0;
-    BaProgress* h_prog = (BaProgress*)(pin + pl.prog);
-    h_prog->round = 0; h_prog->done = 0; h_prog->iter = 0;
-    b.prog = path.ns > 1 ? h_prog : nullptr;
-    BaState* h_st = (BaState*)(pin + pl.st);
-    BaTrace* h_trace = (BaTrace*)(pin + pl.trace);
-    volatile unsigned long long* h_key = (volatile unsigned long long*)(pin + pl.key);
-    ctx->ba_trace_n = 0;
-    uint8_t* d_cam_free = (uint8_t*)(ws + L.fre);
+    const size_t C = (size_t)d.C;
     const int from_mask = C <= 64 ? 1 : 0;
-    if (!from_mask) {
-        memcpy(pin + pl.slot, slot.data(), sizeof(int32_t) * C);
-        memcpy(pin + pl.fre, q.h_cam_free, C);
-        RS_HIP(ctx, hipMemcpyAsync(b.slot, pin + pl.slot, sizeof(int32_t) * C, hipMemcpyHostToDevice, ctx->stream));
-        RS_HIP(ctx, hipMemcpyAsync(d_cam_free, pin + pl.fre, C, hipMemcpyHostToDevice, ctx->stream));
+    if (!from_mask) {                                       // beyond the mask: both tables through the pinned block
+        memcpy(x.slot, slot.data(), sizeof(int32_t) * C);
+        memcpy(x.fre, q.h_cam_free, C);
+        RS_HIP(ctx, hipMemcpyAsync(b.slot, x.slot, sizeof(int32_t) * C, hipMemcpyHostToDevice, ctx->stream));
+        RS_HIP(ctx, hipMemcpyAsync(w.cam_free, x.fre, C, hipMemcpyHostToDevice, ctx->stream));
     }
 
-    // kernel attributes, landmark grouping, inertial blocks, set-up launches
+    // kernel attributes, inertial blocks, set-up launches
     rc = ba_prepare_kernels(ctx, d, path);
     if (rc) return rc;
-    BaGroup grp;
-    memset(&grp, 0, sizeof grp);
-    int32_t* zero_ptr = nullptr; int zero_n = 0;
-    if (path.use_mfma) {
-        ba_group_carve(ws + L.grp, d.P, d.Cf, d.M, &grp);
-        if (ctx->ba_item) ba_group_set_items(&grp, d.P, true, ctx->ba_item);
-        ba_group_zero_range(grp, &zero_ptr, &zero_n);
-    }
-    b.obs_cs = path.use_mfma ? grp.obs_cs : nullptr;
     hipStream_t s = ctx->stream;
     std::vector<ImuFactorDev> fac_host; std::vector<double> xv_host;      // (sources of ba_inertial_upload's copies: alive until the solve has been waited for)
-    if (in && (rc = ba_inertial_upload(ctx, *in, d, b, path, ws + o_big, ws + o_zacc, inert, Ci, fac_host, xv_host)) != RS_OK) return rc;
+    if (in && (rc = ba_inertial_upload(ctx, *in, d, b, path, x.big, x.zacc, inert, Ci, fac_host, xv_host)) != RS_OK) return rc;
     bool fused_setup = false;
-    rc = ba_enqueue_setup(ctx, q, d, b, opt, grp, path.use_mfma, ws, free_mask, from_mask, d_cam_free, zero_ptr, zero_n, &fused_setup);
+    rc = ba_enqueue_setup(ctx, w, opt, path.use_mfma, ws, from_mask, &fused_setup);
     if (rc) return rc;
 
     // what only exists now: the band form (sharded solves agree on it) and the launch fusion
-    rc = ba_choose_band(ctx, path, in != nullptr, grp, b, h_key, &path.band);
+    rc = ba_choose_band(ctx, path, in != nullptr, w.g, b, x.key, &path.band);
     if (rc) return rc;
     b.hand_timeout = 100ull * (unsigned long long)ctx->ba_handoff_timeout_us;
-    ba_choose_fusion(ctx, d, b, grp, path, allow_fuse, in != nullptr, in_flight.others);
+    ba_choose_fusion(ctx, d, b, w.g, path, allow_fuse, in != nullptr, in_flight.others);
     if (path.fuse_round && ba_prepare_round(d) != 0) return rs_fail(ctx, RS_ERR_HIP, "LDS attribute (round)");
 
     // rounds
     int rounds = 0;
-    const BaProgress* const progs[1] = {h_prog};
+    const BaProgress* const progs[1] = {w.prog};
     rc = ba_follow_rounds(s, opt.max_iter, path.ns, progs, 1,
-                          [&](int it) { return ba_enqueue_round(ctx, d, b, opt, grp, path, bases, in != nullptr, ws + o_big, it); }, rounds);
+                          [&](int it) { return ba_enqueue_round(ctx, w, opt, path, in != nullptr, x.big, it); }, rounds);
     if (rc) return rc;
     {
         rs_prof_scope ps(ctx, "K10_ba_finalize");
         // the last decisions: round index `rounds` reads the blocks of round rounds - 1
         const int itf = rounds;
-        ba_point_round(b, bases, itf, true);
+        ba_point_round(w, itf, true);
         b.prog = nullptr;
-        h_prog->pad = 0;
-        hipLaunchKernelGGL(ba_finalize, dim3(BA_FINALIZE_WGS), dim3(256), 0, s, d, b, opt, itf, q.d_cameras, (const uint8_t*)d_cam_free, q.d_points, h_st, h_trace,
-                           (double*)(pin + pl.cams), h_vb, &h_prog->pad, fused_setup ? zero_ptr : nullptr, fused_setup ? zero_n : 0);
+        w.prog->pad = 0;
+        hipLaunchKernelGGL(ba_finalize, dim3(BA_FINALIZE_WGS), dim3(256), 0, s, d, b, opt, itf, q.d_cameras, (const uint8_t*)w.cam_free, q.d_points, w.h_st, w.h_trace,
+                           w.h_cams, x.vb, &w.prog->pad, fused_setup ? w.zero_ptr : nullptr, fused_setup ? w.zero_n : 0);
         RS_HIP(ctx, hipGetLastError());
-        if (fused_setup) { ctx->grp_zero_ptr = zero_ptr; ctx->grp_zero_n = zero_n; }      // stream-ordered in front of the next solve
+        if (fused_setup) { ctx->grp_zero_ptr = w.zero_ptr; ctx->grp_zero_n = w.zero_n; }      // stream-ordered in front of the next solve
         // wait for the completion flag the last workgroup of ba_finalize raises in pinned memory (summary, trace, camera
         // mirror are then all there); fall back to the stream if it drains without the flag (a failed launch)
-        RS_HIP(ctx, ba_wait_flag(s, &h_prog->pad, itf + 1));
+        RS_HIP(ctx, ba_wait_flag(s, &w.prog->pad, itf + 1));
     }
     RS_HIP(ctx, hipGetLastError());
 
     // results
-    ba_summary_from(*h_st, h_summary);
-    ctx->ba_trace = h_trace;            // stays valid until the next call that uses the pinned block
-    ctx->ba_trace_n = h_st->iter;
-    ctx->ba_stats[0] = h_st->n_rounds; ctx->ba_stats[1] = h_st->n_fresh; ctx->ba_stats[2] = h_st->n_sets; ctx->ba_stats[3] = rounds;
-    *hand_lost = h_st->hand_lost != 0;
+    ba_summary_from(*w.h_st, h_summary);
+    ctx->ba_trace = w.h_trace;            // stays valid until the next call that uses the pinned block
+    ctx->ba_trace_n = w.h_st->iter;
+    ctx->ba_stats[0] = w.h_st->n_rounds; ctx->ba_stats[1] = w.h_st->n_fresh; ctx->ba_stats[2] = w.h_st->n_sets; ctx->ba_stats[3] = rounds;
+    *hand_lost = w.h_st->hand_lost != 0;
     if (rs_comm_active(ctx) && path.may_fuse) {
         // every rank gets here (the conditions are the same on all of them: cameras are replicated), fused or not
         hipLaunchKernelGGL(ba_lost_key, dim3(1), dim3(1), 0, s, (const BaState*)b.st, b.dbg + BA_KEY_LOST);
-        rc = ba_min_key_to_host(ctx, b.dbg + BA_KEY_LOST, h_key);
+        rc = ba_min_key_to_host(ctx, b.dbg + BA_KEY_LOST, x.key);
         if (rc) return rc;
-        *hand_lost = *h_key == 0ull;
+        *hand_lost = *x.key == 0ull;
     }
-    ctx->ba_cams = (const double*)(pin + pl.cams); ctx->ba_cams_n = q.n_cameras;
-    if (in && h_st->usable) ba_inertial_unpack(*in, q, h_vb);
+    ctx->ba_cams = w.h_cams; ctx->ba_cams_n = q.n_cameras;
+    if (in && w.h_st->usable) ba_inertial_unpack(*in, q, x.vb);
     return RS_OK;
 }
 
@@ -970,11 +889,14 @@ static int ba_solve_batch_grid(rs_context* ctx, int B, const rs_ba_problem* Q, c
     const BaOpt opt = ba_opt_from(options);
     if (opt.max_iter < 1 || opt.max_iter > 1000) return 1;
     std::vector<BaWin> wins((size_t)B);
-    std::vector<size_t> ws_off((size_t)B), pin_off((size_t)B);
-    size_t ws_total = rs_align256(sizeof(BaWin) * (size_t)B), pin_total = 0;
     int max_P = 0, max_items = 0, max_n = 0, max_C = 0, ns = 1;
     size_t k5_lds = 0, k8_lds = 0;
-    std::vector<BaLayout> lay((size_t)B);
+    // the single solve's window, one per problem: one rank, one copy of S, no tail; pinned without tables (the mask is the table)
+    BaWinAsk a = {1, opt.max_iter, 1, 0, 1, 0, 0, 0, false, false, true, ctx->ba_batch_item};
+    BaExtra x;
+    // workspace: the device's table of windows, then the windows; pinned: the windows' parts, then the table's staging copy
+    rs_carve ws_size, pin_size;
+    ws_size.take<BaWin>((size_t)B);
     for (int i = 0; i < B; i++) {
         const rs_ba_problem& q = Q[i];
         if (q.n_cameras <= 0 || q.n_points <= 0 || q.n_obs <= 0 || q.n_cameras > 64) return 1;
@@ -987,58 +909,35 @@ static int ba_solve_batch_grid(rs_context* ctx, int B, const rs_ba_problem* Q, c
         // want) and one copy of S whatever "ba_s_replicas" says
         const BaPath path = ba_choose_path(ctx, d, opt.max_iter, false, 0, false, BA_CALIBRATED_SETS, BA_CALIBRATED_SETS);
         if (!path.local_window()) return 1;
-        ns = path.ns;                                   // (the same for every window: context and options decide it)
-        lay[(size_t)i] = ba_layout(d, ns, opt.max_iter, 1, ba_group_bytes(d.P, d.Cf, d.M));   // the single solve's layout, one copy per window
-        ws_off[(size_t)i] = ws_total;
-        ws_total += lay[(size_t)i].bytes;
-        pin_off[(size_t)i] = pin_total;
-        pin_total += ba_pinned_batch((size_t)d.C, opt.max_iter).bytes;
+        a.ns = ns = path.ns;                            // (the same for every window: context and options decide it)
+        a.grp_bytes = ba_group_bytes(d.P, d.Cf, d.M);
+        ba_window_layout(ws_size, a, w, x);
+        ba_pinned_layout(pin_size, a, w, x);
         max_P = std::max(max_P, d.P); max_n = std::max(max_n, d.n); max_C = std::max(max_C, d.C);
         k8_lds = std::max(k8_lds, ba_backsub_lds_bytes(d.C, d.n));
     }
-    void* wsv = nullptr;
-    int rc = rs_workspace(ctx, ws_total, &wsv);
+    pin_size.take<BaWin>((size_t)B);
+    void *ws = nullptr, *pin = nullptr;
+    int rc = rs_workspace(ctx, ws_size.bytes(), &ws);
+    if (!rc) rc = rs_pinned(ctx, pin_size.bytes(), &pin);
     if (rc) { *rc_out = rc; return 0; }
-    char* ws = (char*)wsv;
-    void* pinv = nullptr;
-    const size_t pin_wins = rs_align256(pin_total);
-    rc = rs_pinned(ctx, pin_wins + sizeof(BaWin) * (size_t)B, &pinv);
-    if (rc) { *rc_out = rc; return 0; }
-    char* pin = (char*)pinv;
+    // the same takes in the same order, now on the blocks
+    rs_carve dev(ws), host(pin);
+    const BaWin* d_wins = dev.take<BaWin>((size_t)B);
     std::vector<const BaProgress*> progs((size_t)B);
     for (int i = 0; i < B; i++) {
-        const rs_ba_problem& q = Q[i];
         BaWin& w = wins[(size_t)i];
-        const BaLayout& L = lay[(size_t)i];
-        char* base = ws + ws_off[(size_t)i];
-        const BaDims& d = w.d;
-        BaBufs& b = w.b;
-        b.obs_ptr = q.d_obs_ptr; b.obs_cam = q.d_obs_cam; b.obs_uv = (const float2*)q.d_obs_uv;
-        ba_bind(b, base, L, d, ns, 1, 0);
-        ba_group_carve(base + L.grp, d.P, d.Cf, d.M, &w.g);
-        ba_group_set_items(&w.g, d.P, true, ctx->ba_batch_item);
-        b.obs_cs = w.g.obs_cs;
+        a.grp_bytes = ba_group_bytes(w.d.P, w.d.Cf, w.d.M);
+        ba_bind_window(Q[i], a, dev, host, w);
+        progs[(size_t)i] = w.prog;
         max_items = std::max(max_items, w.g.n_items);
-        k5_lds = std::max(k5_lds, ba_schur_lds_bytes(d.C, d.Cf, w.g.it_l, ns));
-        w.st_base = b.st; w.pts_base = b.pt_scal; w.set_base = b.set_out; w.pts_block = L.pts_block;
-        char* hp = pin + pin_off[(size_t)i];
-        const BaPinned pl = ba_pinned_batch((size_t)d.C, opt.max_iter);
-        w.h_st = (BaState*)(hp + pl.st);
-        w.prog = (BaProgress*)(hp + pl.prog);
-        w.h_trace = (BaTrace*)(hp + pl.trace);
-        w.h_cams = (double*)(hp + pl.cams);
-        w.prog->round = 0; w.prog->done = 0; w.prog->iter = 0;
-        progs[(size_t)i] = b.prog = w.prog;
-        w.cams_in = q.d_cameras; w.pts_in = q.d_points; w.cams_out = q.d_cameras; w.pts_out = q.d_points;
-        w.cam_free = (uint8_t*)(base + L.fre);
-        ba_group_zero_range(w.g, &w.zero_ptr, &w.zero_n);
+        k5_lds = std::max(k5_lds, ba_schur_lds_bytes(w.d.C, w.d.Cf, w.g.it_l, ns));
     }
     if (ba_prepare_reduced_solve_lds_batch(max_n) != 0 || ba_prepare_schur_batch(k5_lds) != 0) { *rc_out = rs_fail(ctx, RS_ERR_HIP, "LDS attribute (batch)"); return 0; }
     hipStream_t s = ctx->stream;
-    BaWin* h_wins = (BaWin*)(pin + pin_wins);
+    BaWin* h_wins = host.take<BaWin>((size_t)B);
     memcpy(h_wins, wins.data(), sizeof(BaWin) * (size_t)B);
-    const BaWin* d_wins = (const BaWin*)ws;
-    if (hipMemcpyAsync(ws, h_wins, sizeof(BaWin) * (size_t)B, hipMemcpyHostToDevice, s) != hipSuccess) { *rc_out = rs_fail(ctx, RS_ERR_HIP, "window table upload"); return 0; }
+    if (hipMemcpyAsync((void*)d_wins, h_wins, sizeof(BaWin) * (size_t)B, hipMemcpyHostToDevice, s) != hipSuccess) { *rc_out = rs_fail(ctx, RS_ERR_HIP, "window table upload"); return 0; }
     {
         rs_prof_scope ps(ctx, "K0_ba_init");
         hipLaunchKernelGGL(ba_init_batch, dim3(32, 1, B), dim3(256), 0, s, d_wins, opt);

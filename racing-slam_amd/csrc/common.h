@@ -219,6 +219,16 @@ int rs_k1_reserve(rs_context* ctx, size_t entries);   // hamming.hip: K1's top-2
 int rs_workspace(rs_context* ctx, size_t bytes, void** out);
 int rs_workspace_quiet(rs_context* ctx, size_t bytes, void** out);   // does not mark the bytes as possibly written (ba.hip keeps its own account)
 int rs_pinned(rs_context* ctx, size_t bytes, void** out);
+// a per-call block cut by a layout (carve.h): sized on a null carver, fetched with `get` (one of the three above), placed
+template <class L>
+static inline int rs_carve_from(rs_context* ctx, int (*get)(rs_context*, size_t, void**), L&& layout)
+{
+    rs_carve size, place;
+    layout(size);
+    const int rc = get(ctx, size.bytes(), (void**)&place.base);
+    if (!rc) layout(place);
+    return rc;
+}
 // hipFuncSetAttribute(fn, MaxDynamicSharedMemorySize, bytes), but only when `bytes` exceeds what was already set for
 // `fn` in this process: the attribute is sticky and the driver call costs microseconds of host time per launch.
 hipError_t rs_lds_attr(const void* fn, size_t bytes);

@@ -2,7 +2,8 @@
 // scratch, the two per-context tables).  It holds a pointer and a capacity that always agree, is move-only and frees
 // itself: whoever destroys the owner has made the device current and drained the stream first.  Included from common.h.
 // rs_dev_block / rs_pin_block: the one owner of a block of fixed size, device or pinned host memory, under the same rule; an
-// object of fixed capacity has one of each at most and cuts it into its arrays with a layout (carve.h).
+// object of fixed capacity has one of each at most and cuts it into its arrays with a layout (carve.h).  (Per-call
+// blocks from the context's workspace and pinned buffer are cut the same way through rs_carve_from, common.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 

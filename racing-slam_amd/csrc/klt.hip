@@ -496,11 +496,9 @@ extern "C" int rs_track_features(rs_context* ctx, const rs_image* prev, const rs
         return RS_OK;
     }
     if (!d_prev_pts || !d_kept_index || !d_kept_pt) return rs_fail(ctx, RS_ERR_INVALID, "null pointer");
-    void* ws = nullptr;
-    const size_t pt_bytes = rs_align256(sizeof(float2) * (size_t)n);
-    if ((rc = rs_workspace(ctx, pt_bytes + (size_t)n, &ws))) return rc;
-    float2* d_next = (float2*)ws;
-    uint8_t* d_keep = (uint8_t*)ws + pt_bytes;
+    float2* d_next = nullptr;
+    uint8_t* d_keep = nullptr;
+    if ((rc = rs_carve_from(ctx, rs_workspace, [&](rs_carve& c) { d_next = c.take<float2>((size_t)n); d_keep = c.take<uint8_t>((size_t)n); }))) return rc;
     {
         rs_prof_scope ps(ctx, "KLT4_track_fb");
         KLT_DISPATCH(prm.win, klt_track_fb, prev->pyr, next->pyr, (const float2*)d_prev_pts, n, prm, d_mask, fb_max, d_next, d_keep);

@@ -7,8 +7,7 @@
 // workgroup: per iteration a block reduction of the 6x6 normal equations of the observations, the one extra block
 // evaluated with dual numbers (imu_dual.h), a register Cholesky of the nu x nu system (nu = 6 or 9) on lane 0 and a second
 // reduction for the candidate cost.  The two kernels are one body, rp_body, compiled with and without the extra block.
-#include "ba_common.h"
-#include "imu_dual.h"
+#include "ba_blocks.h"
 
 #define RP_THREADS 512         // 2000 observations: four per thread; 256 VGPRs per thread keep the 28 accumulators in registers
 
@@ -29,13 +28,6 @@ __device__ __forceinline__ void block_sum(double* vals, int count, double* scrat
     for (int k = 0; k < count; k++) vals[k] = scratch[(RP_THREADS / 64) * 32 + k];
     __syncthreads();
 }
-
-struct RpInertial {
-    int kind;                 // 1 rotation prior, 2 inertial delta
-    double predicted[9], sigma;
-    double prev_pose[6], prev_vel[3], prev_bias[6], gravity[3];
-    ImuFactorDev fac;
-};
 
 // ---- the pieces of one LM iteration.  Thread 0 runs the serial ones; nx = 6 (pose) or 9 (pose, velocity) state entries.
 __device__ __forceinline__ void rp_init(const BaOpt& opt, const double* cam_io, int nx, double* x, double* prep, BaState& st)
@@ -399,31 +391,19 @@ static int refine_pose_solve(rs_context* ctx, double h_camera[6], const double* 
     d.fx = h_intrinsics[0]; d.fy = h_intrinsics[1]; d.cx = h_intrinsics[2]; d.cy = h_intrinsics[3];
     d.huber_a = options->huber_delta;
     const BaOpt opt = ba_opt_from(options);
-    // pinned block: camera (+ velocity) at 0, BaState at 256, completion flag at 448, the device-side count at 456, the inertial block at 1024
-    RpInertial* d_ext = nullptr;
+    // the call's blocks: the inertial constraint in the workspace, where the inner loops read it; the pinned block (ba_blocks.h)
+    RpInertial *d_ext = nullptr, *h_ext = nullptr;
+    double* h_cam; BaState* h_st; volatile int* h_done; int* h_nu;
     int rc;
-    if (in) {
-        const size_t ext_off = 512;
-        void* wsv = nullptr;
-        rc = rs_workspace(ctx, ext_off + rs_align256(sizeof(RpInertial)), &wsv);
-        if (rc) return rc;
-        d_ext = (RpInertial*)((char*)wsv + ext_off);
-    }
-    void* pin = nullptr;
-    rc = rs_pinned(ctx, in ? 1024 + sizeof(RpInertial) : 512, &pin);
-    if (rc) return rc;
+    if (in && (rc = rs_carve_from(ctx, rs_workspace, [&](rs_carve& c) { d_ext = c.take<RpInertial>(1); }))) return rc;
+    if ((rc = rs_carve_from(ctx, rs_pinned, [&](rs_carve& c) { rp_pinned_layout(c, in != nullptr, h_cam, h_st, h_done, h_nu, h_ext); }))) return rc;
     ctx->ba_trace_n = 0;                 // the pinned block is reused: the last BA's record is gone
     ctx->ba_cams = nullptr;
     ctx->ba_cams_n = 0;
-    double* h_cam = (double*)pin;
-    BaState* h_st = (BaState*)((char*)pin + 256);
-    volatile int* h_done = (volatile int*)((char*)pin + 448);
-    int* h_nu = (int*)((char*)pin + 456);
     *h_nu = 0;
     memcpy(h_cam, h_camera, 6 * sizeof(double));
     hipStream_t s = ctx->stream;
     if (in) {
-        RpInertial* h_ext = (RpInertial*)((char*)pin + 1024);
         memset(h_ext, 0, sizeof *h_ext);
         h_ext->kind = in->kind;
         if (in->kind == 1) {

@@ -476,12 +476,10 @@ extern "C" int rs_reanchor_points_host_poses(rs_context* ctx, int n, const int32
         hipLaunchKernelGGL(k13_reanchor_args, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, d_point_idx, d_frame_idx, n_frames, P, d_positions);
     } else {
         // larger sets of frames: both pose arrays through the context's workspace (copied before this call returns)
-        void* ws = nullptr;
         const size_t bytes = sizeof(float) * 16 * (size_t)n_frames;
-        const int rc = rs_workspace(ctx, 2 * bytes + 256, &ws);
+        float *d_before = nullptr, *d_after = nullptr;
+        const int rc = rs_carve_from(ctx, rs_workspace, [&](rs_carve& c) { d_before = c.take<float>(bytes / 4); d_after = c.take<float>(bytes / 4); });
         if (rc) return rc;
-        float* d_before = (float*)ws;
-        float* d_after = (float*)((char*)ws + rs_align256(bytes));
         RS_HIP(ctx, hipMemcpyAsync(d_before, h_poses_before, bytes, hipMemcpyHostToDevice, ctx->stream));
         RS_HIP(ctx, hipMemcpyAsync(d_after, h_poses_after, bytes, hipMemcpyHostToDevice, ctx->stream));
         RS_HIP(ctx, hipStreamSynchronize(ctx->stream));          // pageable sources: the copies have read them
