@@ -27,6 +27,8 @@
  *    transform exactly as Frame::pose() (src/Frame.h:46).
  *  - Descriptors are 32-byte rows (256-bit ORB, src/features/OrbFeatureExtractor.h:14-22),
  *    row i at byte offset 32*i; device descriptor arrays must be 16-byte aligned.
+ *    The *_f32 / *_l2 entry points alone take FLOAT descriptors instead (rows of `dim` f32 under the L2 norm); the
+ *    resident map (rs_frame, rs_map), bag-of-words and the track store are ORB-only.
  *  - One context per GPU / per process rank; a context is not re-entrant
  *    (the reference's callers are single threaded, SURVEY.md §8b "Threading").
  */
@@ -175,6 +177,39 @@ int rs_match_descriptors(rs_context* ctx,
                          int32_t* d_idx0, int32_t* d_dist0,
                          int32_t* d_idx1, int32_t* d_dist1);
 
+/* The same two calls for FLOAT descriptors under the L2 norm (MapMatcher constructed with cv::NORM_L2 and a float
+ * max_descriptor_distance, src/Tracker.cpp:42).  d_query [batch][nq][dim] f32, d_train [batch][nt][dim] f32, row-major,
+ * 16-byte aligned, dim % 4 == 0 and 4 <= dim <= 1024 (any other dim: RS_ERR_UNSUPPORTED, the context stays usable).
+ * The specification is this library's own (agreement with cv::BFMatcher's rounding is not claimed); all arithmetic is f32:
+ *   s    = 0; for k ascending: s = fmaf(q[k], t[k], s)       (what a chain of f32 MFMA steps on one accumulator computes)
+ *   nq2, nt2 = the same chain of a row with itself
+ *   d2   = fmaxf(fmaf(-2.0f, s, nq2 + nt2), 0.0f),  dist = sqrtf(d2) correctly rounded
+ * Candidates are ordered by (d2, train index): the lower train index wins a tie.  Results are bit-exact against that
+ * restatement (tests/match_l2_ref.py) and reproducible from run to run; d2 lies within
+ * gamma (sum q^2 + sum t^2 + 2 sum |q t|), gamma = (dim + 2) u / (1 - (dim + 2) u), u = 2^-24, of the exact value.
+ * The contract covers finite inputs; non-finite values do not fault.
+ *   d_idx0 / d_idx1 [batch][nq] int32, d_dist0 / d_dist1 [batch][nq] f32; idx1 = -1, dist1 = -1.0f when nt == 1.
+ * (fmaxf turns a NaN d2 into 0, here and in the restatement alike: a pair with non-finite rows is outside the contract.)
+ * nq == 0 or nt == 0 is valid: nothing is written (rs_match_descriptors_f32: the counts are zeroed).  nq and nt may be
+ * up to 2^31 - 129 (row numbers are rounded up to whole 128-row passes in int); beyond: RS_ERR_UNSUPPORTED. */
+int rs_l2_knn2(rs_context* ctx,
+               const float* d_query, int nq,
+               const float* d_train, int nt, int dim, int batch,
+               int32_t* d_idx0, float* d_dist0,
+               int32_t* d_idx1, float* d_dist1);
+
+/* rs_l2_knn2 + the filters of src/MapMatcher.cpp:150-161 on dist: keep query q iff
+ *   dist0 <= max_distance  and  (nt < 2 or dist0 <= 0.75f * dist1)      (one f32 product; a NaN max_distance fails both)
+ * Outputs as rs_match_descriptors: ascending query order, compacted per batch item; any of d_idx0..d_dist1 may be NULL. */
+int rs_match_descriptors_f32(rs_context* ctx,
+                             const float* d_query, int nq,
+                             const float* d_train, int nt, int dim, int batch,
+                             float max_distance,
+                             int32_t* d_match_query, int32_t* d_match_train,
+                             int32_t* d_match_count,
+                             int32_t* d_idx0, float* d_dist0,
+                             int32_t* d_idx1, float* d_dist1);
+
 /* ------------------------------------------- a2/a3: reprojection-gated match */
 
 /* KD-tree over a frame's keypoints, flattened.  Mirrors KDTree2D
@@ -283,6 +318,26 @@ int rs_reproj_match_sharded(rs_context* ctx, const rs_frame_view* frame, const r
                             int32_t* d_point_kp, int32_t* d_point_dist,
                             int32_t* d_prop_point, int32_t* d_prop_dist,
                             int32_t* d_match_kp, int32_t* d_match_point, int32_t* d_match_count);
+
+/* rs_reproj_match for FLOAT descriptors under the L2 norm: d_frame_desc [N][dim] f32 are the frame's rows,
+ * d_desc_pool [rows][dim] f32 the pool that map->d_obs_desc indexes (16-byte aligned, dim % 4 == 0, 4 .. 1024; any
+ * other dim: RS_ERR_UNSUPPORTED).  Of the views it reads the pose, intrinsics, image size, keypoints, d_kp_matched,
+ * d_kd_node_kp / left / right, kd_root and the map's CSR, positions, eligibility and centres; both u8 descriptor
+ * pointers, d_kd_packed and d_kd_grid are ignored.  Gates, walk order and f32 operation order are rs_reproj_match's.
+ * The distance of a (candidate, observation) pair, all f32:
+ *   r0..r3 = 0; for k ascending: e = q[k] - t[k]; r[k & 3] = fmaf(e, e, r[k & 3])
+ *   d2 = (r0 + r1) + (r2 + r3),  dist = sqrtf(d2) correctly rounded
+ * Comparisons are the reference's (src/MapMatcher.cpp:77-97): a running best from max_distance with a strict '<' on dist
+ * over candidates in the KD recursion's order and observations in list order; per keypoint a strict '<' over points in map
+ * order.  So max_distance <= 0 (or NaN) proposes nothing.  Outputs as rs_reproj_match with f32 distances
+ * (d_point_dist / d_prop_dist = max_distance where there is none; with no keypoint the count is zeroed and every point
+ * gets -1 and max_distance); bit-exact against tests/match_l2_ref.py. */
+int rs_reproj_match_l2(rs_context* ctx, const rs_frame_view* frame, const rs_map_view* map,
+                       const float* d_frame_desc, const float* d_desc_pool, int dim,
+                       int replace, float max_distance,
+                       int32_t* d_point_kp, float* d_point_dist,
+                       int32_t* d_prop_point, float* d_prop_dist,
+                       int32_t* d_match_kp, int32_t* d_match_point, int32_t* d_match_count);
 
 /* ---------------------------------------- §8(f) rank 4: the map, resident on the device */
 

@@ -118,14 +118,17 @@ constexpr size_t MIN_OBSERVATIONS_TO_OPTIMIZE = 2;             // src/Optimizati
 // MapMatcher::match (src/MapMatcher.cpp:45-98, 117-127, 165-175) -> rs_map_view: positions, eligibility (the pointer-set
 // tests of :53, :121-123, :169), observation CSR of the eligible points, key-frame table (ids in first-seen order) and
 // descriptor pool (each key frame's rows once).  A null point is ineligible and keeps a zero position.
+// F32 (NORM_L2, rs_reproj_match_l2): the pool is pool_f32, rows of `dim` floats read through
+// Access::descriptor_rows_f32(frame, const float*&, size_t& n, size_t dim) — false when the frame's rows are not n x dim f32.
 struct MatchArrays {
-    std::vector<float> pos, centers;
+    std::vector<float> pos, centers, pool_f32;
     std::vector<uint8_t> eligible, pool;
     std::vector<int32_t> obs_ptr, obs_kf, obs_desc;
     bool refused = false;                                      // a key frame's descriptor_rows said no: the arrays are incomplete
 };
-template <class Frame, class Point, class KeyFrame, class Access>
-MatchArrays flatten_match(const Frame& frame, const std::vector<Point*>& points, KeyFrame* required_observer, const Access& A)
+template <bool F32 = false, class Frame, class Point, class KeyFrame, class Access>
+MatchArrays flatten_match(const Frame& frame, const std::vector<Point*>& points, KeyFrame* required_observer, const Access& A,
+                          size_t dim = 0)
 {
     const size_t P = points.size();
     MatchArrays m;
@@ -144,14 +147,21 @@ MatchArrays flatten_match(const Frame& frame, const std::vector<Point*>& points,
                 bool fresh = false;
                 const int id = kf_id.find_or_insert(kf, (int)pool_off.size(), &fresh);
                 if (fresh) {
-                    const uint8_t* rows = nullptr;
                     size_t n_rows = 0;
-                    if (!A.descriptor_rows(*kf, rows, n_rows)) { m.refused = true; return; }
+                    if constexpr (F32) {
+                        const float* rows = nullptr;
+                        if (!A.descriptor_rows_f32(*kf, rows, n_rows, dim)) { m.refused = true; return; }
+                        pool_off.push_back((int32_t)(m.pool_f32.size() / dim));
+                        m.pool_f32.insert(m.pool_f32.end(), rows, rows + n_rows * dim);
+                    } else {
+                        const uint8_t* rows = nullptr;
+                        if (!A.descriptor_rows(*kf, rows, n_rows)) { m.refused = true; return; }
+                        pool_off.push_back((int32_t)(m.pool.size() / RS_DESC_BYTES));
+                        m.pool.insert(m.pool.end(), rows, rows + n_rows * RS_DESC_BYTES);
+                    }
                     float c[3];
                     A.center(*kf, c);
                     m.centers.insert(m.centers.end(), c, c + 3);
-                    pool_off.push_back((int32_t)(m.pool.size() / RS_DESC_BYTES));
-                    m.pool.insert(m.pool.end(), rows, rows + n_rows * RS_DESC_BYTES);
                 }
                 m.obs_kf.push_back(id);
                 m.obs_desc.push_back(pool_off[(size_t)id] + (int32_t)keypoint_index);

@@ -91,6 +91,11 @@ inline void intrinsics(const Eigen::Matrix3f& M, float K[4])
 
 // 32-byte ORB rows (or no rows at all): the only descriptor layout the Hamming kernels take
 inline bool orb_layout(const cv::Mat& d) { return d.empty() || (d.type() == CV_8U && d.cols == RS_DESC_BYTES && d.isContinuous()); }
+// float rows the L2 matchers take (rs_match_descriptors_f32, rs_reproj_match_l2): CV_32F, 4 .. 1024 columns in fours, continuous
+inline bool f32_layout(const cv::Mat& d)
+{
+    return d.empty() || (d.type() == CV_32F && d.cols >= 4 && d.cols <= 1024 && d.cols % 4 == 0 && d.isContinuous());
+}
 
 // How the flatten templates of rs_marshal.h read the reference's objects (Eigen / OpenCV).
 struct Access {
@@ -104,6 +109,13 @@ struct Access {
         const cv::Mat& d = f.features().descriptors;            // N x 32 CV_8U, row-contiguous
         if (!orb_layout(d)) return false;
         rows = d.ptr<uint8_t>(0); n_rows = (size_t)d.rows;
+        return true;
+    }
+    static bool descriptor_rows_f32(const slam::Frame& f, const float*& rows, size_t& n_rows, size_t dim)
+    {
+        const cv::Mat& d = f.features().descriptors;            // N x dim CV_32F, row-contiguous
+        if (!f32_layout(d) || (!d.empty() && (size_t)d.cols != dim)) return false;
+        rows = d.ptr<float>(0); n_rows = (size_t)d.rows;
         return true;
     }
     static size_t n_matches(const slam::Frame& f) { return f.num_map_matches(); }

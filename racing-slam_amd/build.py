@@ -22,6 +22,7 @@ SOURCES = [
     ("hamming.hip", []),
     ("triangulate.hip", ["-ffp-contract=off"]),
     ("reproj_match.hip", ["-ffp-contract=off"]),
+    ("l2_match.hip", ["-ffp-contract=off"]),
     ("tracks.hip", ["-ffp-contract=off"]),
     ("klt.hip", ["-ffp-contract=off"]),
     ("gftt.hip", ["-ffp-contract=off"]),

@@ -28,6 +28,7 @@
 // Built with -ffp-contract=off so the f32 gates execute the oracle's operations.
 #include "common.h"
 #include "tri_core.h"
+#include "reproj_gates.h"      // k2_view_gates: the viewing-angle and distance-range gates
 
 #include <mutex>
 
@@ -253,19 +254,6 @@ __device__ __forceinline__ bool k2_project(const K2Frame& f, const float* T, con
     return u >= 0.0f && u < (float)f.width && v >= 0.0f && v < (float)f.height;
 }
 
-// The viewing gates once the point's observations are accumulated (src/MapPoint.cpp:24-45): `normal` the sum of the unit
-// rays from the observing keyframes, nearest / furthest their distance range; center = Frame::camera_center.
-__device__ __forceinline__ bool k2_view_gates(float* normal, float nearest, float furthest, const float* X, const float* center)
-{
-    const float ray[3] = {X[0] - center[0], X[1] - center[1], X[2] - center[2]};
-    normalize3f(normal);
-    float rn[3] = {ray[0], ray[1], ray[2]};
-    normalize3f(rn);
-    if (dot3f(normal, rn) < 0.5f) return false;                         // :62-66
-    const float distance = sqrtf(dot3f(ray, ray));
-    return !(distance < nearest / 2.0f || distance > furthest * 1.25f);  // :69-73
-}
-
 // An in-range, open keypoint met by the walk (src/MapMatcher.cpp:84-91).  The first K2_MAXC are QUEUED in visiting
 // order, their descriptors compared in phase B.  (Comparing inside the walk costs one global-memory round trip per
 // iteration in which ANY lane of the wave has a candidate — nearly every one; queued, the round trips are one per four
@@ -291,6 +279,7 @@ __device__ __forceinline__ void k2_candidate(const K2Frame& f, const K2Map& m, i
 // examined (their indices are in the node), so the LDS latency of the next visit overlaps this visit's arithmetic; only
 // a node popped from the stack pays a read of its own.  Otherwise (trees too large for LDS) the same walk fetches each
 // node from global memory when it is visited.
+// (l2_match.hip's l2_reproj_match carries a hand copy of the global-memory branch: keep the two in step.)
 // A macro over the kernel's f, m, replace, o0, o1, u, v, L, nc, over_d and over_kp, not a function: as an inlined
 // function the compiler splits this loop into a descent loop inside a pop loop, in which a lane that has to pop waits
 // for the wave's last descent to end (K2 on the benchmark scene: 22.4 us instead of 20.9).

@@ -76,6 +76,14 @@ bool rs_ok(int rc, const char* what)
     return false;
 }
 
+// the norms MapMatcher has a device path for; anything else is refused loudly, like a failed call
+bool norm_supported(int norm_type)
+{
+    if (norm_type == NORM_HAMMING || norm_type == NORM_L2) return true;
+    std::printf("MapMatcher: norm type %d is not supported (NORM_HAMMING on 32-byte rows, NORM_L2 on float rows)\n", norm_type);
+    return false;
+}
+
 rs_ba_summary g_summary{};
 
 // How the flatten templates of rs_marshal.h read the mirror's objects (the shims' Access reads the reference's:
@@ -90,6 +98,12 @@ struct HostAccess {
     static bool descriptor_rows(const Frame& f, const uint8_t*& rows, size_t& n_rows)
     {
         rows = f.features().descriptors.data(); n_rows = f.features().descriptors.size() / RS_DESC_BYTES;
+        return true;
+    }
+    static bool descriptor_rows_f32(const Frame& f, const float*& rows, size_t& n_rows, size_t dim)
+    {
+        if (dim == 0 || (size_t)f.features().descriptor_dim != dim) return false;
+        rows = f.features().descriptors_f32.data(); n_rows = f.features().descriptors_f32.size() / dim;
         return true;
     }
     static size_t n_matches(const Frame& f) { return f.num_map_matches(); }
@@ -242,26 +256,48 @@ std::vector<MapPointMatch> MapMatcher::match(const Frame& frame, const std::vect
         kp[2 * i] = frame.keypoint(i).pt.x; kp[2 * i + 1] = frame.keypoint(i).pt.y;
         matched[i] = frame.is_matched(i) ? 1 : 0;
     }
+    if (!norm_supported(m_norm_type)) return {};
+    const bool l2 = m_norm_type == NORM_L2;
+    const size_t dim = l2 ? (size_t)frame.features().descriptor_dim : 0;
+    if (l2 && (dim == 0 || frame.features().descriptors_f32.size() != N * dim)) {
+        std::printf("MapMatcher: NORM_L2 needs N x descriptor_dim float rows on the frame\n");
+        return {};
+    }
     // map side: positions, eligibility, observation CSR, keyframe table and descriptor pool
-    const rs_marshal::MatchArrays m = rs_marshal::flatten_match(frame, points, required_observer, HostAccess{});
+    const rs_marshal::MatchArrays m = l2 ? rs_marshal::flatten_match<true>(frame, points, required_observer, HostAccess{}, dim)
+                                         : rs_marshal::flatten_match(frame, points, required_observer, HostAccess{});
+    if (m.refused) {
+        std::printf("MapMatcher: a key frame's descriptor rows are not %zu floats wide\n", dim);
+        return {};
+    }
     StageScope stage;
     DevBuf<float> d_kp(kp), d_pos(m.pos), d_centers(m.centers);
-    DevBuf<uint8_t> d_desc(frame.features().descriptors), d_matched(matched), d_elig(m.eligible), d_pool(m.pool);
+    DevBuf<uint8_t> d_matched(matched), d_elig(m.eligible);
     DevBuf<int32_t> d_nk(frame.kd_node_kp()), d_l(frame.kd_left()), d_r(frame.kd_right()), d_optr(m.obs_ptr), d_okf(m.obs_kf),
         d_odesc(m.obs_desc);
     rs_frame_view fv{};
     std::memcpy(fv.pose, frame.pose().data(), sizeof fv.pose);
     fv.fx = m_camera.fx(); fv.fy = m_camera.fy(); fv.cx = m_camera.cx(); fv.cy = m_camera.cy();
     fv.width = m_camera.get_width(); fv.height = m_camera.get_height();
-    fv.n_keypoints = (int)N; fv.d_keypoints = d_kp.get(); fv.d_descriptors = d_desc.get(); fv.d_kp_matched = d_matched.get();
+    fv.n_keypoints = (int)N; fv.d_keypoints = d_kp.get(); fv.d_kp_matched = d_matched.get();
     fv.d_kd_node_kp = d_nk.get(); fv.d_kd_left = d_l.get(); fv.d_kd_right = d_r.get(); fv.kd_root = frame.kd_root();
     rs_map_view mv{};
     mv.n_points = (int)P; mv.d_positions = d_pos.get(); mv.d_eligible = d_elig.get(); mv.d_obs_ptr = d_optr.get();
-    mv.d_obs_kf = d_okf.get(); mv.d_obs_desc = d_odesc.get(); mv.d_kf_centers = d_centers.get(); mv.d_desc_pool = d_pool.get();
-    DevBuf<int32_t> pk(P), pd(P), pp(N), pdist(N), mkp(N), mpt(N), cnt(1);
-    if (!rs_ok(rs_reproj_match(ctx, &fv, &mv, replace ? 1 : 0, (int)m_max_descriptor_distance, pk.get(), pd.get(), pp.get(),
-                               pdist.get(), mkp.get(), mpt.get(), cnt.get()), "rs_reproj_match"))
-        return {};
+    mv.d_obs_kf = d_okf.get(); mv.d_obs_desc = d_odesc.get(); mv.d_kf_centers = d_centers.get();
+    DevBuf<int32_t> pk(P), pp(N), mkp(N), mpt(N), cnt(1);
+    if (l2) {
+        DevBuf<float> d_rows(frame.features().descriptors_f32), d_pool(m.pool_f32), pd(P), pdist(N);
+        if (!rs_ok(rs_reproj_match_l2(ctx, &fv, &mv, d_rows.get(), d_pool.get(), (int)dim, replace ? 1 : 0, m_max_descriptor_distance,
+                                      pk.get(), pd.get(), pp.get(), pdist.get(), mkp.get(), mpt.get(), cnt.get()), "rs_reproj_match_l2"))
+            return {};
+    } else {
+        DevBuf<uint8_t> d_desc(frame.features().descriptors), d_pool(m.pool);
+        DevBuf<int32_t> pd(P), pdist(N);
+        fv.d_descriptors = d_desc.get(); mv.d_desc_pool = d_pool.get();
+        if (!rs_ok(rs_reproj_match(ctx, &fv, &mv, replace ? 1 : 0, (int)m_max_descriptor_distance, pk.get(), pd.get(), pp.get(),
+                                   pdist.get(), mkp.get(), mpt.get(), cnt.get()), "rs_reproj_match"))
+            return {};
+    }
     const auto hn = cnt.fetch(1);
     const auto hk = mkp.fetch(N), hp = mpt.fetch(N);          // at most N matches: one read-back, one synchronisation
     stage_sync();
@@ -275,20 +311,38 @@ std::vector<MapPointMatch> MapMatcher::match(const Frame& frame, const std::vect
 std::vector<MapPointMatch> MapMatcher::match_descriptors(const Frame& frame, const KeyFrame& key_frame) const
 {
     rs_context* ctx = Session::get().ctx();
+    if (!norm_supported(m_norm_type)) return {};
     const auto km = key_frame.map_matches();                  // ascending keypoint order
-    std::vector<uint8_t> train;
-    for (const auto& m : km) {
-        const uint8_t* row = key_frame.features().descriptors.data() + 32 * m.keypoint_index;
-        train.insert(train.end(), row, row + 32);
-    }
     const int nq = (int)frame.features().keypoints.size(), nt = (int)km.size();
     if (nt == 0 || nq == 0) return {};                        // :139-141
     StageScope stage;
-    DevBuf<uint8_t> dq(frame.features().descriptors), dt(train);
     DevBuf<int32_t> mq((size_t)nq), mt((size_t)nq), cnt(1);
-    if (!rs_ok(rs_match_descriptors(ctx, dq.get(), nq, dt.get(), nt, 1, (int)m_max_descriptor_distance, mq.get(), mt.get(),
-                                    cnt.get(), nullptr, nullptr, nullptr, nullptr), "rs_match_descriptors"))
-        return {};
+    if (m_norm_type == NORM_L2) {
+        const size_t dim = (size_t)frame.features().descriptor_dim;
+        if (dim == 0 || (size_t)key_frame.features().descriptor_dim != dim || frame.features().descriptors_f32.size() != (size_t)nq * dim) {
+            std::printf("MapMatcher: NORM_L2 needs float rows of one width on both frames\n");
+            return {};
+        }
+        std::vector<float> train;
+        for (const auto& m : km) {
+            const float* row = key_frame.features().descriptors_f32.data() + dim * m.keypoint_index;
+            train.insert(train.end(), row, row + dim);
+        }
+        DevBuf<float> dq(frame.features().descriptors_f32), dt(train);
+        if (!rs_ok(rs_match_descriptors_f32(ctx, dq.get(), nq, dt.get(), nt, (int)dim, 1, m_max_descriptor_distance, mq.get(), mt.get(),
+                                            cnt.get(), nullptr, nullptr, nullptr, nullptr), "rs_match_descriptors_f32"))
+            return {};
+    } else {
+        std::vector<uint8_t> train;
+        for (const auto& m : km) {
+            const uint8_t* row = key_frame.features().descriptors.data() + 32 * m.keypoint_index;
+            train.insert(train.end(), row, row + 32);
+        }
+        DevBuf<uint8_t> dq(frame.features().descriptors), dt(train);
+        if (!rs_ok(rs_match_descriptors(ctx, dq.get(), nq, dt.get(), nt, 1, (int)m_max_descriptor_distance, mq.get(), mt.get(),
+                                        cnt.get(), nullptr, nullptr, nullptr, nullptr), "rs_match_descriptors"))
+            return {};
+    }
     const auto hn = cnt.fetch(1);
     const auto hq = mq.fetch((size_t)nq), ht = mt.fetch((size_t)nq);
     stage_sync();

@@ -53,6 +53,8 @@ struct KeyPoint { Vec2f pt; };
 struct ExtractedFeatures {
     std::vector<KeyPoint> keypoints;
     std::vector<uint8_t> descriptors;   // N x 32, row-major (cv::Mat N x 32 CV_8U)
+    std::vector<float> descriptors_f32; // N x descriptor_dim, row-major (cv::Mat N x dim CV_32F): what a NORM_L2 matcher reads
+    int descriptor_dim = 0;             // floats per row of descriptors_f32 (0: none)
 };
 struct FeatureMatch {
     FeatureMatch(int train, int query) : train_index((size_t)train), query_index((size_t)query) {}
@@ -131,9 +133,11 @@ class Map {
     std::vector<std::unique_ptr<MapPoint>> m_points;
 };
 
-enum NormTypes { NORM_HAMMING = 6 };   // cv::NORM_HAMMING
+enum NormTypes { NORM_L2 = 4, NORM_HAMMING = 6 };   // cv::NORM_L2, cv::NORM_HAMMING
 
-// src/MapMatcher.h:16-38
+// src/MapMatcher.h:16-38.  NORM_HAMMING matches the 32-byte rows (max_descriptor_distance truncated to an int), NORM_L2 the
+// float rows (rs_match_descriptors_f32 / rs_reproj_match_l2); any other norm, or frames whose float rows disagree in width,
+// match nothing and say so.
 class MapMatcher {
   public:
     MapMatcher(const Camera& camera, float max_descriptor_distance, NormTypes norm_type);

@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("RS_LIB") or ("librsgpu_stamps.so"
 EXPORTS = [
     "rs_abi_version", "rs_context_create", "rs_context_destroy", "rs_context_set_stream", "rs_context_wait_for", "rs_context_fork",
     "rs_context_synchronize", "rs_context_set_int", "rs_stage_begin", "rs_stage_alloc", "rs_stage_upload", "rs_stage_download", "rs_stage_sync", "rs_last_error", "rs_hamming_knn2", "rs_match_descriptors",
+    "rs_l2_knn2", "rs_match_descriptors_f32", "rs_reproj_match_l2",
     "rs_kdtree_build", "rs_kdtree_pack", "rs_kdtree_grid_bytes", "rs_kdtree_grid_build", "rs_reproj_match", "rs_reproj_match_sharded", "rs_map_create", "rs_map_destroy", "rs_frame_create", "rs_frame_destroy",
     "rs_frame_create_device", "rs_frame_assign_device", "rs_frame_download",
     "rs_frame_matches_clear", "rs_frame_matches_add", "rs_frame_matches_download",
@@ -66,6 +67,11 @@ def load():
         _lib.rs_last_error.argtypes = [C.c_void_p]
         if hasattr(_lib, "rs_kdtree_grid_bytes"):        # (an A/B library named by RS_LIB may predate the cell grid)
             _lib.rs_kdtree_grid_bytes.restype = C.c_size_t
+        if hasattr(_lib, "rs_l2_knn2"):                  # the float-descriptor entries take a float by value: declared in full
+            p, i, f = C.c_void_p, C.c_int, C.c_float
+            _lib.rs_l2_knn2.argtypes = [p, p, i, p, i, i, i, p, p, p, p]
+            _lib.rs_match_descriptors_f32.argtypes = [p, p, i, p, i, i, i, f, p, p, p, p, p, p, p]
+            _lib.rs_reproj_match_l2.argtypes = [p, p, p, p, p, i, i, f, p, p, p, p, p, p, p]
     return _lib
 
 
@@ -512,6 +518,44 @@ class Context:
                                              _dp(out["point_kp"]), _dp(out["point_dist"]), _dp(out["prop_point"]),
                                              _dp(out["prop_dist"]), _dp(out["match_kp"]), _dp(out["match_point"]),
                                              _dp(out["count"])), "rs_reproj_match")
+        return out
+
+    # -- the same three for float descriptors under L2 (rows of `dim` f32)
+    def l2_knn2(self, d_query, d_train, nq, nt, dim, batch=1):
+        t = self.torch
+        outs = [self.empty((batch, max(nq, 1)), dt) for dt in (t.int32, t.float32, t.int32, t.float32)]
+        self._check(self.lib.rs_l2_knn2(self.h, _dp(d_query), nq, _dp(d_train), nt, int(dim), batch,
+                                        *[_dp(o) for o in outs]), "rs_l2_knn2")
+        return outs
+
+    def match_descriptors_f32(self, d_query, d_train, nq, nt, dim, batch=1, max_distance=0.7, raw=False, out=None):
+        t = self.torch
+        if out is None:
+            out = dict(mq=self.empty((batch, max(nq, 1)), t.int32), mt=self.empty((batch, max(nq, 1)), t.int32),
+                       cnt=self.empty((batch,), t.int32))
+            if raw:
+                out["raw"] = [self.empty((batch, max(nq, 1)), dt) for dt in (t.int32, t.float32, t.int32, t.float32)]
+        rawp = [_dp(o) for o in out["raw"]] if "raw" in out else [None] * 4
+        self._check(self.lib.rs_match_descriptors_f32(self.h, _dp(d_query), nq, _dp(d_train), nt, int(dim), batch,
+                                                      float(max_distance), _dp(out["mq"]), _dp(out["mt"]),
+                                                      _dp(out["cnt"]), *rawp), "rs_match_descriptors_f32")
+        return out
+
+    def reproj_match_l2(self, fv, mv, d_frame_desc, d_desc_pool, dim, replace=0, max_distance=0.7, out=None):
+        """rs_reproj_match_l2: fv / mv as for reproj_match (their u8 descriptor pointers are not read), the float rows
+        of the frame's keypoints and of the pool that mv's d_obs_desc indexes."""
+        t = self.torch
+        N, P = fv.n_keypoints, mv.n_points
+        if out is None:
+            out = dict(point_kp=self.empty((max(P, 1),), t.int32), point_dist=self.empty((max(P, 1),), t.float32),
+                       prop_point=self.empty((max(N, 1),), t.int32), prop_dist=self.empty((max(N, 1),), t.float32),
+                       match_kp=self.empty((max(N, 1),), t.int32), match_point=self.empty((max(N, 1),), t.int32),
+                       count=self.empty((1,), t.int32))
+        self._check(self.lib.rs_reproj_match_l2(self.h, C.addressof(fv), C.addressof(mv), _dp(d_frame_desc), _dp(d_desc_pool),
+                                                int(dim), int(replace), float(max_distance),
+                                                _dp(out["point_kp"]), _dp(out["point_dist"]), _dp(out["prop_point"]),
+                                                _dp(out["prop_dist"]), _dp(out["match_kp"]), _dp(out["match_point"]),
+                                                _dp(out["count"])), "rs_reproj_match_l2")
         return out
 
     # -- a5-a7
